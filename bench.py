@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X FastSpeech2 mel-generation path (BASELINE.json metric: mel-frames/sec).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...,
    or as the plain command above: without WORLD_SIZE in the environment the script re-launches itself under torch.distributed.run
    with N ranks on 127.0.0.1 and a free port; rank 0 prints the one JSON line either way)
@@ -21,6 +21,11 @@ Workloads (BASELINE.json configs, fastspeech2_amd/synthetic.py):
 Random-init default model (portable generator, seed 0) with the duration bias set so that predicted durations are
 LJSpeech-like; there is no network for real checkpoints or datasets.
 value = valid mel frames of the global batch / max-over-ranks wall time of exactly K steps.
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the one JSON line.  Everything else the line
+can carry -- the CPU baseline and its decision agreement, the roofline figures and the scouting step they come from, the sustained and
+one-stream regions, the multi-GPU diagnostics -- runs behind --full.  --dump-outputs DIR writes what the last timed step returned
+(DIR/<name>.npy, see dump_outputs) so that two builds can be compared output for output: the inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -327,6 +332,47 @@ def dist_diagnostics(model, synth, xs, il, parts, rank, world, dev, k, ms_per_st
                      "forward alone; exposed_overlapped = the line's ms_per_step - the busiest rank's forward in the SAME schedule (comparable figures)")
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6          # (--dump-outputs: 64 MB in all)
+
+
+def timed_outputs(out, packed):
+    """What a caller of the timed path received from its last step, as named host arrays: `olens` (mel frames per utterance) and either
+    `mel` = the padded mels [B, max(olens), odim] (the capacity rows behind the longest utterance hold zeros and depend on what the capacity
+    predictor learnt, so they are cut) or, for the packed gather, `mel_packed` = the valid frames of every utterance back to back in global
+    utterance order [sum(olens), odim] (the gathered buffer's capacity rows and frame-count rows are cut)."""
+    if packed:
+        recv, starts, olens = out
+        ol = torch.as_tensor(olens).cpu().long()
+        st = torch.as_tensor(starts).cpu().long()
+        idx = torch.cat([torch.arange(int(s), int(s) + int(n)) for s, n in zip(st, ol)]) if ol.numel() else torch.zeros(0, dtype=torch.int64)
+        return {"olens": ol, "mel_packed": recv[idx.to(recv.device)].cpu()}
+    mel, olens = out
+    ol = torch.as_tensor(olens).cpu().long()
+    return {"olens": ol, "mel": mel[:, : int(ol.max()) if ol.numel() else 0].cpu()}
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as <outdir>/<name>.npy, float32 tensors as float32 and all others as float64, at most `budget` bytes in
+    all (smallest arrays first).  An array that does not fit in what is left is cut to a fixed sample of its rows (all axes but the last
+    folded into rows; numpy RandomState(0), sorted), and the row numbers of the sample go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    hdr = 4096                  # (allowance per file for the .npy header)
+    left = budget
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes + hdr > left:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            k = min(rows.shape[0], max(left - 2 * hdr, 0) // (rows.shape[1] * a.itemsize + 8))
+            pick = np.sort(np.random.RandomState(0).choice(rows.shape[0], k, replace=False)).astype(np.float64)
+            np.save(os.path.join(outdir, name + "_rows.npy"), pick)
+            a = rows[pick.astype(np.int64)] if a.ndim > 1 else rows[pick.astype(np.int64), 0]
+            left -= pick.nbytes + hdr
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes + hdr
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s_:
         s_.bind(("127.0.0.1", 0))
@@ -362,21 +408,28 @@ def fake_main(args, json_fd):
     dist.barrier()
     dt = time.perf_counter() - t0
     frames = int(torch.as_tensor(out[-1]).sum())
-    # the fields of dist_diagnostics() that exist without a GPU: the same collectives in the same order, stand-in numbers
-    from fastspeech2_amd.parallel import shard_indices, utterance_cost
-    parts = shard_indices(il.tolist(), world)
-    costs = [sum(utterance_cost(int(il[i])) for i in p) for p in parts]
-    t = torch.tensor([1.0 + rank], dtype=torch.float64)
-    every = [torch.zeros_like(t) for _ in range(world)]
-    dist.all_gather(every, t)
-    fwd_all = [float(x) for x in every]
-    diag = dict(backend=dist.get_backend(), world_size=dist.get_world_size(), lpt_cost_imbalance_max_over_mean=round(max(costs) / (sum(costs) / len(costs)), 4),
-                forward_ms_per_rank=fwd_all, forward_ms_min=min(fwd_all), forward_ms_max=max(fwd_all))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_outputs(out, packed=not args.padded))
+    diag = None
+    if args.full:
+        # the fields of dist_diagnostics() that exist without a GPU: the same collectives in the same order, stand-in numbers
+        from fastspeech2_amd.parallel import shard_indices, utterance_cost
+        parts = shard_indices(il.tolist(), world)
+        costs = [sum(utterance_cost(int(il[i])) for i in p) for p in parts]
+        t = torch.tensor([1.0 + rank], dtype=torch.float64)
+        every = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(every, t)
+        fwd_all = [float(x) for x in every]
+        diag = dict(backend=dist.get_backend(), world_size=dist.get_world_size(), lpt_cost_imbalance_max_over_mean=round(max(costs) / (sum(costs) / len(costs)), 4),
+                    forward_ms_per_rank=fwd_all, forward_ms_min=min(fwd_all), forward_ms_max=max(fwd_all))
     if rank == 0:
-        os.write(json_fd, (json.dumps({"metric": "mel-frames/sec", "value": round(frames * args.steps / dt, 1), "unit": "mel-frames/s", "n_gpus": world,
-                                       "steps": args.steps, "warmup": args.warmup, "data": "FAKE (FS2_BENCH_FAKE test harness: gloo, stand-in model, measures nothing)",
-                                       "config": {"workload": "fake", "gather": "padded" if args.padded else "packed", "collective_world_size": dist.get_world_size()},
-                                       "multi_gpu": diag}) + "\n").encode())
+        line = {"metric": "mel-frames/sec", "value": round(frames * args.steps / dt, 1), "unit": "mel-frames/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+                "data": "FAKE (FS2_BENCH_FAKE test harness: gloo, stand-in model, measures nothing)",
+                "config": {"workload": "fake", "gather": "padded" if args.padded else "packed", "collective_world_size": dist.get_world_size()}}
+        if diag is not None:
+            line["multi_gpu"] = diag
+        os.write(json_fd, (json.dumps(line) + "\n").encode())
     dist.destroy_process_group()
 
 
@@ -401,7 +454,16 @@ def main():
                     "alike): the kernel variants of the larger batch on this one, what every rank of the sharded path does (fs2_batch.regime_*); measures the cost of that choice")
     ap.add_argument("--padded", action="store_true", help="N > 1: every rank also unpacks the gathered mels into the padded [B, Lcap, odim] tensor "
                                                            "(default: the packed form, gathered packs + offsets, no unpack launch)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond `value`: the CPU baseline (--no-cpu-baseline drops it), "
+                    "the roofline figures, the sustained (--sustain) and one-stream regions, the multi-GPU diagnostics (a plain run: set-up, warm-up, "
+                    "the timed steps and the line only; --profile-kernels implies --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB in all, a fixed sample of the rows beyond that): `olens` and `mel` (padded, cut at the longest utterance) or "
+                    "`mel_packed` (the packed gather's valid frames in utterance order)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    args.full = args.full or args.profile_kernels
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched as a plain command: become `torch.distributed.run ... bench.py <same arguments>` (one rank per GPU, 127.0.0.1, a free port)
         cmd = relaunch_command(sys.argv[1:], args.gpus)
@@ -477,6 +539,7 @@ def main():
     step_streams = StepStreams(n_streams, device=dev) if n_streams > 1 else None
     step_no = [0]
     one_stream = [False]        # (the A/B region behind the timed one)
+    packed_last = [None]        # (recv, starts, olens) of the latest packed-gather step: what its caller receives
 
     def step(done=None):
         """one pass of the hot path over the batch; `done` (an event) is recorded behind it on the stream it was issued on"""
@@ -503,6 +566,7 @@ def main():
             if args.padded or args.profile_kernels:
                 return synth(xs, il, sync=args.profile_kernels)
             r = synth(xs, il, packed=True)        # (recv, starts, olens); the very first call is synchronous and returns (mels, olens)
+            packed_last[0] = r if len(r) == 3 else None
             return r[0], r[-1]
         # nothing on the host waits for the GPU: the frame layout is built on the device (fs2_decode's device-driven
         # mode); the very first call is synchronous and teaches the capacity predictor the frames-per-phoneme ratio
@@ -528,22 +592,28 @@ def main():
         total_frames = int(olens_all.sum())
         local_frames = int(olens_all.cpu()[torch.as_tensor(mine, dtype=torch.int64)].sum()) if mine else 0
         local_tokens = int(il[torch.as_tensor(mine, dtype=torch.int64)].sum()) if mine else 0
-        # find the dominant launch site with one fully bracketed (untimed) step, then bracket only that site
-        # inside the timed region so that hipEvent records do not perturb the measurement
-        model.set_profiling(True)
-        if graph_run is not None:
-            model.inference_batch(xs, il)        # a graph replay has no per-launch events: scout with an eager step
+        if args.full:
+            # find the dominant launch site with one fully bracketed (untimed) step, then bracket only that site
+            # inside the timed region so that hipEvent records do not perturb the measurement
+            model.set_profiling(True)
+            if graph_run is not None:
+                model.inference_batch(xs, il)        # a graph replay has no per-launch events: scout with an eager step
+            else:
+                step()
+            torch.cuda.synchronize()
+            scout, scout_n = {}, {}
+            scout_prof = model.get_profile()
+            for name, ms, fl, by in scout_prof:
+                scout[name] = scout.get(name, 0.0) + ms
+                scout_n[name] = scout_n.get(name, 0) + 1
+            dom_site = max(scout.items(), key=lambda kv: kv[1])[0]
+            kernel_ms_per_step = sum(scout.values())
+            model.set_profiling(True, only=None if args.profile_kernels else dom_site)
         else:
+            # one more untimed step in the scouting step's place, so that both modes enter the timed region from the same state
+            # (without it the timed steps measured ~0.7 % slower, alternated with the --full form on one MI355X)
             step()
-        torch.cuda.synchronize()
-        scout, scout_n = {}, {}
-        scout_prof = model.get_profile()
-        for name, ms, fl, by in scout_prof:
-            scout[name] = scout.get(name, 0.0) + ms
-            scout_n[name] = scout_n.get(name, 0) + 1
-        dom_site = max(scout.items(), key=lambda kv: kv[1])[0]
-        kernel_ms_per_step = sum(scout.values())
-        model.set_profiling(True, only=None if args.profile_kernels else dom_site)
+            torch.cuda.synchronize()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         if use_dist:
             dist.barrier()
@@ -560,15 +630,19 @@ def main():
         dt = time.perf_counter() - t0
         assert all_ok(), "capacities of the asynchronous path were exceeded in the timed region"
         mel_timed = mel                      # the LAST timed step's result, as its schedule produced it (compared with the checked forward below)
-        # spacing of the steps' completions (with S streams: over windows of S steps, the steps of one stream)
+        if args.dump_outputs and rank == 0:
+            packed = packed_last[0] is not None and not (args.padded or args.profile_kernels)
+            dump_outputs(args.dump_outputs, timed_outputs(packed_last[0] if packed else (mel, olens_all), packed))
+        # spacing of the steps' completions (with S streams: over windows of S steps, the steps of one stream; none with fewer steps than streams)
         step_ms = [ev[i + 1 - n_streams].elapsed_time(ev[i + 1]) / n_streams for i in range(n_streams - 1, args.steps)]
-        prof = model.get_profile() if graph_run is None else scout_prof      # (graph mode: the roofline comes from the eager scouting step)
-        model.set_profiling(False)
+        if args.full:
+            prof = model.get_profile() if graph_run is None else scout_prof      # (graph mode: the roofline comes from the eager scouting step)
+            model.set_profiling(False)
         # ---- steady state: the timed region above is K steps (0.1 s at c3) after ~0.05 s of warm-up, and sustained MFMA load
         # lowers the shader clock within tens of ms.  The same step runs on for >= args.sustain seconds (not part of `value`), timed the same way,
         # while the host samples the shader clock from sysfs between enqueues.
         sustained = None
-        if args.sustain > 0:
+        if args.full and args.sustain > 0:
             n_sus = max(args.steps, int(args.sustain / max(dt / args.steps, 1e-6)) + 1)
             read_clk = sclk_reader(local)
             clk = []
@@ -610,7 +684,7 @@ def main():
         # ---- the same steps on ONE stream (not part of `value`): the A/B of the schedule, and the dominant kernel alone on the chip -- in the
         # timed region above its launches share the CUs with the other step's kernels, so their bracketed duration there is not the kernel's own
         alone = None
-        if step_streams is not None:
+        if args.full and step_streams is not None:
             n_al = max(4, args.steps)               # the same K as the timed region (10 steps behind a 2-s burn were not comparable)
             one_stream[0] = True
             for _ in range(2):
@@ -650,149 +724,150 @@ def main():
     kernels = _fs2lib.kernel_state()
     slow_waves = model.counter("attn_slow_path_waves")
     multi_gpu = None
-    if use_dist and synth is not None and graph_run is None:
+    if args.full and use_dist and synth is not None and graph_run is None:
         with torch.no_grad():
             multi_gpu = dist_diagnostics(model, synth, xs, il, parts, rank, world, dev, max(2, min(args.steps, 5)), 1e3 * dt / args.steps, step_streams, args.steps)
 
-    # ---- per-kernel table (hipEvents on the launch stream, accumulated over the timed steps) ----
-    agg = {}
-    for name, ms, fl, by in prof:
-        a = agg.setdefault(name, [0, 0.0, 0.0])
-        a[0] += 1
-        a[1] += ms
-        a[2] += fl
-    dom = max(agg.items(), key=lambda kv: kv[1][1])
-    dom_name, (dom_n, dom_ms, _) = dom
-    c = model._cfg
-    # algorithmic FLOPs per launch of the dominant kernel, valid frames/tokens of THIS rank only
-    per_row = {"dec.ffn1": 2.0 * c["ffn_kernel"] * c["ddim"] * c["dunits"], "enc.ffn1": 2.0 * c["ffn_kernel"] * c["adim"] * c["eunits"],
-               "dec.ffn2_ln": 2.0 * c["dunits"] * c["ddim"], "dec.qkv": 6.0 * c["ddim"] ** 2, "dec.out_ln": 2.0 * c["ddim"] ** 2}
-    rows = local_tokens if dom_name.startswith("enc") or dom_name.startswith("dur") else local_frames
-    mine_t = torch.as_tensor(mine, dtype=torch.int64)
-    ol_mine = olens_all.cpu()[mine_t].double() if mine else torch.zeros(0, dtype=torch.float64)
-    il_mine = il[mine_t].double() if mine else torch.zeros(0, dtype=torch.float64)
-    per_launch = {"dec.attn": 4.0 * c["ddim"] * float((ol_mine * ol_mine).sum()),       # 4 D L^2 per utterance and layer
-                  "enc.attn": 4.0 * c["adim"] * float((il_mine * il_mine).sum())}
-    if dom_name in per_row:
-        algo = per_row[dom_name] * rows
-    elif dom_name in per_launch:
-        algo = per_launch[dom_name]
-    else:   # fall back to the launch's own count (includes the ~1.5 % gap rows)
-        algo = sum(fl for n_, ms, fl, by in prof if n_ == dom_name) / dom_n
-    avg_ms = dom_ms / dom_n
-    bracket_in_flight = None
-    if alone is not None and alone["avg_launch_ms"] > 0:
-        # With several steps in flight a hipEvent bracket is not the kernel's duration: the second event waits for the kernel, the kernel waits in its
-        # hardware queue for CUs that other streams' kernels hold (c3, 3 streams: bracket 0.57 ms, rocprofv3 dispatch timestamps of the same region
-        # 0.46 ms, the kernel alone 0.42 ms: profiles/r06_kernel_trace_by_region.txt).  The roofline of the kernel is therefore taken where the
-        # bracket IS the duration: the same launch site in the one-stream region behind the timed one (it agrees with rocprofv3 to 1 %).
-        bracket_in_flight = avg_ms
-        avg_ms = alone["avg_launch_ms"]
-    achieved = algo / (avg_ms * 1e-3) / 1e12
-    peak = PEAK_TFLOPS[args.precision]
-    roofline = dict(bound="mfma", kernel=dom_name, achieved=round(achieved, 2), peak=peak, unit="TFLOP/s",
-                    frac=round(achieved / peak, 4), traffic=None, avg_launch_ms=round(avg_ms, 4),
-                    launches_per_step=dom_n // max(args.steps, 1),
-                    # this site's launches (events around it alone, inside the timed region) as a share of the step's wall time: cannot exceed 1
-                    share_of_step_time=round(dom_ms / (1e3 * dt), 3))
-    if bracket_in_flight is not None:
-        lps = dom_n // max(args.steps, 1)
-        roofline["share_of_step_time"] = round(lps * avg_ms / (1e3 * dt / args.steps), 3)      # (kernel time / step interval: steps overlap)
-        roofline["measured_in"] = ("the one-stream region behind the timed one (%d steps, hipEvents around this site on the launch stream): with %d steps "
-                                   "in flight an event bracket also holds the launch's wait in its hardware queue" % (alone["steps"], n_streams))
-        roofline["timed_region_bracket"] = dict(steps_in_flight=n_streams, avg_bracket_ms=round(bracket_in_flight, 4),
-                                                frac_if_read_as_duration=round(algo / (bracket_in_flight * 1e-3) / 1e12 / peak, 4),
-                                                note="rocprofv3 dispatch timestamps of this region: profiles/r06_kernel_trace_by_region.txt")
-    if args.precision != "fp32":
-        # what the chip sustains on random bf16 operands with nothing but MFMAs in flight (tools/probes/mfma_shape_probe.hip,
-        # profiles/r02_mfma_shape_power_probe.txt: 1.8-2.1 PFLOP/s at 1.8-2.1 GHz, power-limited); `peak` stays the nominal figure
-        # -- and the chip's clock gives way under that load: the figure is a band, quoted from the committed probe record
-        # (profiles/mfma_rate_probe.json: random operands 1,710, all-ones 2,470 TFLOP/s at 32.0 cycles per MFMA in both cases)
-        rec = mfma_peak_record()
-        if rec is not None:
-            roofline["measured_mfma_peak"] = rec["random_operands_tflops"]
-            roofline["measured_mfma_peak_all_ones"] = rec["all_ones_operands_tflops"]
-            roofline["measured_mfma_peak_source"] = rec["source"]
-            roofline["issued_frac_of_measured_peak"] = round(achieved * {"bf16x3": 3, "mix_f16x2": 2, "mix_f16x1": 1, "mix_mx": 2, "mix_mx4": 1.5}.get(args.precision, 1)
-                                                             / rec["random_operands_tflops"], 4) \
-                if dom_name.endswith("ffn1") or args.precision == "bf16x3" else None
-    # Algorithmic HBM bytes of one launch of the dominant kernel, from the launch's own shapes (valid rows of this rank): every operand read
-    # once, every result written once.  bf16 modes: an activation travels as planes of 4 bytes per element (hi + lo bf16, or the mx image
-    # of the same size), a weight image has 4 bytes per weight; the attention kernel reads the Q | K | V^T planes and writes the context planes.
-    eb = 4
-    shapes = {"dec.ffn1": (c["ddim"], c["dunits"], c["ffn_kernel"]), "enc.ffn1": (c["adim"], c["eunits"], c["ffn_kernel"]),
-              "dec.ffn2_ln": (c["dunits"], c["ddim"], 1), "dec.qkv": (c["ddim"], 3 * c["ddim"], 1), "dec.out_ln": (c["ddim"], c["ddim"], 1)}
-    algo_bytes = None
-    if dom_name in shapes:
-        Cc, Nn, kk = shapes[dom_name]
-        # (mix_mx4, decoder FFN conv: 9 of the 12 units of a plane row are read -- fp16 + the fp4 cross units -- and the weight image has those 9 only: 3 bytes per element;
-        #  the LayerNorm-fused launches write planes only since round 6: 4 bytes per element, not 8)
-        ab = 3 if (args.precision == "mix_mx4" and dom_name == "dec.ffn1") else eb
-        algo_bytes = dict(a_planes_read=rows * Cc * ab, weight_image_read=Nn * kk * Cc * ab, result_written=rows * Nn * eb)
-    elif dom_name in per_launch:
-        Dd = c["ddim"] if dom_name.startswith("dec") else c["adim"]
-        algo_bytes = dict(qkv_planes_read=rows * 3 * Dd * eb, context_planes_written=rows * Dd * eb)
-    if algo_bytes is not None:
-        roofline["algorithmic_bytes"] = int(sum(algo_bytes.values()))
-        roofline["algorithmic_bytes_parts"] = {k: int(v) for k, v in algo_bytes.items()}
-    # the whole step against the same peak: algorithmic FLOP of the step (valid tokens / frames of the global batch)
-    # / wall time per step / (peak x GPUs) -- `frac` above is the best kernel's, this is the path's
-    step_flop = sum(path_flops(int(t), int(l)) for t, l in zip(il, olens_all.cpu()))
-    roofline["step_frac"] = round(step_flop / (dt / args.steps) / 1e12 / (peak * world), 4)
-    try:    # HBM-side bytes per launch + the matrix-pipe occupancy of the same kernel: rocprofv3 PMC passes of this same command (tools/profile_round.sh
-        # -> tools/pmc_summary.py -> profiles/).  The record names the kernel sources it was measured on: after any change to them it is stale and
-        # the fields stay null instead of quoting an old kernel
-        tr = json.load(open(os.path.join(ROOT, "profiles", "r06_traffic.json")))
-        if (tr["workload"] == workload and tr["precision"] == args.precision and tr["kernel_site"] == dom_name and world == 1
-                and tr.get("csrc_sha16") == csrc_sha16()):
-            roofline["traffic"] = tr["traffic_bytes"]
-            roofline["traffic_note"] = ("rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) per launch, profiles/r06_traffic.json (separate --pmc passes of this "
-                                        "command on these kernel sources)")
-            if roofline.get("algorithmic_bytes"):
-                roofline["traffic_over_algorithmic"] = round(tr["traffic_bytes"] / roofline["algorithmic_bytes"], 2)
-            if tr.get("mfma_busy") is not None:
-                roofline["mfma_busy"] = tr["mfma_busy"]          # SQ_VALU_MFMA_BUSY_CYCLES / (4 * SQ_BUSY_CU_CYCLES) of the dominant kernel
-    except (OSError, KeyError, ValueError):
-        pass
-    if args.precision in MFMA_PER_PRODUCT and dom_name.endswith("ffn1"):   # split operands: several MFMAs are issued per algorithmic product
-        m = MFMA_PER_PRODUCT[args.precision]
-        roofline["issued_tflops"] = round(m * achieved, 1)
-        roofline["issued_frac"] = round(m * achieved / peak, 4)
-    # HBM-bound kernels of the path against the 8 TB/s roofline: algorithmic bytes of the valid rows / time
-    ad, dd, od = c["adim"], c["ddim"], c["odim"]
-    pl = 2 if args.precision != "fp32" else 1          # fp32 tensor + split-bf16 planes of the same size
-    hbm_bytes = {"lr.expand": local_frames * ad * 4 * pl + local_tokens * ad * 4 + local_frames * 4,
-                 "var.embed": local_frames * ad * 4 * (1 + pl) + local_frames * 16,
-                 "enc.embed": local_tokens * ad * 4 * (1 + pl),
-                 "unpack": local_frames * od * 4 + len(mine) * int(mel.shape[1]) * od * 4}
-    roofline_hbm = []
-    for name, nbytes in hbm_bytes.items():
-        if name in scout and scout[name] > 0:
-            ms = scout[name] / scout_n[name]
-            gbps = nbytes / (ms * 1e-3) / 1e9
-            roofline_hbm.append(dict(kernel=name, bytes=int(nbytes), avg_launch_ms=round(ms, 4), achieved=round(gbps, 1), peak=HBM_PEAK_GBPS,
-                                     unit="GB/s", frac=round(gbps / HBM_PEAK_GBPS, 4)))
-    # the weak end of the step: the three largest launch sites that run below 0.10 of the peak, from the fully
-    # bracketed (untimed) scouting step: FLOPs as the launches count them (rows in use incl. ~1.5 % gap rows), time by hipEvents
-    scout_fl = {}
-    for name, ms, fl, by in scout_prof:
-        scout_fl[name] = scout_fl.get(name, 0.0) + fl
-    weak = []
-    for name, ms in scout.items():
-        if scout_fl.get(name, 0.0) > 0 and ms > 0:
-            tf = scout_fl[name] / (ms * 1e-3) / 1e12
-            if tf / peak < 0.10:
-                weak.append(dict(site=name, launches_per_step=scout_n[name], ms_per_step=round(ms, 4), tflops=round(tf, 1), frac=round(tf / peak, 4),
-                                 share_of_step_kernel_time=round(ms / max(kernel_ms_per_step, 1e-9), 4)))
-    weak.sort(key=lambda w: -w["ms_per_step"])
-    below = sum(w["ms_per_step"] for w in weak)
-    roofline_worst = dict(threshold_frac=0.10, sites=weak[:3], sites_below_threshold=len(weak),
-                          share_of_step_kernel_time_below_threshold=round(below / max(kernel_ms_per_step, 1e-9), 4))
-    if args.profile_kernels and rank == 0:
-        tot = sum(v[1] for v in agg.values())
-        for name, (n, ms, fl) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
-            print("%-14s launches %4d  avg %8.3f ms  %5.1f %%  %7.1f TFLOP/s" % (name, n, ms / n, 100 * ms / tot, fl / max(ms, 1e-9) / 1e9),
-                  file=sys.stderr)
+    if args.full:
+        # ---- per-kernel table (hipEvents on the launch stream, accumulated over the timed steps) ----
+        agg = {}
+        for name, ms, fl, by in prof:
+            a = agg.setdefault(name, [0, 0.0, 0.0])
+            a[0] += 1
+            a[1] += ms
+            a[2] += fl
+        dom = max(agg.items(), key=lambda kv: kv[1][1])
+        dom_name, (dom_n, dom_ms, _) = dom
+        c = model._cfg
+        # algorithmic FLOPs per launch of the dominant kernel, valid frames/tokens of THIS rank only
+        per_row = {"dec.ffn1": 2.0 * c["ffn_kernel"] * c["ddim"] * c["dunits"], "enc.ffn1": 2.0 * c["ffn_kernel"] * c["adim"] * c["eunits"],
+                   "dec.ffn2_ln": 2.0 * c["dunits"] * c["ddim"], "dec.qkv": 6.0 * c["ddim"] ** 2, "dec.out_ln": 2.0 * c["ddim"] ** 2}
+        rows = local_tokens if dom_name.startswith("enc") or dom_name.startswith("dur") else local_frames
+        mine_t = torch.as_tensor(mine, dtype=torch.int64)
+        ol_mine = olens_all.cpu()[mine_t].double() if mine else torch.zeros(0, dtype=torch.float64)
+        il_mine = il[mine_t].double() if mine else torch.zeros(0, dtype=torch.float64)
+        per_launch = {"dec.attn": 4.0 * c["ddim"] * float((ol_mine * ol_mine).sum()),       # 4 D L^2 per utterance and layer
+                      "enc.attn": 4.0 * c["adim"] * float((il_mine * il_mine).sum())}
+        if dom_name in per_row:
+            algo = per_row[dom_name] * rows
+        elif dom_name in per_launch:
+            algo = per_launch[dom_name]
+        else:   # fall back to the launch's own count (includes the ~1.5 % gap rows)
+            algo = sum(fl for n_, ms, fl, by in prof if n_ == dom_name) / dom_n
+        avg_ms = dom_ms / dom_n
+        bracket_in_flight = None
+        if alone is not None and alone["avg_launch_ms"] > 0:
+            # With several steps in flight a hipEvent bracket is not the kernel's duration: the second event waits for the kernel, the kernel waits in its
+            # hardware queue for CUs that other streams' kernels hold (c3, 3 streams: bracket 0.57 ms, rocprofv3 dispatch timestamps of the same region
+            # 0.46 ms, the kernel alone 0.42 ms: profiles/r06_kernel_trace_by_region.txt).  The roofline of the kernel is therefore taken where the
+            # bracket IS the duration: the same launch site in the one-stream region behind the timed one (it agrees with rocprofv3 to 1 %).
+            bracket_in_flight = avg_ms
+            avg_ms = alone["avg_launch_ms"]
+        achieved = algo / (avg_ms * 1e-3) / 1e12
+        peak = PEAK_TFLOPS[args.precision]
+        roofline = dict(bound="mfma", kernel=dom_name, achieved=round(achieved, 2), peak=peak, unit="TFLOP/s",
+                        frac=round(achieved / peak, 4), traffic=None, avg_launch_ms=round(avg_ms, 4),
+                        launches_per_step=dom_n // max(args.steps, 1),
+                        # this site's launches (events around it alone, inside the timed region) as a share of the step's wall time: cannot exceed 1
+                        share_of_step_time=round(dom_ms / (1e3 * dt), 3))
+        if bracket_in_flight is not None:
+            lps = dom_n // max(args.steps, 1)
+            roofline["share_of_step_time"] = round(lps * avg_ms / (1e3 * dt / args.steps), 3)      # (kernel time / step interval: steps overlap)
+            roofline["measured_in"] = ("the one-stream region behind the timed one (%d steps, hipEvents around this site on the launch stream): with %d steps "
+                                       "in flight an event bracket also holds the launch's wait in its hardware queue" % (alone["steps"], n_streams))
+            roofline["timed_region_bracket"] = dict(steps_in_flight=n_streams, avg_bracket_ms=round(bracket_in_flight, 4),
+                                                    frac_if_read_as_duration=round(algo / (bracket_in_flight * 1e-3) / 1e12 / peak, 4),
+                                                    note="rocprofv3 dispatch timestamps of this region: profiles/r06_kernel_trace_by_region.txt")
+        if args.precision != "fp32":
+            # what the chip sustains on random bf16 operands with nothing but MFMAs in flight (tools/probes/mfma_shape_probe.hip,
+            # profiles/r02_mfma_shape_power_probe.txt: 1.8-2.1 PFLOP/s at 1.8-2.1 GHz, power-limited); `peak` stays the nominal figure
+            # -- and the chip's clock gives way under that load: the figure is a band, quoted from the committed probe record
+            # (profiles/mfma_rate_probe.json: random operands 1,710, all-ones 2,470 TFLOP/s at 32.0 cycles per MFMA in both cases)
+            rec = mfma_peak_record()
+            if rec is not None:
+                roofline["measured_mfma_peak"] = rec["random_operands_tflops"]
+                roofline["measured_mfma_peak_all_ones"] = rec["all_ones_operands_tflops"]
+                roofline["measured_mfma_peak_source"] = rec["source"]
+                roofline["issued_frac_of_measured_peak"] = round(achieved * {"bf16x3": 3, "mix_f16x2": 2, "mix_f16x1": 1, "mix_mx": 2, "mix_mx4": 1.5}.get(args.precision, 1)
+                                                                 / rec["random_operands_tflops"], 4) \
+                    if dom_name.endswith("ffn1") or args.precision == "bf16x3" else None
+        # Algorithmic HBM bytes of one launch of the dominant kernel, from the launch's own shapes (valid rows of this rank): every operand read
+        # once, every result written once.  bf16 modes: an activation travels as planes of 4 bytes per element (hi + lo bf16, or the mx image
+        # of the same size), a weight image has 4 bytes per weight; the attention kernel reads the Q | K | V^T planes and writes the context planes.
+        eb = 4
+        shapes = {"dec.ffn1": (c["ddim"], c["dunits"], c["ffn_kernel"]), "enc.ffn1": (c["adim"], c["eunits"], c["ffn_kernel"]),
+                  "dec.ffn2_ln": (c["dunits"], c["ddim"], 1), "dec.qkv": (c["ddim"], 3 * c["ddim"], 1), "dec.out_ln": (c["ddim"], c["ddim"], 1)}
+        algo_bytes = None
+        if dom_name in shapes:
+            Cc, Nn, kk = shapes[dom_name]
+            # (mix_mx4, decoder FFN conv: 9 of the 12 units of a plane row are read -- fp16 + the fp4 cross units -- and the weight image has those 9 only: 3 bytes per element;
+            #  the LayerNorm-fused launches write planes only since round 6: 4 bytes per element, not 8)
+            ab = 3 if (args.precision == "mix_mx4" and dom_name == "dec.ffn1") else eb
+            algo_bytes = dict(a_planes_read=rows * Cc * ab, weight_image_read=Nn * kk * Cc * ab, result_written=rows * Nn * eb)
+        elif dom_name in per_launch:
+            Dd = c["ddim"] if dom_name.startswith("dec") else c["adim"]
+            algo_bytes = dict(qkv_planes_read=rows * 3 * Dd * eb, context_planes_written=rows * Dd * eb)
+        if algo_bytes is not None:
+            roofline["algorithmic_bytes"] = int(sum(algo_bytes.values()))
+            roofline["algorithmic_bytes_parts"] = {k: int(v) for k, v in algo_bytes.items()}
+        # the whole step against the same peak: algorithmic FLOP of the step (valid tokens / frames of the global batch)
+        # / wall time per step / (peak x GPUs) -- `frac` above is the best kernel's, this is the path's
+        step_flop = sum(path_flops(int(t), int(l)) for t, l in zip(il, olens_all.cpu()))
+        roofline["step_frac"] = round(step_flop / (dt / args.steps) / 1e12 / (peak * world), 4)
+        try:    # HBM-side bytes per launch + the matrix-pipe occupancy of the same kernel: rocprofv3 PMC passes of this same command (tools/profile_round.sh
+            # -> tools/pmc_summary.py -> profiles/).  The record names the kernel sources it was measured on: after any change to them it is stale and
+            # the fields stay null instead of quoting an old kernel
+            tr = json.load(open(os.path.join(ROOT, "profiles", "r06_traffic.json")))
+            if (tr["workload"] == workload and tr["precision"] == args.precision and tr["kernel_site"] == dom_name and world == 1
+                    and tr.get("csrc_sha16") == csrc_sha16()):
+                roofline["traffic"] = tr["traffic_bytes"]
+                roofline["traffic_note"] = ("rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) per launch, profiles/r06_traffic.json (separate --pmc passes of this "
+                                            "command on these kernel sources)")
+                if roofline.get("algorithmic_bytes"):
+                    roofline["traffic_over_algorithmic"] = round(tr["traffic_bytes"] / roofline["algorithmic_bytes"], 2)
+                if tr.get("mfma_busy") is not None:
+                    roofline["mfma_busy"] = tr["mfma_busy"]          # SQ_VALU_MFMA_BUSY_CYCLES / (4 * SQ_BUSY_CU_CYCLES) of the dominant kernel
+        except (OSError, KeyError, ValueError):
+            pass
+        if args.precision in MFMA_PER_PRODUCT and dom_name.endswith("ffn1"):   # split operands: several MFMAs are issued per algorithmic product
+            m = MFMA_PER_PRODUCT[args.precision]
+            roofline["issued_tflops"] = round(m * achieved, 1)
+            roofline["issued_frac"] = round(m * achieved / peak, 4)
+        # HBM-bound kernels of the path against the 8 TB/s roofline: algorithmic bytes of the valid rows / time
+        ad, dd, od = c["adim"], c["ddim"], c["odim"]
+        pl = 2 if args.precision != "fp32" else 1          # fp32 tensor + split-bf16 planes of the same size
+        hbm_bytes = {"lr.expand": local_frames * ad * 4 * pl + local_tokens * ad * 4 + local_frames * 4,
+                     "var.embed": local_frames * ad * 4 * (1 + pl) + local_frames * 16,
+                     "enc.embed": local_tokens * ad * 4 * (1 + pl),
+                     "unpack": local_frames * od * 4 + len(mine) * int(mel.shape[1]) * od * 4}
+        roofline_hbm = []
+        for name, nbytes in hbm_bytes.items():
+            if name in scout and scout[name] > 0:
+                ms = scout[name] / scout_n[name]
+                gbps = nbytes / (ms * 1e-3) / 1e9
+                roofline_hbm.append(dict(kernel=name, bytes=int(nbytes), avg_launch_ms=round(ms, 4), achieved=round(gbps, 1), peak=HBM_PEAK_GBPS,
+                                         unit="GB/s", frac=round(gbps / HBM_PEAK_GBPS, 4)))
+        # the weak end of the step: the three largest launch sites that run below 0.10 of the peak, from the fully
+        # bracketed (untimed) scouting step: FLOPs as the launches count them (rows in use incl. ~1.5 % gap rows), time by hipEvents
+        scout_fl = {}
+        for name, ms, fl, by in scout_prof:
+            scout_fl[name] = scout_fl.get(name, 0.0) + fl
+        weak = []
+        for name, ms in scout.items():
+            if scout_fl.get(name, 0.0) > 0 and ms > 0:
+                tf = scout_fl[name] / (ms * 1e-3) / 1e12
+                if tf / peak < 0.10:
+                    weak.append(dict(site=name, launches_per_step=scout_n[name], ms_per_step=round(ms, 4), tflops=round(tf, 1), frac=round(tf / peak, 4),
+                                     share_of_step_kernel_time=round(ms / max(kernel_ms_per_step, 1e-9), 4)))
+        weak.sort(key=lambda w: -w["ms_per_step"])
+        below = sum(w["ms_per_step"] for w in weak)
+        roofline_worst = dict(threshold_frac=0.10, sites=weak[:3], sites_below_threshold=len(weak),
+                              share_of_step_kernel_time_below_threshold=round(below / max(kernel_ms_per_step, 1e-9), 4))
+        if args.profile_kernels and rank == 0:
+            tot = sum(v[1] for v in agg.values())
+            for name, (n, ms, fl) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
+                print("%-14s launches %4d  avg %8.3f ms  %5.1f %%  %7.1f TFLOP/s" % (name, n, ms / n, 100 * ms / tot, fl / max(ms, 1e-9) / 1e9),
+                      file=sys.stderr)
 
     if rank == 0:
         ol_host = olens_all.cpu()
@@ -805,7 +880,7 @@ def main():
         line = {
             "metric": "mel-frames/sec", "value": round(total_frames * args.steps / dt, 1), "unit": "mel-frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
-            "ms_per_step_median": round(statistics.median(step_ms), 3),
+            "ms_per_step_median": round(statistics.median(step_ms), 3) if step_ms else None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE_NAME[args.precision],
             "data": "synthetic",
             "config": {"workload": "%s%s; default.yaml dims, free-running, random-init weights (seed 0), duration bias calibrated to 7.87 frames/phoneme"
@@ -818,10 +893,9 @@ def main():
                                        % (world, ", overlapped with the next step's forward (side stream)" if synth.overlap else ""))
                                       if use_dist else "single GPU",
                        "launch": launch, "overlap_encoder": bool(model.overlap_encoder), "streams": n_streams},
-            "roofline": roofline,
-            "roofline_worst": roofline_worst,
-            "roofline_hbm": roofline_hbm,
         }
+        if args.full:
+            line.update(roofline=roofline, roofline_worst=roofline_worst, roofline_hbm=roofline_hbm)
         if sustained is not None:
             line["sustained_ms_per_step"] = sustained["ms_per_step"]
             # (sustained.sclk_mhz: boxes of one pool differ -- one ran capped at 1,412 MHz with every kernel 40 % slower; the sysfs node is not always
@@ -843,13 +917,14 @@ def main():
             line["one_stream"] = dict(steps=alone["steps"], ms_per_step=alone["ms_per_step"], value=round(total_frames * 1e3 / alone["ms_per_step"], 1),
                                       note="the same steps issued on one stream (rounds 1-4's schedule%s), measured behind the timed region"
                                            % (" + overlap_encoder" if model.overlap_encoder else ""))
-        elif not model.overlap_encoder:      # --streams 1 --no-overlap-encoder (or --graph / --profile-kernels): the timed schedule IS one forward after another
+        elif step_streams is None and not model.overlap_encoder:      # --streams 1 --no-overlap-encoder (or --graph / --profile-kernels): the timed schedule IS one forward after another
             line["value_one_forward"], line["ms_per_forward"] = line["value"], line["ms_per_step"]
         if use_dist:
             line["config"]["gather"] = "padded" if (args.padded or args.profile_kernels) else "packed"
             line["config"]["collective_world_size"] = dist.get_world_size()
-            line["multi_gpu"] = multi_gpu
-        if world == 1 and not use_dist and not args.no_cpu_baseline:      # the only leg of this script that touches oracle/ (as the measured CPU baseline and the checker)
+            if args.full:
+                line["multi_gpu"] = multi_gpu
+        if args.full and world == 1 and not use_dist and not args.no_cpu_baseline:      # the only leg of this script that touches oracle/ (as the measured CPU baseline and the checker)
             from oracle import fs2_oracle as O
             cfg = O.config_from_hp(hp, N_PHONEME_SYMBOLS, odim)
             with torch.no_grad():

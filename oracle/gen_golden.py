@@ -337,6 +337,31 @@ def weighted_masking_fixture():
                         loss=np.float64(loss.item()), report_names=np.array(rep_names), report_values=rep_vals)
 
 
+MKL_PATHS = ("AVX512", "AVX2", "COMPATIBLE")        # MKL_CBWR branches: Intel AVX-512 hosts, AVX2-only hosts, the path MKL takes on AMD CPUs
+
+
+def positional_mkl_paths_fixture():
+    """G4b: the reference's positional tables (rows 0, 1, 4999 at d = 256 and 384) on each of MKL's x86 code paths.  torch.exp / sin / cos
+    of float32 CPU tensors run MKL's vector math, whose last bits depend on the path MKL dispatches to (G4 holds the AVX-512 path's);
+    at t = 4999 one ulp of a frequency moves the table by ~1e-4, so the table is only reproducible per path.  Each path in a fresh
+    interpreter (MKL reads MKL_CBWR once)."""
+    import subprocess
+    import tempfile
+    rows = [0, 1, 4999]
+    prog = ("import sys, numpy as np; sys.path.insert(0, sys.argv[1]); from core.embedding import PositionalEncoding; "
+            "np.save(sys.argv[3], PositionalEncoding(int(sys.argv[2]), 0.0).pe[0, %r].numpy())" % rows)
+    arrays = {}
+    with tempfile.TemporaryDirectory() as td:
+        for path in MKL_PATHS:
+            for d in (256, 384):
+                f = os.path.join(td, "pe%d_%s.npy" % (d, path.lower()))
+                subprocess.run([sys.executable, "-c", prog, REF, str(d), f], env=dict(os.environ, MKL_CBWR=path), check=True)
+                arrays[os.path.basename(f)[:-4]] = np.load(f)
+    for k, v in sorted(arrays.items()):
+        print("G4b %-16s vs the avx512 path: max-abs %.3e" % (k, float(np.abs(v - arrays[k.split("_")[0] + "_avx512"]).max())))
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g4b_positional_mkl_paths.npz"), pe_rows=np.array(rows), **arrays)
+
+
 def math_log(v):
     import math
     return math.log(v)
@@ -349,8 +374,11 @@ if __name__ == "__main__":
         reduction_factor_fixture()
     elif len(sys.argv) > 1 and sys.argv[1] == "g9":
         weighted_masking_fixture()
+    elif len(sys.argv) > 1 and sys.argv[1] == "g4b":
+        positional_mkl_paths_fixture()
     else:
         main()
         block_variants()
         reduction_factor_fixture()
         weighted_masking_fixture()
+        positional_mkl_paths_fixture()

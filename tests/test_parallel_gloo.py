@@ -266,3 +266,63 @@ def test_bench_relaunch_command_shape():
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "8"
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and 1024 < int(cmd[cmd.index("--master-port") + 1]) < 65536
     assert cmd[-4:] == ["--gpus", "8", "--steps", "3"] and cmd[-5].endswith("bench.py")
+
+
+def _fake_bench(args, out_dir):
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env["FS2_BENCH_FAKE"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dump-outputs", str(out_dir)] + args,
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path's caller received from its last step: `olens` and the packed gather's valid
+    frames in utterance order (`mel_packed`; the capacity rows behind them are cut) or, with --padded, the padded mels cut at the longest
+    utterance; float32 / float64 only.  The inputs depend on the arguments alone, so runs with other step counts dump the same arrays, and the
+    two gather forms hold the same frames.  The line carries `ms_per_step` and `steps` as given."""
+    import numpy as np
+    rec = _fake_bench(["--steps", "3", "--warmup", "1"], tmp_path / "a")
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    _fake_bench(["--steps", "1", "--warmup", "2"], tmp_path / "b")
+    _fake_bench(["--steps", "2", "--warmup", "1", "--padded"], tmp_path / "p")
+    assert sorted(os.listdir(tmp_path / "a")) == ["mel_packed.npy", "olens.npy"]
+    assert sorted(os.listdir(tmp_path / "p")) == ["mel.npy", "olens.npy"]
+    ol, packed = np.load(tmp_path / "a" / "olens.npy"), np.load(tmp_path / "a" / "mel_packed.npy")
+    assert ol.dtype == np.float64 and packed.dtype == np.float32
+    assert packed.shape == (int(ol.sum()), ODIM) and np.isfinite(packed).all()
+    for name in ("olens.npy", "mel_packed.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
+    padded = np.load(tmp_path / "p" / "mel.npy")
+    assert np.array_equal(np.load(tmp_path / "p" / "olens.npy"), ol) and padded.shape == (len(ol), int(ol.max()), ODIM)
+    assert np.array_equal(np.concatenate([padded[b, : int(n)] for b, n in enumerate(ol)]), packed)
+    xs, il = _make_inputs(B=4 * 2 + 3)                  # (fake_main's batch at world size 2)
+    mel, ol_ref = _fake_run_local(xs, il)
+    assert np.array_equal(ol, ol_ref.double().numpy()) and np.array_equal(padded, mel.numpy())
+
+
+def test_bench_dump_outputs_keep_to_the_budget(tmp_path):
+    """An output beyond the 64 MB budget is cut to a fixed sample of its rows (the same rows on every call), whose row numbers are written
+    beside it; what fits is written whole; integer arrays become float64."""
+    import numpy as np
+    import bench
+    big = torch.arange(300 * 1000 * 80, dtype=torch.float32).view(300, 1000, 80)          # 96 MB
+    small = torch.arange(300, dtype=torch.int64)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"mel": big, "olens": small})
+    files = sorted(os.listdir(tmp_path / "x"))
+    assert files == ["mel.npy", "mel_rows.npy", "olens.npy"]
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in files) <= bench.DUMP_BUDGET_BYTES
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "x" / f), np.load(tmp_path / "y" / f)), f
+    rows, mel = np.load(tmp_path / "x" / "mel_rows.npy"), np.load(tmp_path / "x" / "mel.npy")
+    assert rows.dtype == np.float64 and mel.dtype == np.float32 and mel.shape == (len(rows), 80) and len(rows) > 100000
+    assert np.array_equal(mel, big.view(-1, 80).numpy()[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "x" / "olens.npy"), small.double().numpy())

@@ -34,22 +34,22 @@ tests)
   tail -n 3 $D/${TAG}_pytest_gpu_summary.txt; tail -n 2 $D/smoke.txt
   ;;
 bench)
-  python bench.py > $D/bench_${TAG}_c3_mix_mx4.json 2> $D/bench_c3.err
+  python bench.py --full > $D/bench_${TAG}_c3_mix_mx4.json 2> $D/bench_c3.err
   for spec in "c3 mix_mx" "c3 bf16x3" "c3 fp32" "c2 mix_mx4" "c2 fp32" "c1 mix_mx4" "c4 mix_mx4" "c4 mix_mx" "c4 bf16x3" "c5 mix_mx4" "c5 mix_mx"; do set -- $spec
-    python bench.py --workload $1 --precision $2 --no-cpu-baseline > $D/bench_${TAG}_$1_$2.json 2>/dev/null
+    python bench.py --full --workload $1 --precision $2 --no-cpu-baseline > $D/bench_${TAG}_$1_$2.json 2>/dev/null
   done
   for wl in c3 c2 c4 c5; do      # the schedule's A/B: one stream + overlap_encoder; and c3 with every launch of a step on one stream (rounds 1-4's schedule as the TIMED region)
-    python bench.py --workload $wl --no-cpu-baseline --streams 1 > $D/bench_${TAG}_${wl}_mix_mx4_one_stream.json 2>/dev/null
+    python bench.py --full --workload $wl --no-cpu-baseline --streams 1 > $D/bench_${TAG}_${wl}_mix_mx4_one_stream.json 2>/dev/null
   done
-  python bench.py --no-cpu-baseline --streams 1 --no-overlap-encoder > $D/bench_${TAG}_c3_mix_mx4_one_stream_no_overlap.json 2>/dev/null
-  python bench.py --workload c1 --no-cpu-baseline --graph > $D/bench_${TAG}_c1_mix_mx4_graph.json 2>/dev/null
-  FS2_FORCE_DIST=1 python bench.py --workload c5 --no-cpu-baseline > $D/bench_${TAG}_c5_rccl_single_rank.json 2>/dev/null
-  python bench.py --workload c5 --no-cpu-baseline --regime-utterances 1024 > $D/bench_${TAG}_c5_mix_mx4_regime_of_1024.json 2>/dev/null      # the shard with the whole batch's kernel variants (what every rank runs)
-  FS2_ROW4=0 FS2_FFN2_MX=0 python bench.py --precision mix_mx --no-cpu-baseline > $D/bench_${TAG}_c3_mix_mx_row8_fp32_residual.json 2>/dev/null   # rounds 1-4's row kernels, fp32 residual rows
+  python bench.py --full --no-cpu-baseline --streams 1 --no-overlap-encoder > $D/bench_${TAG}_c3_mix_mx4_one_stream_no_overlap.json 2>/dev/null
+  python bench.py --full --workload c1 --no-cpu-baseline --graph > $D/bench_${TAG}_c1_mix_mx4_graph.json 2>/dev/null
+  FS2_FORCE_DIST=1 python bench.py --full --workload c5 --no-cpu-baseline > $D/bench_${TAG}_c5_rccl_single_rank.json 2>/dev/null
+  python bench.py --full --workload c5 --no-cpu-baseline --regime-utterances 1024 > $D/bench_${TAG}_c5_mix_mx4_regime_of_1024.json 2>/dev/null      # the shard with the whole batch's kernel variants (what every rank runs)
+  FS2_ROW4=0 FS2_FFN2_MX=0 python bench.py --full --precision mix_mx --no-cpu-baseline > $D/bench_${TAG}_c3_mix_mx_row8_fp32_residual.json 2>/dev/null   # rounds 1-4's row kernels, fp32 residual rows
   for wl in c3 c4 c2 c1; do
-    python bench.py --no-cpu-baseline --sustain 0 --workload $wl --profile-kernels > /dev/null 2> $D/${TAG}_${wl}_launch_sites_hipevents.txt
+    python bench.py --full --no-cpu-baseline --sustain 0 --workload $wl --profile-kernels > /dev/null 2> $D/${TAG}_${wl}_launch_sites_hipevents.txt
   done
-  python bench.py --no-cpu-baseline --sustain 0 --precision mix_mx --profile-kernels > /dev/null 2> $D/${TAG}_c3_launch_sites_hipevents_mix_mx.txt
+  python bench.py --full --no-cpu-baseline --sustain 0 --precision mix_mx --profile-kernels > /dev/null 2> $D/${TAG}_c3_launch_sites_hipevents_mix_mx.txt
   python tools/latency_c1.py > $D/${TAG}_latency_c1.txt 2>&1; python tools/launch_floor.py 85 >> $D/${TAG}_latency_c1.txt 2>&1
   for f in $D/bench_${TAG}_*.json; do echo "$f $(python -c "import json,sys;d=json.load(open('$f'));print(d['value'], d['ms_per_step'], d.get('value_one_forward'), d.get('ms_per_forward'), d['roofline']['kernel'], d['roofline']['avg_launch_ms'], d['roofline']['frac'])")"; done
   ;;

@@ -11,9 +11,10 @@ PMC=${4:-1}
 ARGS=${5:---steps 4 --warmup 2}
 OUT=/root/repo/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 cd /tmp
-CMD="python /root/repo/bench.py --workload $WL --precision $PREC $ARGS --no-cpu-baseline --sustain 0"
+CMD="python $REPO/bench.py --full --workload $WL --precision $PREC $ARGS --no-cpu-baseline --sustain 0"      # (--full: the scouting step and the one-stream region behind the timed one)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- $CMD > "$OUT/trace.log" 2>&1
 if [ "$PMC" = "1" ]; then
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o p -- $CMD > "$OUT/fetch.log" 2>&1
