@@ -29,6 +29,7 @@
 #include "gemm_row4.h"
 #include "gemm_mx.h"
 #include "gemm_f32.h"
+#include "griffin_lim.h"
 
 using namespace fs2;
 
@@ -1695,6 +1696,71 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
     return FS2_OK;
 }
 
+
+// ---------------------------------------------------------------------------------- vocoder (griffin_lim.h)
+// Workspace of fs2_op_griffin_lim / fs2_op_stft: tables, tile records, then (synthesis only) M, the two spectrum buffers and the
+// momentum state, all over the utterances' frames packed back to back.  frames[b] = L_b; tiles cover utterances with L_b >= 2
+// (synthesis: they own samples) or every utterance with frames (analysis).
+struct GlPlan {
+    std::vector<GlTile> tiles;
+    int64_t frames = 0, samples = 0;
+    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
+};
+
+// analysis = false: lens are frame counts L_b, samples 256 max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
+// frames T_b / 256 + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
+int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, GlPlan& p) {
+    if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
+    int64_t row = 0, wav = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "vocoder: negative length / start of utterance %d", b);
+        const int L = analysis ? lens[b] / kGlHop + 1 : lens[b];
+        const int T = analysis ? lens[b] : kGlHop * std::max(L - 1, 0);
+        const bool owns = analysis ? L > 0 : L >= 2;
+        if (owns)
+            for (int f0 = 0; f0 < L; f0 += kGlTile) {
+                GlTile t{};
+                t.src_row0 = analysis ? (int)row : (starts ? starts[b] : 0);
+                t.ws_row0 = (int)row;
+                t.L = L; t.f0 = f0; t.T = T;
+                t.wav0 = analysis ? (starts ? starts[b] : 0) : (int)wav;
+                p.tiles.push_back(t);
+            }
+        row += L;
+        wav += T;
+        if (row > INT32_MAX / kGlBins || wav > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: batch too large (%lld frames, %lld samples)", (long long)row, (long long)wav);
+    }
+    p.frames = row;
+    p.samples = wav;
+    size_t off = 0;
+    auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
+    p.off_tw = take(kGlNfft * sizeof(float2));
+    p.off_win = take(kGlNfft * sizeof(float));
+    p.off_tiles = take(std::max<size_t>(p.tiles.size(), 1) * sizeof(GlTile));
+    if (!analysis) {
+        const size_t n = (size_t)p.frames * kGlBins;
+        p.off_M = take(n * sizeof(float));
+        p.off_C0 = take(n * sizeof(float2));
+        p.off_C1 = take(n * sizeof(float2));
+        p.off_T = take(n * sizeof(float2));
+    }
+    p.bytes = align_up(off, 256);
+    return FS2_OK;
+}
+
+// tables + tile records into the workspace (kernel arguments, no host copy)
+hipError_t gl_setup(hipStream_t s, const GlPlan& p, char* ws) {
+    hipLaunchKernelGGL(gl_tables, dim3(kGlNfft / 256), dim3(256), 0, s, (float2*)(ws + p.off_tw), (float*)(ws + p.off_win));
+    for (size_t i = 0; i < p.tiles.size(); i += kGlTilesPerChunk) {
+        GlTileChunk c{};
+        c.n = (int)std::min<size_t>(kGlTilesPerChunk, p.tiles.size() - i);
+        c.base = (int)i;
+        std::copy(p.tiles.begin() + i, p.tiles.begin() + i + c.n, c.t);
+        hipLaunchKernelGGL(gl_upload_tiles, dim3(1), dim3(128), 0, s, c, (GlTile*)(ws + p.off_tiles));
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -2425,6 +2491,72 @@ int fs2_op_bucketize(void* stream, const float* x, int64_t n, const float* bins,
     hipLaunchKernelGGL(bucketize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n, bins, nb, idx);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "bucketize: %s", hipGetErrorString(e));
+    return FS2_OK;
+}
+
+size_t fs2_op_vocode_workspace_bytes(int32_t B, const int32_t* lens) {
+    GlPlan p;
+    return gl_plan(B, nullptr, lens, false, p) == FS2_OK ? p.bytes : 0;
+}
+
+int fs2_op_griffin_lim(void* stream, const float* src, int32_t src_width, const float* mel_pinv, int32_t B, const int32_t* starts,
+                       const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase, void* workspace,
+                       size_t workspace_bytes, float* wav) {
+    if (src_width != 80 && src_width != kGlBins)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED, "fs2_op_griffin_lim: src_width %d (80 mel bins or 513 linear bins of the 1024-point STFT)", src_width);
+    if (src_width == 80 && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: mel input needs mel_pinv [513, 80]");
+    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: n_iter %d, momentum %g", n_iter, momentum);
+    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: null starts / lens");
+    GlPlan p;
+    if (int rc = gl_plan(B, starts, lens, false, p)) return rc;
+    if (p.tiles.empty()) return FS2_OK;
+    if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: null pointer");
+    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "fs2_op_griffin_lim: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipError_t e = gl_setup(s, p, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
+    const GlTile* tiles = (const GlTile*)(ws + p.off_tiles);
+    const float2* tw = (const float2*)(ws + p.off_tw);
+    const float* win = (const float*)(ws + p.off_win);
+    float* M = (float*)(ws + p.off_M);
+    float2* C[2] = {(float2*)(ws + p.off_C0), (float2*)(ws + p.off_C1)};
+    float2* Tm = momentum > 0.f ? (float2*)(ws + p.off_T) : nullptr;
+    const float beta = momentum / (1.f + momentum);
+    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
+    hipLaunchKernelGGL(gl_prologue, grid, blk, 0, s, tiles, src, src_width, mel_pinv, init_phase, seed, M, C[0], Tm);
+    for (int it = 0; it < n_iter; ++it) {
+        if (Tm) hipLaunchKernelGGL((gl_iterate<0, true>), grid, blk, 0, s, tiles, tw, win, M, C[it & 1], C[(it + 1) & 1], Tm, beta, wav);
+        else hipLaunchKernelGGL((gl_iterate<0, false>), grid, blk, 0, s, tiles, tw, win, M, C[it & 1], C[(it + 1) & 1], Tm, beta, wav);
+    }
+    hipLaunchKernelGGL((gl_iterate<1, false>), grid, blk, 0, s, tiles, tw, win, M, C[n_iter & 1], C[(n_iter + 1) & 1], nullptr, 0.f, wav);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
+    return FS2_OK;
+}
+
+size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) {
+    GlPlan p;
+    return gl_plan(B, nullptr, wav_lens, true, p) == FS2_OK ? p.bytes : 0;
+}
+
+int fs2_op_stft(void* stream, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens, void* workspace,
+                size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel) {
+    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: null starts / lens");
+    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: logmel needs mel_basis [80, 513]");
+    GlPlan p;
+    if (int rc = gl_plan(B, wav_starts, wav_lens, true, p)) return rc;
+    if (p.tiles.empty() || (!mag && !logmel)) return FS2_OK;
+    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: null pointer");
+    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "fs2_op_stft: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipError_t e = gl_setup(s, p, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(gl_stft, dim3((unsigned)p.tiles.size()), dim3(kGlThreads), 0, s, (const GlTile*)(ws + p.off_tiles),
+                       (const float2*)(ws + p.off_tw), (const float*)(ws + p.off_win), wav, mag, mel_basis, logmel);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
     return FS2_OK;
 }
 

@@ -277,6 +277,36 @@ int fs2_op_bucketize(void *stream, const float *x, int64_t n, const float *bins,
  * .long() of +inf is implementation defined). */
 int fs2_op_duration(void *stream, const float *d_log, int64_t n, int64_t *d);
 
+/* ---- Griffin-Lim vocoder and analysis STFT (fastspeech2_amd/csrc/griffin_lim.h; reference utils/stft.py:41-151,
+ * dataset/audio_processing.py:224-240).  Fixed transform: n_fft = win_length = 1024, hop 256, 513 bins, periodic Hann window.
+ * starts / lens are HOST int32 arrays; every launch goes to `stream`; nothing synchronises with the host.  An utterance of L frames
+ * gives 256 * (L - 1) samples (none for L <= 1); utterance b's samples start at 256 * sum_{j<b} max(L_j - 1, 0) of `wav`.  L < 4 is
+ * too short for the reflect padding of the reference's STFT: those utterances give zeros.  Every utterance's waveform is
+ * bit-identical whether it is vocoded alone or inside any batch (the seeded phase is keyed by utterance-local frame indices). ---- */
+
+/* workspace bytes of fs2_op_griffin_lim for B utterances of lens[b] frames (0 on a bad argument) */
+size_t fs2_op_vocode_workspace_bytes(int32_t B, const int32_t *lens);
+
+/* src [rows, src_width]: utterance b = rows [starts[b], starts[b] + lens[b]).  src_width 80: log-mel frames (log(clamp(mel_basis .
+ * |S|, 1e-5)), the model's output), magnitudes M = max(mel_pinv . exp(mel), 0) with mel_pinv = pinv(mel basis) [513, 80];
+ * src_width 513: linear magnitudes M (mel_pinv ignored); any other width FS2_ERR_UNSUPPORTED.  Initial phase: init_phase [rows, 513]
+ * angles in src's row layout, or (NULL) uniform on [-pi, pi) from a counter-based hash of (seed, utterance-local frame, bin).
+ * n_iter >= 0 iterations of C = M . A / |A|, A = X - momentum / (1 + momentum) . X_prev (momentum 0: the reference's griffin_lim;
+ * > 0: fast Griffin-Lim).  wav: float32 [256 * sum max(L_b - 1, 0)]. */
+int fs2_op_griffin_lim(void *stream, const float *src, int32_t src_width, const float *mel_pinv, int32_t B, const int32_t *starts,
+                       const int32_t *lens, int32_t n_iter, float momentum, uint32_t seed, const float *init_phase, void *workspace,
+                       size_t workspace_bytes, float *wav);
+
+/* workspace bytes of fs2_op_stft for B waveforms of wav_lens[b] samples */
+size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t *wav_lens);
+
+/* Analysis STFT (STFT.transform / TacotronSTFT.mel_spectrogram, stft.py:80-110,188-204): waveform b = wav[wav_starts[b] ..
+ * + wav_lens[b]) gives wav_lens[b] / 256 + 1 frames, packed back to back in batch order: mag [frames, 513] = |X| (or NULL),
+ * logmel [frames, 80] = log(clamp(mel_basis . |X|, 1e-5)) with mel_basis [80, 513] (or NULL).  A waveform of <= 512 samples
+ * cannot be reflect-padded: its frames give |X| = 0, log-mel log(1e-5). */
+int fs2_op_stft(void *stream, const float *wav, int32_t B, const int32_t *wav_starts, const int32_t *wav_lens, void *workspace,
+                size_t workspace_bytes, float *mag, const float *mel_basis, float *logmel);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
