@@ -1698,6 +1698,35 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 
 
 // ---------------------------------------------------------------------------------- vocoder (griffin_lim.h)
+// Geometry of a call: validated (n_fft, hop, win, n_mels) plus the tile rule (F, halo, tail frame, L_min, signal buffer) derived from it.
+struct GlGeomHost {
+    int n_fft = kGlNfft, hop = kGlHop, win = kGlNfft, n_mels = 80, n_bins = kGlBins;
+    GlGeom g{};
+    size_t sig_bytes = 0;                // dynamic LDS of the fused kernel (0: the default instantiation, static LDS)
+    bool is_default() const { return n_fft == kGlNfft && hop == kGlHop; }
+};
+
+int gl_geom(int n_fft, int hop, int win, int n_mels, const char* who, GlGeomHost& out) {
+    GlGeomHost h;
+    h.n_fft = n_fft; h.hop = hop; h.win = win; h.n_mels = n_mels;
+    if (h.n_fft != 512 && h.n_fft != 1024 && h.n_fft != 2048)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: n_fft %d (512, 1024 or 2048)", who, h.n_fft);
+    if (h.hop < 1 || h.hop > h.win || h.win > h.n_fft || (h.n_fft + h.hop - 1) / h.hop > 8)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: hop %d, win %d at n_fft %d (hop <= win <= n_fft, ceil(n_fft / hop) <= 8)", who, h.hop, h.win, h.n_fft);
+    if (h.n_mels < 1 || h.n_mels > kGlMaxMels) return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: n_mels %d (1 .. %d)", who, h.n_mels, kGlMaxMels);
+    h.n_bins = h.n_fft / 2 + 1;
+    h.g.hop = h.hop;
+    h.g.F = h.is_default() ? kGlTile : gl_tile_frames(h.n_fft, h.hop);
+    h.g.halo = gl_halo(h.n_fft, h.hop);
+    h.g.tail = gl_tail(h.n_fft, h.hop);
+    h.g.lmin = gl_lmin(h.n_fft, h.hop);
+    h.g.sig_max = gl_sig_max(h.n_fft, h.hop, h.g.F);
+    h.g.n_mels = h.n_mels;
+    h.sig_bytes = h.is_default() ? 0 : (size_t)h.g.sig_max * sizeof(float);
+    out = h;
+    return FS2_OK;
+}
+
 // Workspace of fs2_op_griffin_lim / fs2_op_stft: tables, tile records, then (synthesis only) M, the two spectrum buffers and the
 // momentum state, all over the utterances' frames packed back to back.  frames[b] = L_b; tiles cover utterances with L_b >= 2
 // (synthesis: they own samples) or every utterance with frames (analysis).
@@ -1707,38 +1736,40 @@ struct GlPlan {
     size_t off_tw = 0, off_win = 0, off_tiles = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
 };
 
-// analysis = false: lens are frame counts L_b, samples 256 max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
-// frames T_b / 256 + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
-int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, GlPlan& p) {
+// analysis = false: lens are frame counts L_b, samples hop max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
+// frames T_b / hop + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
+int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p) {
     if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
+    const int hop = gh.hop, F = gh.g.F, nb = gh.n_bins;
     int64_t row = 0, wav = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "vocoder: negative length / start of utterance %d", b);
-        const int L = analysis ? lens[b] / kGlHop + 1 : lens[b];
-        const int T = analysis ? lens[b] : kGlHop * std::max(L - 1, 0);
+        const int L = analysis ? lens[b] / hop + 1 : lens[b];
+        const int64_t T = analysis ? (int64_t)lens[b] : (int64_t)hop * std::max(L - 1, 0);
         const bool owns = analysis ? L > 0 : L >= 2;
+        if (T > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: utterance %d too long (%lld samples)", b, (long long)T);
         if (owns)
-            for (int f0 = 0; f0 < L; f0 += kGlTile) {
+            for (int f0 = 0; f0 < L; f0 += F) {
                 GlTile t{};
                 t.src_row0 = analysis ? (int)row : (starts ? starts[b] : 0);
                 t.ws_row0 = (int)row;
-                t.L = L; t.f0 = f0; t.T = T;
+                t.L = L; t.f0 = f0; t.T = (int)T;
                 t.wav0 = analysis ? (starts ? starts[b] : 0) : (int)wav;
                 p.tiles.push_back(t);
             }
         row += L;
         wav += T;
-        if (row > INT32_MAX / kGlBins || wav > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: batch too large (%lld frames, %lld samples)", (long long)row, (long long)wav);
+        if (row > INT32_MAX / nb || wav > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: batch too large (%lld frames, %lld samples)", (long long)row, (long long)wav);
     }
     p.frames = row;
     p.samples = wav;
     size_t off = 0;
     auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
-    p.off_tw = take(kGlNfft * sizeof(float2));
-    p.off_win = take(kGlNfft * sizeof(float));
+    p.off_tw = take(gh.n_fft * sizeof(float2));
+    p.off_win = take(gh.n_fft * sizeof(float));
     p.off_tiles = take(std::max<size_t>(p.tiles.size(), 1) * sizeof(GlTile));
     if (!analysis) {
-        const size_t n = (size_t)p.frames * kGlBins;
+        const size_t n = (size_t)p.frames * nb;
         p.off_M = take(n * sizeof(float));
         p.off_C0 = take(n * sizeof(float2));
         p.off_C1 = take(n * sizeof(float2));
@@ -1749,8 +1780,9 @@ int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, Gl
 }
 
 // tables + tile records into the workspace (kernel arguments, no host copy)
-hipError_t gl_setup(hipStream_t s, const GlPlan& p, char* ws) {
-    hipLaunchKernelGGL(gl_tables, dim3(kGlNfft / 256), dim3(256), 0, s, (float2*)(ws + p.off_tw), (float*)(ws + p.off_win));
+hipError_t gl_setup(hipStream_t s, const GlPlan& p, const GlGeomHost& gh, char* ws) {
+    hipLaunchKernelGGL(gl_tables, dim3((gh.n_fft + 255) / 256), dim3(256), 0, s, (float2*)(ws + p.off_tw), (float*)(ws + p.off_win),
+                       gh.n_fft, gh.win);
     for (size_t i = 0; i < p.tiles.size(); i += kGlTilesPerChunk) {
         GlTileChunk c{};
         c.n = (int)std::min<size_t>(kGlTilesPerChunk, p.tiles.size() - i);
@@ -1759,6 +1791,98 @@ hipError_t gl_setup(hipStream_t s, const GlPlan& p, char* ws) {
         hipLaunchKernelGGL(gl_upload_tiles, dim3(1), dim3(128), 0, s, c, (GlTile*)(ws + p.off_tiles));
     }
     return hipGetLastError();
+}
+
+struct GlIterArgs {
+    const GlTile* tiles; const float2* tw; const float* win; const float* M; float2* C[2]; float2* Tm; float beta; float* wav;
+};
+
+// prologue, n_iter fused iterations and the final ISTFT of one geometry (NFFT; HOP_C = 256: the default instantiation)
+template <int NFFT, int HOP_C>
+hipError_t gl_run(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const float* src, int src_width, const float* pinv,
+                  const float* init_phase, uint32_t seed, int n_iter, const GlIterArgs& a) {
+    const dim3 grid(n_tiles), blk(kGlThreads);
+    const GlGeom g = gh.g;
+    const size_t lds = gh.sig_bytes;
+    if (lds) {
+        hipError_t e;
+        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+    }
+    if (src_width == 80 && gh.n_mels == 80 && src_width != gh.n_bins)
+        hipLaunchKernelGGL((gl_prologue<NFFT, 80>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
+    else
+        hipLaunchKernelGGL((gl_prologue<NFFT, 0>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
+    for (int it = 0; it < n_iter; ++it) {
+        if (a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
+        else hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
+    }
+    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[n_iter & 1], a.C[(n_iter + 1) & 1], nullptr, 0.f, a.wav);
+    return hipGetLastError();
+}
+
+int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
+                   const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
+                   void* workspace, size_t workspace_bytes, float* wav) {
+    if (src_width != gh.n_mels && src_width != gh.n_bins)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
+                    gh.n_bins, gh.n_fft);
+    if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
+    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
+    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+    GlPlan p;
+    if (int rc = gl_plan(B, starts, lens, false, gh, p)) return rc;
+    if (p.tiles.empty()) return FS2_OK;
+    if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipError_t e = gl_setup(s, p, gh, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
+    GlIterArgs a{};
+    a.tiles = (const GlTile*)(ws + p.off_tiles);
+    a.tw = (const float2*)(ws + p.off_tw);
+    a.win = (const float*)(ws + p.off_win);
+    a.M = (const float*)(ws + p.off_M);
+    a.C[0] = (float2*)(ws + p.off_C0);
+    a.C[1] = (float2*)(ws + p.off_C1);
+    a.Tm = momentum > 0.f ? (float2*)(ws + p.off_T) : nullptr;
+    a.beta = momentum / (1.f + momentum);
+    a.wav = wav;
+    const unsigned nt = (unsigned)p.tiles.size();
+    if (gh.is_default()) e = gl_run<1024, kGlHop>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else if (gh.n_fft == 512) e = gl_run<512, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else if (gh.n_fft == 1024) e = gl_run<1024, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else e = gl_run<2048, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
+    return FS2_OK;
+}
+
+int gl_stft_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,
+                const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy) {
+    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
+    GlPlan p;
+    if (int rc = gl_plan(B, wav_starts, wav_lens, true, gh, p)) return rc;
+    if (p.tiles.empty() || (!mag && !logmel && !energy)) return FS2_OK;
+    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipError_t e = gl_setup(s, p, gh, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
+    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
+    const GlTile* tiles = (const GlTile*)(ws + p.off_tiles);
+    const float2* tw = (const float2*)(ws + p.off_tw);
+    const float* win = (const float*)(ws + p.off_win);
+    if (gh.is_default()) hipLaunchKernelGGL((gl_stft<1024, kGlHop>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
+    else if (gh.n_fft == 512) hipLaunchKernelGGL((gl_stft<512, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
+    else if (gh.n_fft == 1024) hipLaunchKernelGGL((gl_stft<1024, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
+    else hipLaunchKernelGGL((gl_stft<2048, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
+    return FS2_OK;
 }
 
 }  // namespace
@@ -2494,70 +2618,54 @@ int fs2_op_bucketize(void* stream, const float* x, int64_t n, const float* bins,
     return FS2_OK;
 }
 
-size_t fs2_op_vocode_workspace_bytes(int32_t B, const int32_t* lens) {
+size_t fs2_op_vocode_workspace_bytes(int32_t B, const int32_t* lens) { return fs2_op_vocode_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, lens); }
+
+size_t fs2_op_vocode_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
+    GlGeomHost gh;
     GlPlan p;
-    return gl_plan(B, nullptr, lens, false, p) == FS2_OK ? p.bytes : 0;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_geom", gh)) return 0;
+    return gl_plan(B, nullptr, lens, false, gh, p) == FS2_OK ? p.bytes : 0;
 }
 
 int fs2_op_griffin_lim(void* stream, const float* src, int32_t src_width, const float* mel_pinv, int32_t B, const int32_t* starts,
                        const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase, void* workspace,
                        size_t workspace_bytes, float* wav) {
-    if (src_width != 80 && src_width != kGlBins)
-        return fail(nullptr, FS2_ERR_UNSUPPORTED, "fs2_op_griffin_lim: src_width %d (80 mel bins or 513 linear bins of the 1024-point STFT)", src_width);
-    if (src_width == 80 && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: mel input needs mel_pinv [513, 80]");
-    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: n_iter %d, momentum %g", n_iter, momentum);
-    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: null starts / lens");
-    GlPlan p;
-    if (int rc = gl_plan(B, starts, lens, false, p)) return rc;
-    if (p.tiles.empty()) return FS2_OK;
-    if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "fs2_op_griffin_lim: null pointer");
-    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "fs2_op_griffin_lim: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
-    const GlTile* tiles = (const GlTile*)(ws + p.off_tiles);
-    const float2* tw = (const float2*)(ws + p.off_tw);
-    const float* win = (const float*)(ws + p.off_win);
-    float* M = (float*)(ws + p.off_M);
-    float2* C[2] = {(float2*)(ws + p.off_C0), (float2*)(ws + p.off_C1)};
-    float2* Tm = momentum > 0.f ? (float2*)(ws + p.off_T) : nullptr;
-    const float beta = momentum / (1.f + momentum);
-    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
-    hipLaunchKernelGGL(gl_prologue, grid, blk, 0, s, tiles, src, src_width, mel_pinv, init_phase, seed, M, C[0], Tm);
-    for (int it = 0; it < n_iter; ++it) {
-        if (Tm) hipLaunchKernelGGL((gl_iterate<0, true>), grid, blk, 0, s, tiles, tw, win, M, C[it & 1], C[(it + 1) & 1], Tm, beta, wav);
-        else hipLaunchKernelGGL((gl_iterate<0, false>), grid, blk, 0, s, tiles, tw, win, M, C[it & 1], C[(it + 1) & 1], Tm, beta, wav);
-    }
-    hipLaunchKernelGGL((gl_iterate<1, false>), grid, blk, 0, s, tiles, tw, win, M, C[n_iter & 1], C[(n_iter + 1) & 1], nullptr, 0.f, wav);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
-    return FS2_OK;
+    GlGeomHost gh;
+    if (int rc = gl_geom(kGlNfft, kGlHop, kGlNfft, 80, "fs2_op_griffin_lim", gh)) return rc;
+    return gl_griffin_lim("fs2_op_griffin_lim", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
+                          workspace, workspace_bytes, wav);
 }
 
-size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) {
+int fs2_op_griffin_lim_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
+                            const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
+                            void* workspace, size_t workspace_bytes, float* wav) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_geom", gh)) return rc;
+    return gl_griffin_lim("fs2_op_griffin_lim_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
+                          workspace, workspace_bytes, wav);
+}
+
+size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) { return fs2_op_stft_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, wav_lens); }
+
+size_t fs2_op_stft_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* wav_lens) {
+    GlGeomHost gh;
     GlPlan p;
-    return gl_plan(B, nullptr, wav_lens, true, p) == FS2_OK ? p.bytes : 0;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_workspace_bytes_geom", gh)) return 0;
+    return gl_plan(B, nullptr, wav_lens, true, gh, p) == FS2_OK ? p.bytes : 0;
 }
 
 int fs2_op_stft(void* stream, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens, void* workspace,
                 size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel) {
-    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: null starts / lens");
-    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: logmel needs mel_basis [80, 513]");
-    GlPlan p;
-    if (int rc = gl_plan(B, wav_starts, wav_lens, true, p)) return rc;
-    if (p.tiles.empty() || (!mag && !logmel)) return FS2_OK;
-    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft: null pointer");
-    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "fs2_op_stft: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(gl_stft, dim3((unsigned)p.tiles.size()), dim3(kGlThreads), 0, s, (const GlTile*)(ws + p.off_tiles),
-                       (const float2*)(ws + p.off_tw), (const float*)(ws + p.off_win), wav, mag, mel_basis, logmel);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
-    return FS2_OK;
+    GlGeomHost gh;
+    if (int rc = gl_geom(kGlNfft, kGlHop, kGlNfft, 80, "fs2_op_stft", gh)) return rc;
+    return gl_stft_run("fs2_op_stft", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, nullptr);
+}
+
+int fs2_op_stft_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens,
+                     void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_geom", gh)) return rc;
+    return gl_stft_run("fs2_op_stft_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy);
 }
 
 }  // extern "C"

@@ -8,7 +8,9 @@ TacotronSTFT's log(clamp(B . |S|, 1e-5)), stft.py:188-204).  The whole batch is 
 STFT (reflect padding at its own ends), nothing goes through the host, and an utterance's waveform is bit-identical whether it is
 vocoded alone or inside any batch.
 
-``stft_magnitude`` is the analysis direction (TacotronSTFT.mel_spectrogram): waveforms -> |STFT| or log-mel on the GPU.
+``stft_magnitude`` is the analysis direction (TacotronSTFT.mel_spectrogram): waveforms -> |STFT| or log-mel on the GPU;
+``mel_energy`` gives the log-mel and the per-frame energy (the reference preprocessing's targets) from one launch.  Other transform
+geometries (n_fft 512 / 1024 / 2048, any hop <= win_length <= n_fft with ceil(n_fft / hop) <= 8, 1 .. 128 mels) come from hp.audio.
 There is no CPU fallback: CPU tensors raise.
 """
 import ctypes as C
@@ -53,23 +55,92 @@ def mel_basis(sample_rate=22050, n_fft=1024, n_mels=80, fmin=0.0, fmax=8000.0):
     return weights * (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
 
 
-def _audio_params(hp):
-    """mel_basis arguments from hp.audio where the keys exist; the transform itself must be the kernels' 1024 / 256 / 1024."""
+class Geometry(NamedTuple):
+    """The STFT a GriffinLim / stft_magnitude works in (the reference's STFT(filter_length, hop_length, win_length) and TacotronSTFT's
+    n_mel_channels).  The window is a periodic Hann of ``win`` samples zero-padded to ``n_fft`` at the centre."""
+    n_fft: int = N_FFT
+    hop: int = HOP
+    win: int = WIN
+    n_mels: int = 80
+
+    @property
+    def n_bins(self):
+        return self.n_fft // 2 + 1
+
+    @property
+    def l_min(self):
+        """Fewest frames an utterance needs for the reference's reflect padding (hop (L - 1) > n_fft / 2); shorter ones give zeros."""
+        return self.n_fft // (2 * self.hop) + 2
+
+
+SUPPORTED_N_FFT = (512, 1024, 2048)
+MAX_MELS = 128
+
+
+def check_geometry(g):
+    """Raise ValueError unless the kernels implement ``g`` (include/fs2.h: fs2_op_griffin_lim_geom)."""
+    if g.n_fft not in SUPPORTED_N_FFT:
+        raise ValueError("n_fft must be one of %s (radix-2/4/8 transforms only), got %r" % (SUPPORTED_N_FFT, g.n_fft))
+    if not (1 <= g.hop <= g.win <= g.n_fft):
+        raise ValueError("need hop <= win_length <= n_fft, got hop %r, win_length %r, n_fft %r" % (g.hop, g.win, g.n_fft))
+    if -(-g.n_fft // g.hop) > 8:
+        raise ValueError("ceil(n_fft / hop) must be <= 8 (a sample lies in at most 8 frames), got n_fft %d, hop %d" % (g.n_fft, g.hop))
+    if not 1 <= g.n_mels <= MAX_MELS:
+        raise ValueError("n_mels must be 1 .. %d, got %r" % (MAX_MELS, g.n_mels))
+    return g
+
+
+def _audio_config(hp):
+    """(mel_basis arguments, Geometry) from hp.audio.  The transform defaults to 1024 / 256 / 1024; any other one must be named in
+    full (n_fft, hop_length and win_length together, as the reference's preprocessing reads all three): a partial departure raises
+    and names what is missing, the transform is never guessed.  n_mels: hp.audio.n_mels, else hp.audio.num_mels, else 80."""
     p = dict(_AUDIO_DEFAULTS)
     a = getattr(hp, "audio", None) if hp is not None else None
+    tr = {}
     if a is not None:
         get = a.get if hasattr(a, "get") else (lambda k, d=None: getattr(a, k, d))
-        for k, hk in (("sample_rate", "sample_rate"), ("n_fft", "n_fft"), ("n_mels", "n_mels"), ("fmin", "fmin"), ("fmax", "fmax")):
-            if get(hk, None) is not None:
-                p[k] = type(_AUDIO_DEFAULTS[k])(get(hk))
-        for k, want in (("n_fft", N_FFT), ("hop_length", HOP), ("win_length", WIN)):
-            if get(k, None) is not None and int(get(k)) != want:
-                raise ValueError("the Griffin-Lim kernels implement n_fft = win_length = 1024, hop 256 only; hp.audio.%s = %s" % (k, get(k)))
-    if p["n_fft"] != N_FFT:
-        raise ValueError("n_fft must be 1024, got %r" % p["n_fft"])
-    if p["n_mels"] != 80:
-        raise ValueError("the Griffin-Lim kernels take 80 mel bins, got %r" % p["n_mels"])
-    return p
+        for k in ("sample_rate", "fmin", "fmax"):
+            if get(k, None) is not None:
+                p[k] = type(_AUDIO_DEFAULTS[k])(get(k))
+        nm = get("n_mels", None)
+        nm = get("num_mels", None) if nm is None else nm
+        if nm is not None:
+            p["n_mels"] = int(nm)
+        tr = {k: int(get(k)) for k in ("n_fft", "hop_length", "win_length") if get(k, None) is not None}
+    default = dict(n_fft=N_FFT, hop_length=HOP, win_length=WIN)
+    if any(tr[k] != default[k] for k in tr) and len(tr) < 3:
+        named = ", ".join("%s = %d" % (k, v) for k, v in tr.items())
+        missing = ", ".join(k for k in default if k not in tr)
+        raise ValueError("hp.audio departs from the default transform (n_fft 1024, hop_length 256, win_length 1024) with %s but does not "
+                         "name %s: a transform other than the default must name n_fft, hop_length and win_length together" % (named, missing))
+    tr = dict(default, **tr)
+    g = check_geometry(Geometry(tr["n_fft"], tr["hop_length"], tr["win_length"], p["n_mels"]))
+    p["n_fft"] = g.n_fft
+    return p, g
+
+
+# ---- tile rule of csrc/griffin_lim.h (gl_halo, gl_tail, gl_lmin, gl_sig_max, gl_tile_frames), restated for the host checks ----
+LDS_BYTES = 163840
+
+
+def tile_rule(n_fft, hop):
+    """dict(F, halo, tail, lmin, sig_max) of the fused kernel at (n_fft, hop): frames per tile, halo frames each side, the extra frame
+    L - tail of a tile at the utterance's end, L_min, and the signal buffer (floats).  F: the largest of 32, 16, ... whose LDS fits."""
+    R = -(-n_fft // hop)
+    halo, tail, lmin = max(R - 1, 1), n_fft // hop + 1, n_fft // (2 * hop) + 2
+    sig = lambda F: hop * (F + 2 * halo - 1) + n_fft
+    F = 32
+    if not (n_fft == N_FFT and hop == HOP):
+        while F > 1 and 28 * n_fft + 4 * sig(F) > LDS_BYTES:
+            F //= 2
+    return dict(F=F, halo=halo, tail=tail, lmin=lmin, sig_max=sig(F))
+
+
+def tile_span(n_fft, hop, L, f0, rule=None):
+    """Frames [fa, fb] the tile starting at f0 inverse-transforms (its own frames, the halo and the reflection's extra frame)."""
+    r = rule or tile_rule(n_fft, hop)
+    nf = min(r["F"], L - f0)
+    return max(0, min(f0 - r["halo"], L - r["tail"])), min(L - 1, f0 + nf - 1 + r["halo"])
 
 
 # ---- seeded initial phase: the formula of csrc/griffin_lim.h (gl_seed_angle), restated ----
@@ -83,14 +154,14 @@ def _mix32(x):
     return x
 
 
-def seed_angles(seed, n_frames):
-    """Initial angles [n_frames, 513] (float32) of an utterance for ``seed``: uniform on [-pi, pi) from a counter-based hash of
-    (seed, utterance-local frame, bin), exactly as the kernel computes them."""
+def seed_angles(seed, n_frames, n_bins=N_BINS):
+    """Initial angles [n_frames, n_bins] (float32) of an utterance for ``seed``: uniform on [-pi, pi) from a counter-based hash of
+    (seed, utterance-local frame, bin) = hash(k + n_bins f), exactly as the kernel computes them."""
     with np.errstate(over="ignore"):
         f = np.arange(n_frames, dtype=np.uint32)[:, None]
-        k = np.arange(N_BINS, dtype=np.uint32)[None, :]
+        k = np.arange(n_bins, dtype=np.uint32)[None, :]
         s = _mix32(np.uint32((int(seed) + 0x9E3779B9) & 0xFFFFFFFF))
-        h = _mix32((k + np.uint32(513) * f) ^ s)
+        h = _mix32((k + np.uint32(n_bins) * f) ^ s)
     u = (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
     return u * np.float32(6.28318548) - np.float32(3.14159274)
 
@@ -137,19 +208,21 @@ def _i32(a):
 class GriffinLim:
     """Griffin-Lim on the GPU, batched.  ``GriffinLim(hp)(mels, olens)`` -> ``Waveforms(wav_packed, sample_lens)``.
 
-    An utterance of L frames gives 256 (L - 1) samples (the reference's STFT.inverse trims n_fft / 2 at both ends); L < 4 is too
-    short for the reference's reflect padding and gives 256 (L - 1) zeros (none for L <= 1), without failing the batch."""
+    The transform comes from hp.audio (``geometry``; default n_fft = win_length = 1024, hop 256, 80 mel bins).  An utterance of L
+    frames gives hop (L - 1) samples (the reference's STFT.inverse trims n_fft / 2 at both ends); L < L_min = n_fft // (2 hop) + 2
+    (4 at the default) is too short for the reference's reflect padding and gives hop (L - 1) zeros (none for L <= 1), without
+    failing the batch."""
 
     def __init__(self, hp=None, device=None):
-        self.params = _audio_params(hp)
+        self.params, self.geometry = _audio_config(hp)
         self.device = torch.device(device) if device is not None else None
         B = mel_basis(**self.params)
         self._basis_np = B
-        self._pinv_np = np.linalg.pinv(B)          # [513, 80], float64 on the host
+        self._pinv_np = np.linalg.pinv(B)          # [bins, n_mels], float64 on the host
         self._dev = {}
 
     def constants(self, device):
-        """(pinv [513, 80], mel basis [80, 513]) as fp32 tensors on ``device``."""
+        """(pinv [bins, n_mels], mel basis [n_mels, bins]) as fp32 tensors on ``device``."""
         device = torch.device(device)
         if device not in self._dev:
             self._dev[device] = (torch.tensor(self._pinv_np, dtype=torch.float32, device=device).contiguous(),
@@ -157,13 +230,15 @@ class GriffinLim:
         return self._dev[device]
 
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False):
-        """mels: packed [N, 80] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, 80] with
-        ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
-        [.., 513] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout of
-        ``mels`` with 513 bins, or None: seeded.  ``momentum`` > 0: fast Griffin-Lim (0 = the reference).  Runs on the current
-        stream of the input's device without synchronising."""
+        """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
+        with ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
+        [.., n_fft / 2 + 1] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout
+        of ``mels`` with n_fft / 2 + 1 bins, or None: seeded.  ``momentum`` > 0: fast Griffin-Lim (0 = the reference).  Runs on the
+        current stream of the input's device without synchronising."""
         _require_cuda(mels, "mels")
-        W = N_BINS if magnitudes else 80
+        g = self.geometry
+        NB = g.n_bins
+        W = NB if magnitudes else g.n_mels
         if mels.dim() not in (2, 3) or mels.shape[-1] != W:
             raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
         if self.device is not None and mels.device != self.device:
@@ -189,40 +264,36 @@ class GriffinLim:
             src = mels.reshape(Bp * Lmax, W)
         if init_phase is not None:
             _require_cuda(init_phase, "init_phase")
-            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != N_BINS:
-                raise ValueError("init_phase must have the layout of mels with 513 bins, got %s" % (tuple(init_phase.shape),))
-            init_phase = init_phase.reshape(-1, N_BINS).contiguous().float()
+            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
+                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
+            init_phase = init_phase.reshape(-1, NB).contiguous().float()
         src = src.contiguous().float()
         dev = mels.device
-        sample_lens = HOP * torch.clamp(L - 1, min=0)
+        sample_lens = g.hop * torch.clamp(L - 1, min=0)
         wav = torch.empty(int(sample_lens.sum()), dtype=torch.float32, device=dev)
         if wav.numel() == 0:
             return Waveforms(wav, sample_lens)
-        if int(L.sum()) * N_BINS >= 2 ** 31 or wav.numel() >= 2 ** 31:
+        if int(L.sum()) * NB >= 2 ** 31 or wav.numel() >= 2 ** 31:
             raise ValueError("batch too large for one call (%d frames)" % int(L.sum()))
         lib = _lib.lib()
         s_np, s_p = _i32(starts)
         l_np, l_p = _i32(L.numpy())
         B = len(l_np)
-        ws_bytes = int(lib.fs2_op_vocode_workspace_bytes(B, l_p))
+        ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_geom(*g, B, l_p))
         with torch.cuda.device(dev):
             pinv = self.constants(dev)[0] if not magnitudes else None
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_griffin_lim(_stream(dev), src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, B, s_p, l_p,
-                                              n_iter, momentum, int(seed) & 0xFFFFFFFF,
-                                              init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
-                                              wav.data_ptr()))
+            _lib.check(lib.fs2_op_griffin_lim_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
+                                                   B, s_p, l_p, n_iter, momentum, int(seed) & 0xFFFFFFFF,
+                                                   init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
+                                                   wav.data_ptr()))
         return Waveforms(wav, sample_lens)
 
 
 _DEFAULT_GL = None
 
 
-def stft_magnitude(wav_packed, sample_lens, mel=False, hp=None):
-    """Analysis STFT (the reference's STFT.transform / TacotronSTFT.mel_spectrogram, stft.py:80-110,188-204) of packed waveforms:
-    waveform b = ``sample_lens[b]`` samples, giving ``sample_lens[b] // 256 + 1`` frames (reflect padding at its own ends), packed back
-    to back.  Returns |X| [frames, 513], or with ``mel=True`` the log-mel [frames, 80] = log(clamp(B . |X|, 1e-5)).  A waveform of
-    <= 512 samples cannot be reflect-padded: its frames are |X| = 0 (log-mel log(1e-5))."""
+def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy):
     global _DEFAULT_GL
     _require_cuda(wav_packed, "wav_packed")
     if wav_packed.dim() != 1:
@@ -233,23 +304,45 @@ def stft_magnitude(wav_packed, sample_lens, mel=False, hp=None):
     gl = GriffinLim(hp) if hp is not None else (_DEFAULT_GL or GriffinLim())
     if hp is None:
         _DEFAULT_GL = gl
+    g = gl.geometry
     dev = wav_packed.device
-    frames = int((T // HOP + 1).sum()) if T.numel() else 0
-    out = torch.empty(frames, 80 if mel else N_BINS, dtype=torch.float32, device=dev)
+    frames = int((T // g.hop + 1).sum()) if T.numel() else 0
+    mag = torch.empty(frames, g.n_bins, dtype=torch.float32, device=dev) if want_mag else None
+    mel = torch.empty(frames, g.n_mels, dtype=torch.float32, device=dev) if want_mel else None
+    en = torch.empty(frames, dtype=torch.float32, device=dev) if want_energy else None
     if frames == 0:
-        return out
+        return mag, mel, en
     x = wav_packed.contiguous().float()
     lib = _lib.lib()
     st_np, st_p = _i32(np.concatenate([[0], np.cumsum(T.numpy())[:-1]]))
     t_np, t_p = _i32(T.numpy())
     B = len(t_np)
-    ws_bytes = int(lib.fs2_op_stft_workspace_bytes(B, t_p))
+    ws_bytes = int(lib.fs2_op_stft_workspace_bytes_geom(*g, B, t_p))
+    ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(dev):
         basis = gl.constants(dev)[1]
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.fs2_op_stft(_stream(dev), x.data_ptr(), B, st_p, t_p, ws.data_ptr(), ws_bytes, None if mel else out.data_ptr(),
-                                   basis.data_ptr() if mel else None, out.data_ptr() if mel else None))
-    return out
+        _lib.check(lib.fs2_op_stft_geom(_stream(dev), *g, x.data_ptr(), B, st_p, t_p, ws.data_ptr(), ws_bytes, ptr(mag),
+                                        basis.data_ptr() if want_mel else None, ptr(mel), ptr(en)))
+    return mag, mel, en
+
+
+def stft_magnitude(wav_packed, sample_lens, mel=False, hp=None):
+    """Analysis STFT (the reference's STFT.transform / TacotronSTFT.mel_spectrogram, stft.py:80-110,188-204) of packed waveforms in
+    the geometry of ``hp.audio`` (default 1024 / 256 / 1024, 80 mels): waveform b = ``sample_lens[b]`` samples, giving
+    ``sample_lens[b] // hop + 1`` frames (reflect padding at its own ends), packed back to back.  Returns |X| [frames, n_fft / 2 + 1],
+    or with ``mel=True`` the log-mel [frames, n_mels] = log(clamp(B . |X|, 1e-5)).  A waveform of <= n_fft / 2 samples cannot be
+    reflect-padded: its frames are |X| = 0 (log-mel log(1e-5))."""
+    mag, lm, _ = _analysis(wav_packed, sample_lens, hp, not mel, mel, False)
+    return lm if mel else mag
+
+
+def mel_energy(wav_packed, sample_lens, hp=None):
+    """(log-mel [frames, n_mels], energy [frames]) of packed waveforms from one launch: the reference preprocessing's mel and energy
+    targets (nvidia_preprocessing.py: TacotronSTFT.mel_spectrogram and torch.norm(|X|, dim=0)), without pitch.  Frames as in
+    ``stft_magnitude``; a waveform of <= n_fft / 2 samples gives energy 0."""
+    _, lm, en = _analysis(wav_packed, sample_lens, hp, False, True, True)
+    return lm, en
 
 
 def save_wav(path, wav, sample_rate=22050):

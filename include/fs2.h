@@ -307,6 +307,29 @@ size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t *wav_lens);
 int fs2_op_stft(void *stream, const float *wav, int32_t B, const int32_t *wav_starts, const int32_t *wav_lens, void *workspace,
                 size_t workspace_bytes, float *mag, const float *mel_basis, float *logmel);
 
+/* ---- The same four operations for another transform geometry (the reference's STFT(filter_length, hop_length, win_length) and
+ * TacotronSTFT's n_mel_channels), named by the four int32 arguments n_fft, hop, win, n_mels.  Supported: n_fft 512, 1024 or 2048;
+ * hop <= win <= n_fft; ceil(n_fft / hop) <= 8; n_mels 1 .. 128.  The window is a periodic Hann of `win` samples zero-padded to n_fft
+ * at the centre; bins = n_fft / 2 + 1.  Anything else: FS2_ERR_UNSUPPORTED (workspace queries: 0).  Everything said above holds with
+ * 256 -> hop, 513 -> bins, 80 -> n_mels, L < 4 -> L < L_min = n_fft / (2 hop) + 2 (integer division) and 512 samples -> n_fft / 2.
+ * At (1024, 256, 1024, 80) the results equal those of the entry points above bit for bit. ---- */
+
+size_t fs2_op_vocode_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *lens);
+
+/* src_width n_mels (with mel_pinv [bins, n_mels]) or bins; init_phase [rows, bins]; wav: float32 [hop * sum max(L_b - 1, 0)]. */
+int fs2_op_griffin_lim_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                            const float *mel_pinv, int32_t B, const int32_t *starts, const int32_t *lens, int32_t n_iter, float momentum,
+                            uint32_t seed, const float *init_phase, void *workspace, size_t workspace_bytes, float *wav);
+
+size_t fs2_op_stft_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *wav_lens);
+
+/* wav_lens[b] / hop + 1 frames per waveform: mag [frames, bins], logmel [frames, n_mels] with mel_basis [n_mels, bins], and
+ * energy [frames] = the L2 norm of each frame's |X| over its bins (the reference preprocessing's energy target), each optional (NULL),
+ * all from one launch. */
+int fs2_op_stft_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *wav, int32_t B,
+                     const int32_t *wav_starts, const int32_t *wav_lens, void *workspace, size_t workspace_bytes, float *mag,
+                     const float *mel_basis, float *logmel, float *energy);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */

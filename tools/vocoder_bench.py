@@ -7,6 +7,11 @@ seconds of work.  Bytes and FLOP per iteration come from shapes (csrc/griffin_li
 rocprofv3 --kernel-trace --stats separately.
 
 Usage:  python tools/vocoder_bench.py [--n-iter 30] [--min-s 0.5] [--workload c3]
+
+--geometry N,H,W [--sample-rate SR] [--repeats K]: another transform (n_fft, hop, win_length).  The workload is then the c3
+utterances' audio durations (olens x 256 / 22050 s) at SR, as synthetic harmonic waveforms whose magnitudes come from
+stft_magnitude at that geometry; 30 iterations of the HIP path and of TorchGL at the same geometry are each timed K times
+(median and max - min spread reported).  With neither flag the run is the default one above.
 """
 import argparse
 import json
@@ -53,21 +58,24 @@ def timed(fn, min_s):
 
 
 class TorchGL:
-    """The reference's griffin_lim with torch.stft / torch.istft (center=True, reflect padding, periodic Hann, wss normalisation:
-    the same transform), batched over padded utterances, lengths honoured by istft(length=)."""
+    """The reference's griffin_lim with torch.stft / torch.istft (center=True, reflect padding, periodic Hann of win_length padded
+    to n_fft at the centre, wss normalisation: the same transform), batched over padded utterances, lengths honoured by
+    istft(length=)."""
 
-    def __init__(self, device):
-        self.win = torch.hann_window(1024, periodic=True, device=device)
+    def __init__(self, device, n_fft=1024, hop=256, win=1024):
+        self.n_fft, self.hop, self.wl = n_fft, hop, win
+        self.win = torch.hann_window(win, periodic=True, device=device)
 
     def __call__(self, M, lens, n_iter, angles):
-        # M [B, 513, Lmax] (zero past each utterance's frames), angles same shape
+        # M [B, bins, Lmax] (zero past each utterance's frames), angles same shape
+        n, h, w = self.n_fft, self.hop, self.wl
         C = M * torch.exp(1j * angles)
-        length = 256 * (M.shape[-1] - 1)
-        sig = torch.istft(C, 1024, 256, 1024, self.win, center=True, length=length)
+        length = h * (M.shape[-1] - 1)
+        sig = torch.istft(C, n, h, w, self.win, center=True, length=length)
         for _ in range(n_iter):
-            X = torch.stft(sig, 1024, 256, 1024, self.win, center=True, pad_mode="reflect", return_complex=True)
+            X = torch.stft(sig, n, h, w, self.win, center=True, pad_mode="reflect", return_complex=True)
             C = M * torch.exp(1j * torch.angle(X))
-            sig = torch.istft(C, 1024, 256, 1024, self.win, center=True, length=length)
+            sig = torch.istft(C, n, h, w, self.win, center=True, length=length)
         return sig
 
 
@@ -77,8 +85,13 @@ def main():
     ap.add_argument("--min-s", type=float, default=0.5)
     ap.add_argument("--workload", default="c3")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--geometry", default=None, help="n_fft,hop,win_length (default: the 1024,256,1024 run)")
+    ap.add_argument("--sample-rate", type=int, default=None)
+    ap.add_argument("--repeats", type=int, default=5, help="timings per path in the --geometry run")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "vocoder_bench needs a GPU"
+    if args.geometry is not None or args.sample_rate is not None:
+        return geometry_main(args)
     from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude
     hp, mels, olens = c3_mels(args.workload)
     N, B = mels.shape[0], len(olens)
@@ -128,6 +141,68 @@ def main():
         sc_torch = float(torch.linalg.norm(Mt - Xt)) / float(torch.linalg.norm(Mt)) if Xt.shape == Mt.shape else float("nan")
         rec.update(torch_ms_per_call=round(ms_torch, 3), torch_reps=treps, speedup_vs_torch=round(ms_torch / ms_call, 2),
                    sc_torch=round(sc_torch, 5))
+    print(json.dumps(rec))
+
+
+def geometry_main(args):
+    from fastspeech2_amd.hparams import DotDict
+    from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude, tile_rule
+    from tests.vocoder_oracle import harmonic_signal
+    n_fft, hop, win = (int(x) for x in (args.geometry or "1024,256,1024").split(","))
+    sr = args.sample_rate or 22050
+    hp = DotDict({"audio": {"n_fft": n_fft, "hop_length": hop, "win_length": win, "sample_rate": sr, "n_mels": 80}})
+    gl = GriffinLim(hp)
+    _, _, c3_olens = c3_mels(args.workload)
+    T = [int(round(L * 256 / 22050.0 * sr)) for L in c3_olens]                   # the c3 utterances' durations at this rate
+    dev = torch.device("cuda")
+    wav = torch.from_numpy(np.concatenate([harmonic_signal(t, seed=b, f0=110.0 + 3 * (b % 40), sr=sr, noise=0.01) for b, t in enumerate(T)])
+                           .astype(np.float32)).to(dev)
+    M = stft_magnitude(wav, T, hp=hp)                                              # [N, bins]
+    olens = [t // hop + 1 for t in T]
+    N, B, NB = M.shape[0], len(olens), n_fft // 2 + 1
+    run = lambda n: gl(M, olens, n_iter=n, seed=0, magnitudes=True)
+    med = lambda xs: float(np.median(xs))
+    hip = [timed(lambda: run(args.n_iter), args.min_s)[0] for _ in range(args.repeats)]
+    ms_zero = med([timed(lambda: run(0), args.min_s)[0] for _ in range(max(1, args.repeats // 2))])
+    ms_call = med(hip)
+    ms_iter = (ms_call - ms_zero) / max(args.n_iter, 1)
+    out = run(args.n_iter)
+    Xh = stft_magnitude(out.wav, out.sample_lens, hp=hp)
+    sc_hip = float(torch.linalg.norm(M - Xh)) / float(torch.linalg.norm(M))
+    r = tile_rule(n_fft, hop)
+    F, halo = r["F"], r["halo"]
+    tiles = [(L, f0) for L in olens if L >= r["lmin"] for f0 in range(0, L, F)]
+    span = sum(min(L - 1, f0 + min(F, L - f0) - 1 + halo) - max(0, min(f0 - halo, L - r["tail"])) + 1 for L, f0 in tiles)
+    bytes_iter = span * NB * 8 + N * NB * 4 + N * NB * 8
+    fft_flop = 2.5 * n_fft * math.log2(n_fft)
+    flop_iter = (span + N) * fft_flop + N * NB * 12
+    t_bytes = bytes_iter / (PEAK_HBM_TBS * 1e12) * 1e3
+    t_flop = flop_iter / (PEAK_FP32_TFLOPS * 1e12) * 1e3
+    rec = dict(workload=args.workload, geometry=[n_fft, hop, win], sample_rate=sr, tile_frames=F, halo=halo, utterances=B, frames=N,
+               tiles=len(tiles), n_iter=args.n_iter, samples=int(out.wav.numel()), audio_seconds=round(sum(T) / sr, 3),
+               hip_ms_runs=[round(x, 3) for x in hip], hip_ms_per_call=round(ms_call, 3), hip_ms_spread=round(max(hip) - min(hip), 3),
+               hip_ms_call_n_iter0=round(ms_zero, 3), hip_ms_per_iter=round(ms_iter, 4), bytes_per_iter=bytes_iter, flop_per_iter=flop_iter,
+               bound_ms_bytes=round(t_bytes, 4), bound_ms_flop=round(t_flop, 4),
+               share_of_larger_bound=round(max(t_bytes, t_flop) / ms_iter, 3) if ms_iter > 0 else None,
+               larger_bound="bytes" if t_bytes >= t_flop else "flop", sc_hip=round(sc_hip, 5))
+    if not args.no_torch:
+        Lmax = max(olens)
+        Mp = torch.zeros(B, NB, Lmax, device=dev)
+        o = 0
+        for b, L in enumerate(olens):
+            Mp[b, :, :L] = M[o:o + L].T
+            o += L
+        ang = (torch.rand(B, NB, Lmax, device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 2 - 1) * math.pi
+        tg = TorchGL(dev, n_fft, hop, win)
+        tt = [timed(lambda: tg(Mp, olens, args.n_iter, ang), args.min_s)[0] for _ in range(args.repeats)]
+        sig = tg(Mp, olens, args.n_iter, ang)
+        parts = [sig[b, :hop * (L - 1)] for b, L in enumerate(olens)]
+        Xt = stft_magnitude(torch.cat(parts).contiguous(), [hop * (L - 1) for L in olens], hp=hp)
+        sc_torch = float(torch.linalg.norm(M - Xt)) / float(torch.linalg.norm(M))
+        rec.update(torch_ms_runs=[round(x, 3) for x in tt], torch_ms_per_call=round(med(tt), 3), torch_ms_spread=round(max(tt) - min(tt), 3),
+                   speedup_vs_torch=round(med(tt) / ms_call, 2), sc_torch=round(sc_torch, 5),
+                   hip_beats_torch_by_more_than_spread=bool(med(tt) - ms_call > max(tt) - min(tt)),
+                   sc_hip_within_1pct_of_torch=bool(sc_hip <= 1.01 * sc_torch))
     print(json.dumps(rec))
 
 
