@@ -1804,7 +1804,9 @@ hipError_t gl_run(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const f
     const dim3 grid(n_tiles), blk(kGlThreads);
     const GlGeom g = gh.g;
     const size_t lds = gh.sig_bytes;
-    if (lds) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (lds && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
+    if (lds && cap == hipStreamCaptureStatusNone) {     // (one-time host work: a captured call relies on the eager call before it)
         hipError_t e;
         if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
         if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
@@ -1851,6 +1853,91 @@ int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const fl
     a.beta = momentum / (1.f + momentum);
     a.wav = wav;
     const unsigned nt = (unsigned)p.tiles.size();
+    if (gh.is_default()) e = gl_run<1024, kGlHop>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else if (gh.n_fft == 512) e = gl_run<512, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else if (gh.n_fft == 1024) e = gl_run<1024, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    else e = gl_run<2048, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
+    return FS2_OK;
+}
+
+static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvfUpstream == FS2_OVF_UPSTREAM && kGlOvfNegative == FS2_OVF_NEG_LEN &&
+              kGlOvfWav == FS2_OVF_WAV, "griffin_lim.h restates the FS2_OVF_* bits");
+
+// Workspace of the device-driven call: the layout of gl_plan with every size taken from the capacities, plus the planner's
+// per-utterance arrays.  0 slots / 0 frames still reserve one record, as gl_plan does.
+struct GlCapLayout {
+    int64_t slots = 0;
+    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
+};
+
+bool gl_cap_layout(const GlGeomHost& gh, int64_t B, int64_t frame_capacity, GlCapLayout& c) {
+    if (B < 0 || frame_capacity < 0 || frame_capacity > INT32_MAX / gh.n_bins) return false;
+    c.slots = gl_slot_capacity(frame_capacity, gh.g.F, (int)B);
+    if (c.slots > INT32_MAX) return false;
+    size_t off = 0;
+    auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
+    c.off_tw = take(gh.n_fft * sizeof(float2));
+    c.off_win = take(gh.n_fft * sizeof(float));
+    c.off_tiles = take(std::max<size_t>((size_t)c.slots, 1) * sizeof(GlTile));
+    c.off_plan = take(std::max<size_t>((size_t)B, 1) * 4 * sizeof(int));
+    const size_t n = (size_t)frame_capacity * gh.n_bins;
+    c.off_M = take(n * sizeof(float));
+    c.off_C0 = take(n * sizeof(float2));
+    c.off_C1 = take(n * sizeof(float2));
+    c.off_T = take(n * sizeof(float2));
+    c.bytes = align_up(off, 256);
+    return true;
+}
+
+int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
+                       const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
+                       float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav,
+                       int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
+    if (src_width != gh.n_mels && src_width != gh.n_bins)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
+                    gh.n_bins, gh.n_fft);
+    if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
+    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
+    if (B < 1 || frame_capacity < 1 || src_stride < 0 || wav_stride < 0)
+        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d", who, B, (long long)frame_capacity, src_stride, wav_stride);
+    if (frame_capacity > INT32_MAX / gh.n_bins || wav_capacity < 0 || wav_capacity > INT32_MAX || (int64_t)B * src_stride > INT32_MAX)
+        return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call (%lld frames, %lld samples)", who, (long long)frame_capacity, (long long)wav_capacity);
+    if ((int64_t)B * wav_stride > wav_capacity)
+        return fail(nullptr, FS2_ERR_ARG, "%s: padded output of %d x %d samples in a wav of %lld", who, B, wav_stride, (long long)wav_capacity);
+    if (!src || !lens_dev || !workspace || !sample_lens_dev || !status || (wav_capacity > 0 && !wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    GlCapLayout c;
+    if (!gl_cap_layout(gh, B, frame_capacity, c)) return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call", who);
+    if (workspace_bytes < c.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, c.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(gl_tables, dim3((gh.n_fft + 255) / 256), dim3(256), 0, s, (float2*)(ws + c.off_tw), (float*)(ws + c.off_win), gh.n_fft, gh.win);
+    GlPlanArgs pa{};
+    pa.lens = lens_dev; pa.upstream = upstream_status;
+    pa.B = B; pa.hop = gh.hop; pa.F = gh.g.F;
+    pa.src_stride = src_stride; pa.wav_stride = wav_stride;
+    pa.frame_capacity = frame_capacity; pa.wav_capacity = wav_capacity;
+    int* plan = (int*)(ws + c.off_plan);
+    pa.row0 = plan; pa.wav0 = plan + B; pa.tile_end = plan + 2 * (size_t)B; pa.Lv = plan + 3 * (size_t)B;
+    pa.sample_lens = sample_lens_dev; pa.status = status;
+    const int n_slots = (int)c.slots;        // >= B >= 1
+    hipLaunchKernelGGL(gl_plan_scan, dim3(1), dim3(kGlPlanThreads), 0, s, pa);
+    hipLaunchKernelGGL(gl_plan_emit, dim3((n_slots + 255) / 256), dim3(256), 0, s, pa, n_slots, (GlTile*)(ws + c.off_tiles));
+    if (wav_capacity > 0)
+        hipLaunchKernelGGL(gl_plan_fill, dim3((unsigned)std::min<int64_t>((wav_capacity + 1023) / 1024, 2048)), dim3(256), 0, s, pa, wav);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim plan: %s", hipGetErrorString(e));
+    GlIterArgs a{};
+    a.tiles = (const GlTile*)(ws + c.off_tiles);
+    a.tw = (const float2*)(ws + c.off_tw);
+    a.win = (const float*)(ws + c.off_win);
+    a.M = (const float*)(ws + c.off_M);
+    a.C[0] = (float2*)(ws + c.off_C0);
+    a.C[1] = (float2*)(ws + c.off_C1);
+    a.Tm = momentum > 0.f ? (float2*)(ws + c.off_T) : nullptr;
+    a.beta = momentum / (1.f + momentum);
+    a.wav = wav;
+    const unsigned nt = (unsigned)n_slots;
     if (gh.is_default()) e = gl_run<1024, kGlHop>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
     else if (gh.n_fft == 512) e = gl_run<512, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
     else if (gh.n_fft == 1024) e = gl_run<1024, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
@@ -2643,6 +2730,23 @@ int fs2_op_griffin_lim_geom(void* stream, int32_t n_fft, int32_t hop, int32_t wi
     if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_geom", gh)) return rc;
     return gl_griffin_lim("fs2_op_griffin_lim_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
                           workspace, workspace_bytes, wav);
+}
+
+size_t fs2_op_vocode_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
+    GlGeomHost gh;
+    GlCapLayout c;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_cap", gh)) return 0;
+    return gl_cap_layout(gh, B, frame_capacity, c) ? c.bytes : 0;
+}
+
+int fs2_op_griffin_lim_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
+                           int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
+                           float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav, int32_t wav_stride,
+                           int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_dev", gh)) return rc;
+    return gl_griffin_lim_dev("fs2_op_griffin_lim_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, n_iter,
+                              momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status);
 }
 
 size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) { return fs2_op_stft_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, wav_lens); }

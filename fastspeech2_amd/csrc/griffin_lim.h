@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gl_slot_rule.h"
 #include "gl_tile_rule.h"
 
 namespace fs2 {
@@ -501,6 +502,126 @@ __global__ __launch_bounds__(kGlThreads) void gl_stft(const GlTile* tiles, GlGeo
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) e2 += __shfl_xor(e2, o);
             if (valid && j == 0) energy[t.src_row0 + f] = sqrtf(e2);
+        }
+    }
+}
+
+// ---- device-driven plan (fs2_op_griffin_lim_dev) ----
+// The frame counts stay on the device: gl_plan_scan validates them and scans the batch, gl_plan_emit writes one GlTile per slot of a
+// grid sized from the capacities (gl_slot_rule.h), gl_plan_fill writes the samples no tile owns.  The tile kernels above then run
+// over all slots; an empty record (L = 0) leaves each of them at once.  The records are the only thing the tile kernels index with,
+// and they are emitted only after every length passed the checks: whatever lens holds, nothing is read or written outside src, the
+// workspace and wav as sized from the capacities.  No atomics.
+constexpr int kGlPlanThreads = 1024;
+constexpr int kGlOvfRows = 1, kGlOvfLmax = 2, kGlOvfUpstream = 32, kGlOvfNegative = 64, kGlOvfWav = 128;     // FS2_OVF_* (include/fs2.h)
+
+struct GlPlanArgs {
+    const int64_t* lens;          // [B] frames per utterance (device)
+    const int32_t* upstream;      // int32[8] status of the producer of src (fs2_decode), or NULL
+    int B, hop, F;
+    int src_stride;               // 0: packed source (utterance b at the prefix sum of L); else rows per utterance
+    int wav_stride;               // 0: packed waveform; else samples per utterance
+    int64_t frame_capacity;       // rows of the workspace spectra (and of a packed source)
+    int64_t wav_capacity;         // floats of wav
+    int *row0, *wav0, *tile_end, *Lv;     // [B] each, workspace: what gl_plan_emit reads
+    int64_t* sample_lens;         // [B] out
+    int32_t* status;              // int32[8] out: {frames, tiles, flags, longest utterance, valid samples, 0, 0, 0}
+};
+
+// One workgroup.  Thread t owns the utterances [t per, (t + 1) per); their sums are scanned across the block in LDS (Hillis-Steele).
+// A length is clamped to [0, frame_capacity + 1] before it enters a sum, so no sum can overflow whatever lens holds.
+__global__ __launch_bounds__(kGlPlanThreads) void gl_plan_scan(GlPlanArgs a) {
+    __shared__ int64_t sL[kGlPlanThreads], sW[kGlPlanThreads], sT[kGlPlanThreads];
+    __shared__ int sF[kGlPlanThreads], sM[kGlPlanThreads];
+    const int tid = threadIdx.x, per = (a.B + kGlPlanThreads - 1) / kGlPlanThreads;
+    const int b0 = min(a.B, tid * per), b1 = min(a.B, b0 + per);
+    int64_t nL = 0, nW = 0, nT = 0;
+    int fl = 0, mx = 0;
+    for (int b = b0; b < b1; ++b) {
+        int64_t L = a.lens[b];
+        if (L < 0) { fl |= kGlOvfNegative; L = 0; }
+        if (L > a.frame_capacity) { fl |= kGlOvfRows; L = a.frame_capacity + 1; }
+        const int64_t T = (int64_t)a.hop * (L > 1 ? L - 1 : 0);
+        if (a.src_stride && L > a.src_stride) fl |= kGlOvfLmax;
+        if (a.wav_stride && T > a.wav_stride) fl |= kGlOvfLmax;
+        nL += L; nW += T; nT += gl_tile_count((int)L, a.F);
+        mx = max(mx, (int)L);
+    }
+    sL[tid] = nL; sW[tid] = nW; sT[tid] = nT; sF[tid] = fl; sM[tid] = mx;
+    __syncthreads();
+    for (int o = 1; o < kGlPlanThreads; o <<= 1) {
+        int64_t pL = 0, pW = 0, pT = 0;
+        int pF = 0, pM = 0;
+        if (tid >= o) { pL = sL[tid - o]; pW = sW[tid - o]; pT = sT[tid - o]; pF = sF[tid - o]; pM = sM[tid - o]; }
+        __syncthreads();
+        sL[tid] += pL; sW[tid] += pW; sT[tid] += pT; sF[tid] |= pF; sM[tid] = max(sM[tid], pM);
+        __syncthreads();
+    }
+    const int64_t frames = sL[kGlPlanThreads - 1], samples = sW[kGlPlanThreads - 1], tiles = sT[kGlPlanThreads - 1];
+    int flags = sF[kGlPlanThreads - 1];
+    if (frames > a.frame_capacity) flags |= kGlOvfRows;
+    if (!a.wav_stride && samples > a.wav_capacity) flags |= kGlOvfWav;
+    if (a.upstream && a.upstream[2] != 0) flags |= kGlOvfUpstream | a.upstream[2];
+    // exclusive prefixes of this thread's first utterance, then the chunk once more
+    int64_t rL = sL[tid] - nL, rW = sW[tid] - nW, rT = sT[tid] - nT;
+    for (int b = b0; b < b1; ++b) {
+        if (flags) {
+            a.row0[b] = 0; a.wav0[b] = 0; a.tile_end[b] = 0; a.Lv[b] = 0; a.sample_lens[b] = 0;
+            continue;
+        }
+        const int L = (int)a.lens[b];                   // validated: 0 <= L <= frame_capacity
+        const int T = a.hop * max(L - 1, 0);
+        rT += gl_tile_count(L, a.F);
+        a.row0[b] = (int)rL;
+        a.wav0[b] = a.wav_stride ? b * a.wav_stride : (int)rW;
+        a.tile_end[b] = (int)rT;
+        a.Lv[b] = L;
+        a.sample_lens[b] = T;
+        rL += L; rW += T;
+    }
+    if (tid == 0) {
+        const int64_t big = 2147483647;
+        a.status[0] = (int)(frames < big ? frames : big);
+        a.status[1] = flags ? 0 : (int)tiles;
+        a.status[2] = flags;
+        a.status[3] = sM[kGlPlanThreads - 1];
+        a.status[4] = flags ? 0 : (int)samples;
+        a.status[5] = 0; a.status[6] = 0; a.status[7] = 0;
+    }
+}
+
+// One thread per slot: the GlTile the host plan (fs2_runtime.hip: gl_plan) writes for the slot's tile, or an empty record.
+__global__ void gl_plan_emit(GlPlanArgs a, int n_slots, GlTile* tiles) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    GlTile t{};
+    if (a.status[2] == 0) {
+        const GlSlot r = gl_slot_tile(a.tile_end, a.B, a.F, s);
+        if (r.b >= 0) {
+            const int L = a.Lv[r.b];
+            t.ws_row0 = a.row0[r.b];
+            t.src_row0 = a.src_stride ? r.b * a.src_stride : t.ws_row0;
+            t.L = L; t.f0 = r.f0;
+            t.wav0 = a.wav0[r.b];
+            t.T = a.hop * (L - 1);
+        }
+    }
+    tiles[s] = t;
+}
+
+// The samples no tile owns: zeros beyond the valid total (packed) or beyond each utterance's samples (padded); on any flag the whole
+// capacity is NaN.  Grid-stride over wav_capacity.
+__global__ void gl_plan_fill(GlPlanArgs a, float* wav) {
+    const int flags = a.status[2];
+    const int64_t valid = a.status[4], n = a.wav_capacity, step = (int64_t)gridDim.x * blockDim.x;
+    const float nan = __int_as_float(0x7fc00000);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        if (flags) { wav[i] = nan; continue; }
+        if (!a.wav_stride) {
+            if (i >= valid) wav[i] = 0.f;
+        } else {
+            const int64_t b = i / a.wav_stride;
+            if (b >= a.B || i - b * a.wav_stride >= a.sample_lens[b]) wav[i] = 0.f;
         }
     }
 }

@@ -777,14 +777,22 @@ class FeedForwardTransformer(nn.Module):
             self._learn_ratio(il, r["olens"], 1.0)
         return (r["after_packed"] if packed else r["after"]), r["olens"] * self.reduction_factor
 
-    def capture_graph(self, xs, ilens, d_override=None):
+    def capture_graph(self, xs, ilens, d_override=None, vocoder=None, **vocoder_args):
         """HIP-graph replay of the whole free-running forward for a fixed batch shape (``xs.shape`` and ``ilens``): the
         launch-bound small-batch case (one utterance: 85 launches) becomes one graph launch.  Returns ``run(new_xs) ->
         (mels [B, Lcap, odim], olens_dev, status_dev)``; the tensors are the graph's static outputs (overwritten by the
         next replay).  ``status_dev[2] != 0`` means the capacities captured with the graph were too small for that input
         (the mels are then NaN): fall back to ``inference_batch``.  Capacities come from one synchronous run on ``xs``
         (x 1.5 head-room).  The graph holds pointers into the library's weight copies: ``run`` raises if the weights were
-        re-uploaded since the capture (load_state_dict, a grown positional table, .to()): capture again."""
+        re-uploaded since the capture (load_state_dict, a grown positional table, .to()): capture again.
+
+        ``vocoder`` (a ``GriffinLim``; ``vocoder_args``: its ``n_iter``, ``momentum``, ``seed``): the graph also runs the device-driven
+        vocoder on the mels (``vocoder(AsyncMels, sync=False, padded_out=True)``: the frame counts never leave the device), and
+        ``run(new_xs)`` returns ``(wav [B, hop (Lcap - 1)] zero-padded, sample_lens_dev, status_dev)`` instead -- text to waveform
+        in one graph launch.  ``status_dev`` is the vocoder's, with the mel status folded in: a mel overflow shows as
+        FS2_OVF_UPSTREAM plus the mel call's own flags, and the waveforms are then NaN."""
+        if vocoder is None and vocoder_args:
+            raise TypeError("capture_graph: %s given without a vocoder" % sorted(vocoder_args))
         with torch.no_grad():
             il = torch.as_tensor(ilens).detach().to("cpu", torch.int64)
             _, ol = self.inference_batch(xs, il, d_override=d_override)            # builds the handle, learns the sizes
@@ -794,8 +802,16 @@ class FeedForwardTransformer(nn.Module):
             self._ensure_ready(xs.device, xs.shape[1], Lcap)                        # a grown table is uploaded BEFORE the capture
             static_xs = xs.clone()
             static_ds = d_override.clone() if d_override is not None else None
-            run_once = lambda: self._run(static_xs, il, is_inference=True, compat=False, want=("after",), d_override=static_ds,
-                                         capacity=(total, Lcap))
+            run_mel = lambda: self._run(static_xs, il, is_inference=True, compat=False, want=("after",), d_override=static_ds,
+                                        capacity=(total, Lcap))
+
+            def run_once():
+                r = run_mel()
+                if vocoder is None:
+                    return r["after"], r["olens"], r["status"]
+                mel_lens = r["olens"] if self.reduction_factor == 1 else r["olens"] * self.reduction_factor
+                w = vocoder(AsyncMels(r["after"], mel_lens, r["status"], None), sync=False, padded_out=True, **vocoder_args)
+                return w[0], w[1], w.status
             side = torch.cuda.Stream(device=xs.device)
             side.wait_stream(torch.cuda.current_stream(xs.device))
             with torch.cuda.stream(side):
@@ -804,8 +820,7 @@ class FeedForwardTransformer(nn.Module):
             graph = torch.cuda.CUDAGraph()
             # "relaxed": the library pins a small host staging block for the token layout while capturing (hipHostMalloc)
             with torch.cuda.graph(graph, capture_error_mode="relaxed"):
-                r = run_once()
-        after, olens_dev, status = r["after"], r["olens"], r["status"]
+                after, olens_dev, status = run_once()
         generation, handle = self._weights_generation, self._handle
 
         def run(new_xs, new_ds=None):

@@ -12,6 +12,10 @@ vocoded alone or inside any batch.
 ``mel_energy`` gives the log-mel and the per-frame energy (the reference preprocessing's targets) from one launch.  Other transform
 geometries (n_fft 512 / 1024 / 2048, any hop <= win_length <= n_fft with ceil(n_fft / hop) <= 8, 1 .. 128 mels) come from hp.audio.
 There is no CPU fallback: CPU tensors raise.
+
+``GriffinLim(...)(..., sync=False)`` is the device-driven form (fs2_op_griffin_lim_dev): the frame counts stay
+on the device (an ``AsyncMels`` of ``inference_batch(sync=False)`` can be passed as it is), the tiles are planned by kernels inside
+capacities, nothing waits for the GPU and the call can be captured into a HIP graph; it returns an ``AsyncWaveforms``.
 """
 import ctypes as C
 import math
@@ -22,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .fastspeech import AsyncMels, Fs2CapacityError
 
 N_FFT, HOP, WIN, N_BINS = 1024, 256, 1024, 513
 _AUDIO_DEFAULTS = dict(sample_rate=22050, n_fft=1024, n_mels=80, fmin=0.0, fmax=8000.0)
@@ -143,6 +148,31 @@ def tile_span(n_fft, hop, L, f0, rule=None):
     return max(0, min(f0 - r["halo"], L - r["tail"])), min(L - 1, f0 + nf - 1 + r["halo"])
 
 
+# ---- slot rule of the device-driven planner (csrc/gl_slot_rule.h: gl_tile_count, gl_slot_capacity, gl_slot_tile), restated ----
+def slot_capacity(frame_capacity, F, B):
+    """Workgroups of a device-driven call: enough for the tiles of any batch of B utterances with sum L <= frame_capacity."""
+    return int(frame_capacity) // int(F) + int(B)
+
+
+def slot_tiles(lens, F, frame_capacity):
+    """int array [slots, 2] of (utterance, first frame) the planner gives each slot, (-1, 0) for a slot without a tile: the batch's
+    tiles in batch order (``f0 = 0, F, 2F, ..`` per utterance with L >= 2), found as the kernel finds them, by binary search in the
+    inclusive prefix sum of the tile counts."""
+    L = np.asarray(lens, np.int64).reshape(-1)
+    F = int(F)
+    counts = np.where(L >= 2, -(-L // F), 0)
+    end = np.cumsum(counts)
+    slots = np.arange(slot_capacity(frame_capacity, F, L.size), dtype=np.int64)
+    b = np.searchsorted(end, slots, side="right")             # first b with end[b] > slot
+    out = np.zeros((slots.size, 2), np.int64)
+    out[:, 0] = -1
+    has = b < L.size
+    bb = b[has]
+    out[has, 0] = bb
+    out[has, 1] = (slots[has] - (end[bb] - counts[bb])) * F
+    return out
+
+
 # ---- seeded initial phase: the formula of csrc/griffin_lim.h (gl_seed_angle), restated ----
 def _mix32(x):
     x = np.asarray(x, np.uint32).copy()
@@ -178,6 +208,72 @@ class Waveforms(NamedTuple):
 def split(wav, sample_lens):
     """Packed waveform -> list of per-utterance tensors (views)."""
     return list(torch.split(wav, [int(n) for n in sample_lens]))
+
+
+FS2_OVF_UPSTREAM = 32    # include/fs2.h: the producer of the frames had flagged its own status
+
+
+class _WavRecord:
+    """Status of one sync-free vocoder call, copied to pinned host memory behind its kernels.  The pinned block belongs to a ring:
+    the first look after the event has fired moves the flags into the record (a block is resolved before another call gets it)."""
+    __slots__ = ("event", "pin", "_status")
+
+    def __init__(self, event, pin):
+        self.event, self.pin, self._status = event, pin, None
+
+    def status(self):
+        if self._status is None:
+            self.event.synchronize()
+            self._status = [int(v) for v in self.pin]
+            self.pin = None
+        return self._status
+
+
+class AsyncWaveforms(tuple):
+    """What ``GriffinLim(...)(..., sync=False)`` returns: unpacks like ``(wav, sample_lens_dev)`` -- ``wav`` float32 [capacity]
+    whose first ``sum(sample_lens)`` samples are the utterances back to back and the rest zero, or with ``padded_out=True``
+    [B, hop (Lcap - 1)] zero-padded; ``sample_lens_dev`` a DEVICE int64 [B].  ``status`` is the device int32[8] of
+    fs2_op_griffin_lim_dev ({frames, tiles, flags, longest utterance, valid samples, ...}).  ``ok()`` waits for THIS call (its own
+    event and pinned copy of the status) and tells whether its capacities sufficed and its frame counts were valid; ``check()``
+    raises ``Fs2CapacityError`` instead.  On any flag the whole ``wav`` is NaN and ``sample_lens_dev`` zero.  A call made under
+    stream capture keeps no host-side record: read ``status`` after the replay."""
+
+    def __new__(cls, wav, sample_lens, status, record, padded=False):
+        self = super().__new__(cls, (wav, sample_lens))
+        self.status, self._record, self.padded = status, record, padded
+        return self
+
+    @property
+    def wav(self):
+        return self[0]
+
+    @property
+    def sample_lens(self):
+        return self[1]
+
+    def flags(self):
+        """The flag word of this call (waits for it); 0 for a call captured into a graph, which keeps no record."""
+        return 0 if self._record is None else self._record.status()[2]
+
+    def ok(self):
+        return self.flags() == 0
+
+    def check(self):
+        fl = self.flags()
+        if fl:
+            why = "the mel call that produced the frames had flagged its own status" if fl & FS2_OVF_UPSTREAM else \
+                "a capacity was too small or a frame count invalid"
+            raise Fs2CapacityError("device-driven vocoder: %s (flags %d); the waveforms of the call are NaN-filled: rerun with "
+                                   "sync=True or a larger capacity" % (why, fl))
+        return self
+
+    def split(self):
+        """List of per-utterance waveforms (views).  WAITS for the call: the sample counts are read back to the host."""
+        self.check()
+        n = [int(v) for v in self[1].cpu()]
+        if self.padded:
+            return [self[0][b, :k] for b, k in enumerate(n)]
+        return list(torch.split(self[0][:sum(n)], n))
 
 
 def _require_cuda(x, name):
@@ -229,12 +325,22 @@ class GriffinLim:
                                  torch.tensor(self._basis_np, dtype=torch.float32, device=device).contiguous())
         return self._dev[device]
 
-    def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False):
+    def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
+                 padded_out=False):
         """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
         with ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
         [.., n_fft / 2 + 1] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout
         of ``mels`` with n_fft / 2 + 1 bins, or None: seeded.  ``momentum`` > 0: fast Griffin-Lim (0 = the reference).  Runs on the
-        current stream of the input's device without synchronising."""
+        current stream of the input's device without synchronising.
+
+        ``sync=True`` reads ``olens`` on the host (a CUDA ``olens`` is copied back, which waits for the GPU) and sizes the result
+        from it.  ``sync=False``: the frame counts stay on the device -- ``olens`` must be a CUDA int64 tensor, or ``mels`` an
+        :class:`AsyncMels` (``inference_batch(sync=False)``), whose mels, ``olens`` and status are taken -- and nothing waits for
+        the GPU; see :meth:`_call_dev`.  Returns an :class:`AsyncWaveforms`."""
+        if not sync:
+            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out)
+        if capacity is not None or padded_out:
+            raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
         _require_cuda(mels, "mels")
         g = self.geometry
         NB = g.n_bins
@@ -288,6 +394,112 @@ class GriffinLim:
                                                    init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
                                                    wav.data_ptr()))
         return Waveforms(wav, sample_lens)
+
+
+    _PIN_SLOTS = 16
+
+    def _record(self, status, dev):
+        """Queue a pinned copy of a call's status behind its kernels; an event tells when it is there."""
+        ring = self.__dict__.setdefault("_pin_ring", [])
+        if len(ring) < self._PIN_SLOTS:
+            ring.append([torch.empty(8, dtype=torch.int32).pin_memory(), None])
+            slot = ring[-1]
+        else:
+            i = self.__dict__.get("_pin_next", 0)
+            slot, self._pin_next = ring[i], (i + 1) % self._PIN_SLOTS
+            if slot[1] is not None:
+                slot[1].status()                   # a call still in flight owns the block: wait for it and keep its values
+        slot[0].copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        slot[1] = _WavRecord(ev, slot[0])
+        return slot[1]
+
+    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out):
+        """The device-driven call (include/fs2.h: fs2_op_griffin_lim_dev).  ``capacity``: bound on the batch's total frames (default:
+        the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the waveform is
+        sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only) [B, hop (Lcap - 1)].
+        Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own call overflowed, give
+        a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``."""
+        upstream = None
+        if isinstance(mels, AsyncMels):
+            if olens is not None:
+                raise ValueError("olens is taken from the AsyncMels given as mels; pass one or the other")
+            upstream = mels.status
+            mels, olens = mels
+        if not isinstance(olens, torch.Tensor):
+            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), got %s"
+                            % type(olens).__name__)
+        if olens.dtype != torch.int64:
+            raise TypeError("olens must be int64 with sync=False, got %s" % olens.dtype)
+        if capacity is not None and int(capacity) < 1:
+            raise ValueError("capacity must be >= 1, got %r" % (capacity,))
+        if not olens.is_cuda:
+            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), it is on %s; "
+                            "use sync=True for host lengths" % olens.device)
+        _require_cuda(mels, "mels")
+        g = self.geometry
+        NB = g.n_bins
+        W = NB if magnitudes else g.n_mels
+        if mels.dim() not in (2, 3) or mels.shape[-1] != W:
+            raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
+        if self.device is not None and mels.device != self.device:
+            raise ValueError("mels on %s, this GriffinLim on %s" % (mels.device, self.device))
+        if olens.device != mels.device:
+            raise ValueError("olens on %s, mels on %s" % (olens.device, mels.device))
+        n_iter, momentum = int(n_iter), float(momentum)
+        if n_iter < 0:
+            raise ValueError("n_iter must be >= 0")
+        if not (momentum >= 0.0 and math.isfinite(momentum)):
+            raise ValueError("momentum must be finite and >= 0")
+        olens = olens.reshape(-1).contiguous()
+        B = olens.numel()
+        if mels.dim() == 2:
+            rows, stride, Lcap = mels.shape[0], 0, None
+            if padded_out:
+                raise ValueError("padded_out needs padded mels [B, Lcap, %d] (the waveform's row length is hop * (Lcap - 1))" % W)
+            if capacity is not None and int(capacity) > rows:
+                raise ValueError("capacity %d exceeds the %d rows of the packed mels" % (int(capacity), rows))
+            src = mels
+        else:
+            if mels.shape[0] != B:
+                raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
+            Lcap = mels.shape[1]
+            rows, stride = B * Lcap, Lcap
+            src = mels.reshape(rows, W)
+        cap = rows if capacity is None else min(int(capacity), rows)
+        if init_phase is not None:
+            _require_cuda(init_phase, "init_phase")
+            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
+                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
+            init_phase = init_phase.reshape(-1, NB).contiguous().float()
+        src = src.contiguous().float()
+        dev = mels.device
+        padded = bool(padded_out) and Lcap >= 2
+        wav_stride = g.hop * (Lcap - 1) if padded else 0
+        wav_cap = B * wav_stride if padded_out else g.hop * max(cap - 1, 0)        # (padded_out at Lcap < 2: no utterance owns a sample)
+        if cap * NB >= 2 ** 31 or wav_cap >= 2 ** 31:
+            raise ValueError("capacity too large for one call (%d frames)" % cap)
+        with torch.cuda.device(dev):
+            wav = torch.empty(wav_cap, dtype=torch.float32, device=dev)
+            shaped = wav.reshape(B, wav_stride) if padded_out else wav
+            if B == 0 or cap == 0:
+                return AsyncWaveforms(shaped, torch.zeros(B, dtype=torch.int64, device=dev), torch.zeros(8, dtype=torch.int32, device=dev),
+                                      None, bool(padded_out))
+            sample_lens = torch.empty(B, dtype=torch.int64, device=dev)        # both written in full by the planner
+            status = torch.empty(8, dtype=torch.int32, device=dev)
+            lib = _lib.lib()
+            ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_cap(*g, B, cap))
+            pinv = self.constants(dev)[0] if not magnitudes else None
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.fs2_op_griffin_lim_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, B,
+                                                  olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
+                                                  n_iter, momentum, int(seed) & 0xFFFFFFFF,
+                                                  init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
+                                                  wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(),
+                                                  status.data_ptr()))
+            rec = None if torch.cuda.is_current_stream_capturing() else self._record(status, dev)
+        return AsyncWaveforms(shaped, sample_lens, status, rec, bool(padded_out))
 
 
 _DEFAULT_GL = None

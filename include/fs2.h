@@ -191,6 +191,10 @@ typedef struct fs2_decode_io {
 #define FS2_OVF_EMPTY 8       /* an utterance has no frames                                                  */
 #define FS2_OVF_BAD_ID 16     /* an utterance holds a phoneme id outside [0, idim): fs2_encode left the frame count -1
                                  for it (the reference's torch.nn.Embedding raises, fastspeech.py:65-67)                */
+/* flags of the device-driven vocoder only (fs2_op_griffin_lim_dev, below; it also reports FS2_OVF_ROWS / FS2_OVF_LMAX) */
+#define FS2_OVF_UPSTREAM 32   /* the status block of the call that produced the frames carries flags (they are OR-ed in as well) */
+#define FS2_OVF_NEG_LEN 64    /* a frame count is negative                                                    */
+#define FS2_OVF_WAV 128       /* packed samples needed > wav_capacity                                         */
 
 /* rows to reserve for fs2_decode's device-driven layout given an estimate of the total frame count (alignment
  * and gap rows of the packed layout included) */
@@ -329,6 +333,34 @@ size_t fs2_op_stft_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win,
 int fs2_op_stft_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *wav, int32_t B,
                      const int32_t *wav_starts, const int32_t *wav_lens, void *workspace, size_t workspace_bytes, float *mag,
                      const float *mel_basis, float *logmel, float *energy);
+
+/* ---- Device-driven Griffin-Lim: the frame counts stay on the device (what fs2_decode's device-driven layout leaves there), so mel
+ * frames become waveforms without a host read-back in between.  The tiles are planned by kernels inside capacities the host knows;
+ * grids are sized for the capacities and surplus workgroups exit at once.  Results equal those of fs2_op_griffin_lim_geom for the same
+ * frame counts bit for bit. ---- */
+
+/* workspace bytes for B utterances whose frame counts sum to at most frame_capacity (host only; 0 on a bad argument); never less
+ * than fs2_op_vocode_workspace_bytes_geom gives for any such batch */
+size_t fs2_op_vocode_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity);
+
+/* lens_dev: DEVICE int64 [B] frames per utterance.  src_stride 0: packed source, utterance b starts at row sum_{j<b} L_j and src
+ * (and init_phase) hold frame_capacity rows; src_stride > 0: padded source, utterance b starts at row b * src_stride and src holds
+ * B * src_stride rows.  wav_stride 0: packed waveform as fs2_op_griffin_lim_geom writes it, the samples of wav [wav_capacity] beyond
+ * the valid ones zero; wav_stride > 0: utterance b at wav + b * wav_stride (B * wav_stride <= wav_capacity), zero beyond its own
+ * samples.  sample_lens_dev: device int64 [B] = hop * max(L_b - 1, 0).  upstream_status: the device int32[8] status of the
+ * fs2_decode that produced src, or NULL.  status: device int32[8] = {frames used, tiles used, flags, longest utterance, valid
+ * samples, 0, 0, 0}.  flags != 0 (FS2_OVF_NEG_LEN: an L_b < 0; FS2_OVF_ROWS: sum L_b > frame_capacity; FS2_OVF_LMAX: an L_b >
+ * src_stride or hop * (L_b - 1) > wav_stride; FS2_OVF_WAV: packed samples > wav_capacity; FS2_OVF_UPSTREAM | the upstream flags)
+ * means nothing was vocoded: all wav_capacity samples are NaN and sample_lens_dev is zero.  The lengths are validated on the device
+ * before any tile is planned: whatever lens_dev holds, nothing outside src, the workspace and wav as sized above is touched.
+ * Asynchronous on `stream`: no allocation, no host read of device memory, no synchronisation; may be called while the stream is
+ * being captured into a graph (after one call outside a capture for a geometry other than the default one).  Host-checked limits:
+ * B >= 1, 1 <= frame_capacity, frame_capacity * bins < 2^31, wav_capacity < 2^31. */
+int fs2_op_griffin_lim_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                           const float *mel_pinv, int32_t B, const int64_t *lens_dev, int32_t src_stride, int64_t frame_capacity,
+                           const int32_t *upstream_status, int32_t n_iter, float momentum, uint32_t seed, const float *init_phase,
+                           void *workspace, size_t workspace_bytes, float *wav, int32_t wav_stride, int64_t wav_capacity,
+                           int64_t *sample_lens_dev, int32_t *status);
 
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same

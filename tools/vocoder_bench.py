@@ -12,6 +12,13 @@ Usage:  python tools/vocoder_bench.py [--n-iter 30] [--min-s 0.5] [--workload c3
 utterances' audio durations (olens x 256 / 22050 s) at SR, as synthetic harmonic waveforms whose magnitudes come from
 stft_magnitude at that geometry; 30 iterations of the HIP path and of TorchGL at the same geometry are each timed K times
 (median and max - min spread reported).  With neither flag the run is the default one above.
+
+--pipeline [--steps K] [--repeats R] [--precision P] [--pipeline-workloads c3,c1]: text -> waveform end to end at c3 and at c1 (one utterance), per step, in three
+forms timed alternately (R rounds of K steps each per form; median and max - min spread over the rounds):
+  (a) sync      synchronous inference_batch(packed=True), then the host-driven GriffinLim(mels, olens)
+  (b) async     both halves sync=False (AsyncMels -> AsyncWaveforms), three steps in flight on StepStreams(3)
+  (c) graph     c1 only: capture_graph(vocoder=gl), one graph launch per step
+Every region is K steps between two device synchronisations; (b) and (c) are checked for flags afterwards.
 """
 import argparse
 import json
@@ -88,8 +95,14 @@ def main():
     ap.add_argument("--geometry", default=None, help="n_fft,hop,win_length (default: the 1024,256,1024 run)")
     ap.add_argument("--sample-rate", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=5, help="timings per path in the --geometry run")
+    ap.add_argument("--pipeline", action="store_true", help="time text -> wav end to end (see the module docstring)")
+    ap.add_argument("--pipeline-workloads", default="c3,c1", help="workloads of the --pipeline run (the graph form runs at c1 only)")
+    ap.add_argument("--steps", type=int, default=20, help="steps per timed region of the --pipeline run")
+    ap.add_argument("--precision", default="mix_mx4", help="the model's arithmetic mode in the --pipeline run (bench.py's default)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "vocoder_bench needs a GPU"
+    if args.pipeline:
+        return pipeline_main(args)
     if args.geometry is not None or args.sample_rate is not None:
         return geometry_main(args)
     from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude
@@ -141,6 +154,80 @@ def main():
         sc_torch = float(torch.linalg.norm(Mt - Xt)) / float(torch.linalg.norm(Mt)) if Xt.shape == Mt.shape else float("nan")
         rec.update(torch_ms_per_call=round(ms_torch, 3), torch_reps=treps, speedup_vs_torch=round(ms_torch / ms_call, 2),
                    sc_torch=round(sc_torch, 5))
+    print(json.dumps(rec))
+
+
+def pipeline_main(args):
+    from fastspeech2_amd import FeedForwardTransformer, StepStreams, default_hparams, N_PHONEME_SYMBOLS
+    from fastspeech2_amd.synthetic import portable_state_dict, ljspeech_durations, make_batch
+    from fastspeech2_amd.vocoder import GriffinLim
+    hp = default_hparams()
+    model = FeedForwardTransformer(N_PHONEME_SYMBOLS, hp.audio.num_mels, hp).eval()
+    model.load_state_dict(ljspeech_durations(portable_state_dict(model.state_dict(), seed=0)))
+    model = model.cuda()
+    model.precision = args.precision
+    gl = GriffinLim(hp)
+    K, n_iter = args.steps, args.n_iter
+    rec = dict(mode="pipeline", precision=args.precision, n_iter=n_iter, steps_per_region=K, rounds=args.repeats, workloads={})
+
+    def region(step, finish=None):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(K):
+            step()
+        if finish is not None:
+            finish()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / K * 1e3
+
+    with torch.no_grad():
+        for workload in args.pipeline_workloads.split(","):
+            b = make_batch(workload)
+            xs, il = b["xs"].cuda(), b["ilens"]
+            mels, olens = model.inference_batch(xs, il, packed=True)          # (first call: synchronous, learns the capacities)
+            ref = gl(mels, olens, n_iter=n_iter)
+
+            def step_sync():
+                m, ol = model.inference_batch(xs, il, packed=True)
+                return gl(m, ol, n_iter=n_iter)
+
+            rot = StepStreams(3)
+            keep = []
+
+            def step_async():
+                with rot.next():
+                    am = model.inference_batch(xs, il, packed=True, sync=False)
+                    keep.append((am, gl(am, n_iter=n_iter, sync=False)))
+                del keep[:-3]                                                   # (three steps in flight own their buffers)
+
+            forms = {"sync": (step_sync, None), "async": (step_async, rot.join)}
+            if workload == "c1":
+                run = model.capture_graph(xs, il, vocoder=gl, n_iter=n_iter)
+                forms["graph"] = (lambda: run(xs), None)
+            for step, finish in forms.values():                                # warm-up of every form
+                region(step, finish)
+            ms = {k: [] for k in forms}
+            for _ in range(args.repeats):                                       # alternating: one region of each form per round
+                for k, (step, finish) in forms.items():
+                    ms[k].append(region(step, finish))
+            # validity, and that the three forms computed the same waveform
+            am, w = keep[-1]
+            ok = bool(model.async_ok() and am.ok() and w.ok())
+            n = int(ref.wav.numel())
+            same = bool(torch.equal(w[0][:n], ref.wav))
+            out = dict(utterances=int(il.numel()), frames=int(sum(int(x) for x in olens)), samples=n, async_ok=ok, async_equals_sync=same)
+            if "graph" in forms:
+                wav, sl, status = run(xs)
+                out["graph_flags"] = int(status.cpu()[2])
+                out["graph_equals_sync"] = bool(torch.equal(torch.cat([wav[i, :int(k)] for i, k in enumerate(sl.cpu())]), ref.wav))
+            for k, v in ms.items():
+                out[k + "_ms_per_step"] = round(float(np.median(v)), 4)
+                out[k + "_ms_spread"] = round(max(v) - min(v), 4)
+                out[k + "_ms_runs"] = [round(x, 4) for x in v]
+            out["async_over_sync"] = round(out["async_ms_per_step"] / out["sync_ms_per_step"], 4)
+            if "graph" in forms:
+                out["graph_over_sync"] = round(out["graph_ms_per_step"] / out["sync_ms_per_step"], 4)
+            rec["workloads"][workload] = out
     print(json.dumps(rec))
 
 
