@@ -1698,279 +1698,7 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 
 
 // ---------------------------------------------------------------------------------- vocoder (griffin_lim.h)
-// Geometry of a call: validated (n_fft, hop, win, n_mels) plus the tile rule (F, halo, tail frame, L_min, signal buffer) derived from it.
-struct GlGeomHost {
-    int n_fft = kGlNfft, hop = kGlHop, win = kGlNfft, n_mels = 80, n_bins = kGlBins;
-    GlGeom g{};
-    size_t sig_bytes = 0;                // dynamic LDS of the fused kernel (0: the default instantiation, static LDS)
-    bool is_default() const { return n_fft == kGlNfft && hop == kGlHop; }
-};
-
-int gl_geom(int n_fft, int hop, int win, int n_mels, const char* who, GlGeomHost& out) {
-    GlGeomHost h;
-    h.n_fft = n_fft; h.hop = hop; h.win = win; h.n_mels = n_mels;
-    if (h.n_fft != 512 && h.n_fft != 1024 && h.n_fft != 2048)
-        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: n_fft %d (512, 1024 or 2048)", who, h.n_fft);
-    if (h.hop < 1 || h.hop > h.win || h.win > h.n_fft || (h.n_fft + h.hop - 1) / h.hop > 8)
-        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: hop %d, win %d at n_fft %d (hop <= win <= n_fft, ceil(n_fft / hop) <= 8)", who, h.hop, h.win, h.n_fft);
-    if (h.n_mels < 1 || h.n_mels > kGlMaxMels) return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: n_mels %d (1 .. %d)", who, h.n_mels, kGlMaxMels);
-    h.n_bins = h.n_fft / 2 + 1;
-    h.g.hop = h.hop;
-    h.g.F = h.is_default() ? kGlTile : gl_tile_frames(h.n_fft, h.hop);
-    h.g.halo = gl_halo(h.n_fft, h.hop);
-    h.g.tail = gl_tail(h.n_fft, h.hop);
-    h.g.lmin = gl_lmin(h.n_fft, h.hop);
-    h.g.sig_max = gl_sig_max(h.n_fft, h.hop, h.g.F);
-    h.g.n_mels = h.n_mels;
-    h.sig_bytes = h.is_default() ? 0 : (size_t)h.g.sig_max * sizeof(float);
-    out = h;
-    return FS2_OK;
-}
-
-// Workspace of fs2_op_griffin_lim / fs2_op_stft: tables, tile records, then (synthesis only) M, the two spectrum buffers and the
-// momentum state, all over the utterances' frames packed back to back.  frames[b] = L_b; tiles cover utterances with L_b >= 2
-// (synthesis: they own samples) or every utterance with frames (analysis).
-struct GlPlan {
-    std::vector<GlTile> tiles;
-    int64_t frames = 0, samples = 0;
-    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
-};
-
-// analysis = false: lens are frame counts L_b, samples hop max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
-// frames T_b / hop + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
-int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p) {
-    if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
-    const int hop = gh.hop, F = gh.g.F, nb = gh.n_bins;
-    int64_t row = 0, wav = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "vocoder: negative length / start of utterance %d", b);
-        const int L = analysis ? lens[b] / hop + 1 : lens[b];
-        const int64_t T = analysis ? (int64_t)lens[b] : (int64_t)hop * std::max(L - 1, 0);
-        const bool owns = analysis ? L > 0 : L >= 2;
-        if (T > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: utterance %d too long (%lld samples)", b, (long long)T);
-        if (owns)
-            for (int f0 = 0; f0 < L; f0 += F) {
-                GlTile t{};
-                t.src_row0 = analysis ? (int)row : (starts ? starts[b] : 0);
-                t.ws_row0 = (int)row;
-                t.L = L; t.f0 = f0; t.T = (int)T;
-                t.wav0 = analysis ? (starts ? starts[b] : 0) : (int)wav;
-                p.tiles.push_back(t);
-            }
-        row += L;
-        wav += T;
-        if (row > INT32_MAX / nb || wav > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: batch too large (%lld frames, %lld samples)", (long long)row, (long long)wav);
-    }
-    p.frames = row;
-    p.samples = wav;
-    size_t off = 0;
-    auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
-    p.off_tw = take(gh.n_fft * sizeof(float2));
-    p.off_win = take(gh.n_fft * sizeof(float));
-    p.off_tiles = take(std::max<size_t>(p.tiles.size(), 1) * sizeof(GlTile));
-    if (!analysis) {
-        const size_t n = (size_t)p.frames * nb;
-        p.off_M = take(n * sizeof(float));
-        p.off_C0 = take(n * sizeof(float2));
-        p.off_C1 = take(n * sizeof(float2));
-        p.off_T = take(n * sizeof(float2));
-    }
-    p.bytes = align_up(off, 256);
-    return FS2_OK;
-}
-
-// tables + tile records into the workspace (kernel arguments, no host copy)
-hipError_t gl_setup(hipStream_t s, const GlPlan& p, const GlGeomHost& gh, char* ws) {
-    hipLaunchKernelGGL(gl_tables, dim3((gh.n_fft + 255) / 256), dim3(256), 0, s, (float2*)(ws + p.off_tw), (float*)(ws + p.off_win),
-                       gh.n_fft, gh.win);
-    for (size_t i = 0; i < p.tiles.size(); i += kGlTilesPerChunk) {
-        GlTileChunk c{};
-        c.n = (int)std::min<size_t>(kGlTilesPerChunk, p.tiles.size() - i);
-        c.base = (int)i;
-        std::copy(p.tiles.begin() + i, p.tiles.begin() + i + c.n, c.t);
-        hipLaunchKernelGGL(gl_upload_tiles, dim3(1), dim3(128), 0, s, c, (GlTile*)(ws + p.off_tiles));
-    }
-    return hipGetLastError();
-}
-
-struct GlIterArgs {
-    const GlTile* tiles; const float2* tw; const float* win; const float* M; float2* C[2]; float2* Tm; float beta; float* wav;
-};
-
-// prologue, n_iter fused iterations and the final ISTFT of one geometry (NFFT; HOP_C = 256: the default instantiation)
-template <int NFFT, int HOP_C>
-hipError_t gl_run(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const float* src, int src_width, const float* pinv,
-                  const float* init_phase, uint32_t seed, int n_iter, const GlIterArgs& a) {
-    const dim3 grid(n_tiles), blk(kGlThreads);
-    const GlGeom g = gh.g;
-    const size_t lds = gh.sig_bytes;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (lds && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-    if (lds && cap == hipStreamCaptureStatusNone) {     // (one-time host work: a captured call relies on the eager call before it)
-        hipError_t e;
-        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void*)gl_iterate<NFFT, HOP_C, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    }
-    if (src_width == 80 && gh.n_mels == 80 && src_width != gh.n_bins)
-        hipLaunchKernelGGL((gl_prologue<NFFT, 80>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
-    else
-        hipLaunchKernelGGL((gl_prologue<NFFT, 0>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
-    for (int it = 0; it < n_iter; ++it) {
-        if (a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
-        else hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
-    }
-    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[n_iter & 1], a.C[(n_iter + 1) & 1], nullptr, 0.f, a.wav);
-    return hipGetLastError();
-}
-
-int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                   const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
-                   void* workspace, size_t workspace_bytes, float* wav) {
-    if (src_width != gh.n_mels && src_width != gh.n_bins)
-        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
-                    gh.n_bins, gh.n_fft);
-    if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
-    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
-    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    GlPlan p;
-    if (int rc = gl_plan(B, starts, lens, false, gh, p)) return rc;
-    if (p.tiles.empty()) return FS2_OK;
-    if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, gh, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
-    GlIterArgs a{};
-    a.tiles = (const GlTile*)(ws + p.off_tiles);
-    a.tw = (const float2*)(ws + p.off_tw);
-    a.win = (const float*)(ws + p.off_win);
-    a.M = (const float*)(ws + p.off_M);
-    a.C[0] = (float2*)(ws + p.off_C0);
-    a.C[1] = (float2*)(ws + p.off_C1);
-    a.Tm = momentum > 0.f ? (float2*)(ws + p.off_T) : nullptr;
-    a.beta = momentum / (1.f + momentum);
-    a.wav = wav;
-    const unsigned nt = (unsigned)p.tiles.size();
-    if (gh.is_default()) e = gl_run<1024, kGlHop>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else if (gh.n_fft == 512) e = gl_run<512, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else if (gh.n_fft == 1024) e = gl_run<1024, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else e = gl_run<2048, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
-    return FS2_OK;
-}
-
-static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvfUpstream == FS2_OVF_UPSTREAM && kGlOvfNegative == FS2_OVF_NEG_LEN &&
-              kGlOvfWav == FS2_OVF_WAV, "griffin_lim.h restates the FS2_OVF_* bits");
-
-// Workspace of the device-driven call: the layout of gl_plan with every size taken from the capacities, plus the planner's
-// per-utterance arrays.  0 slots / 0 frames still reserve one record, as gl_plan does.
-struct GlCapLayout {
-    int64_t slots = 0;
-    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
-};
-
-bool gl_cap_layout(const GlGeomHost& gh, int64_t B, int64_t frame_capacity, GlCapLayout& c) {
-    if (B < 0 || frame_capacity < 0 || frame_capacity > INT32_MAX / gh.n_bins) return false;
-    c.slots = gl_slot_capacity(frame_capacity, gh.g.F, (int)B);
-    if (c.slots > INT32_MAX) return false;
-    size_t off = 0;
-    auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
-    c.off_tw = take(gh.n_fft * sizeof(float2));
-    c.off_win = take(gh.n_fft * sizeof(float));
-    c.off_tiles = take(std::max<size_t>((size_t)c.slots, 1) * sizeof(GlTile));
-    c.off_plan = take(std::max<size_t>((size_t)B, 1) * 4 * sizeof(int));
-    const size_t n = (size_t)frame_capacity * gh.n_bins;
-    c.off_M = take(n * sizeof(float));
-    c.off_C0 = take(n * sizeof(float2));
-    c.off_C1 = take(n * sizeof(float2));
-    c.off_T = take(n * sizeof(float2));
-    c.bytes = align_up(off, 256);
-    return true;
-}
-
-int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                       const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
-                       float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav,
-                       int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
-    if (src_width != gh.n_mels && src_width != gh.n_bins)
-        return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
-                    gh.n_bins, gh.n_fft);
-    if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
-    if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
-    if (B < 1 || frame_capacity < 1 || src_stride < 0 || wav_stride < 0)
-        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d", who, B, (long long)frame_capacity, src_stride, wav_stride);
-    if (frame_capacity > INT32_MAX / gh.n_bins || wav_capacity < 0 || wav_capacity > INT32_MAX || (int64_t)B * src_stride > INT32_MAX)
-        return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call (%lld frames, %lld samples)", who, (long long)frame_capacity, (long long)wav_capacity);
-    if ((int64_t)B * wav_stride > wav_capacity)
-        return fail(nullptr, FS2_ERR_ARG, "%s: padded output of %d x %d samples in a wav of %lld", who, B, wav_stride, (long long)wav_capacity);
-    if (!src || !lens_dev || !workspace || !sample_lens_dev || !status || (wav_capacity > 0 && !wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    GlCapLayout c;
-    if (!gl_cap_layout(gh, B, frame_capacity, c)) return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call", who);
-    if (workspace_bytes < c.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, c.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipLaunchKernelGGL(gl_tables, dim3((gh.n_fft + 255) / 256), dim3(256), 0, s, (float2*)(ws + c.off_tw), (float*)(ws + c.off_win), gh.n_fft, gh.win);
-    GlPlanArgs pa{};
-    pa.lens = lens_dev; pa.upstream = upstream_status;
-    pa.B = B; pa.hop = gh.hop; pa.F = gh.g.F;
-    pa.src_stride = src_stride; pa.wav_stride = wav_stride;
-    pa.frame_capacity = frame_capacity; pa.wav_capacity = wav_capacity;
-    int* plan = (int*)(ws + c.off_plan);
-    pa.row0 = plan; pa.wav0 = plan + B; pa.tile_end = plan + 2 * (size_t)B; pa.Lv = plan + 3 * (size_t)B;
-    pa.sample_lens = sample_lens_dev; pa.status = status;
-    const int n_slots = (int)c.slots;        // >= B >= 1
-    hipLaunchKernelGGL(gl_plan_scan, dim3(1), dim3(kGlPlanThreads), 0, s, pa);
-    hipLaunchKernelGGL(gl_plan_emit, dim3((n_slots + 255) / 256), dim3(256), 0, s, pa, n_slots, (GlTile*)(ws + c.off_tiles));
-    if (wav_capacity > 0)
-        hipLaunchKernelGGL(gl_plan_fill, dim3((unsigned)std::min<int64_t>((wav_capacity + 1023) / 1024, 2048)), dim3(256), 0, s, pa, wav);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim plan: %s", hipGetErrorString(e));
-    GlIterArgs a{};
-    a.tiles = (const GlTile*)(ws + c.off_tiles);
-    a.tw = (const float2*)(ws + c.off_tw);
-    a.win = (const float*)(ws + c.off_win);
-    a.M = (const float*)(ws + c.off_M);
-    a.C[0] = (float2*)(ws + c.off_C0);
-    a.C[1] = (float2*)(ws + c.off_C1);
-    a.Tm = momentum > 0.f ? (float2*)(ws + c.off_T) : nullptr;
-    a.beta = momentum / (1.f + momentum);
-    a.wav = wav;
-    const unsigned nt = (unsigned)n_slots;
-    if (gh.is_default()) e = gl_run<1024, kGlHop>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else if (gh.n_fft == 512) e = gl_run<512, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else if (gh.n_fft == 1024) e = gl_run<1024, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    else e = gl_run<2048, 0>(s, gh, nt, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
-    return FS2_OK;
-}
-
-int gl_stft_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,
-                const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy) {
-    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
-    GlPlan p;
-    if (int rc = gl_plan(B, wav_starts, wav_lens, true, gh, p)) return rc;
-    if (p.tiles.empty() || (!mag && !logmel && !energy)) return FS2_OK;
-    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    if (workspace_bytes < p.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, gh, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
-    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
-    const GlTile* tiles = (const GlTile*)(ws + p.off_tiles);
-    const float2* tw = (const float2*)(ws + p.off_tw);
-    const float* win = (const float*)(ws + p.off_win);
-    if (gh.is_default()) hipLaunchKernelGGL((gl_stft<1024, kGlHop>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
-    else if (gh.n_fft == 512) hipLaunchKernelGGL((gl_stft<512, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
-    else if (gh.n_fft == 1024) hipLaunchKernelGGL((gl_stft<1024, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
-    else hipLaunchKernelGGL((gl_stft<2048, 0>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
-    return FS2_OK;
-}
+#include "griffin_lim_host.h"
 
 }  // namespace
 
@@ -2711,7 +2439,7 @@ size_t fs2_op_vocode_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t wi
     GlGeomHost gh;
     GlPlan p;
     if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, lens, false, gh, p) == FS2_OK ? p.bytes : 0;
+    return gl_plan(B, nullptr, lens, false, gh, p) == FS2_OK ? p.at.bytes : 0;
 }
 
 int fs2_op_griffin_lim(void* stream, const float* src, int32_t src_width, const float* mel_pinv, int32_t B, const int32_t* starts,
@@ -2734,9 +2462,9 @@ int fs2_op_griffin_lim_geom(void* stream, int32_t n_fft, int32_t hop, int32_t wi
 
 size_t fs2_op_vocode_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
     GlGeomHost gh;
-    GlCapLayout c;
     if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_cap", gh)) return 0;
-    return gl_cap_layout(gh, B, frame_capacity, c) ? c.bytes : 0;
+    const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
+    return slots < 0 ? 0 : gl_layout(gh, (size_t)slots, B, frame_capacity, false).bytes;
 }
 
 int fs2_op_griffin_lim_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
@@ -2755,7 +2483,7 @@ size_t fs2_op_stft_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win,
     GlGeomHost gh;
     GlPlan p;
     if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, wav_lens, true, gh, p) == FS2_OK ? p.bytes : 0;
+    return gl_plan(B, nullptr, wav_lens, true, gh, p) == FS2_OK ? p.at.bytes : 0;
 }
 
 int fs2_op_stft(void* stream, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens, void* workspace,

@@ -10,7 +10,7 @@
 
 namespace fs2 {
 
-// tiles of an utterance of L frames (the host plan's rule, fs2_runtime.hip: gl_plan)
+// tiles of an utterance of L frames (the host plan's rule, griffin_lim_host.h: gl_plan)
 GL_HD constexpr int gl_tile_count(int L, int F) { return L >= 2 ? (L + F - 1) / F : 0; }
 
 // slots that hold the tiles of ANY batch of B utterances with sum L <= frame_capacity: ceil(L / F) <= L / F + (F - 1) / F, so

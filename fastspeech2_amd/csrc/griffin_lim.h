@@ -590,7 +590,7 @@ __global__ __launch_bounds__(kGlPlanThreads) void gl_plan_scan(GlPlanArgs a) {
     }
 }
 
-// One thread per slot: the GlTile the host plan (fs2_runtime.hip: gl_plan) writes for the slot's tile, or an empty record.
+// One thread per slot: the GlTile the host plan (griffin_lim_host.h: gl_plan) writes for the slot's tile, or an empty record.
 __global__ void gl_plan_emit(GlPlanArgs a, int n_slots, GlTile* tiles) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slots) return;

@@ -316,6 +316,7 @@ class GriffinLim:
         self._basis_np = B
         self._pinv_np = np.linalg.pinv(B)          # [bins, n_mels], float64 on the host
         self._dev = {}
+        self._pin_ring, self._pin_next = [], 0     # pinned status blocks of the sync=False calls (_record)
 
     def constants(self, device):
         """(pinv [bins, n_mels], mel basis [n_mels, bins]) as fp32 tensors on ``device``."""
@@ -324,6 +325,31 @@ class GriffinLim:
             self._dev[device] = (torch.tensor(self._pinv_np, dtype=torch.float32, device=device).contiguous(),
                                  torch.tensor(self._basis_np, dtype=torch.float32, device=device).contiguous())
         return self._dev[device]
+
+    def _checked(self, mels, n_iter, momentum, init_phase, magnitudes, olens=None):
+        """What both forms of the call check of ``mels``, ``n_iter``, ``momentum`` and ``init_phase`` (and of a device ``olens``: that
+        it lives where ``mels`` does).  Returns (source rows [rows, W] and initial phase [rows, bins] or None, both contiguous fp32,
+        W, n_iter, momentum)."""
+        _require_cuda(mels, "mels")
+        NB = self.geometry.n_bins
+        W = NB if magnitudes else self.geometry.n_mels
+        if mels.dim() not in (2, 3) or mels.shape[-1] != W:
+            raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
+        if self.device is not None and mels.device != self.device:
+            raise ValueError("mels on %s, this GriffinLim on %s" % (mels.device, self.device))
+        if olens is not None and olens.device != mels.device:
+            raise ValueError("olens on %s, mels on %s" % (olens.device, mels.device))
+        n_iter, momentum = int(n_iter), float(momentum)
+        if n_iter < 0:
+            raise ValueError("n_iter must be >= 0")
+        if not (momentum >= 0.0 and math.isfinite(momentum)):
+            raise ValueError("momentum must be finite and >= 0")
+        if init_phase is not None:
+            _require_cuda(init_phase, "init_phase")
+            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
+                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
+            init_phase = init_phase.reshape(-1, NB).contiguous().float()
+        return mels.reshape(-1, W).contiguous().float(), init_phase, W, n_iter, momentum
 
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
                  padded_out=False):
@@ -341,39 +367,21 @@ class GriffinLim:
             return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out)
         if capacity is not None or padded_out:
             raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
-        _require_cuda(mels, "mels")
+        src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
         g = self.geometry
         NB = g.n_bins
-        W = NB if magnitudes else g.n_mels
-        if mels.dim() not in (2, 3) or mels.shape[-1] != W:
-            raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
-        if self.device is not None and mels.device != self.device:
-            raise ValueError("mels on %s, this GriffinLim on %s" % (mels.device, self.device))
-        n_iter, momentum = int(n_iter), float(momentum)
-        if n_iter < 0:
-            raise ValueError("n_iter must be >= 0")
-        if not (momentum >= 0.0 and math.isfinite(momentum)):
-            raise ValueError("momentum must be finite and >= 0")
         if mels.dim() == 2:
             N = mels.shape[0]
             L = _lens([N] if olens is None else olens)
             if int(L.sum()) != N:
                 raise ValueError("packed mels: olens sum to %d, mels have %d rows" % (int(L.sum()), N))
             starts = np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
-            src = mels
         else:
             Bp, Lmax = mels.shape[0], mels.shape[1]
             L = _lens([Lmax] * Bp if olens is None else olens, Bp)
             if Bp and int(L.max()) > Lmax:
                 raise ValueError("padded mels: an olens entry exceeds Lmax = %d" % Lmax)
             starts = np.arange(Bp, dtype=np.int64) * Lmax
-            src = mels.reshape(Bp * Lmax, W)
-        if init_phase is not None:
-            _require_cuda(init_phase, "init_phase")
-            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
-                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
-            init_phase = init_phase.reshape(-1, NB).contiguous().float()
-        src = src.contiguous().float()
         dev = mels.device
         sample_lens = g.hop * torch.clamp(L - 1, min=0)
         wav = torch.empty(int(sample_lens.sum()), dtype=torch.float32, device=dev)
@@ -400,13 +408,12 @@ class GriffinLim:
 
     def _record(self, status, dev):
         """Queue a pinned copy of a call's status behind its kernels; an event tells when it is there."""
-        ring = self.__dict__.setdefault("_pin_ring", [])
+        ring = self._pin_ring
         if len(ring) < self._PIN_SLOTS:
             ring.append([torch.empty(8, dtype=torch.int32).pin_memory(), None])
             slot = ring[-1]
         else:
-            i = self.__dict__.get("_pin_next", 0)
-            slot, self._pin_next = ring[i], (i + 1) % self._PIN_SLOTS
+            slot, self._pin_next = ring[self._pin_next], (self._pin_next + 1) % self._PIN_SLOTS
             if slot[1] is not None:
                 slot[1].status()                   # a call still in flight owns the block: wait for it and keep its values
         slot[0].copy_(status, non_blocking=True)
@@ -437,21 +444,9 @@ class GriffinLim:
         if not olens.is_cuda:
             raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), it is on %s; "
                             "use sync=True for host lengths" % olens.device)
-        _require_cuda(mels, "mels")
+        src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes, olens)
         g = self.geometry
         NB = g.n_bins
-        W = NB if magnitudes else g.n_mels
-        if mels.dim() not in (2, 3) or mels.shape[-1] != W:
-            raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
-        if self.device is not None and mels.device != self.device:
-            raise ValueError("mels on %s, this GriffinLim on %s" % (mels.device, self.device))
-        if olens.device != mels.device:
-            raise ValueError("olens on %s, mels on %s" % (olens.device, mels.device))
-        n_iter, momentum = int(n_iter), float(momentum)
-        if n_iter < 0:
-            raise ValueError("n_iter must be >= 0")
-        if not (momentum >= 0.0 and math.isfinite(momentum)):
-            raise ValueError("momentum must be finite and >= 0")
         olens = olens.reshape(-1).contiguous()
         B = olens.numel()
         if mels.dim() == 2:
@@ -460,20 +455,12 @@ class GriffinLim:
                 raise ValueError("padded_out needs padded mels [B, Lcap, %d] (the waveform's row length is hop * (Lcap - 1))" % W)
             if capacity is not None and int(capacity) > rows:
                 raise ValueError("capacity %d exceeds the %d rows of the packed mels" % (int(capacity), rows))
-            src = mels
         else:
             if mels.shape[0] != B:
                 raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
             Lcap = mels.shape[1]
             rows, stride = B * Lcap, Lcap
-            src = mels.reshape(rows, W)
         cap = rows if capacity is None else min(int(capacity), rows)
-        if init_phase is not None:
-            _require_cuda(init_phase, "init_phase")
-            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
-                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
-            init_phase = init_phase.reshape(-1, NB).contiguous().float()
-        src = src.contiguous().float()
         dev = mels.device
         padded = bool(padded_out) and Lcap >= 2
         wav_stride = g.hop * (Lcap - 1) if padded else 0

@@ -1,5 +1,5 @@
 """Griffin-Lim and the analysis STFT at other transform geometries on the MI355X (fs2_op_griffin_lim_geom / fs2_op_stft_geom)
-against the generic float64 oracle (tests/stft_geometry_oracle.py) and the reference's recordings (tests/golden/g11_stft_geometries.npz;
+against the generic float64 oracle (tests/vocoder_oracle.py) and the reference's recordings (tests/golden/g11_stft_geometries.npz;
 g10_griffin_lim.npz at the default geometry, run here through the new entry points).  The bars are those of test_gpu_vocoder.py."""
 import ctypes as C
 import os
@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 import torch
 
-from tests import stft_geometry_oracle as G
 from tests import vocoder_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +57,7 @@ def _fixture_or_synthetic(fixtures, geom):
     from fastspeech2_amd.vocoder import seed_angles
     n_fft, hop, win = geom
     sig = O.harmonic_signal(43 * hop, seed=3, noise=0.01, sr=SR.get(geom, 22050))
-    M = np.abs(G.Stft(*geom).stft(sig)).astype(np.float32)
+    M = np.abs(O.Stft(*geom).stft(sig)).astype(np.float32)
     return dict(signal=sig.astype(np.float32), magnitudes=M, angles=seed_angles(4, M.shape[0], n_fft // 2 + 1))
 
 
@@ -70,7 +69,7 @@ def test_istft_alone_matches_oracle(fixtures, geom):
     M, A = d["magnitudes"], d["angles"]
     w = gl(_cuda(M), [M.shape[0]], n_iter=0, init_phase=_cuda(A), magnitudes=True)
     got = w.wav.cpu().numpy().astype(np.float64)
-    want = G.Stft(*geom).griffin_lim(M, A, 0)
+    want = O.Stft(*geom).griffin_lim(M, A, 0)
     err = np.abs(got - want).max() / np.abs(want).max()
     _record("vocoder_geom_%s_istft_rel" % _tag(geom), err)
     assert got.shape == want.shape and int(w.sample_lens[0]) == want.size == geom[1] * (M.shape[0] - 1)
@@ -83,7 +82,7 @@ def test_stft_magnitude_logmel_energy_match_oracle(fixtures, geom, n_mels):
     from fastspeech2_amd.vocoder import GriffinLim, mel_energy, stft_magnitude
     n_fft, hop, win = geom
     hp = _hp(geom, n_mels)
-    o = G.Stft(*geom)
+    o = O.Stft(*geom)
     sig = _fixture_or_synthetic(fixtures, geom)["signal"]
     wavs = [sig, sig[:int(0.6 * sig.size)] * 0.5, O.harmonic_signal(2 * n_fft + 37, seed=5)]
     T = [x.size for x in wavs]
@@ -149,7 +148,7 @@ def test_griffin_lim_30_iterations_matches_oracle_and_reference(fixtures, geom):
     gl = GriffinLim(_hp(geom))
     d = _fixture_or_synthetic(fixtures, geom)
     M, A = d["magnitudes"], d["angles"]
-    o = G.Stft(*geom)
+    o = O.Stft(*geom)
     w = gl(_cuda(M), [M.shape[0]], n_iter=30, init_phase=_cuda(A), magnitudes=True)
     got = w.wav.cpu().numpy().astype(np.float64)
     want = o.griffin_lim(M, A, 30)
@@ -182,7 +181,7 @@ def test_mel_input_other_widths_matches_oracle(geom, n_mels, sr):
     hp.audio.sample_rate = sr
     gl = GriffinLim(hp)
     assert gl.geometry.n_mels == n_mels and gl.params["sample_rate"] == sr
-    o = G.Stft(*geom)
+    o = O.Stft(*geom)
     B = gl._basis_np
     lens = [97, 40]
     mels = []
@@ -240,7 +239,7 @@ def test_seeded_phase_uses_n_bins():
     from fastspeech2_amd.vocoder import GriffinLim, seed_angles
     geom = (2048, 300, 1200)
     gl = GriffinLim(_hp(geom))
-    M = np.abs(G.Stft(*geom).stft(O.harmonic_signal(300 * 40, seed=2)))
+    M = np.abs(O.Stft(*geom).stft(O.harmonic_signal(300 * 40, seed=2)))
     a = gl(_cuda(M), [M.shape[0]], n_iter=2, seed=9, magnitudes=True).wav
     b = gl(_cuda(M), [M.shape[0]], n_iter=2, init_phase=_cuda(seed_angles(9, M.shape[0], n_bins=1025)), magnitudes=True).wav
     assert torch.equal(a, b)
@@ -299,7 +298,7 @@ def test_unsupported_geometry_is_refused_by_the_library():
 def test_non_default_stream(geom):
     from fastspeech2_amd.vocoder import GriffinLim
     gl = GriffinLim(_hp(geom))
-    M = _cuda(np.abs(G.Stft(*geom).stft(O.harmonic_signal(geom[1] * 300, seed=4, sr=SR.get(geom, 22050)))))
+    M = _cuda(np.abs(O.Stft(*geom).stft(O.harmonic_signal(geom[1] * 300, seed=4, sr=SR.get(geom, 22050)))))
     ref = gl(M, [M.shape[0]], n_iter=8, seed=1, magnitudes=True).wav
     torch.cuda.synchronize()
     s = torch.cuda.Stream()

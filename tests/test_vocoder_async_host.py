@@ -151,3 +151,159 @@ def test_sync_false_argument_checks_need_no_gpu():
         gl(mels, [10])
     with pytest.raises(ValueError, match="sync=False"):
         gl(mels, [10], capacity=10)
+
+
+# ---- characterisation of the host side the entry points share: the workspace sizes themselves and the calls refused before a launch ----
+def _layout_bytes(n_fft, records, planner_B, frames):
+    """The documented workspace layout (include/fs2.h): twiddles 8 n_fft, window 4 n_fft, tile records
+    32 max(records, 1), then for the capacity form the planner's arrays 16 max(B, 1) (planner_B None: a host-planned call), then for
+    synthesis M, C0, C1, T = 4, 8, 8, 8 bytes times frames times bins (frames None: analysis).  Every region starts 256-aligned and so
+    does the end."""
+    regions = [8 * n_fft, 4 * n_fft, 32 * max(records, 1)]
+    if planner_B is not None:
+        regions.append(16 * max(planner_B, 1))
+    if frames is not None:
+        n = frames * (n_fft // 2 + 1)
+        regions += [4 * n, 8 * n, 8 * n, 8 * n]
+    off = 0
+    for r in regions:
+        off = -(-off // 256) * 256 + r
+    return -(-off // 256) * 256
+
+
+def test_workspace_sizes_are_the_documented_layout(lib):
+    from fastspeech2_amd.vocoder import slot_capacity, tile_rule
+    n = 0
+    for n_fft, hop, win in GEOMS:
+        F = tile_rule(n_fft, hop)["F"]
+        g = (n_fft, hop, win, 80)
+        default = (n_fft, hop, win) == (1024, 256, 1024)
+        rng = np.random.default_rng(n_fft * 7 + hop)
+        for B in (1, 3, 64, 1000):
+            for hi in (4, 70, 400):
+                L = rng.integers(0, hi, size=B)                      # frame counts of a synthesis call
+                T = rng.integers(0, hi * hop, size=B)                # sample counts of an analysis call
+                Lc, Tc = (C.c_int32 * B)(*L.tolist()), (C.c_int32 * B)(*T.tolist())
+                tiles = int(np.where(L >= 2, -(-L // F), 0).sum())
+                want = _layout_bytes(n_fft, tiles, None, int(L.sum()))
+                assert int(lib.fs2_op_vocode_workspace_bytes_geom(*g, B, Lc)) == want, (g, B, hi)
+                cap = int(L.sum())
+                want_cap = _layout_bytes(n_fft, slot_capacity(cap, F, B), B, cap)
+                assert int(lib.fs2_op_vocode_workspace_bytes_cap(*g, B, cap)) == want_cap, (g, B, hi)
+                want_stft = _layout_bytes(n_fft, int((-(-(T // hop + 1) // F)).sum()), None, None)
+                assert int(lib.fs2_op_stft_workspace_bytes_geom(*g, B, Tc)) == want_stft, (g, B, hi)
+                n += 3
+                if default:
+                    assert int(lib.fs2_op_vocode_workspace_bytes(B, Lc)) == want
+                    assert int(lib.fs2_op_stft_workspace_bytes(B, Tc)) == want_stft
+    assert n == 144
+    # no utterance, no tile, no frame: one record is still reserved
+    for g in GEOMS:
+        assert int(lib.fs2_op_vocode_workspace_bytes_geom(*g, 80, 0, None)) == _layout_bytes(g[0], 0, None, 0)
+        assert int(lib.fs2_op_stft_workspace_bytes_geom(*g, 80, 0, None)) == _layout_bytes(g[0], 0, None, None)
+        assert int(lib.fs2_op_vocode_workspace_bytes_cap(*g, 80, 0, 0)) == _layout_bytes(g[0], 0, 0, 0)
+
+
+OK, ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = 0, -1, -5, -6      # include/fs2.h
+PTR = 0x1000           # stands for a device pointer: no call below gets as far as using one
+DEFAULT_G = (1024, 256, 1024, 80)
+
+
+def _i32s(v):
+    return None if v is None else (C.c_int32 * len(v))(*v)
+
+
+def _synthesis_call(entry, g=DEFAULT_G, src=PTR, width=80, pinv=PTR, B=None, lens=(10, 5), n_iter=2, momentum=0.0, ws=PTR, ws_bytes=0, wav=PTR):
+    """(function name, arguments) of a host-planned synthesis call through the fixed or the _geom entry point."""
+    B = (0 if lens is None else len(lens)) if B is None else B
+    starts = None if lens is None else np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(int).tolist()
+    tail = (src, width, pinv, B, _i32s(starts), _i32s(lens), n_iter, momentum, 0, None, ws, ws_bytes, wav)
+    return ("fs2_op_griffin_lim", (None,) + tail) if entry == "fixed" else ("fs2_op_griffin_lim_geom", (None,) + tuple(g) + tail)
+
+
+def _dev_call(g=DEFAULT_G, src=PTR, width=80, pinv=PTR, B=2, lens_dev=PTR, src_stride=0, frame_capacity=15, n_iter=2, momentum=0.0, ws=PTR,
+              ws_bytes=0, wav=PTR, wav_stride=0, wav_capacity=256 * 14, sample_lens=PTR, status=PTR):
+    return "fs2_op_griffin_lim_dev", (None,) + tuple(g) + (src, width, pinv, B, lens_dev, src_stride, frame_capacity, None, n_iter, momentum, 0, None,
+                                                          ws, ws_bytes, wav, wav_stride, wav_capacity, sample_lens, status)
+
+
+def _analysis_call(entry, g=DEFAULT_G, wav=PTR, B=None, lens=(3000, 700), ws=PTR, ws_bytes=0, mag=PTR, basis=None, logmel=None):
+    B = (0 if lens is None else len(lens)) if B is None else B
+    starts = None if lens is None else np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(int).tolist()
+    tail = (wav, B, _i32s(starts), _i32s(lens), ws, ws_bytes, mag, basis, logmel)
+    return ("fs2_op_stft", (None,) + tail) if entry == "fixed" else ("fs2_op_stft_geom", (None,) + tuple(g) + tail + (None,))
+
+
+def _refused_or_empty_calls(lib):
+    """(label, function name, arguments, return code) of calls that end before any launch: refused, or accepted as empty.  The codes
+    are those of the library before its host code was folded into csrc/griffin_lim_host.h.  Every call passes ``workspace_bytes`` below
+    what its batch needs, and the workspace is the last thing either path checks: a call that passed the check it is here for would
+    still be refused (with FS2_ERR_WORKSPACE, failing the test) and launch nothing."""
+    for e in ("fixed", "geom"):
+        s = lambda **kw: _synthesis_call(e, **kw)
+        a = lambda **kw: _analysis_call(e, **kw)
+        need = int(lib.fs2_op_vocode_workspace_bytes(2, _i32s((10, 5))))
+        need_a = int(lib.fs2_op_stft_workspace_bytes(2, _i32s((3000, 700))))
+        yield ("src_width", e) + s(width=100) + (ERR_UNSUPPORTED,)
+        yield ("src_width of another geometry's bins", e) + s(width=1025) + (ERR_UNSUPPORTED,)
+        yield ("mel without pinv", e) + s(pinv=None) + (ERR_ARG,)
+        yield ("n_iter < 0", e) + s(n_iter=-1) + (ERR_ARG,)
+        yield ("momentum nan", e) + s(momentum=float("nan")) + (ERR_ARG,)
+        yield ("momentum < 0", e) + s(momentum=-0.5) + (ERR_ARG,)
+        yield ("momentum inf", e) + s(momentum=float("inf")) + (ERR_ARG,)
+        yield ("null starts / lens", e) + s(lens=None, B=2) + (ERR_ARG,)
+        yield ("negative length", e) + s(lens=(10, -1)) + (ERR_ARG,)
+        yield ("B < 0", e) + s(lens=None, B=-1) + (ERR_ARG,)
+        yield ("null src", e) + s(src=None) + (ERR_ARG,)
+        yield ("null wav", e) + s(wav=None) + (ERR_ARG,)
+        yield ("null workspace", e) + s(ws=None) + (ERR_ARG,)
+        yield ("workspace one byte short", e) + s(ws_bytes=need - 1) + (ERR_WORKSPACE,)
+        yield ("linear input needs no pinv", e) + s(width=513, pinv=None) + (ERR_WORKSPACE,)
+        yield ("B = 0", e) + s(lens=None, src=None, wav=None, ws=None) + (OK,)
+        yield ("nobody owns a sample", e) + s(lens=(1, 0, 1), src=None, wav=None, ws=None) + (OK,)
+        yield ("stft: null starts / lens", e) + a(lens=None, B=2) + (ERR_ARG,)
+        yield ("stft: logmel without basis", e) + a(logmel=PTR) + (ERR_ARG,)
+        yield ("stft: negative length", e) + a(lens=(3000, -1)) + (ERR_ARG,)
+        yield ("stft: null wav", e) + a(wav=None) + (ERR_ARG,)
+        yield ("stft: null workspace", e) + a(ws=None) + (ERR_ARG,)
+        yield ("stft: workspace one byte short", e) + a(ws_bytes=need_a - 1) + (ERR_WORKSPACE,)
+        yield ("stft: B = 0", e) + a(lens=None, wav=None, ws=None) + (OK,)
+        yield ("stft: nothing asked for", e) + a(mag=None, wav=None, ws=None) + (OK,)
+    # an unsupported geometry is refused before any pointer is looked at
+    for bad in ((1000, 256, 1000, 80), (1024, 100, 1024, 80), (1024, 512, 256, 80), (1024, 256, 2048, 80), (1024, 256, 1024, 129)):
+        yield ("geometry", bad) + _synthesis_call("geom", g=bad, src=None, pinv=None, wav=None, ws=None, n_iter=-1) + (ERR_UNSUPPORTED,)
+        yield ("geometry", bad) + _analysis_call("geom", g=bad, wav=None, ws=None, logmel=PTR) + (ERR_UNSUPPORTED,)
+        yield ("geometry", bad) + _dev_call(g=bad, src=None, lens_dev=None, B=0, n_iter=-1) + (ERR_UNSUPPORTED,)
+    d = _dev_call
+    need = int(lib.fs2_op_vocode_workspace_bytes_cap(*DEFAULT_G, 2, 15))
+    yield ("src_width", "dev") + d(width=100) + (ERR_UNSUPPORTED,)
+    yield ("mel without pinv", "dev") + d(pinv=None) + (ERR_ARG,)
+    yield ("n_iter < 0", "dev") + d(n_iter=-1) + (ERR_ARG,)
+    yield ("momentum nan", "dev") + d(momentum=float("nan")) + (ERR_ARG,)
+    yield ("momentum < 0", "dev") + d(momentum=-0.5) + (ERR_ARG,)
+    yield ("B = 0", "dev") + d(B=0) + (ERR_ARG,)
+    yield ("frame_capacity 0", "dev") + d(frame_capacity=0) + (ERR_ARG,)
+    yield ("negative stride", "dev") + d(src_stride=-1) + (ERR_ARG,)
+    yield ("frame_capacity * bins >= 2^31", "dev") + d(frame_capacity=2 ** 31 // 513 + 1) + (ERR_ARG,)
+    yield ("wav_capacity < 0", "dev") + d(wav_capacity=-1) + (ERR_ARG,)
+    yield ("padded output beyond wav", "dev") + d(wav_stride=256 * 7 + 1) + (ERR_ARG,)
+    yield ("null src", "dev") + d(src=None) + (ERR_ARG,)
+    yield ("null lens_dev", "dev") + d(lens_dev=None) + (ERR_ARG,)
+    yield ("null workspace", "dev") + d(ws=None) + (ERR_ARG,)
+    yield ("null sample_lens", "dev") + d(sample_lens=None) + (ERR_ARG,)
+    yield ("null status", "dev") + d(status=None) + (ERR_ARG,)
+    yield ("null wav with samples", "dev") + d(wav=None) + (ERR_ARG,)
+    yield ("workspace one byte short", "dev") + d(ws_bytes=need - 1) + (ERR_WORKSPACE,)
+    yield ("no samples, no wav", "dev") + d(wav=None, wav_capacity=0) + (ERR_WORKSPACE,)
+    yield ("linear input needs no pinv", "dev") + d(width=513, pinv=None) + (ERR_WORKSPACE,)
+
+
+def test_calls_refused_before_a_launch_keep_their_codes(lib):
+    n = 0
+    for label, where, fn, args, want in _refused_or_empty_calls(lib):
+        got = int(getattr(lib, fn)(*args))
+        assert got == want, (label, where, fn, got, want)
+        if want != OK:
+            assert lib.fs2_last_error(None), (label, where)
+        n += 1
+    assert n >= 80

@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 import torch
 
-from tests import stft_geometry_oracle as G
 from tests import vocoder_oracle as O
 
 # reference fp32 vs float64 oracle, relative to the peak, measured when the fixture was recorded (GL 0 / 1 / 30 iterations, energy)
@@ -29,7 +28,7 @@ def g10(golden_dir):
 
 
 def test_generic_oracle_is_the_default_oracle_at_1024_256(g10):
-    o = G.Stft(1024, 256, 1024)
+    o = O.Stft(1024, 256, 1024)
     sig = g10["signal"].astype(np.float64)
     X, Xd = o.stft(sig), O.stft(sig)
     assert np.abs(X - Xd).max() <= 1e-12 * np.abs(Xd).max()
@@ -37,14 +36,14 @@ def test_generic_oracle_is_the_default_oracle_at_1024_256(g10):
         got, want = o.griffin_lim(g10["magnitudes"], g10["angles"], n), O.griffin_lim(g10["magnitudes"], g10["angles"], n)
         assert got.shape == want.shape
         assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), n
-    assert np.array_equal(G.hann_padded(1024, 1024), O.hann())
+    assert np.array_equal(O.hann_padded(1024, 1024), O.hann())
 
 
 @pytest.mark.parametrize("geom", sorted(MEASURED))
 def test_oracle_matches_reference_fixture(g11, geom):
     n_fft, hop, win = geom
     k = "%d_%d_%d/" % geom
-    o = G.Stft(n_fft, hop, win)
+    o = O.Stft(n_fft, hop, win)
     M, A = g11[k + "magnitudes"], g11[k + "angles"]
     assert M.shape == (44, n_fft // 2 + 1)
     bars = MEASURED[geom]
@@ -68,7 +67,7 @@ def test_oracle_matches_reference_fixture(g11, geom):
 def test_l_min_is_where_reflect_padding_works(geom):
     n_fft, hop, win = geom
     lmin = n_fft // (2 * hop) + 2
-    assert G.l_min(n_fft, hop) == lmin
+    assert O.l_min(n_fft, hop) == lmin
     from fastspeech2_amd.vocoder import Geometry
     assert Geometry(n_fft, hop, win).l_min == lmin
     for L in range(1, lmin + 4):
@@ -83,7 +82,7 @@ def test_l_min_is_where_reflect_padding_works(geom):
         if L >= 2:
             ok_o = True
             try:
-                G.Stft(n_fft, hop, win).stft(np.zeros(T))
+                O.Stft(n_fft, hop, win).stft(np.zeros(T))
             except ValueError:
                 ok_o = False
             assert ok_o == (L >= lmin)

@@ -3,7 +3,7 @@ imports the REFERENCE's own STFT class and griffin_lim with the stubs of tools/g
 n_fft / hop / win_length, a synthetic harmonic signal of 43 hops (44 frames), its magnitudes from STFT.transform, the angles the
 reference's griffin_lim draws after np.random.seed(1234), its waveforms after 0, 1 and 30 iterations, and the frame energy
 torch.norm(magnitudes, dim=0) of the reference's preprocessing (nvidia_preprocessing.py).  Keys are prefixed "<n_fft>_<hop>_<win>/".
-It prints the float64 oracle's distance (tests/stft_geometry_oracle.py) to each, relative to the peak.
+It prints the float64 oracle's distance (tests/vocoder_oracle.py) to each, relative to the peak.
 
 TEST INFRASTRUCTURE ONLY.  Usage (in the build container, with the reference checked out):
     python tools/gen_golden_stft_geometries.py [--all] [REFERENCE_DIR]
@@ -29,8 +29,7 @@ def key(n_fft, hop, win):
 
 
 def main():
-    from tests import vocoder_oracle as VO          # (before the reference's directory joins sys.path: it has a tests package too)
-    from tests import stft_geometry_oracle as O
+    from tests import vocoder_oracle as O           # (before the reference's directory joins sys.path: it has a tests package too)
     from tools.gen_golden_vocoder import import_reference
     args = [a for a in sys.argv[1:] if a != "--all"]
     ref = args[0] if args else os.environ.get("FS2_REFERENCE", "../reference")
@@ -40,7 +39,7 @@ def main():
     for n_fft, hop, win, sr in GEOMETRIES + extra:
         k = key(n_fft, hop, win) + "/"
         stft = STFT(filter_length=n_fft, hop_length=hop, win_length=win)
-        sig = VO.harmonic_signal(43 * hop, seed=3, noise=0.01, sr=sr).astype(np.float32)
+        sig = O.harmonic_signal(43 * hop, seed=3, noise=0.01, sr=sr).astype(np.float32)
         mag, _ = stft.transform(torch.from_numpy(sig)[None])                            # [1, bins, L]
         out[k + "signal"] = sig
         out[k + "magnitudes"] = mag[0].numpy().T.copy()                                  # [L, bins]
