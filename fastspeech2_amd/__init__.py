@@ -6,4 +6,4 @@
 from .hparams import default_hparams, load_hparams, N_PHONEME_SYMBOLS  # noqa: F401
 from .fastspeech import FeedForwardTransformer, StepStreams  # noqa: F401
 from .io import load_checkpoint, vocoder_input, hparams_from_str  # noqa: F401
-from .vocoder import GriffinLim, Geometry, Waveforms, AsyncWaveforms, mel_basis, mel_energy, stft_magnitude, save_wav  # noqa: F401
+from .vocoder import GriffinLim, Geometry, Waveforms, AsyncWaveforms, mel_basis, mel_energy, pitch, wav_features, stft_magnitude, save_wav  # noqa: F401

@@ -85,6 +85,7 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_conv_gemm", "fs2_op_attention", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
            "fs2_op_vocode_workspace_bytes", "fs2_op_griffin_lim", "fs2_op_stft_workspace_bytes", "fs2_op_stft",
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
+           "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
@@ -270,6 +271,10 @@ def lib():
     L.fs2_op_stft_workspace_bytes_geom.restype = C.c_size_t
     L.fs2_op_stft_geom.argtypes = [vp] + gp + [vp, i32, i32p, i32p, vp, C.c_size_t, vp, vp, vp, vp]
     L.fs2_op_stft_geom.restype = C.c_int
+    L.fs2_op_stft_pitch_workspace_bytes_geom.argtypes = gp + [i32, i32p]
+    L.fs2_op_stft_pitch_workspace_bytes_geom.restype = C.c_size_t
+    L.fs2_op_stft_pitch_geom.argtypes = L.fs2_op_stft_geom.argtypes + [i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
+    L.fs2_op_stft_pitch_geom.restype = C.c_int
     L.fs2_op_vocode_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]
     L.fs2_op_vocode_workspace_bytes_cap.restype = C.c_size_t
     # stream, geometry, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, n_iter, momentum, seed, init_phase,

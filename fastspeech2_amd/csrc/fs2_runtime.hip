@@ -30,6 +30,7 @@
 #include "gemm_mx.h"
 #include "gemm_f32.h"
 #include "griffin_lim.h"
+#include "gl_pitch.h"
 
 using namespace fs2;
 
@@ -2498,6 +2499,22 @@ int fs2_op_stft_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int3
     GlGeomHost gh;
     if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_geom", gh)) return rc;
     return gl_stft_run("fs2_op_stft_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy);
+}
+
+size_t fs2_op_stft_pitch_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* wav_lens) {
+    GlGeomHost gh;
+    GlPlan p;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_pitch_workspace_bytes_geom", gh)) return 0;
+    return gl_plan(B, nullptr, wav_lens, true, gh, p, true) == FS2_OK ? p.at.bytes : 0;
+}
+
+int fs2_op_stft_pitch_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* wav, int32_t B, const int32_t* wav_starts,
+                           const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy,
+                           int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold, double octave_cost, float* f0, float* strength) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_pitch_geom", gh)) return rc;
+    return gl_stft_pitch_run("fs2_op_stft_pitch_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy,
+                             sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost, f0, strength);
 }
 
 }  // extern "C"

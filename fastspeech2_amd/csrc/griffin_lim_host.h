@@ -1,5 +1,5 @@
 // Host side of the vocoder (kernels: griffin_lim.h): geometry, workspace layout, host plan, launch sequence and the argument checks
-// behind fs2_op_griffin_lim{,_geom,_dev}, fs2_op_stft{,_geom} and their workspace queries (include/fs2.h).
+// behind fs2_op_griffin_lim{,_geom,_dev}, fs2_op_stft{,_geom}, fs2_op_stft_pitch_geom and their workspace queries (include/fs2.h).
 // The host-planned call, the device-driven call and the analysis STFT share one workspace layout (gl_layout), one check of the
 // synthesis arguments (gl_check_synthesis), one GlIterArgs builder (gl_iter_args) and one choice of instantiation (gl_dispatch).
 // Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up(), so the library
@@ -46,15 +46,15 @@ auto gl_dispatch(const GlGeomHost& gh, Fn&& f) {
 }
 
 // Workspace of every vocoder call: tables, tile records, the device planner's per-utterance arrays (device-driven call only), then
-// (synthesis only) M, the two spectrum buffers and the momentum state over `frames` frames packed back to back.  Each region starts
-// 256-byte aligned.
+// (synthesis only) M, the two spectrum buffers and the momentum state over `frames` frames packed back to back, then (analysis with
+// pitch only) the window-autocorrelation table of gl_pitch.h.  Each region starts 256-byte aligned.
 struct GlLayout {
-    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, bytes = 0;
+    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, off_acw = 0, bytes = 0;
 };
 
 // records: tile records (the exact tile count of a host plan, the slots of a device-driven call); planner_B: utterances the device
 // planner keeps its 4 ints each for, < 0: a host-planned call, no such region.  0 records / 0 utterances still reserve one.
-GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int64_t frames, bool analysis) {
+GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int64_t frames, bool analysis, bool pitch = false) {
     GlLayout l;
     size_t off = 0;
     auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
@@ -69,6 +69,7 @@ GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int6
         l.off_C1 = take(n * sizeof(float2));
         l.off_T = take(n * sizeof(float2));
     }
+    if (pitch) l.off_acw = take(gl_pitch_lags(gh.n_fft) * sizeof(float));
     l.bytes = align_up(off, 256);
     return l;
 }
@@ -83,7 +84,7 @@ struct GlPlan {
 
 // analysis = false: lens are frame counts L_b, samples hop max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
 // frames T_b / hop + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
-int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p) {
+int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p, bool pitch = false) {
     if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
     const int hop = gh.hop, F = gh.g.F, nb = gh.n_bins;
     int64_t row = 0, wav = 0;
@@ -108,7 +109,7 @@ int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, co
     }
     p.frames = row;
     p.samples = wav;
-    p.at = gl_layout(gh, p.tiles.size(), -1, p.frames, analysis);
+    p.at = gl_layout(gh, p.tiles.size(), -1, p.frames, analysis, pitch);
     return FS2_OK;
 }
 
@@ -284,5 +285,61 @@ int gl_stft_run(const char* who, void* stream, const GlGeomHost& gh, const float
     });
     e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
+    return FS2_OK;
+}
+
+// Lags of the pitch scan (gl_pitch.h): tmin = floor(sr / f0_ceil), tmax = ceil(sr / f0_floor), 2 <= tmin <= tmax <= win / 2 -- the
+// window's autocorrelation is divided by, and beyond half the window it is too small to.  Restated in vocoder.py: pitch_lags.
+int gl_pitch_args(const char* who, const GlGeomHost& gh, int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold,
+                  double octave_cost, GlPitch& out) {
+    if (sample_rate < 1 || !(f0_floor > 0.0) || !(f0_ceil >= f0_floor) || !std::isfinite(f0_ceil) || !std::isfinite(voicing_threshold) ||
+        !std::isfinite(octave_cost))
+        return fail(nullptr, FS2_ERR_ARG, "%s: sample_rate %d, f0_floor %g, f0_ceil %g, voicing_threshold %g, octave_cost %g", who, sample_rate, f0_floor,
+                    f0_ceil, voicing_threshold, octave_cost);
+    const double lo = std::floor((double)sample_rate / f0_ceil), hi = std::ceil((double)sample_rate / f0_floor);
+    if (lo < 2.0 || hi > gh.win / 2)
+        return fail(nullptr, FS2_ERR_UNSUPPORTED,
+                    "%s: f0_floor %g .. f0_ceil %g at %d Hz need the lags %.0f .. %.0f, the window of %d samples allows 2 .. %d (lowest usable f0_floor "
+                    "%g Hz = 2 sample_rate / win, highest f0_ceil %g Hz)", who, f0_floor, f0_ceil, sample_rate, lo, hi, gh.win, gh.win / 2,
+                    2.0 * sample_rate / gh.win, sample_rate / 2.0);
+    out.tmin = (int)lo; out.tmax = (int)hi;
+    out.sr = (float)sample_rate;
+    out.floor_over_sr = (float)(f0_floor / (double)sample_rate);
+    out.threshold = (float)voicing_threshold;
+    out.octave_cost = (float)octave_cost;
+    return FS2_OK;
+}
+
+// gl_stft_run with the pitch outputs: the same plan and tables plus the window-autocorrelation table, one gl_features launch.  Without
+// f0 and strength it is gl_stft_run (and needs no more workspace than it).
+int gl_stft_pitch_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,
+                      const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy,
+                      int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold, double octave_cost, float* f0, float* strength) {
+    GlPitch pp{};
+    if (int rc = gl_pitch_args(who, gh, sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost, pp)) return rc;
+    if (!f0 && !strength) return gl_stft_run(who, stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy);
+    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
+    GlPlan p;
+    if (int rc = gl_plan(B, wav_starts, wav_lens, true, gh, p, true)) return rc;
+    if (p.tiles.empty()) return FS2_OK;
+    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    if (workspace_bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.at.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    hipError_t e = gl_setup(s, p, gh, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
+    float* acw = (float*)(ws + p.at.off_acw);
+    hipLaunchKernelGGL(gl_pitch_table, dim3((gl_pitch_lags(gh.n_fft) + 7) / 8), dim3(256), 0, s, acw, gh.n_fft, gh.win);
+    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
+    const GlTile* tiles = (const GlTile*)(ws + p.at.off_tiles);
+    const float2* tw = (const float2*)(ws + p.at.off_tw);
+    const float* win = (const float*)(ws + p.at.off_win);
+    gl_dispatch(gh, [&](auto n, auto h) {
+        hipLaunchKernelGGL((gl_features<decltype(n)::value, decltype(h)::value>), grid, blk, 0, s, tiles, gh.g, tw, win, acw, wav, mag, mel_basis, logmel,
+                           energy, pp, f0, strength);
+    });
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft pitch: %s", hipGetErrorString(e));
     return FS2_OK;
 }

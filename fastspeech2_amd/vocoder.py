@@ -9,7 +9,8 @@ STFT (reflect padding at its own ends), nothing goes through the host, and an ut
 vocoded alone or inside any batch.
 
 ``stft_magnitude`` is the analysis direction (TacotronSTFT.mel_spectrogram): waveforms -> |STFT| or log-mel on the GPU;
-``mel_energy`` gives the log-mel and the per-frame energy (the reference preprocessing's targets) from one launch.  Other transform
+``mel_energy`` gives the log-mel and the per-frame energy (the reference preprocessing's targets) from one launch; ``wav_features``
+adds a per-frame F0 from the same launch and ``pitch`` gives it alone (an autocorrelation estimator, not the reference's DIO).  Other transform
 geometries (n_fft 512 / 1024 / 2048, any hop <= win_length <= n_fft with ceil(n_fft / hop) <= 8, 1 .. 128 mels) come from hp.audio.
 There is no CPU fallback: CPU tensors raise.
 
@@ -492,38 +493,55 @@ class GriffinLim:
 _DEFAULT_GL = None
 
 
-def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy):
+def _gl_for(hp):
+    """The GriffinLim (geometry, mel basis) of ``hp``; the default one is kept."""
     global _DEFAULT_GL
+    if hp is not None:
+        return GriffinLim(hp)
+    if _DEFAULT_GL is None:
+        _DEFAULT_GL = GriffinLim()
+    return _DEFAULT_GL
+
+
+def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=None, pitch=None):
+    """One analysis launch.  ``pitch``: None (fs2_op_stft_geom), or (f0_floor, f0_ceil, voicing_threshold, octave_cost) as
+    ``pitch_lags`` accepted them (fs2_op_stft_pitch_geom); then f0 and strength [frames] follow (mag, mel, energy)."""
     _require_cuda(wav_packed, "wav_packed")
     if wav_packed.dim() != 1:
         raise ValueError("wav_packed must be 1-D, got %s" % (tuple(wav_packed.shape),))
     T = _lens(sample_lens, name="sample_lens")
     if int(T.sum()) != wav_packed.numel():
         raise ValueError("sample_lens sum to %d, wav_packed has %d samples" % (int(T.sum()), wav_packed.numel()))
-    gl = GriffinLim(hp) if hp is not None else (_DEFAULT_GL or GriffinLim())
-    if hp is None:
-        _DEFAULT_GL = gl
+    gl = gl or _gl_for(hp)
     g = gl.geometry
     dev = wav_packed.device
     frames = int((T // g.hop + 1).sum()) if T.numel() else 0
     mag = torch.empty(frames, g.n_bins, dtype=torch.float32, device=dev) if want_mag else None
     mel = torch.empty(frames, g.n_mels, dtype=torch.float32, device=dev) if want_mel else None
     en = torch.empty(frames, dtype=torch.float32, device=dev) if want_energy else None
+    f0 = torch.empty(frames, dtype=torch.float32, device=dev) if pitch is not None else None
+    st = torch.empty(frames, dtype=torch.float32, device=dev) if pitch is not None else None
+    out = (mag, mel, en) if pitch is None else (mag, mel, en, f0, st)
     if frames == 0:
-        return mag, mel, en
+        return out
     x = wav_packed.contiguous().float()
     lib = _lib.lib()
     st_np, st_p = _i32(np.concatenate([[0], np.cumsum(T.numpy())[:-1]]))
     t_np, t_p = _i32(T.numpy())
     B = len(t_np)
-    ws_bytes = int(lib.fs2_op_stft_workspace_bytes_geom(*g, B, t_p))
+    query = lib.fs2_op_stft_workspace_bytes_geom if pitch is None else lib.fs2_op_stft_pitch_workspace_bytes_geom
+    ws_bytes = int(query(*g, B, t_p))
     ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(dev):
         basis = gl.constants(dev)[1]
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.fs2_op_stft_geom(_stream(dev), *g, x.data_ptr(), B, st_p, t_p, ws.data_ptr(), ws_bytes, ptr(mag),
-                                        basis.data_ptr() if want_mel else None, ptr(mel), ptr(en)))
-    return mag, mel, en
+        head = (_stream(dev),) + tuple(g) + (x.data_ptr(), B, st_p, t_p, ws.data_ptr(), ws_bytes, ptr(mag),
+                                             basis.data_ptr() if want_mel else None, ptr(mel), ptr(en))
+        if pitch is None:
+            _lib.check(lib.fs2_op_stft_geom(*head))
+        else:
+            _lib.check(lib.fs2_op_stft_pitch_geom(*head, int(gl.params["sample_rate"]), *pitch, ptr(f0), ptr(st)))
+    return out
 
 
 def stft_magnitude(wav_packed, sample_lens, mel=False, hp=None):
@@ -542,6 +560,66 @@ def mel_energy(wav_packed, sample_lens, hp=None):
     ``stft_magnitude``; a waveform of <= n_fft / 2 samples gives energy 0."""
     _, lm, en = _analysis(wav_packed, sample_lens, hp, False, True, True)
     return lm, en
+
+
+def pitch_lags(sample_rate, win, f0_floor=71.0, f0_ceil=800.0):
+    """(tmin, tmax) = (floor(sr / f0_ceil), ceil(sr / f0_floor)): the integer lags the F0 estimator searches.  It divides the frame's
+    autocorrelation by the window's, which is too small to divide by beyond half the window: raises ValueError unless
+    2 <= tmin and tmax <= win / 2 (csrc/griffin_lim_host.h: gl_pitch_args checks the same)."""
+    sr, lo, hi = float(sample_rate), float(f0_floor), float(f0_ceil)
+    if not (sr >= 1 and lo > 0 and hi >= lo and math.isfinite(hi)):
+        raise ValueError("need sample_rate >= 1 and 0 < f0_floor <= f0_ceil, got %r, %r, %r" % (sample_rate, f0_floor, f0_ceil))
+    tmin, tmax = int(math.floor(sr / hi)), int(math.ceil(sr / lo))
+    if tmin < 2 or tmax > win // 2:
+        raise ValueError("f0_floor %g .. f0_ceil %g at %g Hz need the lags %d .. %d, the window of %d samples allows 2 .. %d: the lowest "
+                         "usable f0_floor is 2 sample_rate / win_length = %g Hz, the highest f0_ceil %g Hz"
+                         % (lo, hi, sr, tmin, tmax, win, win // 2, 2.0 * sr / win, sr / 2.0))
+    return tmin, tmax
+
+
+def _pitch_setup(hp, f0_floor, f0_ceil, voicing_threshold, octave_cost):
+    """(GriffinLim of hp, the four options as floats), checked before anything touches the GPU."""
+    gl = _gl_for(hp)
+    opt = (float(f0_floor), float(f0_ceil), float(voicing_threshold), float(octave_cost))
+    pitch_lags(gl.params["sample_rate"], gl.geometry.win, opt[0], opt[1])
+    if not (math.isfinite(opt[2]) and math.isfinite(opt[3])):
+        raise ValueError("voicing_threshold and octave_cost must be finite, got %r, %r" % (voicing_threshold, octave_cost))
+    return gl, opt
+
+
+def pitch(wav_packed, sample_lens, hp=None, f0_floor=71.0, f0_ceil=800.0, voicing_threshold=0.45, octave_cost=0.02, return_strength=False):
+    """F0 [frames] in Hz of packed waveforms, one value per frame of ``stft_magnitude`` (the same frame count as the mel by
+    construction), 0 where unvoiced; with ``return_strength=True`` also the winner's peak height [frames].
+
+    This is an autocorrelation estimator (Boersma 1993 without the path search), NOT the reference's pitch: the reference calls
+    pyworld's DIO (dataset/audio_processing.py:54-70).  Per frame, with y the windowed frame: r = irfft(|rfft(y)|^2), rw the same of
+    the window, rho[t] = (r[t] / r[0]) / (rw[t] / rw[0]) (r[0] <= 1e-12: unvoiced).  Candidates are the lags t in
+    [floor(sr / f0_ceil), ceil(sr / f0_floor)] with rho[t] > rho[t-1], rho[t] >= rho[t+1], rho[t] > 0, refined by a parabola through
+    a, c, b = rho[t-1], rho[t], rho[t+1]: d = 0.5 (a - b) / (a - 2c + b), t* = t + d, p = c - 0.25 (a - b) d, scored
+    S = p - octave_cost log2(f0_floor t* / sr).  The largest S wins (ties: the smaller t); the frame is voiced iff the winner's
+    p >= voicing_threshold; f0 = sr / t*; strength = p (0 without a candidate).  ``sr`` is hp.audio.sample_rate.  No smoothing or
+    path search across frames.  (t* may lie up to half a sample outside the integer lags, and f0 that far outside the floor / ceiling.)  The lags must fit half the window (``pitch_lags``): a floor below 2 sr / win_length raises ValueError.
+    A waveform of <= n_fft / 2 samples gives 0 on all its frames.  CPU tensors raise."""
+    gl, opt = _pitch_setup(hp, f0_floor, f0_ceil, voicing_threshold, octave_cost)
+    _, _, _, f0, st = _analysis(wav_packed, sample_lens, hp, False, False, False, gl, opt)
+    return (f0, st) if return_strength else f0
+
+
+def wav_features(wav_packed, sample_lens, hp=None, **pitch_options):
+    """(log-mel [frames, n_mels], energy [frames], f0 [frames]) of packed waveforms from one launch: the three arrays the reference's
+    preprocessing saves per utterance (nvidia_preprocessing.py), with the F0 of :func:`pitch` (an autocorrelation estimator, not the
+    reference's DIO) and its options (f0_floor, f0_ceil, voicing_threshold, octave_cost).  The log-mel and the energy are
+    ``mel_energy``'s bit for bit."""
+    if "return_strength" in pitch_options:
+        raise TypeError("wav_features returns (logmel, energy, f0); use pitch(..., return_strength=True) for the strength")
+    o = dict(f0_floor=71.0, f0_ceil=800.0, voicing_threshold=0.45, octave_cost=0.02)
+    unknown = sorted(set(pitch_options) - set(o))
+    if unknown:
+        raise TypeError("unknown pitch option(s) %s" % ", ".join(unknown))
+    o.update(pitch_options)
+    gl, opt = _pitch_setup(hp, o["f0_floor"], o["f0_ceil"], o["voicing_threshold"], o["octave_cost"])
+    _, lm, en, f0, _ = _analysis(wav_packed, sample_lens, hp, False, True, True, gl, opt)
+    return lm, en, f0
 
 
 def save_wav(path, wav, sample_rate=22050):

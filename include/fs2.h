@@ -334,6 +334,26 @@ int fs2_op_stft_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int3
                      const int32_t *wav_starts, const int32_t *wav_lens, void *workspace, size_t workspace_bytes, float *mag,
                      const float *mel_basis, float *logmel, float *energy);
 
+/* ---- Pitch (F0) beside the analysis STFT (fastspeech2_amd/csrc/gl_pitch.h): fs2_op_stft_geom plus, from
+ * the same launch, f0 [frames] in Hz (0 = unvoiced) and strength [frames], each optional (NULL); mag, logmel and energy are those of
+ * fs2_op_stft_geom bit for bit.  The estimator is an autocorrelation one (Boersma 1993 without the path search) and NOT the
+ * reference's pitch, which is pyworld's DIO (dataset/audio_processing.py:54-70).  Per frame, y the windowed frame:
+ *   r = irfft(|rfft(y)|^2), rw the same of the window; rho[t] = (r[t] / r[0]) / (rw[t] / rw[0]); r[0] <= 1e-12: unvoiced
+ *   candidates: lags t in [tmin, tmax] = [floor(sample_rate / f0_ceil), ceil(sample_rate / f0_floor)] with rho[t] > rho[t-1],
+ *   rho[t] >= rho[t+1] and rho[t] > 0, refined by a parabola through a = rho[t-1], c = rho[t], b = rho[t+1]:
+ *   d = 0.5 (a - b) / (a - 2c + b), t* = t + d, p = c - 0.25 (a - b) d, S = p - octave_cost log2(f0_floor t* / sample_rate)
+ *   the winner has the largest S (ties: the smaller t); voiced iff p >= voicing_threshold; f0 = sample_rate / t* where voiced,
+ *   strength = the winner's p, 0 without a candidate.
+ * A waveform of <= n_fft / 2 samples gives f0 = strength = 0.  The lags must satisfy 2 <= tmin and tmax <= win / 2 (the lowest usable
+ * f0_floor is 2 sample_rate / win): otherwise FS2_ERR_UNSUPPORTED.  The workspace holds one table more than fs2_op_stft_geom's. ---- */
+
+size_t fs2_op_stft_pitch_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *wav_lens);
+
+int fs2_op_stft_pitch_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *wav, int32_t B,
+                           const int32_t *wav_starts, const int32_t *wav_lens, void *workspace, size_t workspace_bytes, float *mag,
+                           const float *mel_basis, float *logmel, float *energy, int32_t sample_rate, double f0_floor, double f0_ceil,
+                           double voicing_threshold, double octave_cost, float *f0, float *strength);
+
 /* ---- Device-driven Griffin-Lim: the frame counts stay on the device (what fs2_decode's device-driven layout leaves there), so mel
  * frames become waveforms without a host read-back in between.  The tiles are planned by kernels inside capacities the host knows;
  * grids are sized for the capacities and surplus workgroups exit at once.  Results equal those of fs2_op_griffin_lim_geom for the same
