@@ -25,6 +25,7 @@
 #include "common.h"
 #include "elementwise.h"
 #include "gemm_bf16.h"
+#include "gemm_plan.h"
 #include "gemm_planes.h"
 #include "gemm_row4.h"
 #include "gemm_mx.h"
@@ -80,33 +81,9 @@ struct Stack {
     float *after_g = nullptr, *after_b = nullptr;   // after_norm (applied only when pre_ln, encoder.py:201-202)
 };
 
-// Split-K serves small batches (regime_rows <= kSplitRegime: beyond, the grids fill the chip anyway).  Its scratch holds up to 4 slabs of
-// kSplitRows x 1024 floats, enough for every launch with R <= kSplitRows, so that the decision is a function of regime_rows alone (the same
-// in the host- and the device-driven layout) as long as the row capacity stays below twice the estimate.
-constexpr int kSplitRegime = 8192, kSplitRows = 16384;
 constexpr int kXcds = 8;      // MI355X: 8 accelerator dies, workgroups of a launch are dealt to them round-robin
 
-// A/B switches of the kernel choice.  Read from the environment ONCE, when the library is first used, and
-// changed afterwards only through fs2_set_option(): the launch path never touches the environment.  -1 = automatic choice.
-struct Options {
-    int bm = -1;         // FS2_BM       tile height of gemm_pl_bf16 (64 | 128 | 256)
-    int bal = 0;         // FS2_BAL      tall conv tiles: 0 = always 256 rows (default: interleaved A/B, profiles/r03_ab_conv_tile_balance.txt), 1 = height balanced over
-                         //              whole rounds of the rows in use, 2 = of the row capacity
-    int row8 = -1;       // FS2_ROW8     force (1) / forbid (0) the row-complete LayerNorm-fused k = 1 GEMM
-    int qkv8 = -1;       // FS2_QKV8     force / forbid the 8-wave fused QKV projection
-    int nosplitk = 0;    // FS2_NOSPLITK no split-K of the token-level k = 1 GEMMs
-    int f32_rows = 0;    // FS2_F32_ROWS row-complete fp32 GEMM for LayerNorm-terminated ops
-    int fuse_var = 1;    // FS2_FUSE_VAR the pitch and the energy predictor as one launch per layer (0: separate launches)
-    int mt8 = -1;        // FS2_MT8      m-tiles per wave of the 8-wave row-complete kernels (2 | 3: 128 / 192-row workgroups)
-    int op_att_planes = 0;   // FS2_OP_ATT_PLANES  fs2_op_attention (split-bf16 modes) takes the context from the kernels as planes, the model's form, and converts (tests)
-    int qkv_split = -1;  // FS2_QKV_SPLIT  the Q, K and V passes of gemm_qkv8_bf16 as three workgroups per row tile (-1: by the round count)
-    int w32 = -1;        // FS2_ATTN_W32 split-bf16 attention with 32 queries per wave (attn_w32.h): 0 never, 1 whenever the head dim allows, -1 by regime
-    int row4 = -1;       // FS2_ROW4     the one-wave-per-SIMD row-complete kernel (gemm_row4.h) wherever gemm_row8_bf16 would run and it has the epilogue: 0 never, else yes
-    int mt4 = -1;        // FS2_MT4      its m-tiles per wave (4 | 5: 128 / 160-row workgroups; -1: by the round count)
-    int qkv4 = -1;       // FS2_QKV4     the fused QKV projection's passes on gemm_row4_bf16 (EPI 3) wherever gemm_qkv8_bf16 would run at D = 384: 0 never, else yes
-    int ffn2_mx = 1;     // FS2_FFN2_MX  mix_mx mode: the second FFN GEMM in the mx arithmetic too, wherever gemm_row4_bf16 runs it (0: split-bf16 as in round 4)
-    int post_mx = 1;     // FS2_POST_MX  mixed modes: the Postnet's 512 -> 512 convolutions in the mx arithmetic (0: split-bf16 as until round 5)
-};
+// struct Options -- the A/B switches of the kernel choice -- lives in gemm_plan.h; it is read from the environment ONCE, here, when the library is first used.
 int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
@@ -388,418 +365,182 @@ inline void allow_lds(const void* kernel, size_t bytes, LdsAttr& st) {
 }
 
 // ------------------------------------------------------------------ kernel launchers
-template <int NT>
-hipError_t launch_rows(hipStream_t s, const GemmArgs& a) {
+static_assert(kPlanErrArg == FS2_ERR_ARG && kPlanErrHip == FS2_ERR_HIP && kPlanErrState == FS2_ERR_STATE && kPlanErrUnsupported == FS2_ERR_UNSUPPORTED &&
+              kPlanFp32 == FS2_PREC_FP32 && kPlanBf16x3 == FS2_PREC_BF16X3 && kPlanMaxHalo == kMaxHalo && kPlanBN == kB16BN, "gemm_plan.h restates these");
+
+// One launcher for every GEMM kernel, keyed by the kernel: it owns the per-(kernel, device) flag of the LDS attribute.
+template <auto K>
+hipError_t launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, const GemmArgs& a) {
     static LdsAttr attr;
-    allow_lds(reinterpret_cast<const void*>(&gemm_rows_f32<NT>), rows_lds_bytes<NT>(), attr);
-    dim3 grid((a.R + kRowsBM - 1) / kRowsBM);
-    hipLaunchKernelGGL(gemm_rows_f32<NT>, grid, dim3(256), rows_lds_bytes<NT>(), s, a);
+    allow_lds(reinterpret_cast<const void*>(K), lds, attr);
+    hipLaunchKernelGGL(K, grid, block, lds, s, a);
     return hipGetLastError();
 }
-
-hipError_t launch_tile(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    allow_lds(reinterpret_cast<const void*>(&gemm_tile_f32), kTileLds, attr);
-    dim3 grid((a.R + kTileBM - 1) / kTileBM, (a.N + kTileBN - 1) / kTileBN);
-    hipLaunchKernelGGL(gemm_tile_f32, grid, dim3(256), kTileLds, s, a);
-    return hipGetLastError();
+template <int V> using Int = std::integral_constant<int, V>;
+// pick<V...>(v, f): f(std::integral_constant<int, V>) for the V that equals v -- a run-time template coordinate of the plan to the instantiation built for it
+template <int V, int... Vs, typename F>
+hipError_t pick(int v, F&& f) {
+    if (v == V) return f(Int<V>{});
+    if constexpr (sizeof...(Vs) > 0) return pick<Vs...>(v, f);
+    else return hipErrorInvalidValue;
 }
+// CV(X): the int that pick handed a generic lambda as its integral_constant parameter X, as a constant expression (a template argument).  A macro only
+// because `X.value` / `decltype(X)::value` of a lambda parameter is not usable as one by every compiler this builds with; it lives for run_plan alone.
+#define CV(x) decltype(x)::value
+constexpr int row4_variant(int epi, int arith, int res) { return epi * 100 + arith * 10 + res; }      // gemm_row4_bf16's (EPI, ARITH, RES) as one case label
 
-bool rows_supported(int N) { return N == 80 || N == 256 || N == 384; }
-
-template <int NSPLIT, int BM, bool K1, int ARITH = 0>
-hipError_t launch_pl_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = pl_lds_bytes<BM, K1>();
-    allow_lds(reinterpret_cast<const void*>(&gemm_pl_bf16<NSPLIT, BM, K1, ARITH>), lds, attr);
+template <int NSPLIT, int BM, bool K1, int ARITH>
+hipError_t launch_pl(hipStream_t s, const GemmArgs& a, size_t extra_lds = 0) {
     dim3 grid((a.N + kB16BN - 1) / kB16BN, ((a.qk_hi ? a.Rvt : a.R) + BM - 1) / BM, a.ksplit > 1 ? a.ksplit : 1);
-    hipLaunchKernelGGL((gemm_pl_bf16<NSPLIT, BM, K1, ARITH>), grid, dim3(256), lds, s, a);
-    return hipGetLastError();
+    return launch_kernel<gemm_pl_bf16<NSPLIT, BM, K1, ARITH>>(grid, dim3(256), pl_lds_bytes<BM, K1>() + extra_lds, s, a);
 }
-// Tile height of the 8-wave row-complete kernels (one workgroup per CU): 64 MT rows, MT = 2 or 3.  A launch of T tiles takes ceil(T / #CUs)
-// rounds, and a nearly empty second round costs as much as a full one (c3 at 7.87 frames per phoneme: 286 tiles of 128 rows = 256 + 30).
-// Same-box A/B: a 192-row tile costs 1.55-1.9 x a 128-row one (its epilogue spills), so it pays exactly when it turns two rounds into one
-// (c3: dec.ffn2_ln 0.174 -> 0.134 ms, step 5.68 -> 5.34 ms; c4, 15 rounds against 10: 68.0 -> 70.8 ms, so not there).  Results do not depend on MT.
-constexpr int kCus = 256;
-// Rows a launch will really touch: in the device-driven layout a.R is a capacity (15-25 % above the rows in use, the surplus tiles exit at once);
-// the regime estimate (8 frames per phoneme + alignment rows, the same number in both layout modes) is the better basis for balancing rounds.
-inline long rows_in_use(const GemmArgs& a, long rows) { return a.regime_rows > 0 ? std::min<long>(rows, a.regime_rows) : rows; }
-inline int row8_mt(long rows) {
-    const long t128 = (rows + 127) / 128, t192 = (rows + 191) / 192;
-    return (t128 > kCus && t192 <= kCus) ? 3 : 2;
-}
-
-template <int NSPLIT, int NB, int MT>
-hipError_t launch_row8_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = row8_lds_bytes<NB, MT>();
-    allow_lds(reinterpret_cast<const void*>(&gemm_row8_bf16<NSPLIT, NB, MT>), lds, attr);
-    hipLaunchKernelGGL((gemm_row8_bf16<NSPLIT, NB, MT>), dim3((a.R + 64 * MT - 1) / (64 * MT)), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-template <int NSPLIT, int NB>
-hipError_t launch_row8(hipStream_t s, const GemmArgs& a) {
-    const int mt = opts().mt8 > 0 ? opts().mt8 : row8_mt(rows_in_use(a, a.R));
-    if (mt >= 3) return launch_row8_t<NSPLIT, NB, 3>(s, a);
-    return launch_row8_t<NSPLIT, NB, 2>(s, a);
-}
-
-// gemm_row4_bf16 (gemm_row4.h): one wave per SIMD, 128- or 160-row workgroups, one per CU.  The tile height that minimises rounds x height
-// (ties: the taller tile -- fewer weight bytes per row): c3 (36.6 k rows) 160 rows = 229 workgroups in one round, the c5 shard (78 k rows) 160 rows =
-// 2 rounds instead of 3, c4 either.  Results do not depend on the height (nor on the kernel: bit-identical to gemm_row8_bf16).
-inline int row4_mt(long rows) {
-    const long r4 = ((rows + 127) / 128 + kCus - 1) / kCus * 128, r5 = ((rows + 159) / 160 + kCus - 1) / kCus * 160;
-    return r5 <= r4 ? 5 : 4;
-}
-// the epilogues it has (gemm_row4.h: EPI); -1: none, the launch stays on gemm_row8_bf16.  Since round 6 the kernel serves the PLANES-ONLY form of
-// these launches only (gemm_row4.h: RES): no fp32 rows out (Y == nullptr, Yp given), the residual -- where there is one -- as the producing launch's
-// planes (residp; resid == nullptr).  fs2_decode / run_stack build their arguments in that form exactly when planes_only_regime() says the
-// decoder's LayerNorm-fused launches will run here; a launch in the other form stays on gemm_row8_bf16.
-inline int row4_epi(const GemmArgs& a) {
-    if (a.ktaps != 1 || a.N != 384 || !a.ln_g || a.Y || !a.Yp || a.resid || a.relu_pre || a.dot_w || a.k_groups > 1 || a.ln_groups > 1 || a.qk_hi || a.yp_col_off) return -1;
-    if (a.Cpad % 64 != 0 || a.yp_chunks * 32 != a.N) return -1;      // an even number of k-steps; planes exactly N wide
-    if (a.residp && a.residp_chunks * 32 != a.N) return -1;
-    if (a.pe) return (a.act_post == 1 && a.yp_f16 == 0 && !a.residp) ? 2 : -1;
-    if (a.act_post != 0 || !a.residp) return -1;
-    if (a.yp_f16 == 2) return a.residp_mx ? -1 : 1;      // out-proj + LN1 of mix_mx: residual = split-bf16 planes of the block input, result = mx planes
-    if (a.yp_f16 == 3) return (a.residp_mx || !a.yp_rowscale) ? -1 : 4;      // ... of mix_mx4: result = mx4 planes + one scale byte per row
-    return a.yp_f16 == 0 ? 0 : -1;
-}
+// (the DMA-spreading schedule of gemm_row4_bf16 is fixed at SCHED = 2: same-box A/B in the model, c3: 0 -> 7.21, 2 -> 7.20, 4 -> 7.17 M frames/s; stand-alone 2 and 4 are 5-13 % ahead of 0)
 template <int MT, int EPI, int ARITH, int RES>
-hipError_t launch_row4_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = row4_lds_bytes<3, MT>();
-    allow_lds(reinterpret_cast<const void*>(&gemm_row4_bf16<3, 3, MT, EPI, 2, ARITH, RES>), lds, attr);
-    hipLaunchKernelGGL((gemm_row4_bf16<3, 3, MT, EPI, 2, ARITH, RES>), dim3((a.R + 32 * MT - 1) / (32 * MT)), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-template <int EPI, int ARITH, int RES>
-hipError_t launch_row4_e(hipStream_t s, const GemmArgs& a) {
-    const int mt = (opts().mt4 == 4 || opts().mt4 == 5) ? opts().mt4 : row4_mt(rows_in_use(a, a.R));
-    return mt == 5 ? launch_row4_t<5, EPI, ARITH, RES>(s, a) : launch_row4_t<4, EPI, ARITH, RES>(s, a);
-}
-// (the DMA-spreading schedule is fixed at SCHED = 2: same-box A/B in the model, c3: 0 -> 7.21, 2 -> 7.20, 4 -> 7.17 M frames/s; stand-alone 2 and 4 are 5-13 % ahead of 0)
-// The instantiations the library holds (fastspeech2_amd/_audit.py: EXPECTED_KERNELS counts them): EPI 0 x {split-bf16 arithmetic with the residual from
-// split-bf16 or from mx planes, mx arithmetic with the residual from mx planes}, EPI 1 and EPI 4 (residual from split-bf16 planes), EPI 2 (no residual),
-// each at two tile heights, + the QKV passes (launch_qkv4_t).
-hipError_t launch_row4(hipStream_t s, const GemmArgs& a, int epi) {
-    if (epi == 2) return launch_row4_e<2, 0, 3>(s, a);
-    if (epi == 1) return launch_row4_e<1, 0, 1>(s, a);
-    if (epi == 4) return launch_row4_e<4, 0, 1>(s, a);
-    if (a.mx) return a.residp_mx ? launch_row4_e<0, 2, 2>(s, a) : hipErrorInvalidValue;      // (FFN2 in the mx arithmetic exists in mix_mx only, where LN1's output is mx planes)
-    return a.residp_mx ? launch_row4_e<0, 0, 2>(s, a) : launch_row4_e<0, 0, 1>(s, a);
-}
-// Will the decoder's LayerNorm-fused k = 1 launches (out-proj + LN1, FFN2 + LN2, the input layer) run on gemm_row4_bf16 -- i.e. do its activations
-// travel as planes ONLY?  Same predicates as use_row8 / launch_gemm, asked once per fs2_decode so that every site of the stack agrees.
-inline bool planes_only_regime(const fs2_config& c, const Stack& st, int prec, long regime_rows) {
-    if (prec != FS2_PREC_BF16X3 || opts().row4 == 0 || c.ddim != 384 || st.pre_ln || st.concat || c.dunits % 64 != 0 || c.adim % 64 != 0) return false;
-    if (opts().row8 >= 0) return opts().row8 != 0;
-    return (regime_rows + 127) / 128 >= 128;
+hipError_t launch_row4(hipStream_t s, const GemmArgs& a) {
+    return launch_kernel<gemm_row4_bf16<3, 3, MT, EPI, 2, ARITH, RES>>(dim3((a.R + 32 * MT - 1) / (32 * MT)), dim3(256), row4_lds_bytes<3, MT>(), s, a);
 }
 
-template <int NSPLIT, int NB, int MT, int GROUPS = 1>
-hipError_t launch_row8c_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = row8c_lds_bytes<NB, MT>();
-    allow_lds(reinterpret_cast<const void*>(&gemm_row8c_bf16<NSPLIT, NB, MT, GROUPS>), lds, attr);
-    hipLaunchKernelGGL((gemm_row8c_bf16<NSPLIT, NB, MT, GROUPS>), dim3((a.R + 64 * MT - 1) / (64 * MT), a.k_groups > 1 ? a.k_groups : 1), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-template <int NSPLIT, int NB>
-hipError_t launch_row8c(hipStream_t s, const GemmArgs& a) {
-    const int mt = opts().mt8 > 0 ? opts().mt8 : row8_mt(rows_in_use(a, a.R));
-    if (mt >= 3) return launch_row8c_t<NSPLIT, NB, 3>(s, a);
-    return launch_row8c_t<NSPLIT, NB, 2>(s, a);
-}
-
-template <int NSPLIT, int NB, int MT, bool APART>
-hipError_t launch_qkv8_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = qkv8_lds_bytes<NB, MT>();
-    allow_lds(reinterpret_cast<const void*>(&gemm_qkv8_bf16<NSPLIT, NB, MT, APART>), lds, attr);
-    hipLaunchKernelGGL((gemm_qkv8_bf16<NSPLIT, NB, MT, APART>), dim3((a.Rvt + 64 * MT - 1) / (64 * MT), APART ? 3 : 1), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-// The Q, K and V passes of a row tile are independent (each re-streams the A tile): as three workgroups per tile (grid.y = 3) the
-// unit of work is a third of a tile and the last, partly filled round of a launch costs a third.  Rounds in units of a 128-row
-// tile's three passes, a 192-row tile at 1.7 (row8_mt): c3, 286 tiles of 128 rows: whole tiles 2.0 (128) / 1.7 (192, one round
-// on 191 of 256 CUs: what ran until round 4), passes apart 4/3 (128) / 1.7 (192).  Never more rounds than whole tiles of the
-// same height.  Results do not depend on either choice.
-inline void qkv8_plan(long rows, int& mt, int& apart) {
-    double best = 1e30;
-    for (int m = 2; m <= 3; ++m)
-        for (int ap = 0; ap <= 1; ++ap) {
-            if (opts().mt8 > 0 && m != std::min(std::max(opts().mt8, 2), 3)) continue;
-            if (opts().qkv_split >= 0 && ap != (opts().qkv_split != 0)) continue;
-            const long tiles = (rows + 64 * m - 1) / (64 * m), units = ap ? 3 * tiles : tiles;
-            const double cost = (double)((units + kCus - 1) / kCus) / (ap ? 3.0 : 1.0) * (m == 3 ? 1.7 : 1.0);
-            if (cost < best - 1e-9) { best = cost; mt = m; apart = ap; }
+// The instantiation a plan names, launched on the arguments derived from it (launch_gemm).  The kernels are instantiated, and so laid out in the code
+// object, in the order of the cases and of pick's values (profiles/gemm_plan_kernels.txt holds the list).
+hipError_t run_plan(hipStream_t s, const GemmPlan& p, const GemmArgs& t) {
+    switch (p.kernel) {
+    case GemmKernel::Row4: {
+        auto row4 = [&](auto EPI, auto ARITH, auto RES) { return pick<5, 4>(p.mt, [&](auto MT) { return launch_row4<CV(MT), CV(EPI), CV(ARITH), CV(RES)>(s, t); }); };
+        // the six (EPI, ARITH, RES) variants the library holds (gemm_row4.h; plan_gemm produces no other): a new one is a line here
+        switch (row4_variant(p.epi, p.arith, p.res)) {
+        case row4_variant(2, 0, 3): return row4(Int<2>{}, Int<0>{}, Int<3>{});      // input layer: positional encoding, no residual
+        case row4_variant(1, 0, 1): return row4(Int<1>{}, Int<0>{}, Int<1>{});      // out-proj + LN1 of mix_mx: mx planes out
+        case row4_variant(4, 0, 1): return row4(Int<4>{}, Int<0>{}, Int<1>{});      // ... of mix_mx4: mx4 planes + row scales out
+        case row4_variant(0, 2, 2): return row4(Int<0>{}, Int<2>{}, Int<2>{});      // FFN2 + LN2 in the mx arithmetic, residual from mx planes
+        case row4_variant(0, 0, 2): return row4(Int<0>{}, Int<0>{}, Int<2>{});      // split-bf16 arithmetic, residual from mx planes
+        case row4_variant(0, 0, 1): return row4(Int<0>{}, Int<0>{}, Int<1>{});      // split-bf16 arithmetic, residual from split-bf16 planes
         }
-}
-template <int NSPLIT, int NB>
-hipError_t launch_qkv8(hipStream_t s, const GemmArgs& a) {
-    int mt = 2, apart = 0;
-    qkv8_plan(rows_in_use(a, a.Rvt), mt, apart);
-    if (mt >= 3) return apart ? launch_qkv8_t<NSPLIT, NB, 3, true>(s, a) : launch_qkv8_t<NSPLIT, NB, 3, false>(s, a);
-    return apart ? launch_qkv8_t<NSPLIT, NB, 2, true>(s, a) : launch_qkv8_t<NSPLIT, NB, 2, false>(s, a);
-}
-
-// The fused QKV projection's passes on the one-wave-per-SIMD structure (gemm_row4.h, EPI 3): always one workgroup per (row tile, pass); the tile height that
-// minimises rounds x height of the 3 T pass-workgroups (c3: 160 rows = 687 units = 2.7 rounds against 858 = 3.4 rounds of 128 rows).  Bit-identical to gemm_qkv8_bf16.
-inline int qkv4_mt(long rows) {
-    const long r4 = (3 * ((rows + 127) / 128) + kCus - 1) / kCus * 128, r5 = (3 * ((rows + 159) / 160) + kCus - 1) / kCus * 160;
-    return r5 <= r4 ? 5 : 4;
-}
-template <int MT>
-hipError_t launch_qkv4_t(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    constexpr size_t lds = row4_lds_bytes<3, MT>();
-    static_assert((size_t)32 * MT * kQkvLd * 4 <= row4_lds_bytes<3, MT>(), "the V pass transposes its tile through the operand ring's memory");
-    allow_lds(reinterpret_cast<const void*>(&gemm_row4_bf16<3, 3, MT, 3, 2, 0>), lds, attr);
-    hipLaunchKernelGGL((gemm_row4_bf16<3, 3, MT, 3, 2, 0>), dim3((a.Rvt + 32 * MT - 1) / (32 * MT), 3), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_qkv4(hipStream_t s, const GemmArgs& a) {
-    const int mt = (opts().mt4 == 4 || opts().mt4 == 5) ? opts().mt4 : qkv4_mt(rows_in_use(a, a.Rvt));
-    return mt == 5 ? launch_qkv4_t<5>(s, a) : launch_qkv4_t<4>(s, a);
-}
-
-// Fused QKV projection on the 8-wave structure when there is about a CU's worth of 128-row tiles (FS2_QKV8=0|1 forces the choice)
-bool use_qkv8(const GemmArgs& a) {
-    if (!a.qk_hi || a.ktaps != 1 || (a.att_D != 256 && a.att_D != 384) || a.N != 3 * a.att_D) return false;
-    if (opts().qkv8 >= 0) return opts().qkv8 != 0;
-    return ((a.regime_rows ? a.regime_rows : a.Rvt) + 127) / 128 >= 128;
-}
-
-// Row-complete LN-fused kernel (gemm_row8_bf16) for k = 1 GEMMs that end in a row epilogue: one workgroup per CU, so it
-// needs about a CU's worth of 128-row tiles to pay (FS2_ROW8=0|1 forces the choice).
-bool use_row8(const GemmArgs& a) {
-    const int Ng = a.k_groups > 1 ? a.N / a.k_groups : a.N;      // (grouped conv: one workgroup row per group, gemm_row8c_bf16's grid.y)
-    const bool two_ln_groups = a.ln_groups == 2 && a.k_groups <= 1 && a.N == 512 && a.ktaps > 1;      // two stacked 256-channel layers over one input
-    if (a.qk_hi || (!two_ln_groups && Ng != 256 && Ng != 384)) return false;
-    if (a.ln_groups > 1 && !two_ln_groups && a.ln_groups != a.k_groups) return false;
-    if (a.ktaps > 1) {      // conv form (gemm_row8c_bf16): LayerNorm-terminated convolutions, optionally with the scalar head; no PE
-        if (!a.ln_g || a.pe || a.f16_terms) return false;
-    } else if (a.dot_w || !(a.ln_g || a.pe) || a.k_groups > 1 || a.ln_groups > 1) return false;
-    if (opts().row8 >= 0) return opts().row8 != 0;
-    return ((a.regime_rows ? a.regime_rows : a.R) + 127) / 128 >= 128;
-}
-
-// Will launch_gemm run this LayerNorm-terminated k = 1 GEMM on gemm_row4_bf16, and does that kernel's mx form exist for it?  (run_stack asks before it
-// decides the format of the A planes; launch_gemm makes the same test.)
-bool ffn2_on_row4_mx(const fs2_handle*, const GemmArgs& a) {
-    return use_row8(a) && opts().row4 != 0 && row4_epi(a) == 0 && a.Cpad % 128 == 0 && a.Xp != nullptr;
-}
-
-// In the 256-row regime the conv kernel runs two workgroups per CU: a launch of T y-tiles per N tile takes ceil(T nN / 512) rounds, and a nearly
-// empty last round costs as much as a full one (c3 at 7.87 frames per phoneme: 143 x 8 tiles = 2.2 rounds -> 3).  The smallest tile height (a
-// multiple of 32 rows, 160 .. 256) that keeps that number of rounds spreads the rows evenly instead (191 tiles of 192 rows: 3 full rounds of
-// tiles that are a quarter shorter).  Results do not depend on the tile height.
-inline int conv_bm_balanced(long rows, long nN) {
-    const long ypr = std::max<long>(1, 2 * kCus / nN);
-    const long rounds = std::max<long>(1, (rows + 256 * ypr - 1) / (256 * ypr));
-    const long h = (rows + rounds * ypr - 1) / (rounds * ypr);
-    return (int)std::min<long>(256, std::max<long>(160, (h + 31) / 32 * 32));
-}
-template <int NSPLIT, int ARITH>
-hipError_t launch_pl_tall(hipStream_t s, const GemmArgs& a, int bm) {
-    if (bm <= 160) return launch_pl_t<NSPLIT, 160, false, ARITH>(s, a);
-    if (bm <= 192) return launch_pl_t<NSPLIT, 192, false, ARITH>(s, a);
-    if (bm <= 224) return launch_pl_t<NSPLIT, 224, false, ARITH>(s, a);
-    return launch_pl_t<NSPLIT, 256, false, ARITH>(s, a);
-}
-
-template <int NSPLIT>
-hipError_t launch_pl(hipStream_t s, const GemmArgs& a) {
-    const int force = opts().bm > 0 ? opts().bm : 0;
-    const long rows = a.qk_hi ? a.Rvt : a.R;
-    const long nN = (a.N + kB16BN - 1) / kB16BN;
-    int bm;
-    if (a.ktaps == 1) {
-        bm = (force == 128) ? force : 64;     // measured (c3): 64-row tiles win for every k = 1 GEMM (3 workgroups/CU hide the DMA round trips)
-        return bm == 128 ? launch_pl_t<NSPLIT, 128, true>(s, a) : launch_pl_t<NSPLIT, 64, true>(s, a);
+        break;
     }
-    bm = force ? force : (nN * ((rows + 255) / 256) >= 512 ? 256 : (nN * ((rows + 127) / 128) >= 400 ? 128 : 64));
-    if (bm > 128) {
-        if (!force && a.ksplit <= 1 && opts().bal) bm = conv_bm_balanced(opts().bal == 2 ? rows : rows_in_use(a, rows), nN);
-        if constexpr (NSPLIT == 3) return launch_pl_tall<3, 0>(s, a, bm);
-        else return launch_pl_t<NSPLIT, 256, false>(s, a);
+    case GemmKernel::Qkv4:
+        return pick<5, 4>(p.mt, [&](auto MT) {
+            static_assert((size_t)32 * CV(MT) * kQkvLd * 4 <= row4_lds_bytes<3, CV(MT)>(), "the V pass transposes its tile through the operand ring's memory");
+            return launch_kernel<gemm_row4_bf16<3, 3, CV(MT), 3, 2, 0>>(dim3((t.Rvt + 32 * CV(MT) - 1) / (32 * CV(MT)), 3), dim3(256), row4_lds_bytes<3, CV(MT)>(), s, t);
+        });
+    case GemmKernel::PlMx:
+        return pick<160, 192, 224, 256, 128, 64>(p.bm, [&](auto BM) { return launch_pl<1, CV(BM), false, 2>(s, t); });
+    case GemmKernel::PlMx4:
+        // + the A tile's scale bytes (8 per row and cross unit) + two stages of weight block scales; two workgroups per CU must still fit (a first build reserved 32 bytes per
+        // row = 78.3 KB per workgroup and ran 25 % slower: one workgroup per CU)
+        return launch_pl<1, 256, false, 3>(s, t, kMx4RowScaleLds + 2048);
+    case GemmKernel::PlF16:
+        return pick<3, 2, 1>(p.nsplit, [&](auto NS) {
+            return pick<256, 128, 64>(p.bm, [&](auto BM) { return launch_pl<CV(NS), CV(BM), false, 1>(s, t); });
+        });
+    case GemmKernel::Qkv8:
+        return pick<3, 2>(p.nb, [&](auto NB) {
+            return pick<3, 1>(p.nsplit, [&](auto NS) {
+                return pick<3, 2>(p.mt, [&](auto MT) {
+                    return pick<1, 0>(p.apart, [&](auto AP) {
+                        const dim3 grid((t.Rvt + 64 * CV(MT) - 1) / (64 * CV(MT)), CV(AP) ? 3 : 1);
+                        return launch_kernel<gemm_qkv8_bf16<CV(NS), CV(NB), CV(MT), CV(AP) != 0>>(grid, dim3(512), qkv8_lds_bytes<CV(NB), CV(MT)>(), s, t);
+                    });
+                });
+            });
+        });
+    case GemmKernel::Row8cTwoLn:
+        return pick<3, 1>(p.nsplit, [&](auto NS) { return launch_kernel<gemm_row8c_bf16<CV(NS), 4, 2, 2>>(dim3((t.R + 127) / 128, 1), dim3(512), row8c_lds_bytes<4, 2>(), s, t); });
+    case GemmKernel::Row8c:
+    case GemmKernel::Row8cGrouped:
+        return pick<3, 2>(p.nb, [&](auto NB) {
+            return pick<3, 1>(p.nsplit, [&](auto NS) {
+                return pick<3, 2>(p.mt, [&](auto MT) {
+                    const dim3 grid((t.R + 64 * CV(MT) - 1) / (64 * CV(MT)), t.k_groups > 1 ? t.k_groups : 1);
+                    return launch_kernel<gemm_row8c_bf16<CV(NS), CV(NB), CV(MT), 1>>(grid, dim3(512), row8c_lds_bytes<CV(NB), CV(MT)>(), s, t);
+                });
+            });
+        });
+    case GemmKernel::Row8:
+        return pick<3, 2>(p.nb, [&](auto NB) {
+            return pick<3, 1>(p.nsplit, [&](auto NS) {
+                return pick<3, 2>(p.mt, [&](auto MT) {
+                    const dim3 grid((t.R + 64 * CV(MT) - 1) / (64 * CV(MT)));
+                    return launch_kernel<gemm_row8_bf16<CV(NS), CV(NB), CV(MT)>>(grid, dim3(512), row8_lds_bytes<CV(NB), CV(MT)>(), s, t);
+                });
+            });
+        });
+    case GemmKernel::PlBf16:
+        if (p.nsplit == 3) {
+            if (p.k1) return pick<128, 64>(p.bm, [&](auto BM) { return launch_pl<3, CV(BM), true, 0>(s, t); });
+            return pick<160, 192, 224, 256, 128, 64>(p.bm, [&](auto BM) { return launch_pl<3, CV(BM), false, 0>(s, t); });
+        }
+        if (p.k1) return pick<128, 64>(p.bm, [&](auto BM) { return launch_pl<1, CV(BM), true, 0>(s, t); });
+        return pick<256, 128, 64>(p.bm, [&](auto BM) { return launch_pl<1, CV(BM), false, 0>(s, t); });
+    case GemmKernel::RowsF32:
+        return pick<5, 16, 24>(p.nb, [&](auto NT) { return launch_kernel<gemm_rows_f32<CV(NT)>>(dim3((t.R + kRowsBM - 1) / kRowsBM), dim3(256), rows_lds_bytes<CV(NT)>(), s, t); });
+    case GemmKernel::TileF32:
+    case GemmKernel::TileRowsF32:
+        return launch_kernel<gemm_tile_f32>(dim3((t.R + kTileBM - 1) / kTileBM, (t.N + kTileBN - 1) / kTileBN), dim3(256), kTileLds, s, t);
+    case GemmKernel::None: break;
     }
-    return bm == 128 ? launch_pl_t<NSPLIT, 128, false>(s, a) : launch_pl_t<NSPLIT, 64, false>(s, a);
+    return hipErrorInvalidValue;
 }
+#undef CV
 
-// fp16 + block-scaled-fp8 form of the conv (gemm_mx.h): the planes kernel on mx planes / the mx weight image
-hipError_t launch_mx(hipStream_t s, const GemmArgs& a) {
-    const int force = opts().bm > 0 ? opts().bm : 0;
-    const long nN = (a.N + kB16BN - 1) / kB16BN;
-    int bm = force ? force : (nN * ((a.R + 255) / 256) >= 512 ? 256 : (nN * ((a.R + 127) / 128) >= 400 ? 128 : 64));
-    if (bm > 128) return launch_pl_tall<1, 2>(s, a, (force || !opts().bal) ? bm : conv_bm_balanced(opts().bal == 2 ? a.R : rows_in_use(a, a.R), nN));
-    return bm == 128 ? launch_pl_t<1, 128, false, 2>(s, a) : launch_pl_t<1, 64, false, 2>(s, a);
-}
-
-// fp16 + block-scaled-fp4 form of the conv (gemm_planes.h ARITH = 3): 256-row tiles only -- it runs where the planes-only regime holds (>= 16 k rows: the
-// tile-height rule above picks 256 there for every N >= 1024), + 512 bytes of LDS for the A tile's row-scale bytes
-hipError_t launch_mx4(hipStream_t s, const GemmArgs& a) {
-    static LdsAttr attr;
-    // + the A tile's scale bytes (8 per row and cross unit) + two stages of weight block scales; two workgroups per CU must still fit (a first build reserved 32 bytes per
-    // row = 78.3 KB per workgroup and ran 25 % slower: one workgroup per CU)
-    const size_t lds = pl_lds_bytes<256, false>() + kMx4RowScaleLds + 2048;
-    if (a.Cpad != 384) return hipErrorInvalidValue;      // (the LDS stride of the row scales is a compile-time constant: 8 bytes x 3 cross units; run_stack offers mx4 at D = 384 only)
-    allow_lds(reinterpret_cast<const void*>(&gemm_pl_bf16<1, 256, false, 3>), pl_lds_bytes<256, false>() + kMx4RowScaleLds + 2048, attr);
-    dim3 grid((a.N + kB16BN - 1) / kB16BN, (a.R + 255) / 256, 1);
-    hipLaunchKernelGGL((gemm_pl_bf16<1, 256, false, 3>), grid, dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-
-// fp16-operand form of the conv kernel (FFN w_1 in the mixed modes): NSPLIT MFMAs per fragment pair
-template <int NSPLIT>
-hipError_t launch_pl_f16(hipStream_t s, const GemmArgs& a) {
-    const int force = opts().bm > 0 ? opts().bm : 0;
-    const long nN = (a.N + kB16BN - 1) / kB16BN;
-    const int bm = force ? force : (nN * ((a.R + 255) / 256) >= 512 ? 256 : (nN * ((a.R + 127) / 128) >= 400 ? 128 : 64));
-    if (bm == 256) return launch_pl_t<NSPLIT, 256, false, 1>(s, a);
-    return bm == 128 ? launch_pl_t<NSPLIT, 128, false, 1>(s, a) : launch_pl_t<NSPLIT, 64, false, 1>(s, a);
-}
-
-// Picks the kernel.  fp32: row-complete tiles when the epilogue needs whole rows and N is small, 128x128 tiles (+ ln_rows) otherwise.
-// bf16 / bf16x3 (activation planes in, gemm_planes.h): the row-complete LayerNorm-fused kernel for big k = 1 GEMMs that end in
-// a row epilogue, else the BM x 128 tile kernel followed by ln_rows when a row epilogue is needed.
+// Plan (gemm_plan.h: which kernel, which tile, split-K, where the rows go), then execute: build the A planes if the producer did not, launch the
+// kernel on the arguments the plan implies, run ln_rows where the epilogue is a pass of its own.
 int launch_gemm(fs2_handle* h, hipStream_t s, const char* name, GemmArgs a, int precision = FS2_PREC_FP32) {
-    if (a.ktaps - 1 > kMaxHalo) return fail(h, FS2_ERR_UNSUPPORTED, "%s: kernel size %d > %d", name, a.ktaps, kMaxHalo + 1);
-    if (a.C % 4 != 0 || a.ldx % 4 != 0) return fail(h, FS2_ERR_UNSUPPORTED, "%s: channels %d / ld %d must be multiples of 4", name, a.C, a.ldx);
-    if (h && !a.kpart && h->kp) { a.kpart = h->kp; a.kpart_cap = h->kp_cap; a.ksplit = 3; }
+    if (h && !a.kpart && h->kp) { a.kpart = h->kp; a.kpart_cap = h->kp_cap; a.ksplit = 3; }      // (a.ksplit: how many partial buffers the plan may use)
     if (h && !a.regime_rows) a.regime_rows = h->cur_regime;
-    const int max_extra_splits = a.ksplit;      // on entry: how many partial buffers the caller allows; from here on a.ksplit = splits in use
+    const GemmPlan p = plan_gemm(a, precision, opts());
+    if (p.err) return fail(h, p.err, p.msg, name, p.m0, p.m1);
     a.ksplit = 1;
-    const bool need_rows = a.ln_g || a.dot_w || a.pe;
-    const double flops = 2.0 * a.R * (double)a.N * a.C * a.ktaps;
-    const double bytes = 4.0 * ((double)a.R * a.C + (double)a.N * a.C * a.ktaps + (double)a.R * a.N);
-    hipError_t e;
-    if (precision != FS2_PREC_FP32) {
-        if (!a.Wb) return fail(h, FS2_ERR_STATE, "%s: no bf16 weight image", name);
-        if (a.C % 8 != 0 || a.N % 4 != 0 || (need_rows && a.N > 1024)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: bf16 path needs C %% 8 == 0, N %% 4 == 0 (N <= 1024 with a row epilogue)", name);
-        GemmArgs t = a;
-        t.W = reinterpret_cast<const float*>(a.Wb);
-        // the A operand must exist as split-bf16 planes (Xp) or be convertible into xp_scratch (gemm_planes.h)
-        if (!a.Xp && !a.xp_scratch) return fail(h, FS2_ERR_STATE, "%s: no activation planes and no scratch to build them", name);
-        if (a.ldy % 4 != 0 || (a.resid && a.ldr % 4 != 0)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: bf16 path needs row strides that are multiples of 4", name);
-        const bool row8 = use_row8(a);
-        if ((a.residp || (need_rows && !a.Y && a.Yp && !a.dot_w && a.ktaps == 1 && !a.scratch)) && !(row8 && precision == FS2_PREC_BF16X3 && opts().row4 != 0 && row4_epi(a) >= 0))
-            return fail(h, FS2_ERR_STATE, "%s: a planes-only launch (residual as planes / no fp32 rows) exists on gemm_row4_bf16 only and this one would not run there", name);
-        if (a.yp_col_off && !(row8 && a.ktaps > 1)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: a plane column offset exists in the row-complete conv kernel only", name);
-        const bool y_needed = (need_rows && !row8) || (!a.Yp && !a.qk_hi && !(row8 && a.dot_w));      // (row-complete + scalar head: nothing but dot_out leaves)
-        if (!t.Y && y_needed) { t.Y = a.scratch; t.ldy = a.N; }
-        if (!t.Y && y_needed) return fail(h, FS2_ERR_ARG, "%s: no output or scratch buffer", name);
-        if (t.qk_hi && (a.ktaps != 1 || a.att_D % kB16BN != 0 || a.N != 3 * a.att_D)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: fused QKV split needs D %% 128 == 0", name);
-        // split-K: on a grid that leaves most CUs idle the kernel is a serial chain of k-steps (one utterance: 108 steps of the FFN
-        // conv on 88 workgroups); 2-4 workgroups share the chunks and ln_rows adds their partial sums in a fixed order
-        // (deterministic, unlike atomics) and applies the epilogue.  The choice depends on regime_rows (the same number in the host-
-        // and the device-driven layout), never on the capacity.
-        t.ksplit = 1;
-        size_t y_slab = 0;       // 1: Y lives in the first slab of kpart (no fp32 output buffer of the caller's)
-        const long rr = a.regime_rows ? a.regime_rows : a.R;
-        if (!row8 && !a.qk_hi && a.kpart && !opts().nosplitk && a.N <= 1024 && rr <= kSplitRegime && a.R <= kSplitRows && a.mx != 2) {      // (the mx4 conv walks 9 units per row, not Cpad / 32: it exists unsplit -- its regime never splits unless the row kernels are forced on a small batch)
-            const int nchunks = a.Cpad / 32;
-            const long wgs = (long)((a.N + kB16BN - 1) / kB16BN) * ((rr + 63) / 64);
-            const bool own_y = t.Y != nullptr;
-            const size_t ld = own_y ? (size_t)t.ldy : (size_t)a.N;
-            for (int cand = 4; cand >= 2; --cand)
-                if (nchunks % cand == 0 && (nchunks / cand) * a.ktaps >= 4 && wgs * cand <= 1024 && cand - 1 <= max_extra_splits &&
-                    (size_t)(cand - (own_y ? 1 : 0)) * a.R * ld <= a.kpart_cap) { t.ksplit = cand; break; }
-            if (t.ksplit > 1 && !own_y) y_slab = 1;
-        }
-        const bool rows_pass = (need_rows && !row8) || t.ksplit > 1;
-        if (y_slab) { t.Y = a.kpart; t.ldy = a.N; }
-        if (rows_pass) { t.act_post = 0; t.Yp = nullptr; }      // the row kernel applies the epilogue and writes the planes
-        if (t.ksplit > 1) {
-            t.relu_pre = 0;                                      // partial sums: ReLU only after they are added (ln_rows)
-            t.kpart = a.kpart + y_slab * (size_t)a.R * a.N;
-            t.kpart_stride = (size_t)a.R * t.ldy;
-        }
-        const bool mx_row4 = a.mx && a.ktaps == 1 && precision == FS2_PREC_BF16X3 && ffn2_on_row4_mx(h, a);      // FFN2 + LN2 in the mx arithmetic (gemm_row4.h)
-        if ((a.f16_terms || a.mx) && !mx_row4 && (a.ktaps == 1 || need_rows || a.qk_hi)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: the fp16 arithmetic exists for plain convolutions only", name);
-        if (a.mx && !mx_row4 && (a.ktaps < 3 || a.C % 128 != 0 || a.N % 128 != 0)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: the mx arithmetic needs a convolution with C %% 128 == 0 and N %% 128 == 0", name);
-        if (a.mx == 2 && (!a.x_rowscale || !a.w_rowscale || !a.Xp || t.ksplit > 1)) return fail(h, FS2_ERR_STATE, "%s: the mx4 arithmetic needs mx4 planes with their row scales and the weight image's channel scales", name);
+    // the launched arguments: a, with the output routed and the epilogue split off as the plan says
+    GemmArgs t = a;
+    if (precision != FS2_PREC_FP32) t.W = reinterpret_cast<const float*>(a.Wb);
+    if (p.y == RowsOut::Scratch) { t.Y = a.scratch; t.ldy = a.N; }
+    if (p.y == RowsOut::KpartSlab) { t.Y = a.kpart; t.ldy = a.N; }
+    if (p.rows_pass) { t.act_post = 0; t.Yp = nullptr; }      // the row kernel applies the epilogue and writes the planes
+    if (p.ksplit > 1) {
+        t.ksplit = p.ksplit;
+        t.relu_pre = 0;                                      // partial sums: ReLU only after they are added (ln_rows)
+        t.kpart = a.kpart + (p.y == RowsOut::KpartSlab ? (size_t)a.R * a.N : 0);
+        t.kpart_stride = (size_t)a.R * t.ldy;
+    }
+    if (p.build_planes) t.Xp = a.xp_scratch;
+    if (p.kernel == GemmKernel::Row8cGrouped) { t.N = a.N / a.k_groups; t.ln_groups = 0; }      // a workgroup row per group (grid.y), N = one group's outputs
 
-        if (!a.Xp) {
-            char nm[112];
-            snprintf(nm, sizeof nm, "%s.planes", name);
-            Scope sc(h, s, nm, 0.0, 8.0 * a.R * a.Cpad);
-            const int64_t n = (int64_t)a.R * (a.Cpad / 4);
-            hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.X, a.ldx, a.C, a.R, a.Cpad / 32, a.xp_scratch, a.mx ? 2 : (a.f16_terms ? 1 : 0), a.yp_scale);
-            t.Xp = a.xp_scratch;
-        }
-        {
-            Scope sc(h, s, name, flops, bytes);
-            if (mx_row4) {
-                t.W = reinterpret_cast<const float*>(a.Wb);
-                e = launch_row4(s, t, 0);
-            } else if (a.mx == 2) {
-                e = launch_mx4(s, t);
-            } else if (a.mx) {
-                e = launch_mx(s, t);
-            } else if (a.f16_terms) {
-                e = a.f16_terms == 3 ? launch_pl_f16<3>(s, t) : (a.f16_terms == 2 ? launch_pl_f16<2>(s, t) : launch_pl_f16<1>(s, t));
-            } else if (use_qkv8(t) && precision == FS2_PREC_BF16X3 && opts().qkv4 != 0 && opts().row4 != 0 && a.att_D == 384 && a.Cpad % 64 == 0) {
-                e = launch_qkv4(s, t);
-            } else if (use_qkv8(t)) {
-                if (a.att_D == 384) e = (precision == FS2_PREC_BF16X3) ? launch_qkv8<3, 3>(s, t) : launch_qkv8<1, 3>(s, t);
-                else e = (precision == FS2_PREC_BF16X3) ? launch_qkv8<3, 2>(s, t) : launch_qkv8<1, 2>(s, t);
-            } else if (row8 && a.ktaps > 1 && a.ln_groups == 2 && a.k_groups <= 1) {      // two stacked layers over one input: N = 512, LayerNorm per N-wave
-                e = (precision == FS2_PREC_BF16X3) ? launch_row8c_t<3, 4, 2, 2>(s, t) : launch_row8c_t<1, 4, 2, 2>(s, t);
-            } else if (row8 && a.ktaps > 1) {
-                if (a.k_groups > 1) { t.N = a.N / a.k_groups; t.ln_groups = 0; }      // grouped conv: a workgroup row per group (grid.y), N = one group's outputs
-                if (t.N == 384) e = (precision == FS2_PREC_BF16X3) ? launch_row8c<3, 3>(s, t) : launch_row8c<1, 3>(s, t);
-                else e = (precision == FS2_PREC_BF16X3) ? launch_row8c<3, 2>(s, t) : launch_row8c<1, 2>(s, t);
-            } else if (row8 && precision == FS2_PREC_BF16X3 && opts().row4 != 0 && row4_epi(t) >= 0) {
-                e = launch_row4(s, t, row4_epi(t));
-            } else if (row8) {
-                if (a.N == 384) e = (precision == FS2_PREC_BF16X3) ? launch_row8<3, 3>(s, t) : launch_row8<1, 3>(s, t);
-                else e = (precision == FS2_PREC_BF16X3) ? launch_row8<3, 2>(s, t) : launch_row8<1, 2>(s, t);
-            } else e = (precision == FS2_PREC_BF16X3) ? launch_pl<3>(s, t) : launch_pl<1>(s, t);
-        }
-        if (e == hipSuccess && rows_pass) {
-            char nm[112];
-            snprintf(nm, sizeof nm, "%s.rows", name);
-            Scope sc(h, s, nm, 0.0, 8.0 * a.R * a.N);
-            GemmArgs r = a;
-            r.Y = t.Y; r.ldy = t.ldy; r.ksplit = t.ksplit; r.kpart = t.kpart; r.kpart_stride = t.kpart_stride;
-            hipLaunchKernelGGL(ln_rows, dim3(((size_t)a.R * (a.ln_groups > 1 ? a.ln_groups : 1) + 3) / 4), dim3(256), 0, s, r);
-            e = hipGetLastError();
-        }
-    } else if (need_rows && a.N >= 128 && a.N <= 1024 && a.N % 4 == 0 && (a.Y || a.scratch) && !opts().f32_rows) {
-        // fp32, LayerNorm-terminated: 128x128 MFMA tiles + the HBM-bound row kernel (2x faster than the row-complete
-        // GEMM, whose 16-rows-per-wave shape re-stages the whole weight matrix for every 64 rows)
-        GemmArgs t = a;
-        if (!t.Y) { t.Y = a.scratch; t.ldy = a.N; }
-        t.act_post = 0;
-        {
-            Scope sc(h, s, name, flops, bytes);
-            e = launch_tile(s, t);
-        }
-        if (e == hipSuccess) {
-            char nm[112];
-            snprintf(nm, sizeof nm, "%s.rows", name);
-            Scope sc(h, s, nm, 0.0, 8.0 * a.R * a.N);
-            GemmArgs r = a;
-            r.Y = t.Y; r.ldy = t.ldy;
-            hipLaunchKernelGGL(ln_rows, dim3((a.R + 3) / 4), dim3(256), 0, s, r);
-            e = hipGetLastError();
-        }
-    } else {
-        Scope sc(h, s, name, flops, bytes);
-        if (need_rows || (a.N < 128 && rows_supported(a.N))) {
-            if (!rows_supported(a.N)) return fail(h, FS2_ERR_UNSUPPORTED, "%s: row-epilogue GEMM needs N in {80,256,384}, got %d", name, a.N);
-            if (a.N == 80) e = launch_rows<5>(s, a);
-            else if (a.N == 256) e = launch_rows<16>(s, a);
-            else e = launch_rows<24>(s, a);
-        } else {
-            e = launch_tile(s, a);
-        }
+    char nm[112];
+    if (p.build_planes) {
+        snprintf(nm, sizeof nm, "%s.planes", name);
+        Scope sc(h, s, nm, 0.0, 8.0 * a.R * a.Cpad);
+        const int64_t n = (int64_t)a.R * (a.Cpad / 4);
+        hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.X, a.ldx, a.C, a.R, a.Cpad / 32, a.xp_scratch, a.mx ? 2 : (a.f16_terms ? 1 : 0), a.yp_scale);
+    }
+    hipError_t e;
+    {
+        Scope sc(h, s, name, 2.0 * a.R * (double)a.N * a.C * a.ktaps, 4.0 * ((double)a.R * a.C + (double)a.N * a.C * a.ktaps + (double)a.R * a.N));
+        e = run_plan(s, p, t);
+    }
+    if (e == hipSuccess && p.rows_pass) {
+        snprintf(nm, sizeof nm, "%s.rows", name);
+        Scope sc(h, s, nm, 0.0, 8.0 * a.R * a.N);
+        GemmArgs r = a;
+        r.Y = t.Y; r.ldy = t.ldy; r.ksplit = t.ksplit; r.kpart = t.kpart; r.kpart_stride = t.kpart_stride;
+        hipLaunchKernelGGL(ln_rows, dim3(((size_t)a.R * (a.ln_groups > 1 ? a.ln_groups : 1) + 3) / 4), dim3(256), 0, s, r);
+        e = hipGetLastError();
     }
     if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
     return FS2_OK;
 }
+
+// Will the decoder's LayerNorm-fused k = 1 launches (the input layer, out-proj + LN1, FFN2 + LN2) run on gemm_row4_bf16 -- i.e. do its activations travel
+// as planes ONLY?  Asked of the plan, once per fs2_decode, for these launches in their planes-only form; anything the plan would not put there leaves the
+// decoder on the fp32-rows form.  (run_stack_general, the stack of the pre-LN / concat variants, has no planes-only form.)
+bool planes_only_regime(const fs2_handle* h, int prec, int R, int regime_rows) {
+    const fs2_config& c = h->cfg;
+    if (h->dec.pre_ln || h->dec.concat || h->dec.layers.empty()) return false;
+    const Layer& ly = h->dec.layers[0];
+    const PlaneDims in = c.decoder_input_layer ? PlaneDims{h->dec_in.C, h->dec_in.Cpad} : PlaneDims{0, 0};
+    return planes_only_plan(in, {ly.out.C, ly.out.Cpad}, {ly.w2.C, ly.w2.Cpad}, c.ddim, R, regime_rows, prec, opts());
+}
+// Does FFN2 + LN2 run in gemm_row4_bf16's mx arithmetic if it is offered mx planes?  (run_stack asks before it decides the format FFN1 leaves the hidden layer in.)
+bool ffn2_on_row4_mx(GemmArgs a) { a.mx = 1; const GemmPlan p = plan_gemm(a, FS2_PREC_BF16X3, opts()); return p.kernel == GemmKernel::Row4 && p.arith == 2; }
 
 GemmArgs gemm_args(const Gemm& g, const float* X, int ldx, int R, const int* row_pos, float* Y, int ldy) {
     GemmArgs a;
@@ -1083,7 +824,7 @@ int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, in
         if (po) { a2.residp = b.x1p; a2.residp_chunks = D / 32; a2.residp_mx = mx4l ? 2 : (mxl ? 1 : 0); a2.residp_scale = mxl ? exp2f(-(float)(ly.ka + 11)) : 1.f; }      // (x1p: LN1's output in the format the FFN conv wants)
         else { a2.resid = b.x1; a2.ldr = D; }
         if (pl) { a2.Xp = hidp; a2.Yp = b.x0p; a2.yp_chunks = D / 32; }
-        const bool mx2 = mxl && ly.w2.wm && opts().ffn2_mx && prec == FS2_PREC_BF16X3 && ffn2_on_row4_mx(h, a2);
+        const bool mx2 = mxl && ly.w2.wm && opts().ffn2_mx && prec == FS2_PREC_BF16X3 && ffn2_on_row4_mx(a2);
         if (mx2) { a2.mx = 1; a2.Wb = ly.w2.wm; a2.mx_scale = scale_byte4(127 - ly.kh - 11); a2.mx_scale_b = scale_byte4(127 - ly.w2.kw); }
         snprintf(nm, sizeof nm, "%s.ffn1", tag);
         a = gemm_args(ly.w1, b.x1, D, R, dl.row_pos, pl ? nullptr : b.hid, ly.w1.N);
@@ -1241,8 +982,7 @@ int run_predictors_fused(fs2_handle* h, hipStream_t s, const FusedPredictors& v,
                          const void* Xp, void* xps, float* vp, float* vs, float* e_rows, float* p_rows, int prec) {
     const int chans = v.c0.N / 2;
     int rc;
-    const long regime = h->cur_regime ? h->cur_regime : R;
-    const bool row8 = opts().row8 >= 0 ? opts().row8 != 0 : (regime + 127) / 128 >= 128;
+    const bool row8 = row_regime(h->cur_regime ? h->cur_regime : R, opts().row8);
     if (row8 && (chans == 256 || chans == 384)) {
         // big grids: layer 0 as two row-complete launches (the stacked 512-column form exists at 128-row tiles only -- 128 accumulator
         // registers -- and pays a nearly empty second round where the 192-row form does not: c3 0.169 ms against 2 x 0.07), each filling its half
@@ -2028,7 +1768,7 @@ int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) {
     // Planes-only residual stream (round 6): where the decoder's LayerNorm-fused launches run on gemm_row4_bf16 they write planes and nothing else and
     // read their residual from planes (gemm_row4.h: RES) -- the fp32 rows x0 / x1 are not written at all (0.9 GB per c3 step, 11 GB per c4 step of HBM
     // writes).  Not in the fp16 two- / one-term modes (their LN1 output is a fp16 hi + lo pair, a format the residual reader does not have).
-    const bool po = dec_pl && planes_only_regime(c, h->dec, prec, regime_rows) && (ffn_terms == 0 || ffn_terms == kFfnMx || ffn_terms == kFfnMx4);
+    const bool po = dec_pl && planes_only_regime(h, prec, R, regime_rows) && (ffn_terms == 0 || ffn_terms == kFfnMx || ffn_terms == kFfnMx4);
     if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
         GemmArgs a = gemm_args(h->dec_in, f.hfr, c.adim, R, dl.row_pos, po ? nullptr : f.sb.x0, c.ddim);
         a.Rp = dl.dims; a.regime_rows = regime_rows;
