@@ -86,7 +86,8 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_vocode_workspace_bytes", "fs2_op_griffin_lim", "fs2_op_stft_workspace_bytes", "fs2_op_stft",
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
-           "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev"]
+           "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
+           "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
 
@@ -282,6 +283,11 @@ def lib():
     L.fs2_op_griffin_lim_dev.argtypes = [vp] + gp + [vp, i32, vp, i32, vp, i32, C.c_int64, vp, i32, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp, i32,
                                                      C.c_int64, vp, vp]
     L.fs2_op_griffin_lim_dev.restype = C.c_int
+    L.fs2_op_targets_workspace_bytes.argtypes = [i32]
+    L.fs2_op_targets_workspace_bytes.restype = C.c_size_t
+    # stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats
+    L.fs2_op_clean_targets.argtypes = [vp, vp, i32, i32p, i32p, vp, C.c_size_t, vp, vp, vp, vp]
+    L.fs2_op_clean_targets.restype = C.c_int
     # The kernels with literal-register accumulators run only in a library whose ISA was audited (build()): the LIBRARY looks for the record of
     # its own hash when it is first used (fs2_runtime.hip: audit_clean) and otherwise starts with attn_w32 / gemm_row4_bf16 switched off -- for
     # every consumer, not only this binding; the compiler-scheduled kernels take their place (slower, never silently wrong).  Here: say so.

@@ -1441,6 +1441,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- vocoder (griffin_lim.h)
 #include "griffin_lim_host.h"
 
+// ---------------------------------------------------------------------------------- training targets (kernels and host side)
+#include "targets.h"
+
 }  // namespace
 
 // =====================================================================================================
@@ -2255,6 +2258,13 @@ int fs2_op_stft_pitch_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win
     if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_pitch_geom", gh)) return rc;
     return gl_stft_pitch_run("fs2_op_stft_pitch_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy,
                              sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost, f0, strength);
+}
+
+size_t fs2_op_targets_workspace_bytes(int32_t B) { return B < 0 ? 0 : tg_layout(B).bytes; }
+
+int fs2_op_clean_targets(void* stream, const float* x, int32_t B, const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes,
+                         float* y, float* quartiles, int32_t* n_outliers, double* stats) {
+    return tg_clean_targets(stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats);
 }
 
 }  // extern "C"

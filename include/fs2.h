@@ -382,6 +382,33 @@ int fs2_op_griffin_lim_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win
                            void *workspace, size_t workspace_bytes, float *wav, int32_t wav_stride, int64_t wav_capacity,
                            int64_t *sample_lens_dev, int32_t *status);
 
+/* ---- Training targets from the per-frame energy and F0 arrays (fastspeech2_amd/csrc/targets.h): the
+ * reference's remove_outlier (utils/util.py:26-49, applied to every energy and pitch array its data loader returns) and the corpus
+ * statistics of its compute_statistics.py, for B utterances packed in x: utterance b = x[starts[b] .. + lens[b]).  Per utterance
+ * (float32, n >= 1 values), every operation rounded to float32 on its own, no fused multiply-add:
+ *   s = sort(x); for q in {1, 3}: h = q (n - 1), j = h / 4, g = (h % 4) / 4, a = s[j], b = s[min(j + 1, n - 1)], d = b - a,
+ *   p = g < 0.5 ? a + d g : b - d (1 - g)        (numpy.percentile(x, 25 / 75) of float32 data, bit for bit: p25, p75)
+ *   w = 1.5 (p75 - p25); x[i] is an outlier iff x[i] <= p25 - w or x[i] >= p75 + w  (p25 == p75: every value is one)
+ *   M = max_i (outlier_i ? 0 : x[i]);  y[i] = x[i] == 0 ? 0 : outlier_i ? M : x[i]
+ * An utterance with a NaN or an infinity is copied unchanged: its quartiles are NaN, its outlier count 0, and the statistics leave
+ * it out.  An utterance of 0 values produces nothing (quartiles NaN, count 0).  There is no limit on an utterance's length.
+ * stats: device double[12] over the cleaned values y of the finite utterances --
+ *   [0] n_total        values          [1] n_outliers   flagged values      [2] n_nonfinite  utterances with a NaN / infinity
+ *   [3] n_no_positive  utterances (n >= 1, finite) without any y > 0        [4] n            values y != 0
+ *   [5] min  [6] nonzero_min = min over y > 0 (+inf: none)  [7] max         (min +inf and max -inf without a value)
+ *   [8] mean  [9] std = sqrt(M2 / n)  [10] M2 = sum (y - mean)^2, all three over y != 0, in double (0 when n = 0)   [11] 0
+ * The sums are reduced in a fixed order without floating-point atomics: the same batch gives the same bits on every call, and an
+ * utterance's y, quartiles and count do not depend on the batch it is in. ---- */
+
+/* workspace bytes of fs2_op_clean_targets for B utterances (host only; 0 on a bad argument, B < 0) */
+size_t fs2_op_targets_workspace_bytes(int32_t B);
+
+/* starts, lens: HOST int32 [B] (read before the call returns).  y: device float32, indexed as x, may equal x (in place).
+ * quartiles [B, 2] = p25, p75; n_outliers [B] int32; stats double[12] as above: device, each optional (NULL).  Asynchronous on
+ * `stream`: no allocation, no host read of device memory, no synchronisation. */
+int fs2_op_clean_targets(void *stream, const float *x, int32_t B, const int32_t *starts, const int32_t *lens, void *workspace,
+                         size_t workspace_bytes, float *y, float *quartiles, int32_t *n_outliers, double *stats);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
