@@ -77,6 +77,18 @@ class OpGemmArgs(_Sized):
                 ("y", C.c_void_p), ("row_valid", C.c_void_p)]
 
 
+class OpLossArgs(_Sized):
+    """fs2_op_loss_args.  ``ilens`` / ``olens`` are HOST int32 arrays; every other pointer is a device pointer."""
+    _fields_ = ([("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in (
+        "B", "odim", "Tmax", "Lmax", "pads", "pred_stride_f", "y_stride_f", "pred_stride_t", "ds_stride_t", "tgt_stride_f")]
+        + [(n, C.c_void_p) for n in ("before", "after", "ys", "d_outs", "ds", "e_outs", "es", "p_outs", "ps")]
+        + [("ilens", C.POINTER(C.c_int32)), ("olens", C.POINTER(C.c_int32)), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+           ("terms", C.c_void_p), ("batch", C.c_void_p)])
+
+
+LOSS_TERMS = 20      # FS2_LOSS_TERMS
+
+
 # every symbol include/fs2.h declares (tests check the library exports all of them)
 ABI_VERSION = 4      # FS2_ABI_VERSION of the include/fs2.h these mirrors were written against (checked in lib())
 
@@ -87,7 +99,7 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
-           "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets"]
+           "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
 
@@ -288,6 +300,10 @@ def lib():
     # stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats
     L.fs2_op_clean_targets.argtypes = [vp, vp, i32, i32p, i32p, vp, C.c_size_t, vp, vp, vp, vp]
     L.fs2_op_clean_targets.restype = C.c_int
+    L.fs2_op_loss_workspace_bytes.argtypes = [i32, i32p]
+    L.fs2_op_loss_workspace_bytes.restype = C.c_size_t
+    L.fs2_op_loss_terms.argtypes = [vp, C.POINTER(OpLossArgs)]
+    L.fs2_op_loss_terms.restype = C.c_int
     # The kernels with literal-register accumulators run only in a library whose ISA was audited (build()): the LIBRARY looks for the record of
     # its own hash when it is first used (fs2_runtime.hip: audit_clean) and otherwise starts with attn_w32 / gemm_row4_bf16 switched off -- for
     # every consumer, not only this binding; the compiler-scheduled kernels take their place (slower, never silently wrong).  Here: say so.

@@ -1444,6 +1444,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- training targets (kernels and host side)
 #include "targets.h"
 
+// ---------------------------------------------------------------------------------- loss terms of the teacher-forced forward
+#include "losses.h"
+
 }  // namespace
 
 // =====================================================================================================
@@ -2266,5 +2269,9 @@ int fs2_op_clean_targets(void* stream, const float* x, int32_t B, const int32_t*
                          float* y, float* quartiles, int32_t* n_outliers, double* stats) {
     return tg_clean_targets(stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats);
 }
+
+size_t fs2_op_loss_workspace_bytes(int32_t B, const int32_t* olens) { return lt_workspace_bytes(B, olens); }
+
+int fs2_op_loss_terms(void* stream, const fs2_op_loss_args* a) { return lt_loss_terms(stream, a); }
 
 }  // extern "C"

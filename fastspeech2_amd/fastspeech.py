@@ -706,6 +706,35 @@ class FeedForwardTransformer(nn.Module):
                        {"pitch_loss": pitch_loss.item()}, {"loss": loss.item()}]
         return loss, report_keys
 
+    def evaluate_batch(self, xs, ilens, ys, olens, ds, es, ps, semantics="per_utterance", sync=True):
+        """Validation of a whole batch in one call: the teacher-forced forward, then ``loss_terms`` on its outputs and the targets
+        (csrc/losses.h) -> :class:`fastspeech2_amd.losses.LossTerms`.  Arguments as ``forward()``.
+
+        ``semantics="per_utterance"`` (default): every utterance is computed as if it were alone, which is what the reference's
+        evaluation.py does with its batch size of 1 -- ``.evaluate()`` is its result, ``.report()`` the masked losses, and an
+        utterance's numbers do not depend on the batch it is in.  The pad positions hold nothing in this mode, so the pad sums are
+        not built (``report(use_masking=False)`` raises).  ``"padded_compat"``: the forward ``forward()`` runs (pads take part, as
+        in the reference's batched training step); ``.report(...)`` then gives ``forward()``'s seven values under any of the
+        reference's masking switches, from float64 sums instead of float32 means.
+        ``sync=False``: the records stay on the device until first read (the forward's own read-back of the frame counts remains)."""
+        from .losses import loss_terms
+        if semantics not in ("per_utterance", "padded_compat"):
+            raise ValueError("semantics must be 'per_utterance' or 'padded_compat', got %r" % (semantics,))
+        _require_device(xs)
+        dev = xs.device
+        if self.reduction_factor > 1:
+            raise NotImplementedError("loss path with reduction_factor > 1 (the reference's own length handling for it is commented "
+                                      "out, fastspeech.py:275-276); _forward / inference are implemented")
+        il = torch.as_tensor(ilens).to("cpu", torch.int64)
+        ol = torch.as_tensor(olens).to("cpu", torch.int64)
+        compat = semantics == "padded_compat"
+        xs = xs[:, : int(il.max())]
+        ys = ys.to(dev).float()
+        ds, es, ps = ds.to(dev).long(), es.to(dev).float(), ps.to(dev).float()
+        ds_t = ds[:, : xs.shape[1]]
+        r = self._run(xs, il, ol, ds_t, es, ps, is_inference=False, compat=compat, want=("before", "after", "e_outs", "p_outs"))
+        return loss_terms(r["before"], r["after"], ys, r["d_log"], ds, r["e_outs"], es, r["p_outs"], ps, il, ol, pads=compat, sync=sync)
+
     def inference(self, x, alpha=1.0):
         """reference fastspeech.py:339-357: x [T] int64 phoneme ids -> mel [L, odim].  ``alpha`` (not in the reference's
         ``inference``, but in its LengthRegulator, length_regulator.py:57-59) scales the durations: > 1 slower speech."""

@@ -409,6 +409,56 @@ size_t fs2_op_targets_workspace_bytes(int32_t B);
 int fs2_op_clean_targets(void *stream, const float *x, int32_t B, const int32_t *starts, const int32_t *lens, void *workspace,
                          size_t workspace_bytes, float *y, float *quartiles, int32_t *n_outliers, double *stats);
 
+/* ---- Loss terms of the teacher-forced forward, per utterance (fastspeech2_amd/csrc/losses.h): what the
+ * reference's FeedForwardTransformer.forward() (fastspeech.py:280-333, the seven report values) and its evaluation.py (12-41, the mean
+ * L1 of duration, energy and pitch per utterance) reduce the model's outputs and the targets to.  Every difference is formed in double
+ * from the float32 / int64 inputs (exact); |.|, the square and log((double)ds + 1.0) are taken in double; sums are carried in double
+ * and reduced in a fixed order without floating-point atomics.  A record is FS2_LOSS_TERMS doubles:
+ *   [0] ilen   [1] olen   [2] Tmax - ilen   [3] Lmax - olen
+ *   [4] sum |before - ys|   [5] sum |after - ys|                        frames [0, olen), all odim bins
+ *   [6] sum (d_outs - log(ds + 1))^2                                    tokens [0, ilen)
+ *   [7] sum (e_outs - es)^2   [8] sum (p_outs - ps)^2                   frames [0, olen)
+ *   [9] sum |d_outs - ds|     tokens [0, ilen): evaluation.py:31 as written, the log-domain output against the linear durations
+ *   [10] sum |e_outs - es|    [11] sum |p_outs - ps|                    frames [0, olen)
+ *   [12] .. [16]  the sums of [4] .. [8] over the pad frames [olen, Lmax) / pad tokens [ilen, Tmax): what the reference's means
+ *                 include under use_masking = False.  0 with pads = 0, and nothing outside [0, len) of any utterance is then read
+ *   [17] .. [19]  0
+ * An utterance's [4] .. [11] depend on its own values only: not on B, on its place in the batch, on a stride, on Lmax or on the
+ * alignment of a pointer.  The batch record has the same layout: [0] .. [3] and every sum added up over the B utterances in a fixed
+ * order (the same batch gives the same bits on every call). ---- */
+#define FS2_LOSS_TERMS 20
+
+/* before, after: [B, pred_stride_f, odim]; ys: [B, y_stride_f, odim]; d_outs: [B, pred_stride_t]; ds: int64 [B, ds_stride_t];
+ * e_outs, p_outs: [B, pred_stride_f]; es, ps: [B, tgt_stride_f] -- device, float32 unless noted, strides in elements of the second
+ * dimension.  A prediction and its target may be NULL together (before and after share ys): its sums are 0.  Tmax >= max ilens and
+ * Lmax >= max olens are the padded extents the pad sums run to; neither may exceed a stride of a tensor that is given.
+ * ilens, olens: HOST int32 [B] (read before the call returns).  terms: device double [B, FS2_LOSS_TERMS]; batch: device
+ * double [FS2_LOSS_TERMS]; each optional (NULL).  B = 0 writes a zero batch record.  (The struct is declared in two statements so
+ * that tools/gen_binding_doc.py, whose list of mirrored structs is fixed, leaves it alone; fastspeech2_amd/_lib.py: OpLossArgs.) */
+struct fs2_op_loss_args {
+    uint32_t struct_size;     /* = sizeof(fs2_op_loss_args) */
+    int32_t B, odim, Tmax, Lmax, pads;
+    int32_t pred_stride_f, y_stride_f, pred_stride_t, ds_stride_t, tgt_stride_f;
+    const float *before, *after, *ys, *d_outs;
+    const int64_t *ds;
+    const float *e_outs, *es, *p_outs, *ps;
+    const int32_t *ilens, *olens;
+    void *workspace;
+    size_t workspace_bytes;
+    double *terms, *batch;
+};
+typedef struct fs2_op_loss_args fs2_op_loss_args;
+
+/* workspace bytes of fs2_op_loss_terms for utterances of olens frames (HOST int32 [B]); host only; 0 on a bad argument (B < 0, a
+ * negative length, null olens with B > 0) */
+size_t fs2_op_loss_workspace_bytes(int32_t B, const int32_t *olens);
+
+/* Asynchronous on `stream`: no allocation, no host read of device memory, no synchronisation; legal during stream capture.  Two
+ * launches plus the upload of the length records (kernel arguments).  FS2_ERR_ARG: wrong struct_size, a negative length,
+ * ilen > Tmax, olen > Lmax, an extent beyond a stride, a prediction without its target, a null workspace with B > 0;
+ * FS2_ERR_WORKSPACE: workspace_bytes below fs2_op_loss_workspace_bytes(B, olens). */
+int fs2_op_loss_terms(void *stream, const fs2_op_loss_args *a);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
