@@ -1447,6 +1447,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- loss terms of the teacher-forced forward
 #include "losses.h"
 
+// ---------------------------------------------------------------------------------- DTW distance of the free-running validation
+#include "dtw.h"
+
 }  // namespace
 
 // =====================================================================================================
@@ -2273,5 +2276,11 @@ int fs2_op_clean_targets(void* stream, const float* x, int32_t B, const int32_t*
 size_t fs2_op_loss_workspace_bytes(int32_t B, const int32_t* olens) { return lt_workspace_bytes(B, olens); }
 
 int fs2_op_loss_terms(void* stream, const fs2_op_loss_args* a) { return lt_loss_terms(stream, a); }
+
+size_t fs2_op_dtw_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap_bytes) {
+    return dtw_workspace_bytes(B, a_lens, b_lens, cap_bytes);
+}
+
+int fs2_op_dtw(void* stream, const fs2_op_dtw_args* a) { return dt_dtw(stream, a); }
 
 }  // extern "C"

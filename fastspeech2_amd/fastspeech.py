@@ -735,6 +735,32 @@ class FeedForwardTransformer(nn.Module):
         r = self._run(xs, il, ol, ds_t, es, ps, is_inference=False, compat=compat, want=("before", "after", "e_outs", "p_outs"))
         return loss_terms(r["before"], r["after"], ys, r["d_log"], ds, r["e_outs"], es, r["p_outs"], ps, il, ol, pads=compat, sync=sync)
 
+    def evaluate_free_running(self, xs, ilens, ys, olens, es=None, ps=None, alpha=1.0, features="mel", sync=True):
+        """Validation of the model's real output in one call: the free-running forward (the durations the model predicts itself,
+        scaled by ``alpha``), then ``mel_dtw`` of its mels and per-frame energy / pitch predictions against the targets
+        (csrc/dtw.h) -> :class:`fastspeech2_amd.dtw.DtwTerms`.  ``ys`` [B, >= max olens, odim], ``es`` / ``ps`` [B, >= max olens]
+        (each optional): the recordings' mels and tracks; ``olens``: their lengths.  The synthesized and the recorded utterance
+        differ in length, so each pair is aligned by dynamic time warping and the errors are taken along the path: ``.evaluate()``
+        is the free-running counterpart of ``evaluate_batch(...).evaluate()``.  Per-utterance semantics: an utterance's numbers do
+        not depend on the batch it is in.  ``sync=False``: the records stay on the device until first read (the forward's own
+        read-back of the frame counts remains)."""
+        from .dtw import mel_dtw
+        _require_device(xs)
+        dev = xs.device
+        if self.reduction_factor > 1:
+            raise NotImplementedError("free-running validation with reduction_factor > 1: e_outs / p_outs are per decoder frame, the mels per "
+                                      "mel frame")
+        if not float(alpha) > 0.0:
+            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
+        il = torch.as_tensor(ilens).to("cpu", torch.int64)
+        ol = torch.as_tensor(olens).to("cpu", torch.int64)
+        xs = xs[:, : int(il.max())]
+        r = self._run(xs, il, is_inference=True, compat=False, want=("after", "e_outs", "p_outs"), alpha=alpha)
+        ys = ys.to(dev).float()
+        e = None if es is None else (r["e_outs"], es.to(dev).float())
+        p = None if ps is None else (r["p_outs"], ps.to(dev).float())
+        return mel_dtw(r["after"], r["olens"], ys, ol, e=e, p=p, features=features, sync=sync)
+
     def inference(self, x, alpha=1.0):
         """reference fastspeech.py:339-357: x [T] int64 phoneme ids -> mel [L, odim].  ``alpha`` (not in the reference's
         ``inference``, but in its LengthRegulator, length_regulator.py:57-59) scales the durations: > 1 slower speech."""

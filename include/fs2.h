@@ -459,6 +459,52 @@ size_t fs2_op_loss_workspace_bytes(int32_t B, const int32_t *olens);
  * FS2_ERR_WORKSPACE: workspace_bytes below fs2_op_loss_workspace_bytes(B, olens). */
 int fs2_op_loss_terms(void *stream, const fs2_op_loss_args *a);
 
+/* ---- Dynamic time warping between B pairs of feature sequences a [N, D] (synthesized) and b [M, D] (reference) of different
+ * lengths, with the energy and F0 errors over the aligned frame pairs (fastspeech2_amd/csrc/dtw.h): the
+ * numbers of the free-running validation.  d(i, j) = sqrt(sum_k (a[i, k] - b[j, k])^2) in double, k in increasing order, nothing
+ * contracted; C(i, j) = d(i, j) + min(C(i-1, j-1), C(i-1, j), C(i, j-1)), the predecessor chosen in that order with a strict "<"
+ * (outside the matrix: +inf).  Each cell carries the record of its path, so the record of (N-1, M-1) is the result; the path itself
+ * is not returned.  A record is FS2_DTW_TERMS doubles:
+ *   [0] N   [1] M   [2] steps = frame pairs on the path   [3] cost C(N-1, M-1)
+ *   [4] sum |e_a[i] - e_b[j]|   [5] sum |p_a[i] - p_b[j]|                        over the path, in path order
+ *   [6] pairs with both pitches non-zero   [7] sum |p_a[i] - p_b[j]| over those   [8] pairs with exactly one pitch non-zero
+ *   [9] .. [11]  0
+ * N = 0 or M = 0 gives [0], [1] and zeros.  A pair's record depends on its own values only: not on B, on its place in the batch,
+ * on a stride or on the workspace handed in.  The batch record has the same layout: every entry added up over the pairs in index
+ * order.  A non-finite value in a valid frame makes that pair's cost non-finite and touches no other pair. ---- */
+#define FS2_DTW_TERMS 12
+
+/* a, b: device float32, row r of the a side at a + r * a_stride (strides in floats, >= D); pair i owns the rows
+ * [a_starts[i], a_starts[i] + a_lens[i]) of a and [b_starts[i], b_starts[i] + b_lens[i]) of b, so padded and packed layouts are both
+ * served.  e_a, p_a / e_b, p_b: device float32 scalar tracks indexed by the same rows (energy; pitch, 0 = unvoiced); each track is
+ * given for both sides or for neither (NULL: its sums are 0).  a_starts, a_lens, b_starts, b_lens: HOST int32 [B] (read before the
+ * call returns).  1 <= D <= 128.  terms: device double [B, FS2_DTW_TERMS]; batch: device double [FS2_DTW_TERMS]; each optional.
+ * B = 0 writes a zero batch record.  (Declared in two statements for the reason given at fs2_op_loss_args; _lib.py: OpDtwArgs.) */
+struct fs2_op_dtw_args {
+    uint32_t struct_size;     /* = sizeof(fs2_op_dtw_args) */
+    int32_t B, D;
+    int64_t a_stride, b_stride;
+    const float *a, *b, *e_a, *e_b, *p_a, *p_b;
+    const int32_t *a_starts, *a_lens, *b_starts, *b_lens;
+    void *workspace;
+    size_t workspace_bytes;
+    double *terms, *batch;
+};
+typedef struct fs2_op_dtw_args fs2_op_dtw_args;
+
+/* workspace bytes of fs2_op_dtw for pairs of a_lens x b_lens frames (HOST int32 [B]): min(what all pairs need at once,
+ * max(cap_bytes, what the largest single pair needs)) -- with less than everything the call works through groups of consecutive
+ * pairs, reusing the workspace in stream order.  Host only; 0 on a bad argument (B < 0, a negative length, a null pointer with
+ * B > 0, a matrix of more than 2^40 cells). */
+size_t fs2_op_dtw_workspace_bytes(int32_t B, const int32_t *a_lens, const int32_t *b_lens, size_t cap_bytes);
+
+/* Asynchronous on `stream`: no allocation, no host read of device memory, no synchronisation; legal during stream capture.  Per
+ * group of pairs one launch for the distance matrices and one for the sweep, plus the upload of the pair records (kernel
+ * arguments) and one combining launch.  FS2_ERR_ARG: wrong struct_size, D outside [1, 128], a stride below D, a negative start or
+ * length, a track given for one side only, a null workspace with B > 0; FS2_ERR_WORKSPACE: workspace_bytes below
+ * fs2_op_dtw_workspace_bytes(B, a_lens, b_lens, 0). */
+int fs2_op_dtw(void *stream, const fs2_op_dtw_args *a);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
