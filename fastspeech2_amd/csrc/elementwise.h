@@ -269,6 +269,26 @@ __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, con
     }
 }
 
+// The token a frame belongs to: idx = #{i : cum[b,i] <= j} (first i with cum[b,i] > j); -1 for gap rows and frames beyond the utterance.
+__device__ __forceinline__ int lr_token_index(int b, int j, const int* cum, int Tmax, const int* ilen, const int* vlen) {
+    if (b < 0 || j < 0 || j >= vlen[b]) return -1;
+    const int* c = cum + (size_t)b * Tmax;
+    int lo = 0, hi = ilen[b];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] <= j) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The length regulator's index output and nothing else (one thread per row): what is left of it where every consumer of the expanded rows
+// gathers from token-level products instead (var_gather0 / dec_in_gather below).
+__global__ void lr_index_only(const int* cum, int Tmax, const int* ilen, const int* row_pos, const int* row_seq, const int* vlen, int R, int* index_rows) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= R) return;
+    index_rows[row] = lr_token_index(row_seq[row], row_pos[row], cum, Tmax, ilen, vlen);
+}
+
 // Length-regulator expand (reference length_regulator.py:90-95 + utils/util.py:91-104):
 // out[row] = hs[tok_start[b] + idx], idx = #{i : cum[b,i] <= j}; rows beyond the utterance -> 0.
 // One wavefront per output row.  If row_seq == nullptr the output is a dense [B, uniform_len] layout.
@@ -367,6 +387,176 @@ __global__ __launch_bounds__(256) void bucket_embed(float* h, int D, const int* 
     }
 }
 
+// ---- multiply before expanding (fs2_runtime.hip: tok.proj) ----
+// The length regulator repeats every encoder row once per frame, and the first layer behind it is linear: the products of the encoder rows with the
+// weights of the predictors' first convolution (one k = 1 product per tap) and of the decoder input layer are computed once per TOKEN, as the rows
+// P [token rows, ldp] = [tap0: energy | pitch][tap1: energy | pitch][tap2: energy | pitch][dec.in], and the two kernels below gather them per frame.
+struct TokGatherArgs {
+    const float* P; int ldp;            // token-level products (fs2_encode), fp32 rows
+    const int* tok_start;               // [B] first token row of every utterance
+    const int* lri;                     // [R] token of every frame row (lr_index_only), -1: none
+    const int *row_pos, *row_seq;       // frame-row metadata
+    int R;
+    // var_gather0
+    int chans;                          // channels of one predictor's first layer
+    const float *bias, *ln_g, *ln_b;    // stacked energy | pitch: [2 chans]
+    void* vp;                           // planes of the stacked hidden layer [R][2 chans]
+    // dec_in_gather
+    int col0, D;                        // first dec.in column of P; decoder width
+    const float *es, *ps; int es_stride, ps_stride;      // teacher forcing ([B, stride]) or nullptr
+    const float *e_rows, *p_rows;       // the predictions per packed row
+    const float *ebins, *pbins; int nb;
+    const float *TE, *TP;               // [n_bins, D]: the embedding tables behind the input layer's weights (TP carries its bias)
+    int *qe_rows, *qp_rows;
+    const float *ln_g2, *ln_b2;         // LayerNorm of the input layer
+    const float* pe; const float* pe_alpha; float x_scale;
+    float* x0; void* x0p;               // fp32 rows (or nullptr: planes only) and split-bf16 planes of the decoder input
+};
+
+// First layer of both variance predictors from the token-level products: y[f] = P0[tok(f-1)] + P1[tok(f)] + P2[tok(f+1)] + b -> ReLU -> LayerNorm(1e-12),
+// written as split-bf16 planes at the column offset of the group.  A neighbour that is a gap row or lies beyond the utterance contributes zero, as the
+// zero rows of the expanded tensor did; rows that are no frame (row_pos < 0) become zero rows.  One wavefront per (row, predictor).
+__global__ __launch_bounds__(256) void var_gather0(TokGatherArgs a) {
+    const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int row = unit >> 1, grp = unit & 1;
+    const int lane = threadIdx.x & 63;
+    if (row >= a.R) return;
+    const int N = a.chans, co = grp * N, nch = 2 * N / 32;
+    if (a.row_pos[row] < 0) {
+        for (int c = lane * 4; c < N; c += 256) store_planes4(a.vp, row, nch, co + c, f32x4{0.f, 0.f, 0.f, 0.f});
+        return;
+    }
+    const int t0 = a.tok_start[a.row_seq[row]];
+    const float* src[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const int r = row + d - 1;
+        const int tk = (r >= 0 && r < a.R) ? a.lri[r] : -1;
+        src[d] = tk >= 0 ? a.P + (size_t)(t0 + tk) * a.ldp + d * 2 * N + co : nullptr;
+    }
+    float4 v[4];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < N) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                if (src[d]) {
+                    const float4 q = *reinterpret_cast<const float4*>(src[d] + c);
+                    v[j].x += q.x; v[j].y += q.y; v[j].z += q.z; v[j].w += q.w;
+                }
+            const float4 b = *reinterpret_cast<const float4*>(a.bias + co + c);
+            v[j].x = fmaxf(v[j].x + b.x, 0.f); v[j].y = fmaxf(v[j].y + b.y, 0.f); v[j].z = fmaxf(v[j].z + b.z, 0.f); v[j].w = fmaxf(v[j].w + b.w, 0.f);
+        }
+        s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)N;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        if (c < N) {
+            const float dx = v[j].x - mean, dy = v[j].y - mean, dz = v[j].z - mean, dw = v[j].w - mean;
+            q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.f / sqrtf(q / (float)N + 1e-12f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        if (c < N) {
+            const float4 g = *reinterpret_cast<const float4*>(a.ln_g + co + c);
+            const float4 b = *reinterpret_cast<const float4*>(a.ln_b + co + c);
+            store_planes4(a.vp, row, nch, co + c, f32x4{(v[j].x - mean) * rstd * g.x + b.x, (v[j].y - mean) * rstd * g.y + b.y,
+                                                      (v[j].z - mean) * rstd * g.z + b.z, (v[j].w - mean) * rstd * g.w + b.w});
+        }
+    }
+}
+
+// Variance-adaptor tail and decoder input layer from the token-level products (replaces bucket_embed + the input layer's GEMM):
+// bucket search with bucket_embed's rule, then (P[tok, dec.in columns] + TP[qp]) + TE[qe] -> LayerNorm(1e-5) -> ReLU -> * x_scale + alpha pe[pos].
+// A frame row without a token (padded-batch semantics: positions beyond the utterance) has a zero first term, as its zero row had.  One wavefront per row.
+__global__ __launch_bounds__(256) void dec_in_gather(TokGatherArgs a) {
+    const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));      // (scalar: the two bin searches become scalar-load chains)
+    const int lane = threadIdx.x & 63;
+    if (row >= a.R) return;
+    const int D = a.D, nch = D / 32;
+    const int pos = a.row_pos[row];
+    float* y = a.x0 ? a.x0 + (size_t)row * D : nullptr;
+    if (pos < 0) {
+        if (lane == 0) { if (a.qe_rows) a.qe_rows[row] = -1; if (a.qp_rows) a.qp_rows[row] = -1; }
+        for (int c = lane * 4; c < D; c += 256) {
+            if (y) *reinterpret_cast<float4*>(y + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+            store_planes4(a.x0p, row, nch, c, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+        return;
+    }
+    const int b = a.row_seq[row];
+    const float e = a.es ? (pos < a.es_stride ? a.es[(size_t)b * a.es_stride + pos] : 0.f) : a.e_rows[row];
+    const float p = a.ps ? (pos < a.ps_stride ? a.ps[(size_t)b * a.ps_stride + pos] : 0.f) : a.p_rows[row];
+    const int qe = bucket_index(e, a.ebins, a.nb);
+    const int qp = bucket_index(p, a.pbins, a.nb);
+    if (lane == 0) { if (a.qe_rows) a.qe_rows[row] = qe; if (a.qp_rows) a.qp_rows[row] = qp; }
+    const int tk = a.lri[row];
+    const float* ph = tk >= 0 ? a.P + (size_t)(a.tok_start[b] + tk) * a.ldp + a.col0 : nullptr;
+    const float* te = a.TE + (size_t)qe * D;
+    const float* tp = a.TP + (size_t)qp * D;
+    float4 v[4];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < D) {
+            if (ph) v[j] = *reinterpret_cast<const float4*>(ph + c);
+            const float4 g = *reinterpret_cast<const float4*>(tp + c);
+            const float4 h = *reinterpret_cast<const float4*>(te + c);
+            v[j].x = (v[j].x + g.x) + h.x; v[j].y = (v[j].y + g.y) + h.y; v[j].z = (v[j].z + g.z) + h.z; v[j].w = (v[j].w + g.w) + h.w;
+        }
+        s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        if (c < D) {
+            const float dx = v[j].x - mean, dy = v[j].y - mean, dz = v[j].z - mean, dw = v[j].w - mean;
+            q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.f / sqrtf(q / (float)D + 1e-5f);
+    const float alpha = a.pe_alpha ? a.pe_alpha[0] : 1.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane * 4 + j * 256;
+        if (c < D) {
+            const float4 g = *reinterpret_cast<const float4*>(a.ln_g2 + c);
+            const float4 bt = *reinterpret_cast<const float4*>(a.ln_b2 + c);
+            const float4 pv = *reinterpret_cast<const float4*>(a.pe + (size_t)pos * D + c);
+            float4 t;
+            t.x = fmaxf((v[j].x - mean) * rstd * g.x + bt.x, 0.f) * a.x_scale + alpha * pv.x;
+            t.y = fmaxf((v[j].y - mean) * rstd * g.y + bt.y, 0.f) * a.x_scale + alpha * pv.y;
+            t.z = fmaxf((v[j].z - mean) * rstd * g.z + bt.z, 0.f) * a.x_scale + alpha * pv.z;
+            t.w = fmaxf((v[j].w - mean) * rstd * g.w + bt.w, 0.f) * a.x_scale + alpha * pv.w;
+            if (y) *reinterpret_cast<float4*>(y + c) = t;
+            store_planes4(a.x0p, row, nch, c, f32x4{t.x, t.y, t.z, t.w});
+        }
+    }
+}
+
+// tap `tap` of a convolution weight [N][C][k] as a Linear weight [N][C] (load time: the rows of tok.proj's stacked weight)
+__global__ void conv_tap_rows(const float* w, int N, int C, int k, int tap, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N * C) out[i] = w[(size_t)i * k + tap];
+}
+
 // packed rows [R, W] -> padded [B, Lout, W]; positions >= limit[b] are filled with `fill`.
 template <typename T>
 __global__ void unpack_rows(const T* src, int W, const int* start, const int* limit, int B, int Lout, T* dst, T fill) {
@@ -453,7 +643,7 @@ __global__ __launch_bounds__(256) void transpose_rows(const float* src, int64_t 
 }
 
 // ---- weight repacking (run once per load_state_dict) ----
-// conv / linear weight [N][C][k] -> [Npad][k][Cpad], zero padded, optionally scaled per output channel by
+// conv / linear weight [N][C][k] -> [Npad][k][Cpad] (fs2_runtime.hip: gemm_rows_from restates this row stride), zero padded, optionally scaled per output channel by
 // gamma / sqrt(var + eps) (eval-mode BatchNorm folded into the Postnet convs, reference modules.py:285-348).
 // ldw: elements between consecutive output rows of the source (0: C; larger for a column slice of a wider Linear weight, k = 1).
 __global__ void repack_weight(const float* w, int N, int C, int k, int Npad, int Cpad, const float* bn_g,

@@ -50,6 +50,17 @@ struct Gemm {          // one repacked Linear / Conv1d
     float* bias = nullptr;   // [N] or null
     int N = 0, C = 0, Cpad = 0, ktaps = 1;
 };
+// Output rows [n0, N) of a repacked layer as a layer of its own (n0 a multiple of 128: whole column tiles).  The one place besides the repack kernels that knows the
+// row strides of their images: fp32 [Npad][ktaps][Cpad] (elementwise.h: repack_weight), split-bf16 [Npad][Cpad / 32][ktaps][64] (gemm_bf16.h: repack_weight_bf16).
+// The fp16 / mx images are not carried over.
+inline Gemm gemm_rows_from(const Gemm& g, int n0) {
+    Gemm r;
+    r.N = g.N - n0; r.C = g.C; r.Cpad = g.Cpad; r.ktaps = g.ktaps;
+    r.w = g.w + (size_t)n0 * g.ktaps * g.Cpad;
+    r.wb = reinterpret_cast<__bf16*>(g.wb) + (size_t)n0 * (g.Cpad / 32) * g.ktaps * 64;
+    r.bias = g.bias ? g.bias + n0 : nullptr;
+    return r;
+}
 struct Layer {
     Gemm qkv, out, w1, w2;
     Gemm cat_x, cat_a;       // concat_after: concat_linear [D, 2D] split into its x half (carries the bias) and its attention half
@@ -178,6 +189,7 @@ Options& opts() {
         x.bm = env_int("FS2_BM", -1); x.row8 = env_int("FS2_ROW8", -1); x.qkv8 = env_int("FS2_QKV8", -1);
         x.nosplitk = env_int("FS2_NOSPLITK", 0) != 0; x.f32_rows = env_int("FS2_F32_ROWS", 0) != 0; x.mt8 = env_int("FS2_MT8", -1); x.qkv_split = env_int("FS2_QKV_SPLIT", -1); x.op_att_planes = env_int("FS2_OP_ATT_PLANES", 0); x.fuse_var = env_int("FS2_FUSE_VAR", 1); x.bal = env_int("FS2_BAL", 0); x.w32 = env_int("FS2_ATTN_W32", -1);
         x.row4 = env_int("FS2_ROW4", -1); x.mt4 = env_int("FS2_MT4", -1); x.ffn2_mx = env_int("FS2_FFN2_MX", 1); x.qkv4 = env_int("FS2_QKV4", -1); x.post_mx = env_int("FS2_POST_MX", 1);
+        x.tokproj = env_int("FS2_TOKPROJ", 3) & 3; x.tokproj_f32 = env_int("FS2_TOKPROJ_F32", 0) != 0;
         if (!audit_clean()) {
             x.w32 = 0; x.row4 = 0; x.qkv4 = 0;
             fprintf(stderr, "libfs2_hip: no clean ISA-audit record of this binary (libfs2_hip.audit.json next to it): attn_w32 and gemm_row4_bf16 are switched "
@@ -283,6 +295,9 @@ struct fs2_handle {
     FusedPredictors var2;
     float *ebins = nullptr, *pbins = nullptr, *Te = nullptr, *Tp = nullptr;
     Gemm dec_in; float *dec_in_lng = nullptr, *dec_in_lnb = nullptr;
+    // multiply before expanding (FS2_TOKPROJ): the stacked k = 1 weight [tap0: energy | pitch][tap1: ..][tap2: ..][dec.in] of tok.proj (N == 0: this model has none)
+    // and the embedding tables behind the input layer's weights, TPd = (pitch_embed.W^T + b_p) W_in^T + b_in, TEd = (energy_embed.W^T + b_e) W_in^T: [n_bins, ddim]
+    Gemm tokw; float *TEd = nullptr, *TPd = nullptr;
     Gemm feat;
     std::vector<Gemm> post;
     // state carried from encode to decode
@@ -290,6 +305,8 @@ struct fs2_handle {
     HostLayout tok;
     DevLayout dtok;
     float* enc_final = nullptr;
+    float* tokP = nullptr;     // tok.proj's output of the encoded batch [token rows, tokw.N] (nullptr: not computed)
+    bool tokP_conv = false;    // ... its predictor columns were computed too (else only the input layer's)
     int* cum = nullptr;
     int* o32 = nullptr;        // device frame counts (int32) left by the duration scan
     int enc_B = 0, enc_Tmax = 0, enc_compat = 0;
@@ -979,11 +996,16 @@ int run_predictor(fs2_handle* h, hipStream_t s, const char* tag, const Predictor
 // The pitch and the energy predictor of the bf16 modes as one launch per layer (FusedPredictors).  Every output column is accumulated in the
 // order of the separate launches; the LayerNorm of a 256-column group may be summed in another order than the two-wave form (1e-7).
 int run_predictors_fused(fs2_handle* h, hipStream_t s, const FusedPredictors& v, const float* X, int ldx, int R, const int* row_pos, const int* Rp,
-                         const void* Xp, void* xps, float* vp, float* vs, float* e_rows, float* p_rows, int prec) {
+                         const void* Xp, void* xps, float* vp, float* vs, float* e_rows, float* p_rows, int prec, const TokGatherArgs* tg = nullptr) {
     const int chans = v.c0.N / 2;
     int rc;
     const bool row8 = row_regime(h->cur_regime ? h->cur_regime : R, opts().row8);
-    if (row8 && (chans == 256 || chans == 384)) {
+    if (tg) {      // layer 0 from the token-level products (tok.proj): a row kernel in place of the convolution(s)
+        Scope sc(h, s, "var.gather0", 0.0, 4.0 * R * chans * (6.0 + 2.0));
+        hipLaunchKernelGGL(var_gather0, dim3((2 * (size_t)R + 3) / 4), dim3(256), 0, s, *tg);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "var.gather0 launch: %s", hipGetErrorString(e));
+    } else if (row8 && (chans == 256 || chans == 384)) {
         // big grids: layer 0 as two row-complete launches (the stacked 512-column form exists at 128-row tiles only -- 128 accumulator
         // registers -- and pays a nearly empty second round where the 192-row form does not: c3 0.169 ms against 2 x 0.07), each filling its half
         // of the stacked plane rows
@@ -1266,6 +1288,48 @@ void load_predictor(Loader& L, Predictor& p, const std::string& pre, int nlayers
     p.lin_b = L.copy(pre + ".linear.bias", {1});
 }
 
+// Columns of tok.proj's output (fs2_handle::tokw) for this configuration, 0 where the token-level form does not exist: it needs the decoder input layer and the
+// fused predictors (FusedPredictors: two layers, var_chans % 128 == 0, adim % 32 == 0) with a 3-tap first convolution (the derivation holds for any odd size; 3 is built).
+// A function of the configuration alone: the token workspace reserves the rows whatever FS2_TOKPROJ says, so the option can change between calls.
+inline int tok_proj_cols(const fs2_config& c) {
+    const bool ok = c.decoder_input_layer && c.var_kernel == 3 && c.var_layers == 2 && c.var_chans % 128 == 0 && c.var_chans <= 1024 && c.adim % 32 == 0 &&
+                    c.ddim % 32 == 0 && c.ddim <= 1024;
+    return ok ? 6 * c.var_chans + c.ddim : 0;
+}
+
+// Load-time half of "multiply before expanding": the stacked weight of tok.proj and the two tables behind the input layer's weights (exact fp32 GEMMs on the device;
+// the tables depend on weights only).  Needs h->Te / h->Tp / h->dec_in.
+void load_tok_proj(Loader& L, fs2_handle* h) {
+    const fs2_config& c = h->cfg;
+    hipStream_t s = L.s;
+    const int ch = c.var_chans, Nt = tok_proj_cols(c);
+    const fs2_tensor_desc* wsrc[2] = {L.get("energy_predictor.predictor.conv.0.0.weight", {ch, c.adim, 3}), L.get("pitch_predictor.predictor.conv.0.0.weight", {ch, c.adim, 3})};
+    const fs2_tensor_desc* win = L.get("decoder.embed.0.weight", {c.ddim, c.adim});
+    if (!wsrc[0] || !wsrc[1] || !win) return;
+    float* stk = nullptr;
+    if (hipMalloc((void**)&stk, (size_t)Nt * c.adim * sizeof(float)) != hipSuccess) { if (!L.rc) L.rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return; }
+    L.synth_mem.push_back(stk);
+    for (int tap = 0; tap < 3; ++tap)
+        for (int g = 0; g < 2; ++g)
+            hipLaunchKernelGGL(conv_tap_rows, dim3((ch * c.adim + 255) / 256), dim3(256), 0, s, (const float*)wsrc[g]->data, ch, c.adim, 3, tap, stk + (size_t)(tap * 2 + g) * ch * c.adim);
+    hipMemcpyAsync(stk + (size_t)6 * ch * c.adim, win->data, (size_t)c.ddim * c.adim * sizeof(float), hipMemcpyDeviceToDevice, s);
+    auto* nd = new fs2_tensor_desc(*win);
+    auto* nn = new std::string("tok_proj#stack");
+    nd->name = nn->c_str(); nd->data = stk; nd->ndim = 2; nd->shape[0] = Nt; nd->shape[1] = c.adim;
+    L.synth.push_back(nd); L.synth_names.push_back(nn);
+    L.m[*nn] = nd;
+    h->tokw = L.gemm({*nn}, {}, Nt, c.adim, 1, true);
+    h->TPd = L.dalloc((size_t)c.n_bins * c.ddim);
+    h->TEd = L.dalloc((size_t)c.n_bins * c.ddim);
+    if (L.rc || !h->TPd || !h->TEd || !h->Te || !h->Tp) { h->tokw = Gemm(); return; }
+    for (int t = 0; t < 2; ++t) {      // TPd carries the input layer's bias
+        GemmArgs a = gemm_args(h->dec_in, t ? h->Te : h->Tp, c.adim, c.n_bins, nullptr, t ? h->TEd : h->TPd, c.ddim);
+        if (t) a.bias = nullptr;
+        const int rc = launch_gemm(nullptr, s, t ? "load.TEd" : "load.TPd", a, FS2_PREC_FP32);
+        if (rc && !L.rc) L.rc = fail(h, rc, "%s", g_create_error.c_str());
+    }
+}
+
 void free_weights(fs2_handle* h) {
     for (void* p : h->allocs) hipFree(p);
     h->allocs.clear();
@@ -1313,7 +1377,7 @@ struct TokenPlan {   // offsets inside the token workspace
 
 // carve the token workspace; if ws == nullptr only sizes it
 size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L, void* ws, size_t cap, int** meta, StackBufs* sb,
-                    float** p0, float** p1, float** dlog_rows, int64_t** dint, int** cum, int** olens32, bool* ok, float** kp = nullptr, size_t* kp_cap = nullptr) {
+                    float** p0, float** p1, float** dlog_rows, int64_t** dint, int** cum, int** olens32, bool* ok, float** kp = nullptr, size_t* kp_cap = nullptr, float** tokp = nullptr) {
     Bump bp(ws, cap);
     const size_t R = L.Rpad;
     int* m = bp.take<int>(layout_dev_ints(L));
@@ -1339,6 +1403,9 @@ size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L
     int* o32 = bp.take<int>(b.B);
     const size_t kcap = (size_t)4 * std::min<size_t>(R, kSplitRows) * 1024;
     float* kpb = bp.take<float>(kcap);
+    // tok.proj's output rows (taken last: every other offset is as it was; none in fp32, which never takes the path)
+    float* tkp = (tok_proj_cols(c) && b.precision != FS2_PREC_FP32) ? bp.take<float>(R * (size_t)tok_proj_cols(c)) : nullptr;
+    if (tokp) *tokp = tkp;
     if (kp) *kp = kpb;
     if (kp_cap) *kp_cap = kcap;
     if (meta) *meta = m;
@@ -1567,6 +1634,8 @@ int fs2_load_weights(fs2_handle* h, const fs2_tensor_desc* t, int32_t n, void* s
         h->dec_in_lng = L.copy("decoder.embed.1.weight", {c.ddim});
         h->dec_in_lnb = L.copy("decoder.embed.1.bias", {c.ddim});
     }
+    h->tokw = Gemm(); h->TEd = h->TPd = nullptr; h->tokP = nullptr;
+    if (tok_proj_cols(c) && h->var2.ok && !L.rc) load_tok_proj(L, h);
     h->feat = L.gemm({"feat_out.weight"}, {"feat_out.bias"}, c.odim * std::max(c.reduction_factor, 1), c.ddim, 1, true);
     h->post.clear();
     for (int l = 0; l < c.postnet_layers; ++l) {
@@ -1639,8 +1708,8 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     const HostLayout& L = h->tok;
     if (L.len.size() && *std::max_element(L.len.begin(), L.len.end()) > h->enc.pe_rows)
         return fail(h, FS2_ERR_ARG, "sequence longer than the positional table (%d rows): extend `pe` and reload", h->enc.pe_rows);
-    int* meta; StackBufs sb; float *p0, *p1, *dlog_rows; int64_t* dint; int* cum; int* o32; bool ok;
-    carve_tokens(c, b, L, io->workspace, io->workspace_bytes, &meta, &sb, &p0, &p1, &dlog_rows, &dint, &cum, &o32, &ok, &h->kp, &h->kp_cap);
+    int* meta; StackBufs sb; float *p0, *p1, *dlog_rows, *tokp; int64_t* dint; int* cum; int* o32; bool ok;
+    carve_tokens(c, b, L, io->workspace, io->workspace_bytes, &meta, &sb, &p0, &p1, &dlog_rows, &dint, &cum, &o32, &ok, &h->kp, &h->kp_cap, &tokp);
     if (!ok) return fail(h, FS2_ERR_WORKSPACE, "fs2_encode: workspace too small");
     const int tok_regime = regime_rows_of(b, /*token_level=*/true);
     h->cur_regime = tok_regime; h->cur_status = nullptr;
@@ -1667,6 +1736,21 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     }
     if (io->enc_out) {
         if ((rc = unpack<float>(h, s, sb.x0, c.adim, dl.start, dl.vlen, b.B, b.Tmax, io->enc_out, 0.f))) return rc;
+    }
+    // tok.proj: the encoder rows times the stacked weights of the predictors' first convolution (one k = 1 product per tap) and of the decoder input layer, once
+    // per token instead of once per frame (fs2_decode: var.gather0 / dec.in.gather).  One kernel whatever the batch (64-row tiles, N > 1024: never split-K).
+    h->tokP = nullptr; h->tokP_conv = false;
+    if (enc_pl && h->tokw.N && tokp && opts().tokproj) {
+        // the predictors' columns only where fs2_decode can use them (bit 0 and the fused predictors); else the launch is sliced to the input layer's columns
+        // (a multiple of 128 rows into the weight images: whole tiles)
+        const bool conv = (opts().tokproj & 1) && opts().fuse_var;
+        const int n0 = conv ? 0 : 6 * c.var_chans;
+        const Gemm g = gemm_rows_from(h->tokw, n0);
+        GemmArgs a = gemm_args(g, sb.x0, c.adim, L.R, dl.row_pos, tokp + n0, h->tokw.N);
+        a.Xp = sb.x0p; a.xp_scratch = sb.xps;
+        a.kpart = h->kp; a.kpart_cap = 0;      // never split-K (no partial buffers allowed): one kernel whatever the batch or the slice
+        if ((rc = launch_gemm(h, s, "tok.proj", a, opts().tokproj_f32 ? FS2_PREC_FP32 : prec))) return rc;
+        h->tokP = tokp; h->tokP_conv = conv;
     }
     h->enc_final = sb.x0; h->cum = cum; h->o32 = o32; h->enc_B = b.B; h->enc_Tmax = b.Tmax; h->enc_compat = b.compat_padded;
     h->enc_ntok = 0;
@@ -1754,20 +1838,33 @@ int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) {
     // bf16 modes: the length-regulator output (and later its sum with the pitch / energy embeddings) is also written as planes,
     // in x1p (free until the decoder stack's first LayerNorm): the A operand of both variance predictors and of the decoder input layer
     void* hfr_planes = (prec != FS2_PREC_FP32 && c.adim % 32 == 0) ? f.sb.x1p : nullptr;
-    {   // length regulator
+    const bool need_e = (io->es == nullptr) || io->e_out, need_p = (io->ps == nullptr) || io->p_out;
+    const bool fused_var = need_e && need_p && prec != FS2_PREC_FP32 && h->var2.ok && hfr_planes && opts().fuse_var;
+    // Multiply before expanding (FS2_TOKPROJ; a function of the model, the precision and which outputs are asked for -- never of the batch): the predictors' first
+    // layer (bit 0; where the fused predictors run) and the decoder input layer (bit 1) gather fs2_encode's token-level products; with both nothing reads the
+    // expanded rows, which are then not built.
+    const int tokproj = (prec != FS2_PREC_FP32 && h->tokP && c.decoder_input_layer) ? (opts().tokproj & ((fused_var && h->tokP_conv) ? 3 : 2)) : 0;
+    TokGatherArgs tg;
+    memset(&tg, 0, sizeof tg);
+    tg.P = h->tokP; tg.ldp = h->tokw.N; tg.tok_start = h->dtok.start; tg.lri = f.lri; tg.row_pos = dl.row_pos; tg.row_seq = dl.row_seq; tg.R = R;
+    tg.chans = c.var_chans; tg.bias = h->var2.c0.bias; tg.ln_g = h->var2.ln0g; tg.ln_b = h->var2.ln0b; tg.vp = f.vp;
+    if (tokproj == 3) {
+        Scope sc(h, s, "lr.index", 0, 4.0 * R);
+        hipLaunchKernelGGL(lr_index_only, dim3((R + 255) / 256), dim3(256), 0, s, h->cum, b.Tmax, h->dtok.vlen, dl.row_pos, dl.row_seq, dl.vlen, R, f.lri);
+        HIP_TRY(h, hipGetLastError());
+    } else {   // length regulator
         Scope sc(h, s, "lr.expand", 0, 4.0 * R * c.adim * 2);
         hipLaunchKernelGGL(lr_expand, dim3((R + 3) / 4), dim3(256), 0, s, h->enc_final, c.adim, h->dtok.start, h->dtok.vlen, h->cum, b.Tmax,
                            dl.row_pos, dl.row_seq, 0, dl.vlen, R, f.hfr, f.lri, hfr_planes);
         HIP_TRY(h, hipGetLastError());
     }
-    const bool need_e = (io->es == nullptr) || io->e_out, need_p = (io->ps == nullptr) || io->p_out;
-    if (need_e && need_p && prec != FS2_PREC_FP32 && h->var2.ok && hfr_planes && opts().fuse_var) {
-        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, R, dl.row_pos, dl.dims, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec))) return rc;
+    if (fused_var) {
+        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, R, dl.row_pos, dl.dims, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (tokproj & 1) ? &tg : nullptr))) return rc;
     } else {
         if (need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
         if (need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
     }
-    {
+    if (!(tokproj & 2)) {
         Scope sc(h, s, "var.embed", 0, 4.0 * R * c.adim * 4);
         hipLaunchKernelGGL(bucket_embed, dim3((R + 3) / 4), dim3(256), 0, s, f.hfr, c.adim, dl.row_pos, dl.row_seq, R, io->es, io->es_stride,
                            io->ps, io->ps_stride, f.e_rows, f.p_rows, h->ebins, h->pbins, c.n_bins - 1, h->Te, h->Tp, f.qe, f.qp, hfr_planes);
@@ -1778,7 +1875,16 @@ int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) {
     // read their residual from planes (gemm_row4.h: RES) -- the fp32 rows x0 / x1 are not written at all (0.9 GB per c3 step, 11 GB per c4 step of HBM
     // writes).  Not in the fp16 two- / one-term modes (their LN1 output is a fp16 hi + lo pair, a format the residual reader does not have).
     const bool po = dec_pl && planes_only_regime(h, prec, R, regime_rows) && (ffn_terms == 0 || ffn_terms == kFfnMx || ffn_terms == kFfnMx4);
-    if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
+    if (tokproj & 2) {   // bucket search + embedding add + decoder input layer as one row kernel over the token-level products
+        tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
+        tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
+        tg.qe_rows = f.qe; tg.qp_rows = f.qp; tg.ln_g2 = h->dec_in_lng; tg.ln_b2 = h->dec_in_lnb;
+        tg.pe = h->dec.pe; tg.pe_alpha = h->dec.alpha; tg.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
+        tg.x0 = po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
+        Scope sc(h, s, "dec.in.gather", 0, 4.0 * R * c.ddim * (po ? 2.0 : 3.0));
+        hipLaunchKernelGGL(dec_in_gather, dim3((R + 3) / 4), dim3(256), 0, s, tg);
+        HIP_TRY(h, hipGetLastError());
+    } else if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
         GemmArgs a = gemm_args(h->dec_in, f.hfr, c.adim, R, dl.row_pos, po ? nullptr : f.sb.x0, c.ddim);
         a.Rp = dl.dims; a.regime_rows = regime_rows;
         a.ln_g = h->dec_in_lng; a.ln_b = h->dec_in_lnb; a.ln_eps = 1e-5f; a.act_post = 1;
@@ -2128,6 +2234,8 @@ int fs2_set_option(const char* name, int32_t value) {
     else if (n == "FS2_FFN2_MX") o.ffn2_mx = value != 0;
     else if (n == "FS2_QKV4") o.qkv4 = value;
     else if (n == "FS2_POST_MX") o.post_mx = value != 0;
+    else if (n == "FS2_TOKPROJ") o.tokproj = value < 0 ? 3 : (value & 3);
+    else if (n == "FS2_TOKPROJ_F32") o.tokproj_f32 = value > 0;
     else return fail(nullptr, FS2_ERR_ARG, "fs2_set_option: unknown option %s", name);
     return FS2_OK;
 }
@@ -2156,6 +2264,8 @@ int fs2_get_option(const char* name, int32_t* value) {
     else if (n == "FS2_FFN2_MX") *value = o.ffn2_mx;
     else if (n == "FS2_QKV4") *value = o.qkv4;
     else if (n == "FS2_POST_MX") *value = o.post_mx;
+    else if (n == "FS2_TOKPROJ") *value = o.tokproj;
+    else if (n == "FS2_TOKPROJ_F32") *value = o.tokproj_f32;
     else return fail(nullptr, FS2_ERR_ARG, "fs2_get_option: unknown option %s", name);
     return FS2_OK;
 }

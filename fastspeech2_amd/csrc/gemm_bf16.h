@@ -268,6 +268,7 @@ __global__ __launch_bounds__(256) void ln_rows(GemmArgs a) {
 }
 
 // weights [N][C][k] fp32 -> split bf16 LDS image [Npad][nchunks][k][hi 32 | lo 32]; optional BatchNorm fold.
+// (fs2_runtime.hip: gemm_rows_from slices this image by output row and restates its row stride: change both together.)
 // f16 != 0: the same image in _Float16 (fp16 hi + fp16 lo), the operand of the two- / one-term FFN arithmetic.
 __global__ void repack_weight_bf16(const float* w, int N, int C, int k, int Npad, int nchunks, const float* bn_g,
                                    const float* bn_v, float bn_eps, __bf16* out, int f16 = 0, int ldw = 0) {

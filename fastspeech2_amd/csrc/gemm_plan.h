@@ -34,6 +34,9 @@ struct Options {
     int qkv4 = -1;       // FS2_QKV4     the fused QKV projection's passes on gemm_row4_bf16 (EPI 3) wherever gemm_qkv8_bf16 would run at D = 384: 0 never, else yes
     int ffn2_mx = 1;     // FS2_FFN2_MX  mix_mx mode: the second FFN GEMM in the mx arithmetic too, wherever gemm_row4_bf16 runs it (0: split-bf16 as in round 4)
     int post_mx = 1;     // FS2_POST_MX  mixed modes: the Postnet's 512 -> 512 convolutions in the mx arithmetic (0: split-bf16 as until round 5)
+    int tokproj = 3;     // FS2_TOKPROJ  multiply before expanding (non-fp32 precisions): bit 0 = the predictors' first convolution (where the fused predictors run), bit 1 = the
+                         //              decoder input layer from token-level products (tok.proj + var.gather0 / dec.in.gather); 0 = the frame-level launches.  Never a function of the batch.
+    int tokproj_f32 = 0; // FS2_TOKPROJ_F32  tok.proj on the exact fp32 GEMM instead of the precision's own arithmetic
 };
 
 // ------------------------------------------------------------------ the rules

@@ -506,7 +506,9 @@ size_t fs2_op_dtw_workspace_bytes(int32_t B, const int32_t *a_lens, const int32_
 int fs2_op_dtw(void *stream, const fs2_op_dtw_args *a);
 
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
- * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX"; -1 = automatic).  Their initial values come from the environment variables of the same
+ * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX", "FS2_TOKPROJ", "FS2_TOKPROJ_F32"; -1 = automatic).
+ * "FS2_TOKPROJ": 0 = frame-level launches, 1 = the predictors' first convolution, 2 = the decoder input layer, 3 (default) = both from the token-level products of fs2_encode
+ * (takes effect with the next fs2_encode; fp32 never takes it); "FS2_TOKPROJ_F32": those products on the exact fp32 GEMM.  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
 int fs2_set_option(const char *name, int32_t value);
 
