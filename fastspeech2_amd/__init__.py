@@ -10,3 +10,4 @@ from .vocoder import GriffinLim, Geometry, Waveforms, AsyncWaveforms, mel_basis,
 from .targets import TargetStats, TrainingTargets, clean_targets, hp_data, remove_outlier, training_targets  # noqa: F401
 from .losses import LossTerms, loss_terms  # noqa: F401
 from .dtw import DtwTerms, mel_dtw  # noqa: F401
+from .align import Alignment, monotonic_align  # noqa: F401

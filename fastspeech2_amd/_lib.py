@@ -100,6 +100,20 @@ class OpDtwArgs(_Sized):
 DTW_TERMS = 12       # FS2_DTW_TERMS
 
 
+class OpAlignArgs(_Sized):
+    """fs2_op_align_args.  ``a_starts`` / ``a_lens`` / ``b_starts`` / ``b_lens`` / ``n_labels`` are HOST int32 arrays; every other pointer is a
+    device pointer."""
+    _fields_ = ([("struct_size", C.c_uint32), ("B", C.c_int32), ("D", C.c_int32), ("max_step", C.c_int32),
+                 ("a_stride", C.c_int64), ("b_stride", C.c_int64), ("dur_stride", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("a", "b", "labels")]
+                + [(n, C.POINTER(C.c_int32)) for n in ("a_starts", "a_lens", "b_starts", "b_lens", "n_labels")]
+                + [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                + [(n, C.c_void_p) for n in ("durations", "state", "terms", "batch")])
+
+
+ALIGN_TERMS = 8      # FS2_ALIGN_TERMS
+
+
 # every symbol include/fs2.h declares (tests check the library exports all of them)
 ABI_VERSION = 4      # FS2_ABI_VERSION of the include/fs2.h these mirrors were written against (checked in lib())
 
@@ -111,7 +125,7 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
-           "fs2_op_dtw_workspace_bytes", "fs2_op_dtw"]
+           "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
 
@@ -320,6 +334,10 @@ def lib():
     L.fs2_op_dtw_workspace_bytes.restype = C.c_size_t
     L.fs2_op_dtw.argtypes = [vp, C.POINTER(OpDtwArgs)]
     L.fs2_op_dtw.restype = C.c_int
+    L.fs2_op_align_workspace_bytes.argtypes = [i32, i32p, i32p, C.c_size_t]
+    L.fs2_op_align_workspace_bytes.restype = C.c_size_t
+    L.fs2_op_align.argtypes = [vp, C.POINTER(OpAlignArgs)]
+    L.fs2_op_align.restype = C.c_int
     # The kernels with literal-register accumulators run only in a library whose ISA was audited (build()): the LIBRARY looks for the record of
     # its own hash when it is first used (fs2_runtime.hip: audit_clean) and otherwise starts with attn_w32 / gemm_row4_bf16 switched off -- for
     # every consumer, not only this binding; the compiler-scheduled kernels take their place (slower, never silently wrong).  Here: say so.

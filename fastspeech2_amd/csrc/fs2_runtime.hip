@@ -1517,6 +1517,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- DTW distance of the free-running validation
 #include "dtw.h"
 
+// ---------------------------------------------------------------------------------- forced alignment: phoneme durations of a recording
+#include "align.h"
+
 }  // namespace
 
 // =====================================================================================================
@@ -2392,5 +2395,11 @@ size_t fs2_op_dtw_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_
 }
 
 int fs2_op_dtw(void* stream, const fs2_op_dtw_args* a) { return dt_dtw(stream, a); }
+
+size_t fs2_op_align_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap_bytes) {
+    return align_workspace_bytes(B, a_lens, b_lens, cap_bytes);
+}
+
+int fs2_op_align(void* stream, const fs2_op_align_args* a) { return al_align(stream, a); }
 
 }  // extern "C"

@@ -121,16 +121,19 @@ def mcep(x, n_mcep=13):
 
 def _side(x, lens, name, tracks):
     """One side of the pairs -> (x, row stride in floats, first row of every pair, tracks), the tracks laid out by the same row offsets.
-    ``x``: padded [B, S, D] or packed [rows, D]; ``tracks``: [(tensor or None, name)], padded [B, S'] or packed [rows]."""
+    ``x``: padded [B, S, D] or packed [rows, D]; ``tracks``: [(tensor or None, name)] or [(tensor or None, name, dtype)] (float32
+    unless given), padded [B, S'] or packed [rows]."""
     _require_cuda(x, name)
     if x.dtype != torch.float32:
         raise TypeError("%s must be torch.float32, got %s" % (name, x.dtype))
     B = int(lens.numel())
+    dtypes = {t[1]: t[2] if len(t) > 2 else torch.float32 for t in tracks}
+    tracks = [(t[0], t[1]) for t in tracks]
     for t, n in tracks:
         if t is not None:
             _require_cuda(t, n)
-            if t.dtype != torch.float32:
-                raise TypeError("%s must be torch.float32, got %s" % (n, t.dtype))
+            if t.dtype != dtypes[n]:
+                raise TypeError("%s must be %s, got %s" % (n, dtypes[n], t.dtype))
             if t.device != x.device:
                 raise ValueError("%s is on %s, %s on %s" % (n, t.device, name, x.device))
             if t.dim() != x.dim() - 1:
@@ -145,7 +148,7 @@ def _side(x, lens, name, tracks):
             if t is not None and (t.shape[0] != B or t.shape[1] < Lmax):
                 raise ValueError("%s is %s, %s needs [%d, >= %d]" % (n, tuple(t.shape), name, B, Lmax))
         x, stride = _rows(x, name, torch.float32, int(x.shape[2]))
-        out = [(None, 0) if t is None else _rows(t, n, torch.float32, 0) for t, n in tracks]
+        out = [(None, 0) if t is None else _rows(t, n, dtypes[n], 0) for t, n in tracks]
         if any(t is not None and s != stride for t, s in out):      # (e.g. targets wider than the mels): narrow copies, one common stride
             x, stride = x[:, :Lmax].contiguous(), Lmax
             out = [(None, 0) if t is None else (t[:, :Lmax].contiguous(), Lmax) for t, _ in out]

@@ -761,6 +761,30 @@ class FeedForwardTransformer(nn.Module):
         p = None if ps is None else (r["p_outs"], ps.to(dev).float())
         return mel_dtw(r["after"], r["olens"], ys, ol, e=e, p=p, features=features, sync=sync)
 
+    def align_durations(self, xs, ilens, ys, olens, alpha=1.0, features="mel", max_step=2, sync=True):
+        """Phoneme durations of recordings in one call: the free-running forward (as ``evaluate_free_running``), then
+        ``monotonic_align`` of each recording's frames to the synthesized frames, labelled with the phoneme each synthesized frame
+        was expanded from (csrc/align.h) -> :class:`fastspeech2_amd.align.Alignment`.  ``ys`` [B, >= max olens, odim]: the
+        recordings' mels; ``olens``: their lengths.  ``.durations`` is int64 [B, Tmax], ready to be passed as ``ds`` to ``forward()``
+        or ``evaluate_batch()``: every row adds up to ``olens[b]``.  A frame advances by at most ``max_step`` synthesized frames, so
+        a recording shorter than about 1 / ``max_step`` of its synthesis has no alignment: that utterance keeps ``.ok[b]`` False and
+        zeros; a SMALLER ``alpha`` shortens the synthesis and makes it feasible.  Per-utterance semantics: an utterance's result
+        does not depend on the batch it is in.  ``sync=False``: the records stay on the device until first read (the forward's own
+        read-back of the frame counts remains)."""
+        from .align import monotonic_align
+        _require_device(xs)
+        dev = xs.device
+        if self.reduction_factor > 1:
+            raise NotImplementedError("alignment with reduction_factor > 1: lr_index is per decoder frame, the mels per mel frame")
+        if not float(alpha) > 0.0:
+            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
+        il = torch.as_tensor(ilens).to("cpu", torch.int64)
+        ol = torch.as_tensor(olens).to("cpu", torch.int64)
+        xs = xs[:, : int(il.max())]
+        r = self._run(xs, il, is_inference=True, compat=False, want=("after", "lr_index"), alpha=alpha)
+        return monotonic_align(r["after"], r["olens"], ys.to(dev).float(), ol, labels=r["lr_index"], n_labels=il, max_step=max_step,
+                               features=features, sync=sync)
+
     def inference(self, x, alpha=1.0):
         """reference fastspeech.py:339-357: x [T] int64 phoneme ids -> mel [L, odim].  ``alpha`` (not in the reference's
         ``inference``, but in its LengthRegulator, length_regulator.py:57-59) scales the durations: > 1 slower speech."""

@@ -505,6 +505,58 @@ size_t fs2_op_dtw_workspace_bytes(int32_t B, const int32_t *a_lens, const int32_
  * fs2_op_dtw_workspace_bytes(B, a_lens, b_lens, 0). */
 int fs2_op_dtw(void *stream, const fs2_op_dtw_args *a);
 
+/* ---- Forced alignment of B pairs: the frames b [M, D] of a recording are assigned, monotonically, to the states a [N, D] (the
+ * frames of the synthesis), each frame to exactly one state, and the frames per label (phoneme) are counted: durations that add up
+ * to M (fastspeech2_amd/csrc/align.h).  d(i, j) as above.  Q(0, 0) = d(0, 0); Q(i, 0) = +inf for i > 0;
+ * Q(i, j) = d(i, j) + min over k = 0 .. max_step of Q(i - k, j - 1), the predecessor chosen in the order k = 0, 1, 2 with a strict
+ * "<" (outside the matrix: +inf).  s(M-1) = N-1, s(j-1) = s(j) - k(s(j), j).  An alignment exists iff N >= 1, M >= 1 and
+ * N - 1 <= max_step (M - 1).  Results per pair:
+ *   state      s(j) for every frame j: the pair-local index of its state
+ *   durations  durations[t] = the frames j with label(s(j)) = t; label(i) = labels[i], or i without labels (n_labels = N then).  The
+ *              whole row [0, dur_stride) is written, zeros beyond n_labels
+ *   a record of FS2_ALIGN_TERMS doubles:
+ *   [0] N   [1] M   [2] flags: 0 fine, 1 no alignment exists, 2 the cost is not finite   [3] cost Q(N-1, M-1)
+ *   [4] states that received a frame   [5] the longest run of frames in one state   [6] labels in [0, n_labels) without a frame   [7] 0
+ * With flags != 0 the durations row is zeros, state is -1 and [4] .. [6] are 0; [3] is 0 for flag 1 and the computed cost for flag 2.
+ * A pair's results depend on its own values only: not on B, on its place in the batch, on a stride or on the workspace handed in; a
+ * non-finite value in one pair touches no other pair.  The batch record has the same layout: [2] = the pairs with flags != 0, every
+ * other entry added up over the pairs with flags 0 in index order.  The labels of a pair must be non-decreasing and lie in
+ * [0, n_labels): a label outside that range is SKIPPED (its frames are counted nowhere), and with a decreasing sequence a label's
+ * count is that of one of its runs; neither writes outside the pair's own durations row. ---- */
+#define FS2_ALIGN_TERMS 8
+
+/* a, b, their strides, starts and lengths: as fs2_op_dtw_args.  max_step: 1 or 2.  labels: device int32 indexed by the rows of a, or
+ * NULL; n_labels: HOST int32 [B], NULL iff labels is NULL, 0 <= n_labels[i] <= dur_stride (without labels: a_lens[i] <= dur_stride).
+ * durations: device int64 [B, dur_stride]; state: device int32 indexed by the rows of b; terms: device double [B, FS2_ALIGN_TERMS];
+ * batch: device double [FS2_ALIGN_TERMS]; each of the four optional.  B = 0 writes a zero batch record.  (Declared in two
+ * statements for the reason given at fs2_op_loss_args; _lib.py: OpAlignArgs.) */
+struct fs2_op_align_args {
+    uint32_t struct_size;     /* = sizeof(fs2_op_align_args) */
+    int32_t B, D, max_step;
+    int64_t a_stride, b_stride, dur_stride;
+    const float *a, *b;
+    const int32_t *labels;
+    const int32_t *a_starts, *a_lens, *b_starts, *b_lens, *n_labels;
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t *durations;
+    int32_t *state;
+    double *terms, *batch;
+};
+typedef struct fs2_op_align_args fs2_op_align_args;
+
+/* workspace bytes of fs2_op_align: min(what all pairs need at once, max(cap_bytes, what the largest single pair needs)), as
+ * fs2_op_dtw_workspace_bytes; host only; 0 on a bad argument. */
+size_t fs2_op_align_workspace_bytes(int32_t B, const int32_t *a_lens, const int32_t *b_lens, size_t cap_bytes);
+
+/* Asynchronous on `stream`: no allocation, no host read of device memory, no synchronisation; legal during stream capture.  Per
+ * group of pairs one launch for the distance matrices and one for the sweep with its walk back, plus the upload of the pair records
+ * (kernel arguments) and one combining launch.  FS2_ERR_ARG: wrong struct_size, D outside [1, 128], max_step outside {1, 2}, a
+ * stride below D, a negative start or length, n_labels[i] outside [0, dur_stride], dur_stride below a_lens[i] without labels, labels
+ * without n_labels (or the reverse), a null workspace with B > 0; FS2_ERR_WORKSPACE: workspace_bytes below
+ * fs2_op_align_workspace_bytes(B, a_lens, b_lens, 0). */
+int fs2_op_align(void *stream, const fs2_op_align_args *a);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX", "FS2_TOKPROJ", "FS2_TOKPROJ_F32"; -1 = automatic).
  * "FS2_TOKPROJ": 0 = frame-level launches, 1 = the predictors' first convolution, 2 = the decoder input layer, 3 (default) = both from the token-level products of fs2_encode
