@@ -11,3 +11,4 @@ from .targets import TargetStats, TrainingTargets, clean_targets, hp_data, remov
 from .losses import LossTerms, loss_terms  # noqa: F401
 from .dtw import DtwTerms, mel_dtw  # noqa: F401
 from .align import Alignment, monotonic_align  # noqa: F401
+from .prosody import ProsodyPrediction, label_means, semitones  # noqa: F401

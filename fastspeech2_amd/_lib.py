@@ -114,6 +114,13 @@ class OpAlignArgs(_Sized):
 ALIGN_TERMS = 8      # FS2_ALIGN_TERMS
 
 
+class Prosody(_Sized):
+    """fs2_prosody: the pitch / energy control of fs2_decode_ctl.  Every pointer is a device float32 [B, cols] or None (neutral);
+    ``*_cols`` is 1 (one value per utterance) or Tmax (one per phoneme)."""
+    _fields_ = ([("struct_size", C.c_uint32)] + [(n, C.c_void_p) for n in ("pitch_scale", "pitch_shift", "energy_scale", "energy_shift")]
+                + [(n, C.c_int32) for n in ("pitch_scale_cols", "pitch_shift_cols", "energy_scale_cols", "energy_shift_cols")])
+
+
 # every symbol include/fs2.h declares (tests check the library exports all of them)
 ABI_VERSION = 4      # FS2_ABI_VERSION of the include/fs2.h these mirrors were written against (checked in lib())
 
@@ -125,7 +132,8 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
-           "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align"]
+           "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align",
+           "fs2_decode_ctl", "fs2_op_label_means"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
 
@@ -338,6 +346,11 @@ def lib():
     L.fs2_op_align_workspace_bytes.restype = C.c_size_t
     L.fs2_op_align.argtypes = [vp, C.POINTER(OpAlignArgs)]
     L.fs2_op_align.restype = C.c_int
+    L.fs2_decode_ctl.argtypes = [vp, vp, C.POINTER(DecodeIO), C.POINTER(Prosody)]
+    L.fs2_decode_ctl.restype = C.c_int
+    # stream, x, labels, lens_dev, B, x_stride, n_labels, positive_only, mean, count
+    L.fs2_op_label_means.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.fs2_op_label_means.restype = C.c_int
     # The kernels with literal-register accumulators run only in a library whose ISA was audited (build()): the LIBRARY looks for the record of
     # its own hash when it is first used (fs2_runtime.hip: audit_clean) and otherwise starts with attn_w32 / gemm_row4_bf16 switched off -- for
     # every consumer, not only this binding; the compiler-scheduled kernels take their place (slower, never silently wrong).  Here: say so.

@@ -1520,6 +1520,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- forced alignment: phoneme durations of a recording
 #include "align.h"
 
+// ---------------------------------------------------------------------------------- pitch / energy control, per-phoneme means
+#include "prosody.h"
+
 }  // namespace
 
 // =====================================================================================================
@@ -1790,9 +1793,29 @@ size_t fs2_frame_workspace_bytes_cap(const fs2_handle* h, const fs2_batch* b, in
     return carve_frames(h->cfg, L, nullptr, 0, nullptr, nullptr);
 }
 
-int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) {
+int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) { return fs2_decode_ctl(h, stream, io, nullptr); }
+
+int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const fs2_prosody* ctl) {
     if (!h || !io) return fail(h, FS2_ERR_ARG, "fs2_decode: null argument");
     ABI_CHECK(h, "fs2_decode", io, fs2_decode_io);
+    // control of the predicted pitch / energy (prosody.h): refused as a whole before anything is launched
+    ProsodyTrack ctl_p{}, ctl_e{};
+    if (ctl) {
+        ABI_CHECK(h, "fs2_decode_ctl", ctl, fs2_prosody);
+        ctl_p = ProsodyTrack{ctl->pitch_scale, ctl->pitch_shift, ctl->pitch_scale_cols, ctl->pitch_shift_cols};
+        ctl_e = ProsodyTrack{ctl->energy_scale, ctl->energy_shift, ctl->energy_scale_cols, ctl->energy_shift_cols};
+    }
+    const bool ctl_pitch = ctl_p.scale || ctl_p.shift, ctl_energy = ctl_e.scale || ctl_e.shift;
+    if (ctl_pitch || ctl_energy) {
+        const int T = io->batch.Tmax;
+        const struct { const float* p; int cols; const char* name; } given[4] = {{ctl_p.scale, ctl_p.scale_cols, "pitch_scale"}, {ctl_p.shift, ctl_p.shift_cols, "pitch_shift"},
+                                                                                  {ctl_e.scale, ctl_e.scale_cols, "energy_scale"}, {ctl_e.shift, ctl_e.shift_cols, "energy_shift"}};
+        for (const auto& g : given)
+            if (g.p && g.cols != 1 && g.cols != T) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: %s_cols = %d is neither 1 (per utterance) nor Tmax = %d (per phoneme)", g.name, g.cols, T);
+        if (ctl_pitch && io->ps) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: pitch control together with given pitches (io->ps): control acts on predictions");
+        if (ctl_energy && io->es) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: energy control together with given energies (io->es): control acts on predictions");
+        if (io->batch.compat_padded) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: control has per-utterance semantics only (batch.compat_padded must be 0)");
+    }
     if (!h->encoded) return fail(h, FS2_ERR_STATE, "fs2_decode called without a preceding fs2_encode");
     const fs2_batch& b = io->batch;
     int rc = check_batch(h, b);
@@ -1866,6 +1889,11 @@ int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) {
     } else {
         if (need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
         if (need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
+    }
+    if (ctl_pitch || ctl_energy) {   // the predictions become the controlled values in place: both consumers below, and e_out / p_out, see those
+        Scope sc(h, s, "var.control", 2.0 * R * (ctl_pitch + ctl_energy), 4.0 * R * (3.0 + 3.0 * (ctl_pitch + ctl_energy)));
+        hipLaunchKernelGGL(prosody_apply, dim3((R + 255) / 256), dim3(256), 0, s, f.p_rows, f.e_rows, dl.row_pos, dl.row_seq, f.lri, R, b.B, b.Tmax, ctl_p, ctl_e);
+        HIP_TRY(h, hipGetLastError());
     }
     if (!(tokproj & 2)) {
         Scope sc(h, s, "var.embed", 0, 4.0 * R * c.adim * 4);
@@ -2401,5 +2429,10 @@ size_t fs2_op_align_workspace_bytes(int32_t B, const int32_t* a_lens, const int3
 }
 
 int fs2_op_align(void* stream, const fs2_op_align_args* a) { return al_align(stream, a); }
+
+int fs2_op_label_means(void* stream, const float* x, const int32_t* labels, const int64_t* lens_dev, int32_t B, int32_t x_stride, int32_t n_labels,
+                       int32_t positive_only, float* mean, int32_t* count) {
+    return pr_label_means(stream, x, labels, lens_dev, B, x_stride, n_labels, positive_only, mean, count);
+}
 
 }  // extern "C"

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from . import prosody as _prosody
 
 __all__ = ["FeedForwardTransformer", "AsyncMels", "Fs2CapacityError", "StepStreams"]
 
@@ -463,7 +464,7 @@ class FeedForwardTransformer(nn.Module):
 
     # ------------------------------------------------------------------ the path
     def _run(self, xs, ilens, olens=None, ds=None, es=None, ps=None, is_inference=False, compat=False,
-             want=("before", "after"), d_override=None, capacity=None, alpha=1.0, packed_out=None, regime=None, inputs_ready=None):
+             want=("before", "after"), d_override=None, capacity=None, alpha=1.0, packed_out=None, regime=None, inputs_ready=None, prosody=None):
         """Runs fs2_encode -> (olens readback) -> fs2_decode.  Returns a dict of device tensors.
 
         ``capacity=(total_frames_bound, per_utterance_bound)`` selects the device-driven frame layout instead: no host
@@ -475,7 +476,11 @@ class FeedForwardTransformer(nn.Module):
         float32 [>= that many rows, odim] tensor) receives them in place instead of a new allocation.
 
         ``regime=(phonemes, utterances)`` of the batch the kernel variants are to be chosen for (include/fs2.h: fs2_batch.regime_*):
-        a shard of a larger batch names the whole batch and is computed bit-identically to the one-call run of the whole batch."""
+        a shard of a larger batch names the whole batch and is computed bit-identically to the one-call run of the whole batch.
+
+        ``prosody``: a dict of ``pitch_scale`` / ``pitch_shift`` / ``energy_scale`` / ``energy_shift`` (prosody.py; each None, a number,
+        [B, 1] or [B, Tmax]): control of the predicted pitch and energy (fs2_decode_ctl).  ``e_outs`` / ``p_outs`` are then the CONTROLLED
+        values, the ones that were quantised.  Free-running, per-utterance semantics only."""
         _require_device(xs)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError(
@@ -488,6 +493,14 @@ class FeedForwardTransformer(nn.Module):
         with torch.cuda.stream(in_stream):
             xs = xs.contiguous().long()
         B, Tmax = xs.shape
+        ctl = None
+        if prosody and any(v is not None for v in prosody.values()):
+            if compat:
+                raise ValueError("pitch / energy control has per-utterance semantics only (batch_semantics='padded_compat')")
+            if not is_inference:
+                raise ValueError("pitch / energy control acts on predictions: the teacher-forced pass quantises the es / ps it is given")
+            with torch.cuda.stream(in_stream):
+                ctl = _prosody.normalize_controls(B, Tmax, dev, **prosody)
         il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).contiguous()   # host lengths (reference: .tolist())
         if il.numel() != B:
             raise ValueError("ilens has %d entries for a batch of %d" % (il.numel(), B))
@@ -551,6 +564,11 @@ class FeedForwardTransformer(nn.Module):
                 xs.record_stream(side)                                      # ... and the other way round
                 if ds_dev is not None:
                     ds_dev.record_stream(side)
+                for t_ in (ctl or {}).values():                             # made on the side stream, read by fs2_decode_ctl on the caller's
+                    if t_ is not None:
+                        t_.record_stream(cur)
+            pro = _prosody.prosody_struct(ctl)
+            pro = C.byref(pro) if pro is not None else None
             if capacity is not None:
                 total_cap, Lcap = int(capacity[0]), int(capacity[1])
                 self.decoder.embed[-1].ensure(Lcap)      # (a grown table is picked up by the next call's fingerprint check)
@@ -586,7 +604,7 @@ class FeedForwardTransformer(nn.Module):
                     dio.after_packed = out["after_packed"].data_ptr()
                 if dio.after is None and dio.after_packed is None:
                     raise ValueError("'after' or 'after_packed' must be requested")
-                _lib.check(L.fs2_decode(h, st, C.byref(dio)), h)
+                _lib.check(L.fs2_decode_ctl(h, st, C.byref(dio), pro), h)
                 out["olens"], out["status"] = olens_dev, status
                 if d_int is not None:
                     out["d_int"] = d_int if d_override is None else ds_dev
@@ -604,7 +622,7 @@ class FeedForwardTransformer(nn.Module):
                     raise ValueError("olens %s do not match the sums of the durations %s" % (given.tolist(), ol.tolist()))
             Lmax = int(ol.max())
             if self.decoder.embed[-1].ensure(Lmax):                # pe table grew: reload and redo the encoder
-                return self._run(xs, ilens, olens, ds, es, ps, is_inference, compat, want, d_override, alpha=alpha, regime=regime)
+                return self._run(xs, ilens, olens, ds, es, ps, is_inference, compat, want, d_override, alpha=alpha, regime=regime, prosody=prosody)
             ol_arr = (C.c_int64 * B)(*ol.tolist())
             frm_ws = torch.empty(L.fs2_frame_workspace_bytes(h, C.byref(batch), ol_arr), dtype=torch.uint8, device=dev)
             odim = self.odim
@@ -630,7 +648,7 @@ class FeedForwardTransformer(nn.Module):
                 buf("after_packed", (int(ol.sum()) * self.reduction_factor, odim)))
             if dio.after is None:
                 raise ValueError("'after' must be requested")
-            _lib.check(L.fs2_decode(h, st, C.byref(dio)), h)
+            _lib.check(L.fs2_decode_ctl(h, st, C.byref(dio), pro), h)
         out["olens"] = ol
         if d_log is not None:
             out["d_log"] = d_log
@@ -785,28 +803,58 @@ class FeedForwardTransformer(nn.Module):
         return monotonic_align(r["after"], r["olens"], ys.to(dev).float(), ol, labels=r["lr_index"], n_labels=il, max_step=max_step,
                                features=features, sync=sync)
 
-    def inference(self, x, alpha=1.0):
+    def _controls(self, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None):
+        """The four control keywords of a public entry point as ``_run``'s ``prosody`` (None: no control).  Control has per-utterance
+        semantics only: a model set to ``batch_semantics="padded_compat"`` refuses it."""
+        pro = dict(pitch_scale=pitch_scale, pitch_shift=pitch_shift, energy_scale=energy_scale, energy_shift=energy_shift)
+        if all(v is None for v in pro.values()):
+            return None
+        if self.batch_semantics == "padded_compat":
+            raise ValueError("pitch / energy control has per-utterance semantics only (batch_semantics='padded_compat')")
+        return pro
+
+    def predict_prosody(self, xs, ilens, alpha=1.0, d_override=None, **controls):
+        """What the model is about to say, per frame and per phoneme -> :class:`fastspeech2_amd.prosody.ProsodyPrediction`: one
+        free-running forward (``alpha``, ``d_override`` and the four control keywords as ``inference_batch``), then the per-phoneme
+        means of its pitch and energy tracks (csrc/prosody.h: label_means; pitch over the frames with a value > 0).  ``durations``,
+        edited and passed as ``d_override``, is duration control per phoneme; ``pitch_tok`` / ``energy_tok``, edited, serve as
+        ``pitch_shift`` / ``energy_shift`` with a scale of 0.  The values are the controlled ones if control was given."""
+        if not float(alpha) > 0.0:
+            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
+        il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).reshape(-1)
+        r = self._run(xs, il, is_inference=True, compat=False, want=("after", "e_outs", "p_outs", "lr_index"), d_override=d_override, alpha=alpha,
+                      prosody=self._controls(**controls))
+        Tmax = int(xs.shape[1])
+        ol_dev = r["olens"].to(xs.device)
+        pitch_tok, voiced_tok = _prosody.label_means(r["p_outs"], r["lr_index"], ol_dev, Tmax, positive_only=True)
+        energy_tok, frames = _prosody.label_means(r["e_outs"], r["lr_index"], ol_dev, Tmax)
+        return _prosody.ProsodyPrediction(frames.long(), r["olens"], r["p_outs"], r["e_outs"], r["lr_index"], pitch_tok, energy_tok, voiced_tok)
+
+    def inference(self, x, alpha=1.0, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None):
         """reference fastspeech.py:339-357: x [T] int64 phoneme ids -> mel [L, odim].  ``alpha`` (not in the reference's
-        ``inference``, but in its LengthRegulator, length_regulator.py:57-59) scales the durations: > 1 slower speech."""
+        ``inference``, but in its LengthRegulator, length_regulator.py:57-59) scales the durations: > 1 slower speech.
+        ``pitch_scale`` / ``pitch_shift`` / ``energy_scale`` / ``energy_shift`` (prosody.py: None, a number, [1, 1] or [1, T]): every
+        predicted pitch / energy value becomes ``v * scale + shift`` before it is quantised."""
         xs, il = x.unsqueeze(0), torch.tensor([x.shape[0]])
+        pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
         if not float(alpha) > 0.0:
             raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
         if self._frames_per_token is not None:
             # device-driven layout inside capacities learnt from earlier utterances: the GPU runs the whole forward without
             # waiting for the host; the frame count is read once, at the end (it is needed for the shape of the result)
             total, Lcap = self.predict_capacity(il, alpha)
-            r = self._run(xs, il, is_inference=True, want=("after",), capacity=(max(total, Lcap), Lcap), alpha=alpha)
+            r = self._run(xs, il, is_inference=True, want=("after",), capacity=(max(total, Lcap), Lcap), alpha=alpha, prosody=pro)
             st = r["status"].cpu()
             if int(st[2]) == 0:
                 L = int(st[3])
                 self._learn_ratio(il, torch.tensor([L]), alpha)
                 return r["after"][0, :L * self.reduction_factor]
-        r = self._run(xs, il, is_inference=True, want=("after",), alpha=alpha)
+        r = self._run(xs, il, is_inference=True, want=("after",), alpha=alpha, prosody=pro)
         self._learn_ratio(il, r["olens"], alpha)
         return r["after"][0]
 
     def inference_batch(self, xs, ilens, d_override=None, packed=False, sync=True, capacity=None, alpha=1.0, packed_out=None, regime=None,
-                        inputs_ready=None):
+                        inputs_ready=None, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None):
         """Batched free-running synthesis (not in the reference, which only has single-utterance
         ``inference``): per-utterance semantics; returns (mels [B, Lmax, odim], olens [B] on the host = MEL frames per utterance,
         i.e. decoder frames x reduction_factor), or with
@@ -830,7 +878,12 @@ class FeedForwardTransformer(nn.Module):
 
         ``inputs_ready`` (a ``torch.cuda.Event``; ``overlap_encoder`` mode only, ignored otherwise): recorded by the caller behind the work that
         produces ``xs`` / ``d_override``; the encoder's side stream waits for it.  Without it the mode relies on the caller's promise that the
-        inputs are complete when the call is made (the side stream does not wait for the caller's stream: that wait is the overlap)."""
+        inputs are complete when the call is made (the side stream does not wait for the caller's stream: that wait is the overlap).
+
+        ``pitch_scale`` / ``pitch_shift`` / ``energy_scale`` / ``energy_shift`` (prosody.py; each None, a number, a float32 [B, 1] tensor = one
+        value per utterance, or [B, Tmax] = one per phoneme): every predicted pitch / energy value becomes ``v * scale + shift`` before it
+        is quantised, in every form of the call (``ShardedSynthesizer`` slices the tensors with the batch)."""
+        pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
         il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).reshape(-1)
         if not float(alpha) > 0.0:
             raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
@@ -843,20 +896,21 @@ class FeedForwardTransformer(nn.Module):
             total, Lcap = capacity if capacity is not None else self.predict_capacity(il, alpha)
             key = "after_packed" if packed else "after"         # (packed: the padded mels are neither built nor written)
             r = self._run(xs, il, is_inference=True, compat=False, want=(key,), d_override=d_override, capacity=(total, Lcap), alpha=alpha,
-                          packed_out=packed_out if packed else None, regime=regime, inputs_ready=inputs_ready)
+                          packed_out=packed_out if packed else None, regime=regime, inputs_ready=inputs_ready, prosody=pro)
             mel_lens = r["olens"] if self.reduction_factor == 1 else r["olens"] * self.reduction_factor     # mel frames per utterance
             if torch.cuda.is_current_stream_capturing():     # graph capture: no host-side bookkeeping inside the graph
                 return AsyncMels(r[key], mel_lens, r["status"], None)
             return AsyncMels(r[key], mel_lens, r["status"], self._record_async(il, r, xs.device, alpha))
         want = ("after", "after_packed") if packed else ("after",)
-        r = self._run(xs, il, is_inference=True, compat=False, want=want, d_override=d_override, alpha=alpha, regime=regime)
+        r = self._run(xs, il, is_inference=True, compat=False, want=want, d_override=d_override, alpha=alpha, regime=regime, prosody=pro)
         if d_override is None:
             self._learn_ratio(il, r["olens"], alpha)
         else:
             self._learn_ratio(il, r["olens"], 1.0)
         return (r["after_packed"] if packed else r["after"]), r["olens"] * self.reduction_factor
 
-    def capture_graph(self, xs, ilens, d_override=None, vocoder=None, **vocoder_args):
+    def capture_graph(self, xs, ilens, d_override=None, vocoder=None, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None,
+                      **vocoder_args):
         """HIP-graph replay of the whole free-running forward for a fixed batch shape (``xs.shape`` and ``ilens``): the
         launch-bound small-batch case (one utterance: 85 launches) becomes one graph launch.  Returns ``run(new_xs) ->
         (mels [B, Lcap, odim], olens_dev, status_dev)``; the tensors are the graph's static outputs (overwritten by the
@@ -864,6 +918,10 @@ class FeedForwardTransformer(nn.Module):
         (the mels are then NaN): fall back to ``inference_batch``.  Capacities come from one synchronous run on ``xs``
         (x 1.5 head-room).  The graph holds pointers into the library's weight copies: ``run`` raises if the weights were
         re-uploaded since the capture (load_state_dict, a grown positional table, .to()): capture again.
+
+        ``pitch_scale`` / ``pitch_shift`` / ``energy_scale`` / ``energy_shift`` (as ``inference_batch``): the controls given here are
+        cloned into static tensors of the graph, and ``run(new_xs, new_ds=None, **new_controls)`` copies new values (a number, or a
+        tensor of the captured shape) into them before the replay; a control that was not captured cannot be given to ``run``.
 
         ``vocoder`` (a ``GriffinLim``; ``vocoder_args``: its ``n_iter``, ``momentum``, ``seed``): the graph also runs the device-driven
         vocoder on the mels (``vocoder(AsyncMels, sync=False, padded_out=True)``: the frame counts never leave the device), and
@@ -881,8 +939,13 @@ class FeedForwardTransformer(nn.Module):
             self._ensure_ready(xs.device, xs.shape[1], Lcap)                        # a grown table is uploaded BEFORE the capture
             static_xs = xs.clone()
             static_ds = d_override.clone() if d_override is not None else None
+            pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
+            static_pro = None
+            if pro is not None:
+                static_pro = {k: (None if v is None else v.clone())
+                              for k, v in _prosody.normalize_controls(xs.shape[0], xs.shape[1], xs.device, **pro).items()}
             run_mel = lambda: self._run(static_xs, il, is_inference=True, compat=False, want=("after",), d_override=static_ds,
-                                        capacity=(total, Lcap))
+                                        capacity=(total, Lcap), prosody=static_pro)
 
             def run_once():
                 r = run_mel()
@@ -902,13 +965,27 @@ class FeedForwardTransformer(nn.Module):
                 after, olens_dev, status = run_once()
         generation, handle = self._weights_generation, self._handle
 
-        def run(new_xs, new_ds=None):
+        def run(new_xs, new_ds=None, **new_controls):
             if self._handle is not handle or self._weights_generation != generation or self._weights_fingerprint() != self._fingerprint:
                 raise RuntimeError("the model's weights changed since capture_graph(): the graph points at released device "
                                    "copies; capture a new graph")
             static_xs.copy_(new_xs)
             if static_ds is not None and new_ds is not None:
                 static_ds.copy_(new_ds)
+            for k, v in new_controls.items():
+                if k not in _prosody.CONTROLS:
+                    raise TypeError("run() got an unexpected keyword argument %r" % k)
+                if v is None:
+                    continue
+                dst = static_pro[k] if static_pro is not None else None
+                if dst is None:
+                    raise ValueError("%s was not given to capture_graph(): the graph holds no such control" % k)
+                if torch.is_tensor(v):
+                    if tuple(v.shape) != tuple(dst.shape):
+                        raise ValueError("%s must have the captured shape %s, got %s" % (k, list(dst.shape), list(v.shape)))
+                    dst.copy_(v)
+                else:
+                    dst.fill_(float(v))
             graph.replay()
             return after, olens_dev, status
 

@@ -557,6 +557,42 @@ size_t fs2_op_align_workspace_bytes(int32_t B, const int32_t *a_lens, const int3
  * fs2_op_align_workspace_bytes(B, a_lens, b_lens, 0). */
 int fs2_op_align(void *stream, const fs2_op_align_args *a);
 
+/* ---- Pitch and energy control of the free-running synthesis (fastspeech2_amd/csrc/prosody.h).  Between the
+ * variance predictors and the quantisation of their outputs, every predicted value v of a frame of utterance b that was expanded from
+ * phoneme t becomes
+ *   v' = fadd_rn(fmul_rn(v, scale), shift),  scale = scale_ptr ? scale_ptr[b * cols_s + (cols_s == 1 ? 0 : t)] : 1.0f,
+ *                                            shift = shift_ptr ? shift_ptr[b * cols_h + (cols_h == 1 ? 0 : t)] : 0.0f
+ * in float32, the product and the sum rounded one after the other (no fused multiply-add), for pitch and for energy alike.  cols = 1:
+ * one value per utterance; cols = batch.Tmax: one per phoneme.  The bucket rule and everything behind it are unchanged; e_out / p_out
+ * return the CONTROLLED values, the ones that were quantised.  The units are the predictors' (the units of the training targets:
+ * with F0 in Hz, pitch_scale = 2^(n / 12) raises the voice by n semitones).  (Declared in two statements for the reason given at
+ * fs2_op_loss_args; _lib.py: Prosody.) ---- */
+struct fs2_prosody {
+    uint32_t struct_size;     /* = sizeof(fs2_prosody) */
+    const float *pitch_scale, *pitch_shift, *energy_scale, *energy_shift;   /* device [B, cols], or NULL = neutral */
+    int32_t pitch_scale_cols, pitch_shift_cols, energy_scale_cols, energy_shift_cols;   /* 1 (per utterance) or Tmax (per phoneme) */
+};
+typedef struct fs2_prosody fs2_prosody;
+
+/* fs2_decode with control: fs2_decode(h, stream, io) is fs2_decode_ctl(h, stream, io, NULL).  ctl == NULL, or all four pointers NULL:
+ * no extra launch, every output is what fs2_decode gives.  Otherwise one launch more (profile name "var.control"), in the host-driven
+ * and in the device-driven layout; like fs2_decode it allocates nothing, reads no device memory and does not synchronise, so it is legal
+ * during stream capture.  FS2_ERR_ARG: wrong struct_size; a cols of a given pointer that is neither 1 nor batch.Tmax; pitch control
+ * together with io->ps, or energy control together with io->es (control acts on predictions); batch.compat_padded != 0 (control has
+ * per-utterance semantics only). */
+int fs2_decode_ctl(fs2_handle *h, void *stream, const fs2_decode_io *io, const fs2_prosody *ctl);
+
+/* Per-label (per-phoneme) means of a per-frame track: x float32 [B, x_stride], labels int32 [B, x_stride] (fs2_decode_io.lr_index:
+ * non-decreasing over the valid frames, anything beyond them), lens_dev DEVICE int64 [B] = the valid frames (clamped to [0, x_stride])
+ * -> mean float32 [B, n_labels], count int32 [B, n_labels], both written whole: count[b, t] = the frames j < lens[b] with
+ * labels[b, j] == t (positive_only != 0: only those with x[b, j] > 0, the voiced frames of an F0 track), mean[b, t] = (float)(their
+ * sum, added in frame order in double, / count), 0 where count is 0.  Labels that are not non-decreasing give unspecified values;
+ * nothing outside the utterance's own valid frames is read.  Asynchronous on `stream`: one launch, no allocation, no host read of
+ * device memory, no synchronisation; legal during stream capture.  FS2_ERR_ARG: B, x_stride or n_labels negative, B * n_labels beyond
+ * 2^31 - 1, a null pointer with a non-empty extent.  B = 0 does nothing. */
+int fs2_op_label_means(void *stream, const float *x, const int32_t *labels, const int64_t *lens_dev, int32_t B, int32_t x_stride,
+                       int32_t n_labels, int32_t positive_only, float *mean, int32_t *count);
+
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
  * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX", "FS2_TOKPROJ", "FS2_TOKPROJ_F32"; -1 = automatic).
  * "FS2_TOKPROJ": 0 = frame-level launches, 1 = the predictors' first convolution, 2 = the decoder input layer, 3 (default) = both from the token-level products of fs2_encode
