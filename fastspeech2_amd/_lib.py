@@ -131,6 +131,7 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
+           "fs2_op_spsi_workspace_bytes_geom", "fs2_op_spsi_workspace_bytes_cap", "fs2_op_spsi_phase_geom", "fs2_op_spsi_phase_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
            "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align",
            "fs2_decode_ctl", "fs2_op_label_means"]
@@ -329,6 +330,16 @@ def lib():
     L.fs2_op_griffin_lim_dev.argtypes = [vp] + gp + [vp, i32, vp, i32, vp, i32, C.c_int64, vp, i32, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp, i32,
                                                      C.c_int64, vp, vp]
     L.fs2_op_griffin_lim_dev.restype = C.c_int
+    L.fs2_op_spsi_workspace_bytes_geom.argtypes = gp + [i32, i32p]
+    L.fs2_op_spsi_workspace_bytes_geom.restype = C.c_size_t
+    L.fs2_op_spsi_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]
+    L.fs2_op_spsi_workspace_bytes_cap.restype = C.c_size_t
+    # stream, geometry, src, src_width, mel_pinv, B, starts, lens, workspace, workspace_bytes, phase, mag_out
+    L.fs2_op_spsi_phase_geom.argtypes = [vp] + gp + [vp, i32, vp, i32, i32p, i32p, vp, C.c_size_t, vp, vp]
+    L.fs2_op_spsi_phase_geom.restype = C.c_int
+    # stream, geometry, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, workspace, workspace_bytes, phase, mag_out
+    L.fs2_op_spsi_phase_dev.argtypes = [vp] + gp + [vp, i32, vp, i32, vp, i32, C.c_int64, vp, vp, C.c_size_t, vp, vp]
+    L.fs2_op_spsi_phase_dev.restype = C.c_int
     L.fs2_op_targets_workspace_bytes.argtypes = [i32]
     L.fs2_op_targets_workspace_bytes.restype = C.c_size_t
     # stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats

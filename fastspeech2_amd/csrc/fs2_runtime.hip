@@ -32,6 +32,7 @@
 #include "gemm_f32.h"
 #include "griffin_lim.h"
 #include "gl_pitch.h"
+#include "gl_spsi.h"
 
 using namespace fs2;
 
@@ -2366,6 +2367,35 @@ int fs2_op_griffin_lim_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win
     if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_dev", gh)) return rc;
     return gl_griffin_lim_dev("fs2_op_griffin_lim_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, n_iter,
                               momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status);
+}
+
+size_t fs2_op_spsi_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
+    GlGeomHost gh;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_workspace_bytes_geom", gh)) return 0;
+    const int64_t frames = spsi_host_frames("fs2_op_spsi_workspace_bytes_geom", gh, B, nullptr, lens);
+    return frames < 0 ? 0 : spsi_layout(gh.n_bins, B, frames).bytes;
+}
+
+size_t fs2_op_spsi_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
+    GlGeomHost gh;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_workspace_bytes_cap", gh)) return 0;
+    return spsi_caps_ok(gh, B, 0, frame_capacity) ? spsi_layout(gh.n_bins, B, frame_capacity).bytes : 0;
+}
+
+int fs2_op_spsi_phase_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
+                           int32_t B, const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes, float* phase, float* mag_out) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_phase_geom", gh)) return rc;
+    return spsi_phase_host("fs2_op_spsi_phase_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, workspace, workspace_bytes, phase, mag_out);
+}
+
+int fs2_op_spsi_phase_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
+                          int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, void* workspace,
+                          size_t workspace_bytes, float* phase, float* mag_out) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_phase_dev", gh)) return rc;
+    return spsi_phase_dev("fs2_op_spsi_phase_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, workspace,
+                          workspace_bytes, phase, mag_out);
 }
 
 size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) { return fs2_op_stft_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, wav_lens); }

@@ -343,3 +343,60 @@ int gl_stft_pitch_run(const char* who, void* stream, const GlGeomHost& gh, const
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft pitch: %s", hipGetErrorString(e));
     return FS2_OK;
 }
+
+// ---- SPSI initial phase (kernels and launch sequences: gl_spsi.h): the argument checks behind fs2_op_spsi_phase_geom / _dev ----
+
+// what both forms check of the source first, by the rules of the synthesis (gl_check_synthesis)
+int spsi_check_source(const char* who, const GlGeomHost& gh, int32_t src_width, const float* mel_pinv) {
+    return gl_check_synthesis(who, gh, src_width, mel_pinv, 0, 0.f);
+}
+
+// frames of a host-planned batch (every utterance with L >= 1 is computed), or a failure code (< 0)
+int64_t spsi_host_frames(const char* who, const GlGeomHost& gh, int B, const int32_t* starts, const int32_t* lens) {
+    if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d)", who, B);
+    int64_t rows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "%s: negative length / start of utterance %d", who, b);
+        if (starts && (int64_t)starts[b] + lens[b] > INT32_MAX / gh.n_bins)
+            return fail(nullptr, FS2_ERR_ARG, "%s: utterance %d ends beyond row %d", who, b, INT32_MAX / gh.n_bins);
+        rows += lens[b];
+        if (rows > INT32_MAX / gh.n_bins) return fail(nullptr, FS2_ERR_ARG, "%s: batch too large (%lld frames)", who, (long long)rows);
+    }
+    return rows;
+}
+
+int spsi_phase_host(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
+                    const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes, float* phase, float* mag_out) {
+    if (int rc = spsi_check_source(who, gh, src_width, mel_pinv)) return rc;
+    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+    const int64_t frames = spsi_host_frames(who, gh, B, starts, lens);
+    if (frames < 0) return (int)frames;
+    if (frames == 0) return FS2_OK;
+    if (!src || !phase || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    const SpsiLayout at = spsi_layout(gh.n_bins, B, frames);
+    if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
+    const hipError_t e = spsi_run_host((hipStream_t)stream, gh.n_fft, gh.hop, src, src_width, mel_pinv, B, starts, lens, frames, (char*)workspace, at, phase, mag_out);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FS2_OK;
+}
+
+// the capacities of a device-driven call, by the rules of gl_griffin_lim_dev
+bool spsi_caps_ok(const GlGeomHost& gh, int64_t B, int64_t src_stride, int64_t frame_capacity) {
+    return B >= 1 && frame_capacity >= 1 && src_stride >= 0 && frame_capacity <= INT32_MAX / gh.n_bins && B * src_stride <= INT32_MAX / gh.n_bins;
+}
+
+int spsi_phase_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
+                   const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, void* workspace,
+                   size_t workspace_bytes, float* phase, float* mag_out) {
+    if (int rc = spsi_check_source(who, gh, src_width, mel_pinv)) return rc;
+    if (!spsi_caps_ok(gh, B, src_stride, frame_capacity))
+        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d (B >= 1, 1 <= frame_capacity, rows * bins < 2^31)", who, B,
+                    (long long)frame_capacity, src_stride);
+    if (!src || !lens_dev || !workspace || !phase) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    const SpsiLayout at = spsi_layout(gh.n_bins, B, frame_capacity);
+    if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
+    const hipError_t e = spsi_run_dev((hipStream_t)stream, gh.n_fft, gh.hop, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status,
+                                      (char*)workspace, at, phase, mag_out);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FS2_OK;
+}

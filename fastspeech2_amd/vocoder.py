@@ -302,6 +302,16 @@ def _i32(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+INITS = ("seeded", "spsi")
+
+
+def _check_init(init, init_phase):
+    if init not in INITS:
+        raise ValueError("init must be one of %s, got %r" % (INITS, init))
+    if init == "spsi" and init_phase is not None:
+        raise ValueError("init='spsi' computes the initial phase itself: pass init_phase or init='spsi', not both")
+
+
 class GriffinLim:
     """Griffin-Lim on the GPU, batched.  ``GriffinLim(hp)(mels, olens)`` -> ``Waveforms(wav_packed, sample_lens)``.
 
@@ -353,19 +363,22 @@ class GriffinLim:
         return mels.reshape(-1, W).contiguous().float(), init_phase, W, n_iter, momentum
 
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
-                 padded_out=False):
+                 padded_out=False, init="seeded"):
         """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
         with ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
         [.., n_fft / 2 + 1] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout
-        of ``mels`` with n_fft / 2 + 1 bins, or None: seeded.  ``momentum`` > 0: fast Griffin-Lim (0 = the reference).  Runs on the
-        current stream of the input's device without synchronising.
+        of ``mels`` with n_fft / 2 + 1 bins, or None: seeded.  ``init="spsi"``: start from the phase-continuity phase of
+        :func:`spsi_phase` instead of the seeded random one (``seed`` is ignored; together with ``init_phase`` it raises): on
+        harmonic signals 10 iterations from it beat 20 from the seeded start.  ``momentum`` > 0: fast
+        Griffin-Lim (0 = the reference).  Runs on the current stream of the input's device without synchronising.
 
         ``sync=True`` reads ``olens`` on the host (a CUDA ``olens`` is copied back, which waits for the GPU) and sizes the result
         from it.  ``sync=False``: the frame counts stay on the device -- ``olens`` must be a CUDA int64 tensor, or ``mels`` an
         :class:`AsyncMels` (``inference_batch(sync=False)``), whose mels, ``olens`` and status are taken -- and nothing waits for
         the GPU; see :meth:`_call_dev`.  Returns an :class:`AsyncWaveforms`."""
+        _check_init(init, init_phase)
         if not sync:
-            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out)
+            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init)
         if capacity is not None or padded_out:
             raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
@@ -394,6 +407,8 @@ class GriffinLim:
         s_np, s_p = _i32(starts)
         l_np, l_p = _i32(L.numpy())
         B = len(l_np)
+        if init == "spsi":
+            init_phase = self._spsi_host(src, W, s_np, l_np, magnitudes, False)[0]
         ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_geom(*g, B, l_p))
         with torch.cuda.device(dev):
             pinv = self.constants(dev)[0] if not magnitudes else None
@@ -404,6 +419,90 @@ class GriffinLim:
                                                    wav.data_ptr()))
         return Waveforms(wav, sample_lens)
 
+
+    def _spsi_host(self, src, W, starts_np, lens_np, magnitudes, want_mag):
+        """fs2_op_spsi_phase_geom on checked arguments: (phase [rows, bins], M [rows, bins] or None), zeros where no utterance is."""
+        g, dev = self.geometry, src.device
+        phase = torch.zeros(src.shape[0], g.n_bins, dtype=torch.float32, device=dev)
+        mag = torch.zeros_like(phase) if want_mag else None
+        if int(lens_np.sum()) == 0:
+            return phase, mag
+        lib = _lib.lib()
+        s_np, s_p = _i32(starts_np)
+        l_np, l_p = _i32(lens_np)
+        ws_bytes = int(lib.fs2_op_spsi_workspace_bytes_geom(*g, len(l_np), l_p))
+        with torch.cuda.device(dev):
+            pinv = self.constants(dev)[0] if not magnitudes else None
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.fs2_op_spsi_phase_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, len(l_np),
+                                                  s_p, l_p, ws.data_ptr(), ws_bytes, phase.data_ptr(), mag.data_ptr() if want_mag else None))
+        return phase, mag
+
+    def _spsi_dev(self, src, W, olens, stride, cap, upstream, magnitudes, want_mag):
+        """fs2_op_spsi_phase_dev on checked arguments (``olens`` a contiguous CUDA int64 [B], B >= 1, cap >= 1)."""
+        g, dev = self.geometry, src.device
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            phase = torch.zeros(src.shape[0], g.n_bins, dtype=torch.float32, device=dev)
+            mag = torch.zeros_like(phase) if want_mag else None
+            pinv = self.constants(dev)[0] if not magnitudes else None
+            ws_bytes = int(lib.fs2_op_spsi_workspace_bytes_cap(*g, olens.numel(), cap))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.fs2_op_spsi_phase_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, olens.numel(),
+                                                 olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
+                                                 ws.data_ptr(), ws_bytes, phase.data_ptr(), mag.data_ptr() if want_mag else None))
+        return phase, mag
+
+    def spsi_phase(self, src, olens=None, magnitudes=False, return_magnitudes=False, sync=True):
+        """The phase-continuity initial phase (:func:`spsi_phase`) in this GriffinLim's geometry."""
+        upstream = None
+        if isinstance(src, AsyncMels):
+            if sync:
+                raise ValueError("an AsyncMels belongs to sync=False (its frame counts are on the device)")
+            if olens is not None:
+                raise ValueError("olens is taken from the AsyncMels given as src; pass one or the other")
+            upstream = src.status
+            src, olens = src
+        if not sync:
+            if not isinstance(olens, torch.Tensor) or not olens.is_cuda or olens.dtype != torch.int64:
+                raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device)")
+        mels = src
+        src, _, W, _, _ = self._checked(mels, 0, 0.0, None, magnitudes, olens if not sync else None)
+        NB = self.geometry.n_bins
+        shape = tuple(mels.shape[:-1]) + (NB,)
+        if sync:
+            if mels.dim() == 2:
+                N = mels.shape[0]
+                L = _lens([N] if olens is None else olens)
+                if int(L.sum()) != N:
+                    raise ValueError("packed src: olens sum to %d, src has %d rows" % (int(L.sum()), N))
+                starts = np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
+            else:
+                Bp, Lmax = mels.shape[0], mels.shape[1]
+                L = _lens([Lmax] * Bp if olens is None else olens, Bp)
+                if Bp and int(L.max()) > Lmax:
+                    raise ValueError("padded src: an olens entry exceeds Lmax = %d" % Lmax)
+                starts = np.arange(Bp, dtype=np.int64) * Lmax
+            if src.shape[0] * NB >= 2 ** 31:
+                raise ValueError("batch too large for one call (%d rows)" % src.shape[0])
+            phase, mag = self._spsi_host(src, W, starts, L.numpy(), magnitudes, return_magnitudes)
+        else:
+            olens = olens.reshape(-1).contiguous()
+            B = olens.numel()
+            if mels.dim() == 2:
+                rows, stride = mels.shape[0], 0
+            else:
+                if mels.shape[0] != B:
+                    raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
+                rows, stride = B * mels.shape[1], mels.shape[1]
+            if rows * NB >= 2 ** 31:
+                raise ValueError("batch too large for one call (%d rows)" % rows)
+            if B == 0 or rows == 0:
+                phase = torch.zeros(rows, NB, dtype=torch.float32, device=mels.device)
+                mag = torch.zeros_like(phase) if return_magnitudes else None
+            else:
+                phase, mag = self._spsi_dev(src, W, olens, stride, rows, upstream, magnitudes, return_magnitudes)
+        return (phase.reshape(shape), mag.reshape(shape)) if return_magnitudes else phase.reshape(shape)
 
     _PIN_SLOTS = 16
 
@@ -423,12 +522,14 @@ class GriffinLim:
         slot[1] = _WavRecord(ev, slot[0])
         return slot[1]
 
-    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out):
+    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init="seeded"):
         """The device-driven call (include/fs2.h: fs2_op_griffin_lim_dev).  ``capacity``: bound on the batch's total frames (default:
         the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the waveform is
         sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only) [B, hop (Lcap - 1)].
         Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own call overflowed, give
-        a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``."""
+        a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``.  ``init="spsi"``: the initial phase is computed on the device
+        from the same frame counts first (fs2_op_spsi_phase_dev), equally without a host read."""
+        _check_init(init, init_phase)
         upstream = None
         if isinstance(mels, AsyncMels):
             if olens is not None:
@@ -479,6 +580,8 @@ class GriffinLim:
             lib = _lib.lib()
             ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_cap(*g, B, cap))
             pinv = self.constants(dev)[0] if not magnitudes else None
+            if init == "spsi":
+                init_phase = self._spsi_dev(src, W, olens, stride, cap, upstream, magnitudes, False)[0]
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             _lib.check(lib.fs2_op_griffin_lim_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, B,
                                                   olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
@@ -501,6 +604,20 @@ def _gl_for(hp):
     if _DEFAULT_GL is None:
         _DEFAULT_GL = GriffinLim()
     return _DEFAULT_GL
+
+
+def spsi_phase(src, olens=None, hp=None, magnitudes=False, return_magnitudes=False, sync=True):
+    """Initial phase for Griffin-Lim from the magnitudes alone: Single Pass Spectrogram Inversion (Beauregard, Harish and Wyse 2015;
+    csrc/gl_spsi.h, include/fs2.h: fs2_op_spsi_phase_geom).  Per frame the spectral peaks are found, each
+    peak's frequency is refined with a parabola, and its phase advances by hop times that frequency from the phase its bin had in the
+    previous frame; the bins around a peak follow it.  ``src``, ``olens`` and ``magnitudes`` as in ``GriffinLim.__call__`` (log-mel
+    frames [.., n_mels], or magnitudes [.., n_fft / 2 + 1]), in the geometry of ``hp.audio``.  Returns the angles (radians in
+    [0, 2 pi)) in the layout of ``src`` with n_fft / 2 + 1 columns, zeros in the rows no utterance covers: what ``init_phase=`` takes
+    (``GriffinLim()(mels, olens, init="spsi")`` does both).  ``return_magnitudes=True``: also the magnitudes the phase was computed
+    from, in the same layout.  ``sync=False``: ``olens`` is a CUDA int64 tensor (or ``src`` an ``AsyncMels``) and nothing waits for
+    the GPU; invalid frame counts leave the phase zero (the vocoder call that follows reports them).  Every utterance with at least
+    one frame is computed; an utterance's phase is bit-identical alone or in any batch.  CPU tensors raise."""
+    return _gl_for(hp).spsi_phase(src, olens, magnitudes=magnitudes, return_magnitudes=return_magnitudes, sync=sync)
 
 
 def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=None, pitch=None):

@@ -382,6 +382,45 @@ int fs2_op_griffin_lim_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win
                            void *workspace, size_t workspace_bytes, float *wav, int32_t wav_stride, int64_t wav_capacity,
                            int64_t *sample_lens_dev, int32_t *status);
 
+/* ---- Phase-continuity initial phase for Griffin-Lim (fastspeech2_amd/csrc/gl_spsi.h): Single Pass
+ * Spectrogram Inversion (Beauregard, Harish and Wyse 2015) builds, from the magnitudes alone, angles to pass as `init_phase` to the
+ * entry points above; from them Griffin-Lim needs fewer iterations than from the seeded random phase.  Geometries, src / src_width /
+ * mel_pinv, starts / lens and the FS2_ERR_UNSUPPORTED / FS2_ERR_ARG rules are those of fs2_op_griffin_lim_geom; every utterance with
+ * L >= 1 is computed (there is no L_min).  Per utterance, M [L, bins] = max(mel_pinv . exp(mel), 0) or the magnitudes given; float32,
+ * every operation rounded on its own, no fused multiply-add; phases in turns, acc[bins] = 0 before frame 0.  For the row m of frame t:
+ *   peak j (1 <= j <= bins - 2): m[j] > m[j-1] and m[j] > m[j+1].  A non-peak bin b is rising iff m[b] < m[b+1], falling iff
+ *   m[b] < m[b-1] (IEEE comparisons: a NaN is neither).  The owner of a non-peak bin is the nearest peak to its right if every bin
+ *   from it up to that peak is rising, else the nearest peak to its left if every bin from it down to that peak is falling, else
+ *   none; bins 0 and bins - 1 have none; a peak owns itself.
+ *   peak j, a, b, c = m[j-1], m[j], m[j+1]: den = (a - 2 b) + c; p = den != 0 ? (0.5 (a - c)) / den : 0;
+ *     w = float((hop j) mod n_fft) / n_fft + p float(hop / n_fft); pk = acc[j] + w; pk -= floorf(pk); right = c > a
+ *   bin k owned by j, d = k - j: new[k] = pk + h, - 1 if >= 1, with h = 0.5 if right and (d == 1 or d < 0), or if not right and
+ *     (d == -1 or d > 0), else 0.  An unowned bin keeps acc[k].  Then acc <- new and phase[t][k] = acc[k] * 6.28318548f.
+ * phase [rows, bins] is written in src's row layout, radians in [0, 2 pi); rows no utterance covers are not written.  mag_out
+ * [rows, bins] (or NULL) receives the M the phase was computed from, in the same layout.  An utterance's phase is bit-identical
+ * alone or inside any batch, packed or padded, and in the host-planned and the device-driven form.  No atomics. ---- */
+
+/* workspace bytes for B utterances of lens[b] frames (HOST array; 0 on a bad argument) */
+size_t fs2_op_spsi_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *lens);
+
+/* workspace bytes of the device-driven form for B utterances whose frame counts sum to at most frame_capacity (0 on a bad argument) */
+size_t fs2_op_spsi_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity);
+
+/* starts / lens: HOST int32 arrays as in fs2_op_griffin_lim_geom.  Every launch goes to `stream`; nothing synchronises. */
+int fs2_op_spsi_phase_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                           const float *mel_pinv, int32_t B, const int32_t *starts, const int32_t *lens, void *workspace,
+                           size_t workspace_bytes, float *phase, float *mag_out);
+
+/* lens_dev (DEVICE int64 [B]), src_stride, frame_capacity and upstream_status as in fs2_op_griffin_lim_dev; phase and mag_out hold
+ * frame_capacity rows (packed) or B * src_stride rows (padded).  The lengths are validated on the device before anything is indexed
+ * with them: on a negative length, a sum beyond frame_capacity, a length above src_stride or upstream flags the call writes nothing
+ * to phase or mag_out and touches nothing outside src, the workspace and phase (the fs2_op_griffin_lim_dev that follows reports the
+ * flags and fills its waveform with NaN).  No allocation, no host read of device memory, no synchronisation; may be captured into a
+ * graph.  Host-checked limits: B >= 1, 1 <= frame_capacity, frame_capacity * bins < 2^31, B * src_stride * bins < 2^31. */
+int fs2_op_spsi_phase_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                          const float *mel_pinv, int32_t B, const int64_t *lens_dev, int32_t src_stride, int64_t frame_capacity,
+                          const int32_t *upstream_status, void *workspace, size_t workspace_bytes, float *phase, float *mag_out);
+
 /* ---- Training targets from the per-frame energy and F0 arrays (fastspeech2_amd/csrc/targets.h): the
  * reference's remove_outlier (utils/util.py:26-49, applied to every energy and pitch array its data loader returns) and the corpus
  * statistics of its compute_statistics.py, for B utterances packed in x: utterance b = x[starts[b] .. + lens[b]).  Per utterance

@@ -19,6 +19,14 @@ forms timed alternately (R rounds of K steps each per form; median and max - min
   (b) async     both halves sync=False (AsyncMels -> AsyncWaveforms), three steps in flight on StepStreams(3)
   (c) graph     c1 only: capture_graph(vocoder=gl), one graph launch per step
 Every region is K steps between two device synchronisations; (b) and (c) are checked for flags afterwards.
+
+--init seeded|spsi: the initial phase of every Griffin-Lim call of the runs above (default seeded; --n-iter as before).
+
+--compare-init [--n-iter 10] [--repeats R] [--steps K] [--pipeline-workloads c3,c1]: the SPSI initial phase against the seeded one, per
+workload, every pair timed alternately over R rounds (median and max - min spread): (i) spsi_phase alone, (ii) the vocoder call
+(seeded, 30) against (spsi, --n-iter), (iii) the text -> wav step, synchronous and sync-free on three streams, for the same two
+settings, (iv) the spectral convergence of both settings on the same mels (stft_magnitude on the GPU).  The mels are those of a
+randomly initialised model: they are not speech.
 """
 import argparse
 import json
@@ -99,8 +107,12 @@ def main():
     ap.add_argument("--pipeline-workloads", default="c3,c1", help="workloads of the --pipeline run (the graph form runs at c1 only)")
     ap.add_argument("--steps", type=int, default=20, help="steps per timed region of the --pipeline run")
     ap.add_argument("--precision", default="mix_mx4", help="the model's arithmetic mode in the --pipeline run (bench.py's default)")
+    ap.add_argument("--init", default="seeded", choices=("seeded", "spsi"), help="initial phase of the Griffin-Lim calls")
+    ap.add_argument("--compare-init", action="store_true", help="(seeded, 30) against (spsi, --n-iter) (see the module docstring)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "vocoder_bench needs a GPU"
+    if args.compare_init:
+        return compare_init_main(args)
     if args.pipeline:
         return pipeline_main(args)
     if args.geometry is not None or args.sample_rate is not None:
@@ -109,7 +121,7 @@ def main():
     hp, mels, olens = c3_mels(args.workload)
     N, B = mels.shape[0], len(olens)
     gl = GriffinLim(hp)
-    run = lambda n: gl(mels, olens, n_iter=n, seed=0)
+    run = lambda n: gl(mels, olens, n_iter=n, seed=0, init=args.init)
     ms_call, reps = timed(lambda: run(args.n_iter), args.min_s)
     ms_zero, _ = timed(lambda: run(0), args.min_s)
     ms_iter = (ms_call - ms_zero) / max(args.n_iter, 1)
@@ -131,7 +143,7 @@ def main():
     flop_iter = (halo_frames + N) * fft_flop + N * 513 * 12
     t_bytes = bytes_iter / (PEAK_HBM_TBS * 1e12) * 1e3
     t_flop = flop_iter / (PEAK_FP32_TFLOPS * 1e12) * 1e3
-    rec = dict(workload=args.workload, utterances=B, frames=N, tiles=tiles, n_iter=args.n_iter, samples=samples,
+    rec = dict(workload=args.workload, utterances=B, frames=N, tiles=tiles, n_iter=args.n_iter, init=args.init, samples=samples,
                audio_seconds=round(audio_s, 3), hip_ms_per_call=round(ms_call, 3), hip_ms_call_n_iter0=round(ms_zero, 3),
                hip_ms_per_iter=round(ms_iter, 4), hip_reps=reps, real_time_factor=round(audio_s / (ms_call / 1e3), 1),
                bytes_per_iter=bytes_iter, flop_per_iter=flop_iter,
@@ -167,8 +179,8 @@ def pipeline_main(args):
     model = model.cuda()
     model.precision = args.precision
     gl = GriffinLim(hp)
-    K, n_iter = args.steps, args.n_iter
-    rec = dict(mode="pipeline", precision=args.precision, n_iter=n_iter, steps_per_region=K, rounds=args.repeats, workloads={})
+    K, n_iter, init = args.steps, args.n_iter, args.init
+    rec = dict(mode="pipeline", precision=args.precision, n_iter=n_iter, init=init, steps_per_region=K, rounds=args.repeats, workloads={})
 
     def region(step, finish=None):
         torch.cuda.synchronize()
@@ -185,11 +197,11 @@ def pipeline_main(args):
             b = make_batch(workload)
             xs, il = b["xs"].cuda(), b["ilens"]
             mels, olens = model.inference_batch(xs, il, packed=True)          # (first call: synchronous, learns the capacities)
-            ref = gl(mels, olens, n_iter=n_iter)
+            ref = gl(mels, olens, n_iter=n_iter, init=init)
 
             def step_sync():
                 m, ol = model.inference_batch(xs, il, packed=True)
-                return gl(m, ol, n_iter=n_iter)
+                return gl(m, ol, n_iter=n_iter, init=init)
 
             rot = StepStreams(3)
             keep = []
@@ -197,12 +209,12 @@ def pipeline_main(args):
             def step_async():
                 with rot.next():
                     am = model.inference_batch(xs, il, packed=True, sync=False)
-                    keep.append((am, gl(am, n_iter=n_iter, sync=False)))
+                    keep.append((am, gl(am, n_iter=n_iter, sync=False, init=init)))
                 del keep[:-3]                                                   # (three steps in flight own their buffers)
 
             forms = {"sync": (step_sync, None), "async": (step_async, rot.join)}
             if workload == "c1":
-                run = model.capture_graph(xs, il, vocoder=gl, n_iter=n_iter)
+                run = model.capture_graph(xs, il, vocoder=gl, n_iter=n_iter, init=init)
                 forms["graph"] = (lambda: run(xs), None)
             for step, finish in forms.values():                                # warm-up of every form
                 region(step, finish)
@@ -231,6 +243,97 @@ def pipeline_main(args):
     print(json.dumps(rec))
 
 
+def compare_init_main(args):
+    from fastspeech2_amd import FeedForwardTransformer, StepStreams, default_hparams, N_PHONEME_SYMBOLS
+    from fastspeech2_amd.synthetic import portable_state_dict, ljspeech_durations, make_batch
+    from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude
+    hp = default_hparams()
+    model = FeedForwardTransformer(N_PHONEME_SYMBOLS, hp.audio.num_mels, hp).eval()
+    model.load_state_dict(ljspeech_durations(portable_state_dict(model.state_dict(), seed=0)))
+    model = model.cuda()
+    model.precision = args.precision
+    gl = GriffinLim(hp)
+    K, R = args.steps, args.repeats
+    settings = {"seeded30": dict(n_iter=30, init="seeded"), "spsi%d" % args.n_iter: dict(n_iter=args.n_iter, init="spsi")}
+    a, b = list(settings)
+    rec = dict(mode="compare_init", precision=args.precision, settings=settings, steps_per_region=K, rounds=R, min_s=args.min_s,
+               note="mels of a randomly initialised model: not speech", workloads={})
+    stat = lambda v: dict(median=round(float(np.median(v)), 4), spread=round(max(v) - min(v), 4), runs=[round(x, 4) for x in v])
+
+    def region(step, finish=None):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(K):
+            step()
+        if finish is not None:
+            finish()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / K * 1e3
+
+    with torch.no_grad():
+        for workload in args.pipeline_workloads.split(","):
+            bt = make_batch(workload)
+            xs, il = bt["xs"].cuda(), bt["ilens"]
+            mels, olens = model.inference_batch(xs, il, packed=True)
+            olens = [int(x) for x in olens]
+            out = dict(utterances=len(olens), frames=sum(olens), longest=max(olens))
+            # (i), (ii): the calls alone, alternately
+            calls = {"spsi_phase": lambda: gl.spsi_phase(mels, olens)}
+            for k, kw in settings.items():
+                calls["vocoder_" + k] = (lambda kw: lambda: gl(mels, olens, seed=0, **kw))(kw)
+            ms = {k: [] for k in calls}
+            for _ in range(R):
+                for k, fn in calls.items():
+                    ms[k].append(timed(fn, args.min_s)[0])
+            for k, v in ms.items():
+                out[k + "_ms"] = stat(v)
+            d = out["vocoder_" + a + "_ms"]["median"] - out["vocoder_" + b + "_ms"]["median"]
+            out["vocoder_ms_saved"] = round(d, 4)
+            out["saved_more_than_spread"] = bool(d > max(out["vocoder_" + a + "_ms"]["spread"], out["vocoder_" + b + "_ms"]["spread"]))
+            # (iv): spectral convergence of both settings on the same mels
+            Mt = torch.clamp(torch.exp(mels) @ gl.constants(mels.device)[0].T, min=0)
+            for k, kw in settings.items():
+                w = gl(mels, olens, seed=0, **kw)
+                X = stft_magnitude(w.wav, w.sample_lens)
+                keep_rows = torch.cat([torch.full((L,), L >= 4, dtype=torch.bool) for L in olens]).to(mels.device)
+                out["sc_" + k] = round(float(torch.linalg.norm((Mt - X)[keep_rows])) / float(torch.linalg.norm(Mt[keep_rows])), 5) \
+                    if X.shape == Mt.shape else None
+            # (iii): text -> wav per step
+            rot = StepStreams(3)
+            keep = []
+
+            def sync_step(kw):
+                def step():
+                    m, ol = model.inference_batch(xs, il, packed=True)
+                    return gl(m, ol, **kw)
+                return step
+
+            def async_step(kw):
+                def step():
+                    with rot.next():
+                        am = model.inference_batch(xs, il, packed=True, sync=False)
+                        keep.append((am, gl(am, sync=False, **kw)))
+                    del keep[:-3]
+                return step
+
+            forms = {}
+            for k, kw in settings.items():
+                forms["sync_" + k] = (sync_step(kw), None)
+                forms["async_" + k] = (async_step(kw), rot.join)
+            for step, finish in forms.values():
+                region(step, finish)
+            pm = {k: [] for k in forms}
+            for _ in range(R):
+                for k, (step, finish) in forms.items():
+                    pm[k].append(region(step, finish))
+            am, w = keep[-1]
+            out["async_ok"] = bool(model.async_ok() and am.ok() and w.ok())
+            for k, v in pm.items():
+                out["step_" + k + "_ms"] = stat(v)
+            rec["workloads"][workload] = out
+    print(json.dumps(rec))
+
+
 def geometry_main(args):
     from fastspeech2_amd.hparams import DotDict
     from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude, tile_rule
@@ -247,7 +350,7 @@ def geometry_main(args):
     M = stft_magnitude(wav, T, hp=hp)                                              # [N, bins]
     olens = [t // hop + 1 for t in T]
     N, B, NB = M.shape[0], len(olens), n_fft // 2 + 1
-    run = lambda n: gl(M, olens, n_iter=n, seed=0, magnitudes=True)
+    run = lambda n: gl(M, olens, n_iter=n, seed=0, magnitudes=True, init=args.init)
     med = lambda xs: float(np.median(xs))
     hip = [timed(lambda: run(args.n_iter), args.min_s)[0] for _ in range(args.repeats)]
     ms_zero = med([timed(lambda: run(0), args.min_s)[0] for _ in range(max(1, args.repeats // 2))])
