@@ -16,44 +16,29 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dtw import FEATURES, _side, mcep
-from .vocoder import _i32, _lens, _require_cuda, _stream
+from .dtw import FEATURES, _pairs
+from .losses import DeviceRecords
+from .vocoder import _i32, _lens, _stream
 
 TERMS = _lib.ALIGN_TERMS
 # index of a record (include/fs2.h)
 N_STATES, N_FRAMES, FLAGS, COST, STATES_USED, LONGEST_STAY, EMPTY_LABELS = range(7)
 
 
-class Alignment:
+class Alignment(DeviceRecords):
     """``durations``: device int64 [B, T], row b = the frames per label of pair b (zeros beyond its labels; all zeros where no
     alignment was found).  ``state``: device int32 laid out like the rows of ``b`` -- the pair-local index of the state every frame
     was assigned to, -1 at pads and where no alignment was found -- or None.  ``terms`` [B, 8] / ``batch`` [8]: the records (float64
     numpy; include/fs2.h lists the indices); after ``sync=False`` they are still on the device and the first read fetches them with
     one copy, which waits for the stream."""
+    TERMS = TERMS
 
     def __init__(self, durations, state, terms, batch, features, D, _device=None):
         if features not in FEATURES:
             raise ValueError("features must be one of %s, got %r" % (FEATURES, features))
+        super().__init__(terms, batch, _device)
         self.durations, self.state = durations, state
-        self._terms = None if terms is None else np.asarray(terms, np.float64).reshape(-1, TERMS)
-        self._batch = None if batch is None else np.asarray(batch, np.float64).reshape(TERMS)
-        self._device = _device          # [B + 1, 8] float64 on the device: the records, then the batch record
         self.features, self.D = features, D
-
-    def _fetch(self):
-        if self._device is not None:
-            host = self._device.cpu().numpy()
-            self._terms, self._batch, self._device = host[:-1], host[-1], None
-
-    @property
-    def terms(self):
-        self._fetch()
-        return self._terms
-
-    @property
-    def batch(self):
-        self._fetch()
-        return self._batch
 
     @property
     def ok(self):
@@ -119,41 +104,15 @@ def monotonic_align(a, a_lens, b, b_lens, labels=None, n_labels=None, max_step=2
         raise ValueError("max_step must be 1 or 2, got %r" % (max_step,))
     if (labels is None) != (n_labels is None):
         raise ValueError("labels and n_labels are given together or not at all")
-    al, bl = _lens(a_lens, name="a_lens"), _lens(b_lens, name="b_lens")
-    B = int(al.numel())
-    if bl.numel() != B:
-        raise ValueError("a_lens has %d entries, b_lens %d" % (B, bl.numel()))
-    nl = al if labels is None else _lens(n_labels, B, name="n_labels")
-    _require_cuda(a, "a")
-    _require_cuda(b, "b")
-    if a.device != b.device:
-        raise ValueError("a is on %s, b on %s" % (a.device, b.device))
-    if a.shape[-1] != b.shape[-1]:
-        raise ValueError("a has %d features per frame, b %d" % (a.shape[-1], b.shape[-1]))
-    if features == "mcep":
-        a, b = mcep(a.float(), n_mcep), mcep(b.float(), n_mcep)
-    D = int(a.shape[-1])
-    if not 1 <= D <= 128:
-        raise ValueError("D = %d outside [1, 128]" % D)
-    dev = a.device
-    a, a_stride, a_starts, (lab,) = _side(a, al, "a", ((labels, "labels", torch.int32),))
-    b, b_stride, b_starts, _ = _side(b, bl, "b", ())
+    q = _pairs(Alignment, "fs2_op_align_workspace_bytes", a, a_lens, b, b_lens, ((labels, "labels", torch.int32),), (), features, n_mcep, workspace_cap)
+    B, b, b_starts, dev, (lab,) = q.B, q.b, q.b_starts, q.dev, q.a_tracks
+    nl = q.al if labels is None else _lens(n_labels, B, name="n_labels")
     if lab is not None and lab.numel() == 0:                    # no state at all: an empty tensor has no address
         lab = None
-    if B and max(int((a_starts + al.numpy()).max()), int((b_starts + bl.numpy()).max())) > 2 ** 31 - 1:
-        raise ValueError("rows beyond 2^31 - 1")
-
-    lib = _lib.lib()
-    keep = [_i32(x) for x in (a_starts, al.numpy(), b_starts, bl.numpy(), nl.numpy())]
-    (_, as_p), (_, al_p), (_, bs_p), (_, bl_p), (_, nl_p) = keep
+    nl_keep, nl_p = _i32(nl.numpy())
     ptr = lambda t: None if t is None else t.data_ptr()
     T = int(nl.max()) if B else 0
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.fs2_op_align_workspace_bytes(B, al_p, bl_p, int(workspace_cap))) if B else 0
-        if B and not ws_bytes:
-            raise ValueError("a pair of more than 2^40 cells")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if B else None
-        rec = torch.empty(B + 1, TERMS, dtype=torch.float64, device=dev)
         durations = torch.empty(B, T, dtype=torch.int64, device=dev)
         if b.dim() == 3:                # indexed by the rows of b: the view [B, S] of a buffer with b's rows per sequence
             per_seq = int(b_starts[1]) if B > 1 else int(b.shape[1])
@@ -162,11 +121,8 @@ def monotonic_align(a, a_lens, b, b_lens, labels=None, n_labels=None, max_step=2
         else:                           # (packed: the rows beyond the lengths' sum stay -1 too)
             state = torch.full((int(b.shape[0]),), -1, dtype=torch.int32, device=dev)
             flat = state
-        args = _lib.OpAlignArgs(B, D, int(max_step), a_stride, b_stride, T, ptr(a), ptr(b), ptr(lab), as_p, al_p, bs_p, bl_p,
-                                nl_p if lab is not None else None, ptr(ws), ws_bytes, durations.data_ptr() if durations.numel() else None,
-                                flat.data_ptr() if flat.numel() else None, rec.data_ptr() if B else None, rec[B].data_ptr())
-        _lib.check(lib.fs2_op_align(_stream(dev), C.byref(args)))
-    out = Alignment(durations, state, None, None, features, D, _device=rec)
-    if sync:
-        out._fetch()
-    return out
+        args = _lib.OpAlignArgs(B, q.D, int(max_step), q.a_stride, q.b_stride, T, ptr(q.a), ptr(b), ptr(lab), *q.lens,
+                                nl_p if lab is not None else None, ptr(q.ws), q.ws_bytes, durations.data_ptr() if durations.numel() else None,
+                                flat.data_ptr() if flat.numel() else None, q.terms_p, q.batch_p)
+        _lib.check(_lib.lib().fs2_op_align(_stream(dev), C.byref(args)))
+    return Alignment(durations, state, None, None, features, q.D, _device=q.rec)._synced(sync)

@@ -1,8 +1,8 @@
 // Forced alignment of recorded frames to synthesized frames: every frame of the recording is assigned to exactly one state (a frame
 // of the synthesis), monotonically, so that the counts per phoneme are durations that add up to the recording's length -- behind
 // fs2_op_align (include/fs2.h; tests/align_oracle.py states the same in numpy).  Not a header of its own:
-// fs2_runtime.hip includes it inside its unnamed namespace, after dtw.h (dtw_dist, DtwPair, DtwGroups, dtw_upload_pairs, fail(),
-// align_up()).  Plain HIP C++, restricted to what tests/kernel_standin/hip_standin.h provides.
+// fs2_runtime.hip includes it inside its unnamed namespace, after dtw.h (dtw_dist, dtw_upload, dtw_launch_dist, and through it
+// pair_plan.h: the host side it shares with dtw.h).  Plain HIP C++, restricted to what tests/kernel_standin/hip_standin.h provides.
 //
 // The definition.  d(i, j) is dtw.h's.  Q(0, 0) = d(0, 0); Q(i, 0) = +inf for i > 0; Q(i, j) = d(i, j) + min over k = 0 .. S of
 // Q(i - k, j - 1), S = max_step: the predecessor is chosen in the order k = 0, 1, 2 with a strict "<" (a tie keeps the smaller k); a
@@ -10,8 +10,8 @@
 //
 // The matrix is kept with the sides SWAPPED: dtw_dist is handed the recording as its a side and the synthesis as its b side, so it
 // writes d as [M, N] -- column j of the recurrence is one contiguous row of memory -- and (a - b)^2 = (b - a)^2 in double, so the
-// values are d(i, j) bit for bit.  A DtwPair of this file therefore reads: a0, n = first frame and frames of the RECORDING (M);
-// b0, m = first state and states of the SYNTHESIS (N); e_off, which dtw_dist does not read, carries n_labels (-1: no labels).
+// values are d(i, j) bit for bit.  pair_plan.h swaps them once (kAlignOp.swapped), so a DtwPair of this file reads: a0, n = first frame
+// and frames of the RECORDING (M); b0, m = first state and states of the SYNTHESIS (N); aux = n_labels (-1: no labels).
 //
 // align_sweep: one workgroup of kAlignThreads threads per pair.  It overwrites d with Q in place, row after row (frame after frame):
 // thread t computes the states t, t + kAlignThreads, ... of frame j from row j - 1, which it reads back from global memory after the
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(kAlignThreads) void align_sweep(const DtwPair* recs
     const int tid = threadIdx.x;
     const DtwPair rec = recs[blockIdx.x];
     const int M = rec.n, N = rec.m;
-    const int nl = labels ? (int)rec.e_off : N;
+    const int nl = labels ? (int)rec.aux : N;
     double* out = terms + (size_t)blockIdx.x * kAlignTerms;
     int64_t* dur = durations ? durations + (int64_t)blockIdx.x * dur_stride : nullptr;
     int32_t* st = state ? state + rec.a0 : nullptr;
@@ -140,104 +140,37 @@ __global__ __launch_bounds__(256) void align_combine(const double* recs, int B, 
     }
 }
 
-// ---- host side: workspace = the pair records, the pairs' result records, then per group of pairs their matrices ----
-// false: a negative length, or a matrix of more than kDtwMaxCells cells
-bool align_layout(int32_t B, const int32_t* a_lens, const int32_t* b_lens, DtwLayout& l) {
-    l = DtwLayout{};
-    size_t sum = 0;
-    for (int b = 0; b < B; ++b) {
-        if (a_lens[b] < 0 || b_lens[b] < 0 || (int64_t)a_lens[b] * b_lens[b] > kDtwMaxCells) return false;
-        const size_t pb = dtw_d_bytes(a_lens[b], b_lens[b]);
-        sum += pb;
-        l.largest = std::max(l.largest, pb);
-    }
-    const size_t nb = (size_t)std::max(B, 1);
-    l.off_terms = align_up(nb * sizeof(DtwPair), 256);
-    l.off_group = align_up(l.off_terms + nb * kAlignTerms * sizeof(double), 256);
-    l.all = l.off_group + sum;
-    l.largest += l.off_group;
-    return true;
-}
-
-size_t align_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap_bytes) {
-    DtwLayout l;
-    if (B < 0 || (B > 0 && (!a_lens || !b_lens)) || !align_layout(B, a_lens, b_lens, l)) return 0;
-    return std::min(l.all, std::max(cap_bytes, l.largest));
-}
+// ---- host side: pair_plan.h's plan, then per group dtw_dist (on the swapped sides) and align_sweep ----
+size_t align_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap) { return pair_workspace_bytes(kAlignOp, B, a_lens, b_lens, cap); }
 
 int al_align(void* stream, const fs2_op_align_args* a) {
-    const char* who = "fs2_op_align";
-    if (!a) return fail(nullptr, FS2_ERR_ARG, "%s: null argument", who);
-    if (a->struct_size != (uint32_t)sizeof(fs2_op_align_args))
-        return fail(nullptr, FS2_ERR_ARG, "%s: fs2_op_align_args.struct_size is %u but this library (ABI %d) expects %zu: the binding does not match include/fs2.h",
-                    who, (unsigned)a->struct_size, FS2_ABI_VERSION, sizeof(fs2_op_align_args));
-    const int32_t B = a->B;
-    if (B < 0 || (B > 0 && (!a->a_starts || !a->a_lens || !a->b_starts || !a->b_lens)))
-        return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d) or null a_starts / a_lens / b_starts / b_lens", who, B);
-    if (a->D < 1 || a->D > kDtwMaxD) return fail(nullptr, FS2_ERR_ARG, "%s: D = %d outside [1, %d]", who, a->D, kDtwMaxD);
+    const char* who = kAlignOp.who;
+    if (const int rc = pair_check_args(kAlignOp, a)) return rc;
     if (a->max_step != 1 && a->max_step != 2) return fail(nullptr, FS2_ERR_ARG, "%s: max_step = %d, not 1 or 2", who, a->max_step);
-    if (a->a_stride < a->D || a->b_stride < a->D)
-        return fail(nullptr, FS2_ERR_ARG, "%s: row stride %lld / %lld below D = %d", who, (long long)a->a_stride, (long long)a->b_stride, a->D);
     if (a->dur_stride < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative dur_stride", who);
+    const int32_t B = a->B;
     if (B > 0 && !a->labels != !a->n_labels) return fail(nullptr, FS2_ERR_ARG, "%s: labels and n_labels must be given together", who);
-    bool any = false;
     for (int b = 0; b < B; ++b) {
-        if (a->a_lens[b] < 0 || a->b_lens[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative length of pair %d", who, b);
-        if (a->a_starts[b] < 0 || a->b_starts[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative start of pair %d", who, b);
-        if ((int64_t)a->a_starts[b] + a->a_lens[b] > INT32_MAX || (int64_t)a->b_starts[b] + a->b_lens[b] > INT32_MAX)
-            return fail(nullptr, FS2_ERR_ARG, "%s: rows of pair %d beyond 2^31 - 1", who, b);
         if (a->labels && (a->n_labels[b] < 0 || a->n_labels[b] > a->dur_stride))
             return fail(nullptr, FS2_ERR_ARG, "%s: n_labels = %d of pair %d outside [0, dur_stride = %lld]", who, a->n_labels[b], b, (long long)a->dur_stride);
         if (!a->labels && a->a_lens[b] > a->dur_stride)
             return fail(nullptr, FS2_ERR_ARG, "%s: dur_stride = %lld below the %d states of pair %d", who, (long long)a->dur_stride, a->a_lens[b], b);
-        any = any || (a->a_lens[b] > 0 && a->b_lens[b] > 0);
     }
-    if (any && (!a->a || !a->b)) return fail(nullptr, FS2_ERR_ARG, "%s: null a / b", who);
-    DtwLayout at;
-    if (!align_layout(B, a->a_lens, a->b_lens, at)) return fail(nullptr, FS2_ERR_ARG, "%s: a matrix of more than 2^40 cells", who);
-    if (B > 0 && !a->workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null workspace", who);
-    if (B > 0 && a->workspace_bytes < at.largest)
-        return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (the largest pair alone)", who, a->workspace_bytes, at.largest);
+    PairPlan p;
+    if (const int rc = pair_plan(kAlignOp, a, a->labels ? a->n_labels : nullptr, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
-    DtwPair* recs = ws ? (DtwPair*)(ws + at.off_recs) : nullptr;            // (B = 0: align_combine reads neither)
-    double* recs_out = ws ? (double*)(ws + at.off_terms) : nullptr;
-    DtwGroups g{B > 0 ? a->workspace_bytes - at.off_group : 0};
-    // the pair records travel as kernel arguments, the sides swapped: no host copy, no synchronisation
-    for (int i = 0; i < B; i += kDtwRecsPerChunk) {
-        DtwPairChunk c{};
-        c.n = std::min(kDtwRecsPerChunk, B - i);
-        c.base = i;
-        for (int k = 0; k < c.n; ++k) {
-            const int32_t n = a->a_lens[i + k], m = a->b_lens[i + k];
-            const size_t pb = dtw_d_bytes(n, m);
-            const int64_t nt = n && m ? dtw_tiles(m, n) : 0;
-            if (g.opens(pb, nt)) g.reset();
-            c.r[k] = DtwPair{a->b_starts[i + k], m, a->a_starts[i + k], n, (int)g.tiles, (int)(((int64_t)n + kDtwTile - 1) / kDtwTile),
-                             (int64_t)(at.off_group + g.used), a->labels ? (int64_t)a->n_labels[i + k] : (int64_t)-1};
-            g.add(pb, nt);
-        }
-        hipLaunchKernelGGL(dtw_upload_pairs, dim3((kDtwRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs);
-    }
+    DtwPair* recs = p.recs(ws);
+    double* recs_out = p.terms(ws);
+    dtw_upload(p, recs, s);
     // one dtw_dist and one align_sweep per group, in stream order: a group's matrices are dead when the next group's are written
-    g.reset();
-    int first = 0;
-    for (int b = 0; b <= B; ++b) {
-        const size_t pb = b < B ? dtw_d_bytes(a->a_lens[b], a->b_lens[b]) : 0;
-        const int64_t nt = b < B && a->a_lens[b] && a->b_lens[b] ? dtw_tiles(a->b_lens[b], a->a_lens[b]) : 0;
-        if (g.count > 0 && (b == B || g.opens(pb, nt))) {
-            if (g.tiles > 0)
-                hipLaunchKernelGGL(dtw_dist, dim3((unsigned)g.tiles), dim3(256), 0, s, recs + first, g.count, a->b, a->a, a->b_stride, a->a_stride, a->D, ws);
-            hipLaunchKernelGGL(align_sweep, dim3((unsigned)g.count), dim3(kAlignThreads), 0, s, recs + first, a->max_step, a->labels, ws,
-                               a->durations ? a->durations + (int64_t)first * a->dur_stride : nullptr, a->dur_stride, a->state,
-                               recs_out + (size_t)first * kAlignTerms);
-            first = b;
-            g.reset();
-        }
-        if (b < B) g.add(pb, nt);
-    }
+    pair_groups(p, [&](const PairGroup& g) {
+        dtw_launch_dist(p, g, recs, ws, s);
+        hipLaunchKernelGGL(align_sweep, dim3((unsigned)g.count), dim3(kAlignThreads), 0, s, recs + g.first, a->max_step, a->labels, ws,
+                           a->durations ? a->durations + (int64_t)g.first * a->dur_stride : nullptr, a->dur_stride, a->state,
+                           recs_out + (size_t)g.first * kAlignTerms);
+    });
     hipLaunchKernelGGL(align_combine, dim3(1), dim3(256), 0, s, recs_out, B, a->terms, a->batch);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FS2_OK;
+    return e == hipSuccess ? FS2_OK : fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
 }

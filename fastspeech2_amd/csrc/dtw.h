@@ -1,7 +1,7 @@
 // Dynamic time warping between pairs of feature sequences of different lengths, with the F0 and energy errors over the aligned frame
 // pairs: the numbers of the FREE-RUNNING validation, behind fs2_op_dtw (include/fs2.h; tests/dtw_oracle.py
 // states the same in numpy).  Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after losses.h (fail(),
-// align_up()).  Plain HIP C++, restricted to what tests/kernel_standin/hip_standin.h provides (the stand-in moves a cell's record
+// align_up()); it includes pair_plan.h, the host side it shares with align.h (DtwPair, the layout, the checks, the groups).  Plain HIP C++, restricted to what tests/kernel_standin/hip_standin.h provides (the stand-in moves a cell's record
 // between lanes in one exchange, hip_standin_record.h beside it, where the device shuffles it field by field).
 //
 // The definition.  d(i, j) = sqrt(sum_k ((double)a[i, k] - (double)b[j, k])^2), k in increasing order, one multiply and one add per
@@ -26,32 +26,21 @@
 //
 // dtw_combine (one workgroup): copies the records out and adds the batch record, term by term, over the pairs in index order.
 
+#include "pair_plan.h"
 constexpr int kDtwCols = 256;             // threads of dtw_sweep = columns of a column block
 constexpr int kDtwLag = 16;               // steps between two barriers of dtw_sweep (= steps a wave runs behind its lower neighbour)
 constexpr int kDtwTile = 64;              // rows and columns of a dtw_dist tile
 constexpr int kDtwKc = 32;                // feature columns staged per pass of dtw_dist
-constexpr int kDtwMaxD = 128;
 constexpr int kDtwTerms = FS2_DTW_TERMS;  // doubles of a record
-constexpr int kDtwRecsPerChunk = 96;      // pair records per upload launch (kernel-argument bytes: 96 * 40 + 8 < 4 KB)
-constexpr int64_t kDtwMaxCells = (int64_t)1 << 40;
 static_assert(FS2_DTW_TERMS == 12, "record layout of include/fs2.h");
 static_assert(kDtwCols == 256 && kDtwTile * kDtwTile == 16 * kDtwCols, "dtw_dist: 256 threads, a 4 x 4 patch each");
-
-struct DtwPair {
-    int a0, n, b0, m;         // first row and rows of the a side, of the b side
-    int tile0, tcols;         // first tile of the pair in its group's dtw_dist grid, tiles per tile row
-    int64_t d_off, e_off;     // byte offsets in the workspace: d [n, m] double; the two edge buffers, [2, n] cells
-};
-struct DtwPairChunk {
-    int n, base;
-    DtwPair r[kDtwRecsPerChunk];
-};
 
 // the record a cell carries (include/fs2.h: indices 2 .. 8 of a pair's record)
 struct DtwCell {
     double cost, se, sp, spv;
     int steps, nv, mis, pad;
 };
+static_assert(sizeof(DtwCell) == kDtwCellBytes && kDtwCols == kPairCols && kDtwTile == kPairTile, "pair_plan.h sizes the matrices and edge buffers");
 
 __global__ void dtw_upload_pairs(DtwPairChunk c, DtwPair* dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -137,7 +126,7 @@ __global__ __launch_bounds__(kDtwCols) void dtw_sweep(const DtwPair* recs, const
     }
     const double inf = __builtin_huge_val();
     const double* d = (const double*)(ws + rec.d_off);
-    DtwCell* edges = (DtwCell*)(ws + rec.e_off);
+    DtwCell* edges = (DtwCell*)(ws + rec.aux);
     const int off = tid + wv * (K - 1);        // this thread handles row s - off at step s
     DtwCell mine = dtw_cell(inf);
     int cb = 0;
@@ -239,123 +228,38 @@ __global__ __launch_bounds__(256) void dtw_combine(const double* recs, int B, do
     }
 }
 
-// ---- host side: workspace = the pair records, the pairs' result records, then per group of pairs their d matrices and edge buffers ----
-struct DtwLayout { size_t off_recs = 0, off_terms = 0, off_group = 0, all = 0, largest = 0; };
-
-inline int64_t dtw_tiles(int32_t n, int32_t m) {
-    return (((int64_t)n + kDtwTile - 1) / kDtwTile) * (((int64_t)m + kDtwTile - 1) / kDtwTile);
+// ---- host side: pair_plan.h's plan, then per group dtw_dist and dtw_sweep ----
+// the pair records travel as kernel arguments: no host copy, no synchronisation
+inline void dtw_upload(const PairPlan& p, DtwPair* recs, hipStream_t s) {
+    pair_chunks(p, [&](const DtwPairChunk& c) { hipLaunchKernelGGL(dtw_upload_pairs, dim3((kDtwRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs); });
 }
-inline size_t dtw_d_bytes(int32_t n, int32_t m) { return n && m ? align_up((size_t)n * (size_t)m * sizeof(double), 256) : 0; }
-inline size_t dtw_pair_bytes(int32_t n, int32_t m) {
-    if (!n || !m) return 0;
-    return dtw_d_bytes(n, m) + (m > kDtwCols ? align_up(2 * (size_t)n * sizeof(DtwCell), 256) : 0);
+inline void dtw_launch_dist(const PairPlan& p, const PairGroup& g, const DtwPair* recs, char* ws, hipStream_t s) {
+    if (g.tiles > 0)
+        hipLaunchKernelGGL(dtw_dist, dim3((unsigned)g.tiles), dim3(256), 0, s, recs + g.first, g.count, p.a, p.b, p.a_stride, p.b_stride, p.D, ws);
 }
 
-// false: a negative length, or a matrix of more than kDtwMaxCells cells
-bool dtw_layout(int32_t B, const int32_t* a_lens, const int32_t* b_lens, DtwLayout& l) {
-    l = DtwLayout{};
-    size_t sum = 0;
-    for (int b = 0; b < B; ++b) {
-        if (a_lens[b] < 0 || b_lens[b] < 0 || (int64_t)a_lens[b] * b_lens[b] > kDtwMaxCells) return false;
-        const size_t pb = dtw_pair_bytes(a_lens[b], b_lens[b]);
-        sum += pb;
-        l.largest = std::max(l.largest, pb);
-    }
-    const size_t nb = (size_t)std::max(B, 1);
-    l.off_terms = align_up(nb * sizeof(DtwPair), 256);
-    l.off_group = align_up(l.off_terms + nb * kDtwTerms * sizeof(double), 256);
-    l.all = l.off_group + sum;
-    l.largest += l.off_group;
-    return true;
-}
-
-size_t dtw_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap_bytes) {
-    DtwLayout l;
-    if (B < 0 || (B > 0 && (!a_lens || !b_lens)) || !dtw_layout(B, a_lens, b_lens, l)) return 0;
-    return std::min(l.all, std::max(cap_bytes, l.largest));
-}
-
-// consecutive pairs share a group while their matrices fit `avail` bytes and their tiles one grid
-struct DtwGroups {
-    size_t avail, used = 0;
-    int64_t tiles = 0;
-    int count = 0;
-    // -> true if the pair opens a new group (the caller closes the previous one first)
-    bool opens(size_t pair_bytes, int64_t pair_tiles) const {
-        return count > 0 && (used + pair_bytes > avail || tiles + pair_tiles > INT32_MAX);
-    }
-    void reset() { used = 0; tiles = 0; count = 0; }
-    void add(size_t pair_bytes, int64_t pair_tiles) { used += pair_bytes; tiles += pair_tiles; ++count; }
-};
+size_t dtw_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap) { return pair_workspace_bytes(kDtwOp, B, a_lens, b_lens, cap); }
 
 int dt_dtw(void* stream, const fs2_op_dtw_args* a) {
-    const char* who = "fs2_op_dtw";
-    if (!a) return fail(nullptr, FS2_ERR_ARG, "%s: null argument", who);
-    if (a->struct_size != (uint32_t)sizeof(fs2_op_dtw_args))
-        return fail(nullptr, FS2_ERR_ARG, "%s: fs2_op_dtw_args.struct_size is %u but this library (ABI %d) expects %zu: the binding does not match include/fs2.h",
-                    who, (unsigned)a->struct_size, FS2_ABI_VERSION, sizeof(fs2_op_dtw_args));
-    const int32_t B = a->B;
-    if (B < 0 || (B > 0 && (!a->a_starts || !a->a_lens || !a->b_starts || !a->b_lens)))
-        return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d) or null a_starts / a_lens / b_starts / b_lens", who, B);
-    if (a->D < 1 || a->D > kDtwMaxD) return fail(nullptr, FS2_ERR_ARG, "%s: D = %d outside [1, %d]", who, a->D, kDtwMaxD);
-    if (a->a_stride < a->D || a->b_stride < a->D)
-        return fail(nullptr, FS2_ERR_ARG, "%s: row stride %lld / %lld below D = %d", who, (long long)a->a_stride, (long long)a->b_stride, a->D);
+    const char* who = kDtwOp.who;
+    if (const int rc = pair_check_args(kDtwOp, a)) return rc;
     if (!a->e_a != !a->e_b) return fail(nullptr, FS2_ERR_ARG, "%s: e_a and e_b must be given together", who);
     if (!a->p_a != !a->p_b) return fail(nullptr, FS2_ERR_ARG, "%s: p_a and p_b must be given together", who);
-    bool any = false;
-    for (int b = 0; b < B; ++b) {
-        if (a->a_lens[b] < 0 || a->b_lens[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative length of pair %d", who, b);
-        if (a->a_starts[b] < 0 || a->b_starts[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative start of pair %d", who, b);
-        if ((int64_t)a->a_starts[b] + a->a_lens[b] > INT32_MAX || (int64_t)a->b_starts[b] + a->b_lens[b] > INT32_MAX)
-            return fail(nullptr, FS2_ERR_ARG, "%s: rows of pair %d beyond 2^31 - 1", who, b);
-        any = any || (a->a_lens[b] > 0 && a->b_lens[b] > 0);
-    }
-    if (any && (!a->a || !a->b)) return fail(nullptr, FS2_ERR_ARG, "%s: null a / b", who);
     if (!a->terms && !a->batch) return FS2_OK;
-    DtwLayout at;
-    if (!dtw_layout(B, a->a_lens, a->b_lens, at)) return fail(nullptr, FS2_ERR_ARG, "%s: a matrix of more than 2^40 cells", who);
-    if (B > 0 && !a->workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null workspace", who);
-    if (B > 0 && a->workspace_bytes < at.largest)
-        return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (the largest pair alone)", who, a->workspace_bytes, at.largest);
+    PairPlan p;
+    if (const int rc = pair_plan(kDtwOp, a, nullptr, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
-    DtwPair* recs = ws ? (DtwPair*)(ws + at.off_recs) : nullptr;            // (B = 0: dtw_combine reads neither)
-    double* recs_out = ws ? (double*)(ws + at.off_terms) : nullptr;
-    DtwGroups g{B > 0 ? a->workspace_bytes - at.off_group : 0};
-    // the pair records travel as kernel arguments: no host copy, no synchronisation
-    for (int i = 0; i < B; i += kDtwRecsPerChunk) {
-        DtwPairChunk c{};
-        c.n = std::min(kDtwRecsPerChunk, B - i);
-        c.base = i;
-        for (int k = 0; k < c.n; ++k) {
-            const int32_t n = a->a_lens[i + k], m = a->b_lens[i + k];
-            const size_t pb = dtw_pair_bytes(n, m);
-            const int64_t nt = n && m ? dtw_tiles(n, m) : 0;
-            if (g.opens(pb, nt)) g.reset();
-            c.r[k] = DtwPair{a->a_starts[i + k], n, a->b_starts[i + k], m, (int)g.tiles, (int)(((int64_t)m + kDtwTile - 1) / kDtwTile),
-                             (int64_t)(at.off_group + g.used), (int64_t)(at.off_group + g.used + dtw_d_bytes(n, m))};
-            g.add(pb, nt);
-        }
-        hipLaunchKernelGGL(dtw_upload_pairs, dim3((kDtwRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs);
-    }
+    DtwPair* recs = p.recs(ws);
+    double* recs_out = p.terms(ws);
+    dtw_upload(p, recs, s);
     // one dtw_dist and one dtw_sweep per group, in stream order: a group's matrices are dead when the next group's are written
-    g.reset();
-    int first = 0;
-    for (int b = 0; b <= B; ++b) {
-        const size_t pb = b < B ? dtw_pair_bytes(a->a_lens[b], a->b_lens[b]) : 0;
-        const int64_t nt = b < B && a->a_lens[b] && a->b_lens[b] ? dtw_tiles(a->a_lens[b], a->b_lens[b]) : 0;
-        if (g.count > 0 && (b == B || g.opens(pb, nt))) {
-            if (g.tiles > 0)
-                hipLaunchKernelGGL(dtw_dist, dim3((unsigned)g.tiles), dim3(256), 0, s, recs + first, g.count, a->a, a->b, a->a_stride, a->b_stride, a->D, ws);
-            hipLaunchKernelGGL(dtw_sweep, dim3((unsigned)g.count), dim3(kDtwCols), 0, s, recs + first, a->e_a, a->e_b, a->p_a, a->p_b, ws,
-                               recs_out + (size_t)first * kDtwTerms);
-            first = b;
-            g.reset();
-        }
-        if (b < B) g.add(pb, nt);
-    }
-    hipLaunchKernelGGL(dtw_combine, dim3(1), dim3(256), 0, s, recs_out, B, a->terms, a->batch);
+    pair_groups(p, [&](const PairGroup& g) {
+        dtw_launch_dist(p, g, recs, ws, s);
+        hipLaunchKernelGGL(dtw_sweep, dim3((unsigned)g.count), dim3(kDtwCols), 0, s, recs + g.first, a->e_a, a->e_b, a->p_a, a->p_b, ws,
+                           recs_out + (size_t)g.first * kDtwTerms);
+    });
+    hipLaunchKernelGGL(dtw_combine, dim3(1), dim3(256), 0, s, recs_out, a->B, a->terms, a->batch);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FS2_OK;
+    return e == hipSuccess ? FS2_OK : fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
 }

@@ -14,12 +14,13 @@ stride or on the workspace.  There is no CPU fallback: CPU tensors raise.
 """
 import ctypes as C
 import math
+import types
 
 import numpy as np
 import torch
 
 from . import _lib
-from .losses import _rows
+from .losses import DeviceRecords, _rows
 from .vocoder import _i32, _lens, _require_cuda, _stream
 
 TERMS = _lib.DTW_TERMS
@@ -28,37 +29,18 @@ N_PRED, N_REF, STEPS, COST, ENERGY_L1, PITCH_L1, VOICED, PITCH_L1_VOICED, VUV = 
 FEATURES = ("mel", "mcep")
 
 
-class DtwTerms:
+class DtwTerms(DeviceRecords):
     """The per-pair records ``terms`` [B, 12] and their batch record ``batch`` [12] (float64 numpy; include/fs2.h lists the
     indices).  After ``mel_dtw(..., sync=False)`` both are still on the device; the first read of either fetches them with one
     copy, which waits for the stream.  ``features`` ("mel" / "mcep") and ``D`` (the width of the compared vectors) say what the
     cost is a distance of."""
+    TERMS = TERMS
 
     def __init__(self, terms, batch, features, D, _device=None):
         if features not in FEATURES:
             raise ValueError("features must be one of %s, got %r" % (FEATURES, features))
-        self._terms = None if terms is None else np.asarray(terms, np.float64).reshape(-1, TERMS)
-        self._batch = None if batch is None else np.asarray(batch, np.float64).reshape(TERMS)
-        self._device = _device          # [B + 1, 12] float64 on the device: the records, then the batch record
+        super().__init__(terms, batch, _device)
         self.features, self.D = features, D
-
-    def _fetch(self):
-        if self._device is not None:
-            host = self._device.cpu().numpy()
-            self._terms, self._batch, self._device = host[:-1], host[-1], None
-
-    @property
-    def terms(self):
-        self._fetch()
-        return self._terms
-
-    @property
-    def batch(self):
-        self._fetch()
-        return self._batch
-
-    def __len__(self):
-        return int(self._device.shape[0] - 1 if self._device is not None else self._terms.shape[0])
 
     def per_utterance(self):
         """Per pair, as a dict of float64 arrays [B]: ``n_pred``, ``n_ref``, ``steps`` (counts), ``distance`` = cost / steps,
@@ -170,6 +152,43 @@ def _side(x, lens, name, tracks):
     return x, int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1]), starts, out
 
 
+def _pairs(cls, query, a, a_lens, b, b_lens, a_tracks, b_tracks, features, n_mcep, workspace_cap):
+    """What ``mel_dtw`` and ``monotonic_align`` do before their call: the checks of the lengths and the two sides, the mcep projection,
+    the layout of each side with its tracks (``_side``), the host int32 arrays ``lens`` = (a_starts, a_lens, b_starts, b_lens) as
+    pointers (``keep`` holds their memory), the workspace ``ws`` of ``ws_bytes`` = ``query`` (the name of the operator's
+    fs2_op_*_workspace_bytes) and the device records of ``cls`` (``rec``, ``terms_p``, ``batch_p``) -> a namespace of all that."""
+    al, bl = _lens(a_lens, name="a_lens"), _lens(b_lens, name="b_lens")
+    B = int(al.numel())
+    if bl.numel() != B:
+        raise ValueError("a_lens has %d entries, b_lens %d" % (B, bl.numel()))
+    _require_cuda(a, "a")
+    _require_cuda(b, "b")
+    if a.device != b.device:
+        raise ValueError("a is on %s, b on %s" % (a.device, b.device))
+    if a.shape[-1] != b.shape[-1]:
+        raise ValueError("a has %d features per frame, b %d" % (a.shape[-1], b.shape[-1]))
+    if features == "mcep":
+        a, b = mcep(a.float(), n_mcep), mcep(b.float(), n_mcep)
+    D = int(a.shape[-1])
+    if not 1 <= D <= 128:
+        raise ValueError("D = %d outside [1, 128]" % D)
+    dev = a.device
+    a, a_stride, a_starts, a_tracks = _side(a, al, "a", a_tracks)
+    b, b_stride, b_starts, b_tracks = _side(b, bl, "b", b_tracks)
+    if B and max(int((a_starts + al.numpy()).max()), int((b_starts + bl.numpy()).max())) > 2 ** 31 - 1:
+        raise ValueError("rows beyond 2^31 - 1")
+    keep = [_i32(x) for x in (a_starts, al.numpy(), b_starts, bl.numpy())]
+    lens = tuple(p for _, p in keep)
+    ws_bytes = int(getattr(_lib.lib(), query)(B, lens[1], lens[3], int(workspace_cap))) if B else 0
+    if B and not ws_bytes:
+        raise ValueError("a pair of more than 2^40 cells")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if B else None
+    rec, terms_p, batch_p = cls._on_device(B, dev)
+    return types.SimpleNamespace(B=B, D=D, dev=dev, al=al, a=a, b=b, a_stride=a_stride, b_stride=b_stride, a_starts=a_starts, b_starts=b_starts,
+                                 a_tracks=a_tracks, b_tracks=b_tracks, keep=keep, lens=lens, ws=ws, ws_bytes=ws_bytes, rec=rec, terms_p=terms_p,
+                                 batch_p=batch_p)
+
+
 def mel_dtw(a, a_lens, b, b_lens, e=None, p=None, features="mel", n_mcep=13, workspace_cap=256 << 20, sync=True):
     """DTW between B pairs of sequences -> :class:`DtwTerms`.
 
@@ -187,45 +206,16 @@ def mel_dtw(a, a_lens, b, b_lens, e=None, p=None, features="mel", n_mcep=13, wor
             raise ValueError("%s must be a (pred, ref) pair: a track is given for both sides or for neither" % n)
     e = None if e is None or e[0] is None else e
     p = None if p is None or p[0] is None else p
-    al, bl = _lens(a_lens, name="a_lens"), _lens(b_lens, name="b_lens")
-    B = int(al.numel())
-    if bl.numel() != B:
-        raise ValueError("a_lens has %d entries, b_lens %d" % (B, bl.numel()))
-    _require_cuda(a, "a")
-    _require_cuda(b, "b")
-    if a.device != b.device:
-        raise ValueError("a is on %s, b on %s" % (a.device, b.device))
-    if a.shape[-1] != b.shape[-1]:
-        raise ValueError("a has %d features per frame, b %d" % (a.shape[-1], b.shape[-1]))
-    if features == "mcep":
-        a, b = mcep(a.float(), n_mcep), mcep(b.float(), n_mcep)
-    D = int(a.shape[-1])
-    if not 1 <= D <= 128:
-        raise ValueError("D = %d outside [1, 128]" % D)
-    dev = a.device
-    a, a_stride, a_starts, (e_a, p_a) = _side(a, al, "a", ((e[0] if e else None, "e[0]"), (p[0] if p else None, "p[0]")))
-    b, b_stride, b_starts, (e_b, p_b) = _side(b, bl, "b", ((e[1] if e else None, "e[1]"), (p[1] if p else None, "p[1]")))
+    q = _pairs(DtwTerms, "fs2_op_dtw_workspace_bytes", a, a_lens, b, b_lens, ((e[0] if e else None, "e[0]"), (p[0] if p else None, "p[0]")),
+               ((e[1] if e else None, "e[1]"), (p[1] if p else None, "p[1]")), features, n_mcep, workspace_cap)
+    (e_a, p_a), (e_b, p_b) = q.a_tracks, q.b_tracks
     if e_a is not None and 0 in (e_a.numel(), e_b.numel()):         # a side without a frame: every pair is empty, and an empty tensor has no address
         e_a = e_b = None
     if p_a is not None and 0 in (p_a.numel(), p_b.numel()):
         p_a = p_b = None
-    if B and max(int((a_starts + al.numpy()).max()), int((b_starts + bl.numpy()).max())) > 2 ** 31 - 1:
-        raise ValueError("rows beyond 2^31 - 1")
-
-    lib = _lib.lib()
-    keep = [_i32(x) for x in (a_starts, al.numpy(), b_starts, bl.numpy())]
-    (_, as_p), (_, al_p), (_, bs_p), (_, bl_p) = keep
     ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        ws_bytes = int(lib.fs2_op_dtw_workspace_bytes(B, al_p, bl_p, int(workspace_cap))) if B else 0
-        if B and not ws_bytes:
-            raise ValueError("a pair of more than 2^40 cells")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if B else None
-        rec = torch.empty(B + 1, TERMS, dtype=torch.float64, device=dev)
-        args = _lib.OpDtwArgs(B, D, a_stride, b_stride, ptr(a), ptr(b), ptr(e_a), ptr(e_b), ptr(p_a), ptr(p_b),
-                              as_p, al_p, bs_p, bl_p, ptr(ws), ws_bytes, rec.data_ptr() if B else None, rec[B].data_ptr())
-        _lib.check(lib.fs2_op_dtw(_stream(dev), C.byref(args)))
-    out = DtwTerms(None, None, features, D, _device=rec)
-    if sync:
-        out._fetch()
-    return out
+    with torch.cuda.device(q.dev):
+        args = _lib.OpDtwArgs(q.B, q.D, q.a_stride, q.b_stride, ptr(q.a), ptr(q.b), ptr(e_a), ptr(e_b), ptr(p_a), ptr(p_b), *q.lens,
+                              ptr(q.ws), q.ws_bytes, q.terms_p, q.batch_p)
+        _lib.check(_lib.lib().fs2_op_dtw(_stream(q.dev), C.byref(args)))
+    return DtwTerms(None, None, features, q.D, _device=q.rec)._synced(sync)

@@ -28,17 +28,23 @@ ILEN, OLEN, PAD_TOKENS, PAD_FRAMES, BEFORE_L1, AFTER_L1, DUR_SQ, ENERGY_SQ, PITC
 PAD_BEFORE_L1, PAD_AFTER_L1, PAD_DUR_SQ, PAD_ENERGY_SQ, PAD_PITCH_SQ = range(12, 17)
 
 
-class LossTerms:
-    """The per-utterance records ``terms`` [B, 20] and their batch record ``batch`` [20] (float64 numpy; include/fs2.h lists the
-    indices).  After ``loss_terms(..., sync=False)`` both are still on the device; the first read of either fetches them with one
-    copy, which waits for the stream.  ``pads`` tells whether the pad sums (indices 12 .. 16) were built; ``odim`` is the number of
-    mel bins behind the two mel sums."""
+class DeviceRecords:
+    """The records of a batched operator, ``terms`` [B, TERMS], and their batch record ``batch`` [TERMS] (float64 numpy): the base of
+    :class:`LossTerms`, ``dtw.DtwTerms`` and ``align.Alignment``, which set ``TERMS``.  An operator leaves them on the device as ONE
+    tensor ``_device`` [B + 1, TERMS] float64 -- the records, then the batch record -- and the first read of either fetches them with one
+    copy, which waits for the stream."""
+    TERMS = None
 
-    def __init__(self, terms, batch, pads, odim, _device=None):
-        self._terms = None if terms is None else np.asarray(terms, np.float64).reshape(-1, TERMS)
-        self._batch = None if batch is None else np.asarray(batch, np.float64).reshape(TERMS)
-        self._device = _device          # [B + 1, 20] float64 on the device: the records, then the batch record
-        self.pads, self.odim = bool(pads), odim
+    def __init__(self, terms, batch, _device=None):
+        self._terms = None if terms is None else np.asarray(terms, np.float64).reshape(-1, self.TERMS)
+        self._batch = None if batch is None else np.asarray(batch, np.float64).reshape(self.TERMS)
+        self._device = _device
+
+    @classmethod
+    def _on_device(cls, B, dev):
+        """-> (an empty ``_device`` tensor for B records, the address of its records -- None for B = 0 --, that of its batch record)"""
+        rec = torch.empty(B + 1, cls.TERMS, dtype=torch.float64, device=dev)
+        return rec, rec.data_ptr() if B else None, rec[B].data_ptr()
 
     def _fetch(self):
         if self._device is not None:
@@ -57,6 +63,23 @@ class LossTerms:
 
     def __len__(self):
         return int(self._device.shape[0] - 1 if self._device is not None else self._terms.shape[0])
+
+    def _synced(self, sync):
+        if sync:
+            self._fetch()
+        return self
+
+
+class LossTerms(DeviceRecords):
+    """The per-utterance records ``terms`` [B, 20] and their batch record ``batch`` [20] (float64 numpy; include/fs2.h lists the
+    indices).  After ``loss_terms(..., sync=False)`` both are still on the device; the first read of either fetches them with one
+    copy, which waits for the stream.  ``pads`` tells whether the pad sums (indices 12 .. 16) were built; ``odim`` is the number of
+    mel bins behind the two mel sums."""
+    TERMS = TERMS
+
+    def __init__(self, terms, batch, pads, odim, _device=None):
+        super().__init__(terms, batch, _device)
+        self.pads, self.odim = bool(pads), odim
 
     def report(self, use_masking=True, use_weighted_masking=False, odim=None):
         """The reference's seven ``(name, value)`` pairs (fastspeech.py:326-334), in its order, in float64 from the batch record.
@@ -205,12 +228,9 @@ def loss_terms(before, after, ys, d_outs, ds, e_outs, es, p_outs, ps, ilens, ole
     with torch.cuda.device(dev):
         ws_bytes = int(lib.fs2_op_loss_workspace_bytes(B, ol_p)) if B else 0
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if B else None
-        rec = torch.empty(B + 1, TERMS, dtype=torch.float64, device=dev)
+        rec, terms_p, batch_p = LossTerms._on_device(B, dev)
         args = _lib.OpLossArgs(B, odim or 0, Tmax, Lmax, int(bool(pads)), psf, ysf, pst, dst, tsf,
                                ptr(before), ptr(after), ptr(ys), ptr(d_outs), ptr(ds), ptr(e_outs), ptr(es), ptr(p_outs), ptr(ps),
-                               il_p, ol_p, ptr(ws), ws_bytes, rec.data_ptr() if B else None, rec[B].data_ptr())
+                               il_p, ol_p, ptr(ws), ws_bytes, terms_p, batch_p)
         _lib.check(lib.fs2_op_loss_terms(_stream(dev), C.byref(args)))
-    out = LossTerms(None, None, pads, odim, _device=rec)
-    if sync:
-        out._fetch()
-    return out
+    return LossTerms(None, None, pads, odim, _device=rec)._synced(sync)

@@ -4,9 +4,10 @@ align_combine) beside fs2_op_dtw on the SAME 64 pairs.  Prints one JSON line.
 Workload: 64 pairs of 80-dimensional frames; M = the c3 batch's recorded lengths, N = M scaled by a factor in [0.85, 1.15] (what a
 free-running synthesis of the same text gives); b is a time-warped noisy copy of a, so every pair has an alignment.  Both ops are
 timed with device events around --calls calls, in alternating rounds after a warm-up round; medians and max - min spreads over the
-rounds are reported.  The walk back is part of the align_sweep launch, so it has no time of its own here.
+rounds are reported.  The walk back is part of the align_sweep launch, so it has no time of its own here.  ``--root DIR`` measures the
+package of another checkout instead (the parent commit's, built there).
 
-Usage:  python tools/time_align.py [--rounds 5] [--calls 10] [--max-step 2]
+Usage:  python tools/time_align.py [--rounds 5] [--calls 10] [--max-step 2] [--root DIR]
 """
 import argparse
 import ctypes as C
@@ -17,16 +18,15 @@ import sys
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--max-step", type=int, default=2)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
     assert torch.cuda.is_available(), "time_align needs a GPU"
     from fastspeech2_amd import _lib
     from fastspeech2_amd.synthetic import make_batch

@@ -11,9 +11,10 @@ synchronisations per round, after a warm-up round): "dtw", fs2_op_dtw alone on r
 "dtw_cap", the same through a workspace of --cap-mb MB (groups of pairs); "forward", model.inference_batch of the same batch
 (synchronous: it reads the frame counts back); "torch_one_pair", the torch loop for the pair of median cell count (--torch-calls
 calls per round: it is slow).  Medians and max - min spreads over the rounds are reported.  The kernels' own durations come from a
-run of their own: rocprofv3 --kernel-trace --stats -- python tools/time_dtw.py --only-op.
+run of their own: rocprofv3 --kernel-trace --stats -- python tools/time_dtw.py --only-op.  ``--root DIR`` measures the package of
+another checkout instead (the parent commit's, built there).
 
-Usage:  python tools/time_dtw.py [--rounds 5] [--calls 10] [--torch-calls 1] [--cap-mb 32] [--only-op]
+Usage:  python tools/time_dtw.py [--rounds 5] [--calls 10] [--torch-calls 1] [--cap-mb 32] [--only-op] [--root DIR]
 """
 import argparse
 import ctypes as C
@@ -24,9 +25,6 @@ import time
 
 import numpy as np
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def torch_dtw_cost(a, b):
@@ -49,7 +47,9 @@ def main():
     ap.add_argument("--torch-calls", type=int, default=1)
     ap.add_argument("--cap-mb", type=int, default=32)
     ap.add_argument("--only-op", action="store_true", help="time fs2_op_dtw only (for a kernel-trace run)")
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
     assert torch.cuda.is_available(), "time_dtw needs a GPU"
     from fastspeech2_amd import FeedForwardTransformer, default_hparams, N_PHONEME_SYMBOLS, _lib
     from fastspeech2_amd.synthetic import ljspeech_durations, portable_state_dict, make_batch
