@@ -28,6 +28,7 @@
 #include "gemm_plan.h"
 #include "gemm_planes.h"
 #include "gemm_row4.h"
+#include "model_launches.h"
 #include "gemm_mx.h"
 #include "gemm_f32.h"
 #include "griffin_lim.h"
@@ -39,59 +40,6 @@ using namespace fs2;
 namespace {
 
 std::string g_create_error;
-
-struct Gemm {          // one repacked Linear / Conv1d
-    float* w = nullptr;      // [Npad][ktaps][Cpad]
-    void* wb = nullptr;      // split-bf16 image [Npad][ktaps][Cpad/32][hi 32 | lo 32]
-    void* wf = nullptr;      // the same image in fp16 (FFN w_1 only): operand of the two- / one-term arithmetic modes
-    void* wm = nullptr;      // weight image of the "mx" mode (gemm_mx.h; FFN w_1 convolutions with C % 128 == 0 and N % 128 == 0) ...
-    int kw = 0;              // ... and the exponent of its static scale: |w| 2^kw <= 448
-    void* wm4 = nullptr;     // weight image of the "mx4" mode (gemm_planes.h ARITH = 3: both cross terms in e2m1) ...
-    unsigned char* ws4 = nullptr;      // ... and its scale image: one E8M0 byte per 16-channel block of every weight row (gemm_mx.h: mx4_scale_image_bytes)
-    float* bias = nullptr;   // [N] or null
-    int N = 0, C = 0, Cpad = 0, ktaps = 1;
-};
-// Output rows [n0, N) of a repacked layer as a layer of its own (n0 a multiple of 128: whole column tiles).  The one place besides the repack kernels that knows the
-// row strides of their images: fp32 [Npad][ktaps][Cpad] (elementwise.h: repack_weight), split-bf16 [Npad][Cpad / 32][ktaps][64] (gemm_bf16.h: repack_weight_bf16).
-// The fp16 / mx images are not carried over.
-inline Gemm gemm_rows_from(const Gemm& g, int n0) {
-    Gemm r;
-    r.N = g.N - n0; r.C = g.C; r.Cpad = g.Cpad; r.ktaps = g.ktaps;
-    r.w = g.w + (size_t)n0 * g.ktaps * g.Cpad;
-    r.wb = reinterpret_cast<__bf16*>(g.wb) + (size_t)n0 * (g.Cpad / 32) * g.ktaps * 64;
-    r.bias = g.bias ? g.bias + n0 : nullptr;
-    return r;
-}
-struct Layer {
-    Gemm qkv, out, w1, w2;
-    Gemm cat_x, cat_a;       // concat_after: concat_linear [D, 2D] split into its x half (carries the bias) and its attention half
-    float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-    int ka = 0;              // "mx" mode: exponent of the static scale of the FFN input (the LN1 output): |x| 2^ka <= 448 from the bound
-                             // |LN(x)_c| <= sqrt(D) |gamma_c| + |beta_c|
-    int kh = 0;              // ... and of the FFN hidden layer (w_2's input in the mx arithmetic, gemm_row4.h ARITH = 2): |h| 2^kh <= 448 from the bound
-                             // |h_n| <= sum_{c,tap} |w_1[n,c,tap]| xmax + |b_1[n]|, xmax = the LayerNorm bound above (w2.wm != nullptr: the mode exists)
-};
-struct Predictor {
-    std::vector<Gemm> conv;
-    std::vector<float*> lng, lnb;
-    float *lin_w = nullptr, *lin_b = nullptr;
-};
-// The energy and the pitch predictor read the same input (reference fastspeech.py:194-196,214-217): in the bf16 modes they run as ONE launch per
-// layer.  Layer 0: the two convolutions stacked along N (2 x chans outputs over one A tile).  Layer 1: a grouped convolution (group g
-// contracts the channels of predictor g's hidden layer) with both scalar heads.  Parameters stacked along N in the order energy | pitch.
-struct FusedPredictors {
-    bool ok = false;
-    Gemm c0, c1;
-    float *ln0g = nullptr, *ln0b = nullptr, *ln1g = nullptr, *ln1b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
-};
-struct Stack {
-    std::vector<Layer> layers;
-    float* pe = nullptr; int pe_rows = 0;
-    float* alpha = nullptr;
-    int dk = 0, Dp = 0;                             // true head dim; attention width heads x padded head dim (= D when dk is a kernel size)
-    bool pre_ln = false, concat = false;            // encoder.py:53-71: normalize_before / concat_after
-    float *after_g = nullptr, *after_b = nullptr;   // after_norm (applied only when pre_ln, encoder.py:201-202)
-};
 
 constexpr int kXcds = 8;      // MI355X: 8 accelerator dies, workgroups of a launch are dealt to them round-robin
 
@@ -200,21 +148,6 @@ Options& opts() {
     }();
     return o;
 }
-
-// The attention kernels exist for head dims 64 / 128 / 192 / 256.  Any other adim / aheads the reference accepts (core/attention.py:18-20)
-// runs with the head dim zero-padded to the next of these: the Q / K / V projection weights get zero rows, the output projection zero
-// columns, at load time, so scores and context are unchanged (the softmax scale keeps the true d_k); the attention buffers are
-// heads x padded wide.  0: unsupported (d_k > 256).
-inline int padded_head_dim(int dk) { return dk <= 64 ? 64 : (dk <= 128 ? 128 : (dk <= 192 ? 192 : (dk <= 256 ? 256 : 0))); }
-inline int att_width(int D, int heads) { return heads * padded_head_dim(D / heads); }
-
-// Mixed modes: everything as bf16x3 except the FFN convolution w_1, which runs on fp16 operands with 2 or 1 MFMA per fragment pair.
-inline int base_precision(int p) { return (p == FS2_PREC_MIX_F16X2 || p == FS2_PREC_MIX_F16X1 || p == FS2_PREC_MIX_MX || p == FS2_PREC_MIX_MX4) ? FS2_PREC_BF16X3 : p; }
-constexpr int kFfnMx = 9;      // value of "ffn_terms" that selects the fp16 + block-scaled-fp8 arithmetic (gemm_mx.h)
-constexpr int kPostKa = 8;     // static scale exponent of the Postnet's mx operands: tanh outputs, |x| <= 1 -> 2^8 = 256 <= 448
-constexpr int kFfnMx4 = 10;    // ... the fp16 + block-scaled-fp4 arithmetic where the planes-only regime offers it (gemm_planes.h ARITH = 3), kFfnMx's elsewhere
-inline int ffn_f16_terms(int p) { return p == FS2_PREC_MIX_F16X2 ? 2 : (p == FS2_PREC_MIX_F16X1 ? 1 : (p == FS2_PREC_MIX_MX ? kFfnMx : (p == FS2_PREC_MIX_MX4 ? kFfnMx4 : 0))); }
-inline int scale_byte4(int e) { const int b = std::min(std::max(e, 1), 254); return b * 0x01010101; }
 
 // max over the rows n of a [N][K] weight of (sum_k |w[n][k]|) xmax + |b[n]|: the a-priori bound of relu(w x + b) for |x| <= xmax (weight-load time only)
 __global__ void row_l1_bound_kernel(const float* w, const float* b, int N, int K, float xmax, unsigned* out) {
@@ -384,7 +317,8 @@ inline void allow_lds(const void* kernel, size_t bytes, LdsAttr& st) {
 
 // ------------------------------------------------------------------ kernel launchers
 static_assert(kPlanErrArg == FS2_ERR_ARG && kPlanErrHip == FS2_ERR_HIP && kPlanErrState == FS2_ERR_STATE && kPlanErrUnsupported == FS2_ERR_UNSUPPORTED &&
-              kPlanFp32 == FS2_PREC_FP32 && kPlanBf16x3 == FS2_PREC_BF16X3 && kPlanMaxHalo == kMaxHalo && kPlanBN == kB16BN, "gemm_plan.h restates these");
+              kPlanFp32 == FS2_PREC_FP32 && kPlanBf16x3 == FS2_PREC_BF16X3 && kPlanMaxHalo == kMaxHalo && kPlanBN == kB16BN && kPrecMixF16x2 == FS2_PREC_MIX_F16X2 &&
+              kPrecMixF16x1 == FS2_PREC_MIX_F16X1 && kPrecMixMx == FS2_PREC_MIX_MX && kPrecMixMx4 == FS2_PREC_MIX_MX4, "gemm_plan.h and model_launches.h restate these");
 
 // One launcher for every GEMM kernel, keyed by the kernel: it owns the per-(kernel, device) flag of the LDS attribute.
 template <auto K>
@@ -503,8 +437,7 @@ hipError_t run_plan(hipStream_t s, const GemmPlan& p, const GemmArgs& t) {
 // Plan (gemm_plan.h: which kernel, which tile, split-K, where the rows go), then execute: build the A planes if the producer did not, launch the
 // kernel on the arguments the plan implies, run ln_rows where the epilogue is a pass of its own.
 int launch_gemm(fs2_handle* h, hipStream_t s, const char* name, GemmArgs a, int precision = FS2_PREC_FP32) {
-    if (h && !a.kpart && h->kp) { a.kpart = h->kp; a.kpart_cap = h->kp_cap; a.ksplit = 3; }      // (a.ksplit: how many partial buffers the plan may use)
-    if (h && !a.regime_rows) a.regime_rows = h->cur_regime;
+    if (h) call_defaults(a, h->kp, h->kp_cap, h->cur_regime);
     const GemmPlan p = plan_gemm(a, precision, opts());
     if (p.err) return fail(h, p.err, p.msg, name, p.m0, p.m1);
     a.ksplit = 1;
@@ -545,27 +478,6 @@ int launch_gemm(fs2_handle* h, hipStream_t s, const char* name, GemmArgs a, int 
     }
     if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
     return FS2_OK;
-}
-
-// Will the decoder's LayerNorm-fused k = 1 launches (the input layer, out-proj + LN1, FFN2 + LN2) run on gemm_row4_bf16 -- i.e. do its activations travel
-// as planes ONLY?  Asked of the plan, once per fs2_decode, for these launches in their planes-only form; anything the plan would not put there leaves the
-// decoder on the fp32-rows form.  (run_stack_general, the stack of the pre-LN / concat variants, has no planes-only form.)
-bool planes_only_regime(const fs2_handle* h, int prec, int R, int regime_rows) {
-    const fs2_config& c = h->cfg;
-    if (h->dec.pre_ln || h->dec.concat || h->dec.layers.empty()) return false;
-    const Layer& ly = h->dec.layers[0];
-    const PlaneDims in = c.decoder_input_layer ? PlaneDims{h->dec_in.C, h->dec_in.Cpad} : PlaneDims{0, 0};
-    return planes_only_plan(in, {ly.out.C, ly.out.Cpad}, {ly.w2.C, ly.w2.Cpad}, c.ddim, R, regime_rows, prec, opts());
-}
-// Does FFN2 + LN2 run in gemm_row4_bf16's mx arithmetic if it is offered mx planes?  (run_stack asks before it decides the format FFN1 leaves the hidden layer in.)
-bool ffn2_on_row4_mx(GemmArgs a) { a.mx = 1; const GemmPlan p = plan_gemm(a, FS2_PREC_BF16X3, opts()); return p.kernel == GemmKernel::Row4 && p.arith == 2; }
-
-GemmArgs gemm_args(const Gemm& g, const float* X, int ldx, int R, const int* row_pos, float* Y, int ldy) {
-    GemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.X = X; a.ldx = ldx; a.C = g.C; a.W = g.w; a.Cpad = g.Cpad; a.ktaps = g.ktaps; a.N = g.N; a.R = R;
-    a.row_pos = row_pos; a.bias = g.bias; a.Y = Y; a.ldy = ldy; a.x_scale = 1.f; a.ln_eps = 1e-5f; a.Wb = g.wb;
-    return a;
 }
 
 int launch_attention(fs2_handle* h, hipStream_t s, const char* name, const float* qkv, float* ctx, int D, int heads,
@@ -776,258 +688,75 @@ int device_layout(fs2_handle* h, hipStream_t s, const HostLayout& L, int* dev, D
     return FS2_OK;
 }
 
-// ------------------------------------------------------------------ FFT block stack
-// x0p / x1p: split-bf16 planes of x0 / x1 (gemm_planes.h); xps: planes scratch for activations produced without planes.
-// In the bf16 modes the attention context and the FFN hidden layer exist ONLY as planes, in the ctx / hid storage.
-struct StackBufs { float *x0, *x1, *qkv, *ctx, *hid; __bf16 *qkh, *qkl, *vth, *vtl; void *x0p, *x1p, *xps; unsigned char* xs4 = nullptr; };      // xs4: row-scale bytes of x1p in the mx4 format
-
-int run_stack_general(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, int D, int heads, int R, const HostLayout& L, const DevLayout& dl,
-                      int mask_q, const StackBufs& b, int prec, bool x0p_ready, int regime_rows);
-
-// x0 holds the input; returns the buffer holding the output (x0 again).
-// po: the planes-only residual stream (gemm_row4.h: RES; fs2_decode decides with planes_only_regime): the LayerNorm-fused launches write no fp32
-// rows and take their residual from the planes of the producing launch -- x0 / x1 are then never written: the output is b.x0p.
-int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, int D, int heads, int R,
-              const HostLayout& L, const DevLayout& dl, int mask_q, const StackBufs& b, int prec, bool x0p_ready = false, bool allow_splitk = false,
-              int regime_rows = 0, int ffn_terms = 0, bool po = false) {
-    if (st.pre_ln || st.concat) return run_stack_general(h, s, tag, st, D, heads, R, L, dl, mask_q, b, prec, x0p_ready, regime_rows);
-    const int Dp = st.Dp;      // attention width (= D unless the head dim is padded)
-    char nm[96];
-    double att_flops = 0;
-    for (size_t i = 0; i < L.klen.size(); ++i) att_flops += 4.0 * D * (double)L.klen[i] * std::min(L.len[i], mask_q ? L.klen[i] : L.len[i]);
-    // bf16 modes: activations travel between the GEMMs as split-bf16 planes (no conversion work inside the MFMA loops)
-    const bool pl = prec != FS2_PREC_FP32;
-    void* ctxp = pl ? (void*)b.ctx : nullptr;
-    void* hidp = pl ? (void*)b.hid : nullptr;
-    if (pl && !x0p_ready) {
-        snprintf(nm, sizeof nm, "%s.in.planes", tag);
-        Scope sc(h, s, nm, 0.0, 8.0 * R * D);
-        const int64_t n = (int64_t)R * (D / 4);
-        hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.x0, D, D, R, D / 32, b.x0p);
-    }
-    for (size_t li = 0; li < st.layers.size(); ++li) {
-        const Layer& ly = st.layers[li];
-        int rc;
-        snprintf(nm, sizeof nm, "%s.qkv", tag);
-        GemmArgs a = gemm_args(ly.qkv, b.x0, D, R, dl.row_pos, b.qkv, 3 * Dp);
-        a.Rp = dl.dims; a.regime_rows = regime_rows;
-        if (pl) a.Xp = b.x0p;
-        const bool fused_split = prec != FS2_PREC_FP32 && Dp % kB16BN == 0;
-        if (fused_split) {   // bf16 attention operands straight from the GEMM epilogue (no fp32 QKV round trip)
-            a.Y = nullptr; a.qk_hi = b.qkh; a.qk_lo = b.qkl; a.vt_hi = b.vth; a.vt_lo = b.vtl; a.att_D = Dp; a.Rvt = L.Rpad;
-            a.q_scale = 1.4426950408889634f / sqrtf((float)st.dk);
-        }
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        snprintf(nm, sizeof nm, "%s.attn", tag);
-        if (prec == FS2_PREC_FP32) rc = launch_attention(h, s, nm, b.qkv, b.ctx, Dp, heads, dl, L.nwork(), mask_q, att_flops, st.dk);
-        else rc = launch_attention_b16(h, s, nm, fused_split ? nullptr : b.qkv, pl ? nullptr : b.ctx, Dp, heads, R, L.Rpad, dl, L.nwork(), mask_q, att_flops, prec, b.qkh, b.qkl, b.vth, b.vtl, ctxp, st.dk);
-        if (rc) return rc;
-        snprintf(nm, sizeof nm, "%s.out_ln", tag);
-        a = gemm_args(ly.out, b.ctx, Dp, R, dl.row_pos, po ? nullptr : b.x1, D);
-        a.Rp = dl.dims; a.regime_rows = regime_rows;
-        a.ln_g = ly.ln1g; a.ln_b = ly.ln1b; a.ln_eps = 1e-5f;
-        if (po) { a.residp = b.x0p; a.residp_chunks = D / 32; }      // (x0p: split-bf16 planes, from the input layer or the previous block's FFN2 + LN2)
-        else { a.resid = b.x0; a.ldr = D; }
-        const bool mx4l = po && ffn_terms == kFfnMx4 && ly.w1.wm4 && b.xs4 && D == 384;                       // this layer's FFN conv in the mx4 arithmetic (fp4 cross terms; planes-only regime)?
-        const bool mxl = pl && (ffn_terms == kFfnMx || ffn_terms == kFfnMx4) && ly.w1.wm;         // ... in the mx arithmetic (also the fallback of mix_mx4 wherever mx4 does not apply)?
-        const int f16t = (pl && ffn_terms && ffn_terms != kFfnMx && ffn_terms != kFfnMx4 && ly.w1.ktaps > 1 && ly.w1.wf) ? ffn_terms : 0;      // ... or on fp16 operands?
-        if (pl) { a.Xp = ctxp; a.Yp = b.x1p; a.yp_chunks = D / 32; a.yp_f16 = mx4l ? 3 : (mxl ? 2 : (f16t ? 1 : 0)); a.yp_scale = mxl ? exp2f((float)ly.ka) : 1.f; }       // x1p feeds only that conv
-        if (mx4l) a.yp_rowscale = b.xs4;
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        // the second FFN GEMM: built first, because WHERE it will run decides the format the hidden layer leaves FFN1 in (mx planes for gemm_row4_bf16's
-        // mx form, split-bf16 planes for everything else)
-        GemmArgs a2 = gemm_args(ly.w2, b.hid, ly.w1.N, R, dl.row_pos, po ? nullptr : b.x0, D);
-        a2.Rp = dl.dims; a2.regime_rows = regime_rows;
-        a2.ln_g = ly.ln2g; a2.ln_b = ly.ln2b; a2.ln_eps = 1e-5f;
-        if (po) { a2.residp = b.x1p; a2.residp_chunks = D / 32; a2.residp_mx = mx4l ? 2 : (mxl ? 1 : 0); a2.residp_scale = mxl ? exp2f(-(float)(ly.ka + 11)) : 1.f; }      // (x1p: LN1's output in the format the FFN conv wants)
-        else { a2.resid = b.x1; a2.ldr = D; }
-        if (pl) { a2.Xp = hidp; a2.Yp = b.x0p; a2.yp_chunks = D / 32; }
-        const bool mx2 = mxl && ly.w2.wm && opts().ffn2_mx && prec == FS2_PREC_BF16X3 && ffn2_on_row4_mx(a2);
-        if (mx2) { a2.mx = 1; a2.Wb = ly.w2.wm; a2.mx_scale = scale_byte4(127 - ly.kh - 11); a2.mx_scale_b = scale_byte4(127 - ly.w2.kw); }
-        snprintf(nm, sizeof nm, "%s.ffn1", tag);
-        a = gemm_args(ly.w1, b.x1, D, R, dl.row_pos, pl ? nullptr : b.hid, ly.w1.N);
-        a.Rp = dl.dims;
-        a.act_post = 1;
-        if (pl) { a.Xp = b.x1p; a.Yp = hidp; a.yp_chunks = round_up(ly.w1.N, 32) / 32; }
-        if (mx2) { a.yp_f16 = 2; a.yp_scale = exp2f((float)ly.kh); }
-        if (f16t) { a.f16_terms = f16t; a.Wb = ly.w1.wf; }
-        if (mx4l) { a.mx = 2; a.Wb = ly.w1.wm4; a.x_rowscale = b.xs4; a.w_rowscale = ly.w1.ws4; }
-        else if (mxl) { a.mx = 1; a.Wb = ly.w1.wm; a.mx_scale = scale_byte4(127 - ly.ka - 11); a.mx_scale_b = scale_byte4(127 - ly.w1.kw); }
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        snprintf(nm, sizeof nm, "%s.ffn2_ln", tag);
-        if ((rc = launch_gemm(h, s, nm, a2, prec))) return rc;
-    }
-    return FS2_OK;
-}
-
-// standalone LayerNorm over rows (out of place): src [R, ld] -> Y [R, N] fp32 and / or planes
-int launch_ln(fs2_handle* h, hipStream_t s, const char* name, const float* src, int ld, int R, int N, const int* row_pos, const float* g,
-              const float* bta, float eps, float* Y, void* Yp) {
-    GemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.N = N; a.R = R; a.row_pos = row_pos; a.Y = Y; a.ldy = N; a.Ysrc = src; a.ldsrc = ld; a.ln_g = g; a.ln_b = bta; a.ln_eps = eps;
-    a.x_scale = 1.f; a.ksplit = 1; a.Yp = Yp; a.yp_chunks = round_up(N, 32) / 32;
-    if (N > 1024 || N % 4) return fail(h, FS2_ERR_UNSUPPORTED, "%s: LayerNorm width %d", name, N);
-    Scope sc(h, s, name, 0.0, 8.0 * R * N);
-    hipLaunchKernelGGL(ln_rows, dim3((R + 3) / 4), dim3(256), 0, s, a);
+// ------------------------------------------------------------------ the model's launches: model_launches.h forms them, these run them
+// standalone LayerNorm over rows (ln_args)
+int launch_ln(fs2_handle* h, hipStream_t s, const char* name, const GemmArgs& a) {
+    if (a.N > 1024 || a.N % 4) return fail(h, FS2_ERR_UNSUPPORTED, "%s: LayerNorm width %d", name, a.N);
+    Scope sc(h, s, name, 0.0, 8.0 * a.R * a.N);
+    hipLaunchKernelGGL(ln_rows, dim3((a.R + 3) / 4), dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
     return FS2_OK;
 }
 
-// FFT-block stack for the non-default block variants (reference core/encoder.py:53-71,201-202): normalize_before (LayerNorm in front of
-// the sub-layers, after_norm at the end) and / or concat_after (x + concat_linear(cat(x, self_attn(x)))).  Same kernels as run_stack,
-// without the LayerNorm fusion where the norm no longer follows a GEMM; cat(x, a) . Wc^T is computed as x . Wc[:, :D]^T + a . Wc[:, D:]^T
-// (two GEMMs chained through the residual input).  Scratch: xn1 -> hid / xps, attention output -> qkv / qkh, xn2 -> qkv / xps.
-int run_stack_general(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, int D, int heads, int R, const HostLayout& L, const DevLayout& dl,
-                      int mask_q, const StackBufs& b, int prec, bool x0p_ready, int regime_rows) {
+// a GEMM or LayerNorm step under its profile name "<tag>.<name>" (tag == nullptr: the name alone)
+int launch_step(fs2_handle* h, hipStream_t s, const char* tag, const Step& st, int prec) {
+    char nm[96];
+    snprintf(nm, sizeof nm, "%s%s%s", tag ? tag : "", tag ? "." : "", st.name);
+    return st.kind == StepKind::LayerNorm ? launch_ln(h, s, nm, st.a) : launch_gemm(h, s, nm, st.a, prec);
+}
+
+// FFT-block stack, every block variant (block_steps).  b.x0 holds the input and then the output; po: the planes b.x0p alone do.
+int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, int D, int heads, const Rows& r, const HostLayout& L, const DevLayout& dl,
+              int mask_q, const StackBufs& b, int prec, bool x0p_ready, int ffn_terms, bool po = false) {
     char nm[96];
     double att_flops = 0;
     for (size_t i = 0; i < L.klen.size(); ++i) att_flops += 4.0 * D * (double)L.klen[i] * std::min(L.len[i], mask_q ? L.klen[i] : L.len[i]);
     const bool pl = prec != FS2_PREC_FP32;
-    const bool pre = st.pre_ln, cat = st.concat;
-    const int Dp = st.Dp;
-    void* ctxp = pl ? (void*)b.ctx : nullptr;
-    void* hidp = pl ? (void*)b.hid : nullptr;
     int rc;
-    if (pl && !pre && !x0p_ready) {
-        const int64_t n = (int64_t)R * (D / 4);
-        hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.x0, D, D, R, D / 32, b.x0p, 0);
+    if (pl && !st.pre_ln && !x0p_ready) {
+        snprintf(nm, sizeof nm, "%s.in.planes", tag);
+        Scope sc(h, s, nm, 0.0, 8.0 * r.R * D);
+        const int64_t n = (int64_t)r.R * (D / 4);
+        hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.x0, D, D, r.R, D / 32, b.x0p);
     }
-    for (size_t li = 0; li < st.layers.size(); ++li) {
-        const Layer& ly = st.layers[li];
-        const float* qin = b.x0; const void* qinp = pl ? b.x0p : nullptr;
-        if (pre) {
-            snprintf(nm, sizeof nm, "%s.ln1", tag);
-            if ((rc = launch_ln(h, s, nm, b.x0, D, R, D, dl.row_pos, ly.ln1g, ly.ln1b, 1e-5f, pl ? nullptr : b.hid, pl ? b.xps : nullptr))) return rc;
-            qin = b.hid; qinp = pl ? b.xps : nullptr;
+    for (const Layer& ly : st.layers)
+        for (const Step& step : block_steps(st, ly, D, r, b, prec, ffn_terms, po, opts())) {
+            if (step.kind != StepKind::Attention) rc = launch_step(h, s, tag, step, prec);
+            else {
+                snprintf(nm, sizeof nm, "%s.%s", tag, step.name);
+                if (!pl) rc = launch_attention(h, s, nm, step.a.X, step.a.Y, st.Dp, heads, dl, L.nwork(), mask_q, att_flops, st.dk);
+                else rc = launch_attention_b16(h, s, nm, step.a.X, step.a.Y, st.Dp, heads, r.R, r.Rpad, dl, L.nwork(), mask_q, att_flops, prec, (__bf16*)b.qkh, (__bf16*)b.qkl,
+                                               (__bf16*)b.vth, (__bf16*)b.vtl, step.a.Yp, st.dk);
+            }
+            if (rc) return rc;
         }
-        snprintf(nm, sizeof nm, "%s.qkv", tag);
-        GemmArgs a = gemm_args(ly.qkv, qin, D, R, dl.row_pos, b.qkv, 3 * Dp);
-        a.Rp = dl.dims; a.regime_rows = regime_rows; a.Xp = qinp;
-        const bool fused_split = pl && Dp % kB16BN == 0;
-        if (fused_split) {
-            a.Y = nullptr; a.qk_hi = b.qkh; a.qk_lo = b.qkl; a.vt_hi = b.vth; a.vt_lo = b.vtl; a.att_D = Dp; a.Rvt = L.Rpad;
-            a.q_scale = 1.4426950408889634f / sqrtf((float)st.dk);
-        }
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        snprintf(nm, sizeof nm, "%s.attn", tag);
-        if (!pl) rc = launch_attention(h, s, nm, b.qkv, b.ctx, Dp, heads, dl, L.nwork(), mask_q, att_flops, st.dk);
-        else rc = launch_attention_b16(h, s, nm, fused_split ? nullptr : b.qkv, nullptr, Dp, heads, R, L.Rpad, dl, L.nwork(), mask_q, att_flops, prec, b.qkh, b.qkl, b.vth, b.vtl, ctxp, st.dk);
-        if (rc) return rc;
-        if (cat) {
-            // a = linear_out(context) (no residual), then x1 = x0 + xq . Wc_x^T + bc, then x1 += a . Wc_a^T (+ LayerNorm when post-LN)
-            float* att = b.qkv; void* attp = pl ? (void*)b.qkh : nullptr;       // both free once the attention kernel has run
-            snprintf(nm, sizeof nm, "%s.out", tag);
-            a = gemm_args(ly.out, b.ctx, Dp, R, dl.row_pos, pl ? nullptr : att, D);
-            a.Rp = dl.dims; a.regime_rows = regime_rows;
-            if (pl) { a.Xp = ctxp; a.Yp = attp; a.yp_chunks = D / 32; }
-            if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-            snprintf(nm, sizeof nm, "%s.cat_x", tag);
-            a = gemm_args(ly.cat_x, qin, D, R, dl.row_pos, b.x1, D);
-            a.Rp = dl.dims; a.regime_rows = regime_rows; a.Xp = qinp; a.resid = b.x0; a.ldr = D;
-            if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-            snprintf(nm, sizeof nm, "%s.cat_a", tag);
-            a = gemm_args(ly.cat_a, att, D, R, dl.row_pos, b.x1, D);
-            a.Rp = dl.dims; a.regime_rows = regime_rows; a.Xp = attp; a.resid = b.x1; a.ldr = D;      // in place: every element is read, then written, by one lane
-            if (!pre) { a.ln_g = ly.ln1g; a.ln_b = ly.ln1b; a.ln_eps = 1e-5f; if (pl) { a.Yp = b.x1p; a.yp_chunks = D / 32; } }
-            if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        } else {
-            snprintf(nm, sizeof nm, "%s.out", tag);
-            a = gemm_args(ly.out, b.ctx, Dp, R, dl.row_pos, b.x1, D);
-            a.Rp = dl.dims; a.regime_rows = regime_rows; a.resid = b.x0; a.ldr = D;
-            if (pl) a.Xp = ctxp;
-            if (!pre) { a.ln_g = ly.ln1g; a.ln_b = ly.ln1b; a.ln_eps = 1e-5f; if (pl) { a.Yp = b.x1p; a.yp_chunks = D / 32; } }
-            if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        }
-        const float* fin = b.x1; const void* finp = pl ? b.x1p : nullptr;
-        if (pre) {
-            snprintf(nm, sizeof nm, "%s.ln2", tag);
-            if ((rc = launch_ln(h, s, nm, b.x1, D, R, D, dl.row_pos, ly.ln2g, ly.ln2b, 1e-5f, pl ? nullptr : b.qkv, pl ? b.xps : nullptr))) return rc;
-            fin = b.qkv; finp = pl ? b.xps : nullptr;
-        }
-        snprintf(nm, sizeof nm, "%s.ffn1", tag);
-        a = gemm_args(ly.w1, fin, D, R, dl.row_pos, pl ? nullptr : b.hid, ly.w1.N);
-        a.Rp = dl.dims; a.regime_rows = regime_rows; a.act_post = 1; a.Xp = finp;
-        if (pl) { a.Yp = hidp; a.yp_chunks = round_up(ly.w1.N, 32) / 32; }
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-        snprintf(nm, sizeof nm, "%s.ffn2", tag);
-        a = gemm_args(ly.w2, b.hid, ly.w1.N, R, dl.row_pos, b.x0, D);
-        a.Rp = dl.dims; a.regime_rows = regime_rows; a.resid = b.x1; a.ldr = D;
-        if (pl) a.Xp = hidp;
-        if (!pre) { a.ln_g = ly.ln2g; a.ln_b = ly.ln2b; a.ln_eps = 1e-5f; if (pl) { a.Yp = b.x0p; a.yp_chunks = D / 32; } }
-        if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-    }
-    if (pre) {      // Encoder.forward: xs = after_norm(xs); downstream consumers read x0 (fp32) and, in the bf16 modes, its planes
+    if (st.pre_ln) {      // Encoder.forward: xs = after_norm(xs); downstream consumers read x0 (fp32) and, in the bf16 modes, its planes
         snprintf(nm, sizeof nm, "%s.after_norm", tag);
-        if ((rc = launch_ln(h, s, nm, b.x0, D, R, D, dl.row_pos, st.after_g, st.after_b, 1e-5f, b.x0, pl ? b.x0p : nullptr))) return rc;
+        if ((rc = launch_ln(h, s, nm, ln_args(b.x0, D, r, D, st.after_g, st.after_b, b.x0, pl ? b.x0p : nullptr)))) return rc;
     }
     return FS2_OK;
 }
 
-// conv stack + scalar head (reference variance_predictor.py:46-51 / duration_predictor.py:70-75);
-// tmp0/tmp1: [R, chans] scratch; out_rows: [R]
-int run_predictor(fs2_handle* h, hipStream_t s, const char* tag, const Predictor& p, const float* X, int ldx, int R,
-                  const int* row_pos, float* tmp0, float* tmp1, float* out_rows, int prec, const void* Xp = nullptr, void* xps = nullptr, const int* Rp = nullptr) {
-    char nm[96];
-    const float* in = X; int ld = ldx;
-    float* bufs[2] = {tmp0, tmp1};
-    for (size_t l = 0; l < p.conv.size(); ++l) {
-        const bool last = (l + 1 == p.conv.size());
-        float* out = bufs[l & 1];
-        // bf16 modes: the next layer consumes the planes; the fp32 copy is written only where a kernel pair needs it as scratch
-        GemmArgs a = gemm_args(p.conv[l], in, ld, R, row_pos, (last || (xps && prec != FS2_PREC_FP32)) ? nullptr : out, p.conv[l].N);
-        a.Rp = Rp;
-        a.relu_pre = 1; a.ln_g = p.lng[l]; a.ln_b = p.lnb[l]; a.ln_eps = 1e-12f;
-        if (last) { a.dot_w = p.lin_w; a.dot_b = p.lin_b; a.dot_out = out_rows; }
-        a.scratch = out;
-        // planes: the first layer's input from the caller (or built in xps), later layers' from the row kernel of the
-        // previous one (it runs after the GEMM that read xps, so the buffer can be reused in place)
-        a.Xp = Xp; a.xp_scratch = xps;
-        if (xps && !last) { a.Yp = xps; a.yp_chunks = round_up(p.conv[l].N, 32) / 32; }
-        if (xps && !last) Xp = xps; else Xp = nullptr;
-        snprintf(nm, sizeof nm, "%s.conv%d", tag, (int)l);
-        int rc = launch_gemm(h, s, nm, a, prec);
-        if (rc) return rc;
-        in = out; ld = p.conv[l].N;
-    }
+int run_predictor(fs2_handle* h, hipStream_t s, const char* tag, const Predictor& p, const float* X, int ldx, const Rows& r, float* tmp0, float* tmp1, float* out_rows,
+                  int prec, const void* Xp, void* xps) {
+    for (size_t l = 0; l < p.conv.size(); ++l)
+        if (int rc = launch_step(h, s, tag, predictor_step(p, l, X, ldx, r, tmp0, tmp1, out_rows, prec, Xp, xps), prec)) return rc;
     return FS2_OK;
 }
 
-// The pitch and the energy predictor of the bf16 modes as one launch per layer (FusedPredictors).  Every output column is accumulated in the
-// order of the separate launches; the LayerNorm of a 256-column group may be summed in another order than the two-wave form (1e-7).
-int run_predictors_fused(fs2_handle* h, hipStream_t s, const FusedPredictors& v, const float* X, int ldx, int R, const int* row_pos, const int* Rp,
-                         const void* Xp, void* xps, float* vp, float* vs, float* e_rows, float* p_rows, int prec, const TokGatherArgs* tg = nullptr) {
-    const int chans = v.c0.N / 2;
-    int rc;
-    const bool row8 = row_regime(h->cur_regime ? h->cur_regime : R, opts().row8);
-    if (tg) {      // layer 0 from the token-level products (tok.proj): a row kernel in place of the convolution(s)
-        Scope sc(h, s, "var.gather0", 0.0, 4.0 * R * chans * (6.0 + 2.0));
-        hipLaunchKernelGGL(var_gather0, dim3((2 * (size_t)R + 3) / 4), dim3(256), 0, s, *tg);
+// tg: layer 0 from the token-level products (tok.proj): a row kernel in place of the convolution(s)
+int run_predictors_fused(fs2_handle* h, hipStream_t s, const FusedPredictors& v, const float* X, int ldx, const Rows& r, const void* Xp, void* xps, float* vp, float* vs,
+                         float* e_rows, float* p_rows, int prec, const TokGatherArgs* tg = nullptr) {
+    if (tg) {
+        Scope sc(h, s, "var.gather0", 0.0, 4.0 * r.R * (v.c0.N / 2) * (6.0 + 2.0));
+        hipLaunchKernelGGL(var_gather0, dim3((2 * (size_t)r.R + 3) / 4), dim3(256), 0, s, *tg);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "var.gather0 launch: %s", hipGetErrorString(e));
-    } else if (row8 && (chans == 256 || chans == 384)) {
-        // big grids: layer 0 as two row-complete launches (the stacked 512-column form exists at 128-row tiles only -- 128 accumulator
-        // registers -- and pays a nearly empty second round where the 192-row form does not: c3 0.169 ms against 2 x 0.07), each filling its half
-        // of the stacked plane rows
-        const Predictor* ps[2] = {&h->energy, &h->pitch};
-        for (int g = 0; g < 2; ++g) {
-            GemmArgs a = gemm_args(ps[g]->conv[0], X, ldx, R, row_pos, nullptr, chans);
-            a.Rp = Rp; a.relu_pre = 1; a.ln_g = ps[g]->lng[0]; a.ln_b = ps[g]->lnb[0]; a.ln_eps = 1e-12f;
-            a.Xp = Xp; a.xp_scratch = xps; a.Yp = vp; a.yp_chunks = v.c0.N / 32; a.yp_col_off = g * chans; a.scratch = vs;
-            if ((rc = launch_gemm(h, s, g ? "pitch.conv0" : "energy.conv0", a, prec))) return rc;
-        }
-    } else {
-        GemmArgs a = gemm_args(v.c0, X, ldx, R, row_pos, nullptr, v.c0.N);
-        a.Rp = Rp; a.relu_pre = 1; a.ln_g = v.ln0g; a.ln_b = v.ln0b; a.ln_eps = 1e-12f; a.ln_groups = 2;
-        a.Xp = Xp; a.xp_scratch = xps; a.Yp = vp; a.yp_chunks = v.c0.N / 32; a.scratch = vs;
-        if ((rc = launch_gemm(h, s, "var.conv0", a, prec))) return rc;
     }
-    GemmArgs a = gemm_args(v.c1, nullptr, v.c0.N, R, row_pos, nullptr, v.c1.N);
-    a.Rp = Rp; a.relu_pre = 1; a.ln_g = v.ln1g; a.ln_b = v.ln1b; a.ln_eps = 1e-12f; a.ln_groups = 2; a.k_groups = 2;
-    a.Xp = vp; a.xp_row_chunks = v.c0.N / 32; a.scratch = vs;
-    a.dot_w = v.lin_w; a.dot_b = v.lin_b; a.dot_out = e_rows; a.dot_gstride = (int)(p_rows - e_rows);
-    return launch_gemm(h, s, "var.conv1", a, prec);
+    for (const Step& st : fused_predictor_steps(v, h->energy, h->pitch, !tg, X, ldx, r, Xp, xps, vp, vs, e_rows, p_rows, opts()))
+        if (int rc = launch_step(h, s, nullptr, st, prec)) return rc;
+    return FS2_OK;
 }
 
 // ------------------------------------------------------------------ weight loading
@@ -1730,8 +1459,9 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
                            enc_pl && c.adim % 32 == 0 ? sb.x0p : nullptr);
         HIP_TRY(h, hipGetLastError());
     }
-    if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, L.R, L, dl, /*mask_q=*/1, sb, prec, /*x0p_ready=*/enc_pl && c.adim % 32 == 0, /*allow_splitk=*/true, /*regime_rows=*/tok_regime, ffn_terms))) return rc;
-    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, L.R, dl.row_pos, p0, p1, dlog_rows, prec, enc_pl ? sb.x0p : nullptr, sb.xps))) return rc;
+    const Rows rows{L.R, L.Rpad, dl.row_pos, dl.dims, tok_regime};
+    if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, rows, L, dl, /*mask_q=*/1, sb, prec, /*x0p_ready=*/enc_pl && c.adim % 32 == 0, ffn_terms))) return rc;
+    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, p0, p1, dlog_rows, prec, enc_pl ? sb.x0p : nullptr, sb.xps))) return rc;
     {
         Scope sc(h, s, "dur.post", 0, 0);
         const int n = b.B * b.Tmax;
@@ -1862,6 +1592,7 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
     // the larger batch the caller says this one is a shard of (fs2_batch.regime_*).
     const int regime_rows = regime_rows_of(b, /*token_level=*/false);
     h->cur_regime = regime_rows; h->cur_status = devlay ? io->status : nullptr;
+    const Rows rows{R, L.Rpad, dl.row_pos, dl.dims, regime_rows};
     // bf16 modes: the length-regulator output (and later its sum with the pitch / energy embeddings) is also written as planes,
     // in x1p (free until the decoder stack's first LayerNorm): the A operand of both variance predictors and of the decoder input layer
     void* hfr_planes = (prec != FS2_PREC_FP32 && c.adim % 32 == 0) ? f.sb.x1p : nullptr;
@@ -1886,10 +1617,10 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         HIP_TRY(h, hipGetLastError());
     }
     if (fused_var) {
-        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, R, dl.row_pos, dl.dims, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (tokproj & 1) ? &tg : nullptr))) return rc;
+        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, rows, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (tokproj & 1) ? &tg : nullptr))) return rc;
     } else {
-        if (need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
-        if (need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, R, dl.row_pos, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps, dl.dims))) return rc;
+        if (need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, rows, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps))) return rc;
+        if (need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, rows, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps))) return rc;
     }
     if (ctl_pitch || ctl_energy) {   // the predictions become the controlled values in place: both consumers below, and e_out / p_out, see those
         Scope sc(h, s, "var.control", 2.0 * R * (ctl_pitch + ctl_energy), 4.0 * R * (3.0 + 3.0 * (ctl_pitch + ctl_energy)));
@@ -1903,10 +1634,11 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         HIP_TRY(h, hipGetLastError());
     }
     const bool dec_pl = prec != FS2_PREC_FP32;
-    // Planes-only residual stream (round 6): where the decoder's LayerNorm-fused launches run on gemm_row4_bf16 they write planes and nothing else and
-    // read their residual from planes (gemm_row4.h: RES) -- the fp32 rows x0 / x1 are not written at all (0.9 GB per c3 step, 11 GB per c4 step of HBM
-    // writes).  Not in the fp16 two- / one-term modes (their LN1 output is a fp16 hi + lo pair, a format the residual reader does not have).
-    const bool po = dec_pl && planes_only_regime(h, prec, R, regime_rows) && (ffn_terms == 0 || ffn_terms == kFfnMx || ffn_terms == kFfnMx4);
+    // Planes-only residual stream: where the decoder's LayerNorm-fused launches run on gemm_row4_bf16 they write planes and nothing else and read their residual
+    // from planes (gemm_row4.h: RES) -- the fp32 rows x0 / x1 are not written at all.
+    DecIn dec_in;
+    if (c.decoder_input_layer) dec_in = DecIn{&h->dec_in, h->dec_in_lng, h->dec_in_lnb, c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim)};
+    const bool po = dec_pl && planes_only(dec_in, h->dec, c.ddim, rows, f.sb, prec, ffn_terms, opts());
     if (tokproj & 2) {   // bucket search + embedding add + decoder input layer as one row kernel over the token-level products
         tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
         tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
@@ -1917,13 +1649,7 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         hipLaunchKernelGGL(dec_in_gather, dim3((R + 3) / 4), dim3(256), 0, s, tg);
         HIP_TRY(h, hipGetLastError());
     } else if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
-        GemmArgs a = gemm_args(h->dec_in, f.hfr, c.adim, R, dl.row_pos, po ? nullptr : f.sb.x0, c.ddim);
-        a.Rp = dl.dims; a.regime_rows = regime_rows;
-        a.ln_g = h->dec_in_lng; a.ln_b = h->dec_in_lnb; a.ln_eps = 1e-5f; a.act_post = 1;
-        a.pe = h->dec.pe; a.pe_ld = c.ddim; a.pe_alpha = h->dec.alpha; a.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
-        a.Xp = hfr_planes; a.xp_scratch = f.sb.xps;
-        if (dec_pl) { a.Yp = f.sb.x0p; a.yp_chunks = c.ddim / 32; }
-        if ((rc = launch_gemm(h, s, "dec.in", a, prec))) return rc;
+        if ((rc = launch_step(h, s, nullptr, dec_in_step(dec_in, h->dec, f.hfr, c.adim, hfr_planes, rows, f.sb, prec, po), prec))) return rc;
     } else {                       // TorchScript twin: the decoder input is just x (* sqrt(d)) + alpha * pe   (encoder.py:138-141)
         Scope sc(h, s, "dec.in.pe", 0.0, 8.0 * R * c.ddim);
         HIP_TRY(h, hipMemcpyAsync(f.sb.x0, f.hfr, (size_t)R * c.ddim * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1936,7 +1662,7 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         HIP_TRY(h, hipGetLastError());
     }
     const int mask_q = (b.compat_padded && io->masked) ? 1 : 0;
-    if ((rc = run_stack(h, s, "dec", h->dec, c.ddim, c.aheads, R, L, dl, mask_q, f.sb, prec, /*x0p_ready=*/dec_pl, /*allow_splitk=*/false, regime_rows, ffn_terms, po))) return rc;
+    if ((rc = run_stack(h, s, "dec", h->dec, c.ddim, c.aheads, rows, L, dl, mask_q, f.sb, prec, /*x0p_ready=*/dec_pl, ffn_terms, po))) return rc;
     if (po && io->dec_out) {      // the API hands the decoder output out as fp32 rows: rebuilt from the planes (hi + lo) only when asked for
         Scope sc(h, s, "dec.out.rows", 0.0, 8.0 * R * c.ddim);
         const int64_t n = (int64_t)R * (c.ddim / 4);
@@ -1962,41 +1688,14 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
     }
     // planes hand-off through the tail: decoder -> feat_out (fp32 mel + planes of it) -> Postnet convs ping-pong x0p / x1p
     const bool post_pl = dec_pl && c.postnet_layers > 1 && rf == 1;     // (r > 1: feat_out's planes would be in the decoder-row layout)
-    {
-        GemmArgs a = gemm_args(h->feat, f.sb.x0, c.ddim, R, dl.row_pos, f.before, c.odim * rf);
-        a.Rp = dl.dims;
-        if (dec_pl) a.Xp = f.sb.x0p;
-        if (post_pl) { a.Yp = f.sb.xps; a.yp_chunks = round_up(c.odim, 32) / 32; }
-        if ((rc = launch_gemm(h, s, "feat_out", a, prec))) return rc;
-    }
-    const float* mel_after = f.before;
+    if ((rc = launch_step(h, s, nullptr, feat_out_step(h->feat, rows, f.sb, f.before, prec, post_pl), prec))) return rc;
     if (c.postnet_layers > 0) {
-        float* pa = rf > 1 ? f.pa2 : f.sb.hid;
-        float* pb = rf > 1 ? f.pb2 : f.sb.hid + (size_t)L.Rpad * c.postnet_chans;
-        const float* in = f.before; int ld = c.odim;
-        for (int l = 0; l < c.postnet_layers; ++l) {
-            const bool last = (l == c.postnet_layers - 1);
-            float* out = last ? f.after : ((l & 1) ? pb : pa);
-            GemmArgs a = gemm_args(h->post[l], in, ld, R2, dl2.row_pos, out, h->post[l].N);
-            a.Rp = dl2.dims;
-            if (!last) a.act_post = 2; else { a.resid = f.before; a.ldr = c.odim; }
-            if (post_pl) {
-                a.Xp = (l == 0) ? f.sb.xps : ((l & 1) ? f.sb.x0p : f.sb.x1p);
-                if (!last) { a.Y = nullptr; a.Yp = (l & 1) ? f.sb.x1p : f.sb.x0p; a.yp_chunks = round_up(h->post[l].N, 32) / 32; }
-                // round 6: the 512 -> 512 layers in the mx arithmetic of the mixed modes (fp16 main term + e4m3 cross terms, 2 MFMA-equivalents instead of 3; simulated:
-                // mel +6e-6, tools/arith_sim_postnet.py): a layer whose image exists takes mx planes, so the layer in front of it writes them (tanh output: static scale 2^8)
-                const bool post_mx = (ffn_terms == kFfnMx || ffn_terms == kFfnMx4) && opts().post_mx;
-                if (post_mx && !last && h->post[l + 1].wm) { a.yp_f16 = 2; a.yp_scale = exp2f((float)kPostKa); }
-                if (post_mx && l > 0 && h->post[l].wm) { a.mx = 1; a.Wb = h->post[l].wm; a.mx_scale = scale_byte4(127 - kPostKa - 11); a.mx_scale_b = scale_byte4(127 - h->post[l].kw); }
-            } else {
-                a.xp_scratch = rf > 1 ? f.xps2 : f.sb.xps;
-            }
-            char nm[32]; snprintf(nm, sizeof nm, "postnet.%d", l);
-            if ((rc = launch_gemm(h, s, nm, a, prec))) return rc;
-            in = out; ld = h->post[l].N;
-        }
-        mel_after = f.after;
+        const Rows rows2{R2, L.Rpad * rf, dl2.row_pos, dl2.dims, 0};
+        const PostBufs pb{f.before, f.after, rf > 1 ? f.pa2 : f.sb.hid, rf > 1 ? f.pb2 : f.sb.hid + (size_t)L.Rpad * c.postnet_chans, rf > 1 ? f.xps2 : f.sb.xps};
+        for (int l = 0; l < c.postnet_layers; ++l)
+            if ((rc = launch_step(h, s, nullptr, postnet_step(h->post, l, c.odim, rows2, pb, f.sb, post_pl, ffn_terms, opts()), prec))) return rc;
     }
+    const float* mel_after = c.postnet_layers > 0 ? f.after : f.before;
     {
         Scope sc(h, s, "unpack", 0, 4.0 * R * c.odim * 4);
         const int* lim_len = dl.len;    // every stored row (pads carry real values in compat mode)

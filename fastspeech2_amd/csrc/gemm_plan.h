@@ -71,8 +71,8 @@ inline int row4_mt(long rows) {
 }
 // the epilogues it has (gemm_row4.h: EPI); -1: none, the launch stays on gemm_row8_bf16.  Since round 6 the kernel serves the PLANES-ONLY form of
 // these launches only (gemm_row4.h: RES): no fp32 rows out (Y == nullptr, Yp given), the residual -- where there is one -- as the producing launch's
-// planes (residp; resid == nullptr).  fs2_decode / run_stack build their arguments in that form exactly when the plans of the decoder's
-// LayerNorm-fused launches land here (planes_only_regime); a launch in the other form stays on gemm_row8_bf16.
+// planes (residp; resid == nullptr).  model_launches.h forms the decoder's launches in that form exactly when the plans of its
+// LayerNorm-fused launches land here (planes_only); a launch in the other form stays on gemm_row8_bf16.
 inline int row4_epi(const GemmArgs& a) {
     if (a.ktaps != 1 || a.N != 384 || !a.ln_g || a.Y || !a.Yp || a.resid || a.relu_pre || a.dot_w || a.k_groups > 1 || a.ln_groups > 1 || a.qk_hi || a.yp_col_off) return -1;
     if (a.Cpad % 64 != 0 || a.yp_chunks * 32 != a.N) return -1;      // an even number of k-steps; planes exactly N wide
@@ -275,7 +275,7 @@ inline GemmPlan plan_gemm(const GemmArgs& a, int precision, const Options& o) {
     } else if (a.mx == 2) {
         // fp16 + block-scaled-fp4 form of the conv (gemm_planes.h ARITH = 3): 256-row tiles only -- it runs where the planes-only regime holds (>= 16 k rows: the
         // tile-height rule picks 256 there for every N >= 1024)
-        if (a.Cpad != 384) return refused(kPlanErrHip, "%s launch: invalid argument");      // (the LDS stride of the row scales is a compile-time constant: 8 bytes x 3 cross units; run_stack offers mx4 at D = 384 only)
+        if (a.Cpad != 384) return refused(kPlanErrHip, "%s launch: invalid argument");      // (the LDS stride of the row scales is a compile-time constant: 8 bytes x 3 cross units; block_steps offers mx4 at D = 384 only)
         p.kernel = GemmKernel::PlMx4; p.nsplit = 1; p.arith = 3; p.bm = 256;
     } else if (a.mx) {      // fp16 + block-scaled-fp8 form of the conv (gemm_mx.h): the planes kernel on mx planes / the mx weight image
         p.kernel = GemmKernel::PlMx; p.nsplit = 1; p.arith = 2; p.bm = conv_bm(a, 2, 1, p.ksplit, o);
@@ -301,29 +301,6 @@ inline GemmPlan plan_gemm(const GemmArgs& a, int precision, const Options& o) {
                     : conv_bm(a, 0, p.nsplit, p.ksplit, o);
     }
     return p;
-}
-
-// ------------------------------------------------------------------ the planes-only regime of the decoder
-// The decoder's LayerNorm-fused k = 1 launches (the input layer, out-proj + LN1, FFN2 + LN2) in their planes-only form, shapes and null-ness only:
-// no fp32 rows out, the result as split-bf16 planes, the residual -- none for the input layer, which adds the positional encoding -- as planes.
-inline GemmArgs planes_only_form(int C, int Cpad, int N, int R, int regime_rows, bool input_layer) {
-    static const float mark = 0.f;      // (a non-null pointer nobody follows)
-    GemmArgs a = GemmArgs();
-    a.C = C; a.ldx = C; a.Cpad = Cpad; a.ktaps = 1; a.N = N; a.R = R; a.regime_rows = regime_rows; a.ldy = N;
-    a.Wb = &mark; a.Xp = &mark; a.ln_g = &mark; a.Yp = const_cast<float*>(&mark); a.yp_chunks = N / 32;
-    if (input_layer) { a.pe = &mark; a.act_post = 1; }
-    else { a.residp = &mark; a.residp_chunks = N / 32; }
-    return a;
-}
-inline bool on_row4(const GemmArgs& a, int precision, const Options& o) { return plan_gemm(a, precision, o).kernel == GemmKernel::Row4; }
-// The decision itself, shapes only (fs2_runtime.hip's planes_only_regime hands in the handle's; the host test sweeps it): true exactly when the three launches
-// all plan onto gemm_row4_bf16.  in / out / w2: input channels (C, padded to Cpad) of the input layer (C = 0: the model has none), of out-proj and of FFN2; D: the
-// decoder width all three produce.
-struct PlaneDims { int C, Cpad; };
-inline bool planes_only_plan(PlaneDims in, PlaneDims out, PlaneDims w2, int D, int R, int regime_rows, int precision, const Options& o) {
-    return (in.C == 0 || on_row4(planes_only_form(in.C, in.Cpad, D, R, regime_rows, true), precision, o)) &&
-           on_row4(planes_only_form(out.C, out.Cpad, D, R, regime_rows, false), precision, o) &&
-           on_row4(planes_only_form(w2.C, w2.Cpad, D, R, regime_rows, false), precision, o);
 }
 
 }  // namespace fs2

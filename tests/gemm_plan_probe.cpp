@@ -1,36 +1,71 @@
-// Host-compiled driver of csrc/gemm_plan.h for tests/test_gemm_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
-//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr>   the plan of every named launch of the default model, in the four tested precisions
-//   probe sweep                                         the planes-only decision: the predicate fs2_decode used to restate against the plan's answer
-//   probe refusals                                      one argument set per refusal of plan_gemm
-// The launches are formed the way fs2_runtime.hip forms them (run_stack, run_predictor, run_predictors_fused, fs2_decode), shapes and the null-ness of
-// pointers only.
+// Host-compiled driver of csrc/gemm_plan.h and csrc/model_launches.h for tests/test_gemm_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
+//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr>      the plan of every named launch of the default model, in the four tested precisions
+//   probe variants <Rtok> <regime_tok> <Rfr> <regime_fr>   every step of the pre-LN / concat_after block variants, and whether its GEMMs plan
+//   probe sweep                                            the planes-only decision: the predicate fs2_decode used to restate against the plan's answer
+//   probe refusals                                         one argument set per refusal of plan_gemm
+// The launches are the ones model_launches.h forms, the header fs2_runtime.hip executes.  This file holds only data: a model described as the loader would leave it
+// (a marker pointer wherever it builds an image or the workspace has a buffer) and the walk over the header's step lists.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "gemm_plan.h"
+#include "model_launches.h"
 
 using namespace fs2;
 
 namespace {
 
-const float kMarkStorage = 0.f;
-float* const M = const_cast<float*>(&kMarkStorage);      // a non-null pointer nobody follows
-constexpr int kFp32 = 0, kBf16x3 = 1, kBf16 = 2;         // FS2_PREC_*
-constexpr int kFfnMx = 9, kFfnMx4 = 10;                  // fs2_runtime.hip: ffn_f16_terms
-
-struct Model { int adim = 256, ddim = 384, heads = 2, eunits = 1024, dunits = 1024, kffn = 9, odim = 80, post_layers = 5, post_chans = 256, post_k = 5,
-               dur_chans = 256, dur_k = 3, var_chans = 256, var_k = 3; };
+float kMarkStorage[2];
+float* const M = kMarkStorage;      // a non-null pointer nobody follows
+unsigned char* const MB = reinterpret_cast<unsigned char*>(kMarkStorage);
+constexpr int kFp32 = kPlanFp32, kBf16x3 = kPlanBf16x3, kBf16 = 2;
 
 int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
-GemmArgs base(int C, int ktaps, int N, int R, bool y) {      // fs2_runtime.hip: gemm_args
-    GemmArgs a = GemmArgs();
-    a.X = M; a.ldx = C; a.C = C; a.W = M; a.Cpad = round_up(C, 32); a.ktaps = ktaps; a.N = N; a.R = R;
-    a.Y = y ? M : nullptr; a.ldy = N; a.x_scale = 1.f; a.Wb = M;
-    return a;
+// a layer as the Loader leaves it: the split-bf16 image always, the others by its rules (mx: the layer is one the mx image is built for when the shape allows)
+Gemm gemm(int C, int ktaps, int N, bool mx = false, bool f16 = false) {
+    Gemm g;
+    g.w = M; g.wb = M; g.C = C; g.Cpad = round_up(C, 32); g.ktaps = ktaps; g.N = N;
+    if (f16) g.wf = M;
+    if (mx && C % 128 == 0 && N % 128 == 0) { g.wm = M; if (ktaps > 1 && f16) { g.wm4 = M; g.ws4 = MB; } }
+    return g;
 }
+GemmArgs base(int C, int ktaps, int N, int R, bool y) { return gemm_args(gemm(C, ktaps, N), M, C, R, nullptr, y ? M : nullptr, N); }      // (the refusal cases start from it)
+
+struct Model { int adim = 256, ddim = 384, heads = 2, eunits = 1024, dunits = 1024, kffn = 9, odim = 80, post_layers = 5, post_chans = 256, post_k = 5,
+               dur_chans = 256, dur_k = 3, var_chans = 256, var_k = 3, layers = 4;
+               bool enc_pre_ln = false, enc_concat = false, dec_pre_ln = false, dec_concat = false; };
+
+Stack stack(int D, int heads, int units, int k, int layers, bool pre_ln, bool concat) {
+    Stack st;
+    st.dk = D / heads; st.Dp = att_width(D, heads); st.pre_ln = pre_ln; st.concat = concat; st.pe = M; st.after_g = st.after_b = M;
+    Layer ly;
+    ly.qkv = gemm(D, 1, 3 * st.Dp); ly.out = gemm(st.Dp, 1, D); ly.w1 = gemm(D, k, units, k > 1, k > 1); ly.w2 = gemm(units, 1, D, k > 1 && D == 384);
+    if (concat) ly.cat_x = ly.cat_a = gemm(D, 1, D);
+    ly.ln1g = ly.ln1b = ly.ln2g = ly.ln2b = M;
+    st.layers.assign(layers, ly);
+    return st;
+}
+Predictor predictor(int cin, int chans, int k) {
+    Predictor p;
+    p.conv = {gemm(cin, k, chans), gemm(chans, k, chans)};
+    p.lng = p.lnb = {M, M}; p.lin_w = p.lin_b = M;
+    return p;
+}
+struct Built {
+    Stack enc, dec; Predictor dur, energy, pitch; FusedPredictors var2; Gemm dec_in, feat; std::vector<Gemm> post;
+    explicit Built(const Model& m)
+        : enc(stack(m.adim, m.heads, m.eunits, m.kffn, m.layers, m.enc_pre_ln, m.enc_concat)), dec(stack(m.ddim, m.heads, m.dunits, m.kffn, m.layers, m.dec_pre_ln, m.dec_concat)),
+          dur(predictor(m.adim, m.dur_chans, m.dur_k)), energy(predictor(m.adim, m.var_chans, m.var_k)), pitch(energy), dec_in(gemm(m.adim, 1, m.ddim)), feat(gemm(m.ddim, 1, m.odim)) {
+        var2.ok = m.var_chans % 128 == 0;
+        var2.c0 = gemm(m.adim, m.var_k, 2 * m.var_chans); var2.c1 = gemm(m.var_chans, m.var_k, 2 * m.var_chans);
+        var2.ln0g = var2.ln0b = var2.ln1g = var2.ln1b = var2.lin_w = var2.lin_b = M;
+        for (int l = 0; l < m.post_layers; ++l) post.push_back(gemm(l ? m.post_chans : m.odim, m.post_k, l == m.post_layers - 1 ? m.odim : m.post_chans, true));
+    }
+    DecIn in() const { return DecIn{&dec_in, M, M, 1.f}; }
+};
+const StackBufs kTokBufs{M, M, M, M, M, M, M, M, M, M, M, M, nullptr}, kFrameBufs{M, M, M, M, M, M, M, M, M, M, M, M, MB};      // (carve_tokens / carve_frames: only the frames have xs4)
 
 const char* kernel_name(GemmKernel k) {
     switch (k) {
@@ -53,157 +88,98 @@ const char* kernel_name(GemmKernel k) {
     return "?";
 }
 
-// what launch_gemm does before it asks: the handle's split-K scratch (carve_tokens / carve_frames: 4 slabs) and regime
-GemmPlan plan_in_call(GemmArgs a, int prec, int Rpad, int cur_regime, const Options& o) {
-    if (!a.kpart) { a.kpart = M; a.kpart_cap = (size_t)4 * std::min(Rpad, kSplitRows) * 1024; a.ksplit = 3; }
-    if (!a.regime_rows) a.regime_rows = cur_regime;
-    return plan_gemm(a, prec, o);
-}
-
-struct Call {      // one fs2_encode / fs2_decode: prints a line per launch, or collects the plans into `all` (capacity test)
-    int prec, terms, R, Rpad, regime;
+struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch, or collects the plans into `all` (capacity test)
+    int prec, terms;
+    Rows r;
     const char* tag;
     Options o;
     std::string* all = nullptr;
-    void emit(const char* name, const GemmArgs& a) const {
-        const GemmPlan p = plan_in_call(a, prec, Rpad, regime, o);
+    bool steps = false;      // print every step with its kind and the plan's refusal code instead
+    void emit(const char* stack, const Step& st) const {
+        const std::string name = std::string(stack ? stack : "") + (stack ? "." : "") + st.name;
+        if (steps && st.kind != StepKind::Gemm) printf("%s %s %s 0\n", tag, name.c_str(), st.kind == StepKind::Attention ? "attention" : "layernorm");
+        if (st.kind != StepKind::Gemm) return;
+        GemmArgs a = st.a;
+        call_defaults(a, M, (size_t)4 * std::min(r.Rpad, kSplitRows) * 1024, r.regime_rows);      // the call's split-K scratch (carve_tokens / carve_frames: 4 slabs) and regime
+        const GemmPlan p = plan_gemm(a, prec, o);
         char line[256];
         if (all) {
-            snprintf(line, sizeof line, "%s %s ns%d nb%d bm%d mt%d k1%d ap%d epi%d ar%d res%d ks%d y%d bp%d rp%d err%d\n", name, kernel_name(p.kernel), p.nsplit, p.nb, p.bm, p.mt,
+            snprintf(line, sizeof line, "%s %s ns%d nb%d bm%d mt%d k1%d ap%d epi%d ar%d res%d ks%d y%d bp%d rp%d err%d\n", name.c_str(), kernel_name(p.kernel), p.nsplit, p.nb, p.bm, p.mt,
                      (int)p.k1, p.apart, p.epi, p.arith, p.res, p.ksplit, (int)p.y, (int)p.build_planes, (int)p.rows_pass, p.err);
             *all += line;
+        } else if (steps) {
+            printf("%s %s gemm %d\n", tag, name.c_str(), p.err);
         } else {
-            printf("%s %s %s %d %d %d\n", tag, name, kernel_name(p.kernel), p.tile_rows(), p.ksplit, (int)p.rows_pass);
+            printf("%s %s %s %d %d %d\n", tag, name.c_str(), kernel_name(p.kernel), p.tile_rows(), p.ksplit, (int)p.rows_pass);
         }
+    }
+    void stack(const char* name, const Stack& st, int D, const StackBufs& b, bool po) const {
+        for (const Layer& ly : st.layers)
+            for (const Step& s : block_steps(st, ly, D, r, b, prec, terms, po, o)) emit(name, s);
+    }
+    void predictor(const char* name, const Predictor& p, const void* Xp) const {
+        for (size_t l = 0; l < p.conv.size(); ++l) emit(name, predictor_step(p, l, M, p.conv[0].C, r, M, M, M, prec, Xp, M));
     }
 };
 
-bool ffn2_on_row4_mx(GemmArgs a, const Options& o) { a.mx = 1; const GemmPlan p = plan_gemm(a, kBf16x3, o); return p.kernel == GemmKernel::Row4 && p.arith == 2; }
+void encode(const Built& m, const Call& c) {
+    c.stack("enc", m.enc, m.enc.layers[0].out.N, kTokBufs, false);
+    c.predictor("dur", m.dur, c.prec != kFp32 ? M : nullptr);
+}
 
-void run_stack(const Call& c, const char* tag, int D, int heads, int units, int kffn, bool po) {
+void decode(const Built& m, const Call& c) {
     const bool pl = c.prec != kFp32;
-    const int dk = D / heads, Dp = heads * (dk <= 64 ? 64 : (dk <= 128 ? 128 : (dk <= 192 ? 192 : 256)));
-    std::string n = tag;
-    GemmArgs a = base(D, 1, 3 * Dp, c.R, true);
-    a.regime_rows = c.regime;
-    if (pl) a.Xp = M;
-    if (pl && Dp % 128 == 0) { a.Y = nullptr; a.qk_hi = M; a.att_D = Dp; a.Rvt = c.Rpad; }
-    c.emit((n + ".qkv").c_str(), a);
-    a = base(Dp, 1, D, c.R, !po);
-    a.regime_rows = c.regime; a.ln_g = M;
-    if (po) { a.residp = M; a.residp_chunks = D / 32; } else { a.resid = M; a.ldr = D; }
-    const bool mx4l = po && c.terms == kFfnMx4 && D == 384;
-    const bool mxl = pl && (c.terms == kFfnMx || c.terms == kFfnMx4);
-    if (pl) { a.Xp = M; a.Yp = M; a.yp_chunks = D / 32; a.yp_f16 = mx4l ? 3 : (mxl ? 2 : 0); }
-    if (mx4l) a.yp_rowscale = reinterpret_cast<unsigned char*>(M);
-    c.emit((n + ".out_ln").c_str(), a);
-    GemmArgs a2 = base(units, 1, D, c.R, !po);
-    a2.regime_rows = c.regime; a2.ln_g = M;
-    if (po) { a2.residp = M; a2.residp_chunks = D / 32; a2.residp_mx = mx4l ? 2 : (mxl ? 1 : 0); } else { a2.resid = M; a2.ldr = D; }
-    if (pl) { a2.Xp = M; a2.Yp = M; a2.yp_chunks = D / 32; }
-    const bool mx2 = mxl && c.o.ffn2_mx && c.prec == kBf16x3 && ffn2_on_row4_mx(a2, c.o);
-    if (mx2) a2.mx = 1;
-    a = base(D, kffn, units, c.R, !pl);
-    a.act_post = 1;
-    if (pl) { a.Xp = M; a.Yp = M; a.yp_chunks = units / 32; }
-    if (mx2) a.yp_f16 = 2;
-    if (mx4l) { a.mx = 2; a.x_rowscale = a.w_rowscale = reinterpret_cast<unsigned char*>(M); }
-    else if (mxl) a.mx = 1;
-    c.emit((n + ".ffn1").c_str(), a);
-    c.emit((n + ".ffn2_ln").c_str(), a2);
+    const int D = m.dec_in.N;
+    if (pl && m.var2.ok && c.o.fuse_var) { for (const Step& s : fused_predictor_steps(m.var2, m.energy, m.pitch, true, M, m.dec_in.C, c.r, M, M, M, M, M, M, c.o)) c.emit(nullptr, s); }
+    else { c.predictor("energy", m.energy, pl ? M : nullptr); c.predictor("pitch", m.pitch, pl ? M : nullptr); }
+    const bool po = pl && planes_only(m.in(), m.dec, D, c.r, kFrameBufs, c.prec, c.terms, c.o);
+    c.emit(nullptr, dec_in_step(m.in(), m.dec, M, m.dec_in.C, pl ? M : nullptr, c.r, kFrameBufs, c.prec, po));
+    c.stack("dec", m.dec, D, kFrameBufs, po);
+    const bool post_pl = pl && m.post.size() > 1;
+    c.emit(nullptr, feat_out_step(m.feat, c.r, kFrameBufs, M, c.prec, post_pl));
+    Rows r2 = c.r; r2.regime_rows = 0;
+    for (int l = 0; l < (int)m.post.size(); ++l) c.emit(nullptr, postnet_step(m.post, l, m.feat.N, r2, PostBufs{M, M, M, M, M}, kFrameBufs, post_pl, c.terms, c.o));
 }
 
-void run_predictor(const Call& c, const char* tag, int cin, int chans, int k, bool planes_in) {
-    for (int l = 0; l < 2; ++l) {
-        const bool last = l == 1;
-        GemmArgs a = base(l ? chans : cin, k, chans, c.R, !(last || c.prec != kFp32));
-        a.relu_pre = 1; a.ln_g = M; a.scratch = M; a.xp_scratch = M;
-        if (last) a.dot_w = M;
-        a.Xp = (l || planes_in) ? M : nullptr;
-        if (!last) { a.Yp = M; a.yp_chunks = chans / 32; }
-        c.emit((std::string(tag) + ".conv" + (l ? "1" : "0")).c_str(), a);
-    }
-}
-
-void run_predictors_fused(const Call& c, int cin, int chans, int k) {
-    if (row_regime(c.regime, c.o.row8) && (chans == 256 || chans == 384)) {
-        for (int g = 0; g < 2; ++g) {
-            GemmArgs a = base(cin, k, chans, c.R, false);
-            a.relu_pre = 1; a.ln_g = M; a.Xp = M; a.xp_scratch = M; a.Yp = M; a.yp_chunks = 2 * chans / 32; a.yp_col_off = g * chans; a.scratch = M;
-            c.emit(g ? "pitch.conv0" : "energy.conv0", a);
-        }
-    } else {
-        GemmArgs a = base(cin, k, 2 * chans, c.R, false);
-        a.relu_pre = 1; a.ln_g = M; a.ln_groups = 2; a.Xp = M; a.xp_scratch = M; a.Yp = M; a.yp_chunks = 2 * chans / 32; a.scratch = M;
-        c.emit("var.conv0", a);
-    }
-    GemmArgs a = base(chans, k, 2 * chans, c.R, false);
-    a.ldx = 2 * chans; a.X = nullptr;
-    a.relu_pre = 1; a.ln_g = M; a.ln_groups = 2; a.k_groups = 2; a.Xp = M; a.xp_row_chunks = 2 * chans / 32; a.scratch = M; a.dot_w = M;
-    c.emit("var.conv1", a);
-}
-
-// the decision of fs2_decode: gemm_plan.h's planes_only_plan on the model's shapes, as fs2_runtime.hip's planes_only_regime calls it, + the ffn_terms condition
-// of the call site
-bool planes_only(const Model& m, int prec, int terms, int R, int regime, const Options& o) {
-    const int dk = m.ddim / m.heads, Dp = m.heads * (dk <= 64 ? 64 : (dk <= 128 ? 128 : (dk <= 192 ? 192 : 256)));
-    return prec != kFp32 && (terms == 0 || terms == kFfnMx || terms == kFfnMx4) &&
-           planes_only_plan({m.adim, round_up(m.adim, 32)}, {Dp, round_up(Dp, 32)}, {m.dunits, round_up(m.dunits, 32)}, m.ddim, R, regime, prec, o);
-}
-
-void encode(const Model& m, const Call& c) {
-    run_stack(c, "enc", m.adim, m.heads, m.eunits, m.kffn, false);
-    run_predictor(c, "dur", m.adim, m.dur_chans, m.dur_k, c.prec != kFp32);
-}
-
-void decode(const Model& m, const Call& c) {
-    const bool pl = c.prec != kFp32;
-    if (pl && m.var_chans % 128 == 0 && c.o.fuse_var) run_predictors_fused(c, m.adim, m.var_chans, m.var_k);
-    else { run_predictor(c, "energy", m.adim, m.var_chans, m.var_k, pl); run_predictor(c, "pitch", m.adim, m.var_chans, m.var_k, pl); }
-    const bool po = planes_only(m, c.prec, c.terms, c.R, c.regime, c.o);
-    GemmArgs a = base(m.adim, 1, m.ddim, c.R, !po);
-    a.regime_rows = c.regime; a.ln_g = M; a.act_post = 1; a.pe = M; a.Xp = pl ? M : nullptr; a.xp_scratch = M;
-    if (pl) { a.Yp = M; a.yp_chunks = m.ddim / 32; }
-    c.emit("dec.in", a);
-    run_stack(c, "dec", m.ddim, m.heads, m.dunits, m.kffn, po);
-    a = base(m.ddim, 1, m.odim, c.R, true);
-    if (pl) { a.Xp = M; a.Yp = M; a.yp_chunks = round_up(m.odim, 32) / 32; }
-    c.emit("feat_out", a);
-    auto has_mx = [&](int l) { const int C = l ? m.post_chans : m.odim, N = l == m.post_layers - 1 ? m.odim : m.post_chans; return C % 128 == 0 && N % 128 == 0; };
-    for (int l = 0; l < m.post_layers; ++l) {
-        const bool last = l == m.post_layers - 1;
-        a = base(l ? m.post_chans : m.odim, m.post_k, last ? m.odim : m.post_chans, c.R, true);
-        if (!last) a.act_post = 2; else { a.resid = M; a.ldr = m.odim; }
-        if (pl) {
-            a.Xp = M;
-            if (!last) { a.Y = nullptr; a.Yp = M; a.yp_chunks = round_up(a.N, 32) / 32; }
-            const bool post_mx = (c.terms == kFfnMx || c.terms == kFfnMx4) && c.o.post_mx;
-            if (post_mx && !last && has_mx(l + 1)) a.yp_f16 = 2;
-            if (post_mx && l > 0 && has_mx(l)) a.mx = 1;
-        } else a.xp_scratch = M;
-        c.emit(("postnet." + std::to_string(l)).c_str(), a);
-    }
-}
+Rows rows_of(int R, int regime) { return Rows{R, round_up(R, 128), nullptr, nullptr, regime}; }
 
 const struct { const char* name; int prec, terms; } kModes[] = {{"fp32", kFp32, 0}, {"bf16x3", kBf16x3, 0}, {"mix_mx", kBf16x3, kFfnMx}, {"mix_mx4", kBf16x3, kFfnMx4}};
 
 int model(int Rtok, int reg_tok, int Rfr, int reg_fr) {
-    const Model m;
+    const Built m{Model()};
     for (const auto& md : kModes) {
-        Call c{md.prec, md.terms, Rtok, round_up(Rtok, 128), reg_tok, md.name, Options()};
+        Call c{md.prec, md.terms, rows_of(Rtok, reg_tok), md.name, Options()};
         encode(m, c);
-        c.R = Rfr; c.Rpad = round_up(Rfr, 128); c.regime = reg_fr;
+        c.r = rows_of(Rfr, reg_fr);
         decode(m, c);
         // the plan does not depend on the row capacity (device-driven layout: 15-25 % above the rows in use)
         std::string plans[3];
         const double caps[3] = {1.0, 1.15, 1.25};
         for (int i = 0; i < 3; ++i) {
             Call k = c;
-            k.R = (int)(reg_fr * caps[i]); k.Rpad = round_up(k.R, 128); k.all = &plans[i];
+            k.r = rows_of((int)(reg_fr * caps[i]), reg_fr); k.all = &plans[i];
             decode(m, k);
         }
         printf("%s capacity_independent %d\n", md.name, (int)(plans[0] == plans[1] && plans[0] == plans[2] && !plans[0].empty()));
     }
+    return 0;
+}
+
+// the block variants of tests/test_oracle_golden.py: one layer per stack, every step
+int variants(int Rtok, int reg_tok, int Rfr, int reg_fr) {
+    const struct { const char* name; bool enc_pre_ln, enc_concat, dec_pre_ln, dec_concat; } kVariants[] = {
+        {"pre_ln", true, false, true, false}, {"concat_after", false, true, false, true}, {"pre_ln_concat", true, true, true, true}, {"enc_pre_ln_dec_concat", true, false, false, true}};
+    for (const auto& v : kVariants)
+        for (const auto& md : kModes) {
+            Model mm; mm.layers = 1; mm.enc_pre_ln = v.enc_pre_ln; mm.enc_concat = v.enc_concat; mm.dec_pre_ln = v.dec_pre_ln; mm.dec_concat = v.dec_concat;
+            const Built m{mm};
+            const std::string tag = std::string(v.name) + " " + md.name;
+            Call c{md.prec, md.terms, rows_of(Rtok, reg_tok), tag.c_str(), Options()};
+            c.steps = true;
+            c.stack("enc", m.enc, mm.adim, kTokBufs, false);
+            c.r = rows_of(Rfr, reg_fr);
+            c.stack("dec", m.dec, mm.ddim, kFrameBufs, c.prec != kFp32 && planes_only(m.in(), m.dec, mm.ddim, c.r, kFrameBufs, c.prec, c.terms, c.o));
+        }
     return 0;
 }
 
@@ -222,13 +198,16 @@ int sweep() {
         for (int row8 = -1; row8 <= 1; ++row8)
             for (int row4 = -1; row4 <= 0; ++row4)
                 for (int prec : {kBf16, kBf16x3})
-                    for (int ddim : {256, 384}) {
-                        Model m; m.ddim = ddim;
-                        Options o; o.row8 = row8; o.row4 = row4;
-                        const bool was = old_planes_only_regime({m.ddim, m.dunits, m.adim}, {false, false}, prec, regime, o);
-                        const bool now = planes_only(m, prec, 0, regime, regime, o), at_cap = planes_only(m, prec, 0, (int)(regime * 1.25) + 1, regime, o);
-                        printf("%d %d %d %s %d %d %d %d\n", regime, row8, row4, prec == kBf16 ? "bf16" : "bf16x3", ddim, (int)was, (int)now, (int)at_cap);
-                    }
+                    for (int ddim : {256, 384})
+                        for (int terms : {0, kFfnMx, kFfnMx4}) {
+                            Model mm; mm.ddim = ddim;
+                            const Built m{mm};
+                            Options o; o.row8 = row8; o.row4 = row4;
+                            const bool was = old_planes_only_regime({mm.ddim, mm.dunits, mm.adim}, {false, false}, prec, regime, o);
+                            const bool now = planes_only(m.in(), m.dec, ddim, rows_of(regime, regime), kFrameBufs, prec, terms, o);
+                            const bool at_cap = planes_only(m.in(), m.dec, ddim, rows_of((int)(regime * 1.25) + 1, regime), kFrameBufs, prec, terms, o);
+                            printf("%d %d %d %s %d %d %d %d %d\n", regime, row8, row4, prec == kBf16 ? "bf16" : "bf16x3", ddim, (int)was, (int)now, (int)at_cap, terms);
+                        }
     return 0;
 }
 
@@ -266,8 +245,9 @@ int refusals() {
 
 int main(int argc, char** argv) {
     if (argc == 6 && !strcmp(argv[1], "model")) return model(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
+    if (argc == 6 && !strcmp(argv[1], "variants")) return variants(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
     if (argc == 2 && !strcmp(argv[1], "sweep")) return sweep();
     if (argc == 2 && !strcmp(argv[1], "refusals")) return refusals();
-    fprintf(stderr, "usage: probe model Rtok regime_tok Rfr regime_fr | sweep | refusals\n");
+    fprintf(stderr, "usage: probe model|variants Rtok regime_tok Rfr regime_fr | sweep | refusals\n");
     return 2;
 }

@@ -1,5 +1,5 @@
-"""Host-side checks of the GEMM plan (no GPU): csrc/gemm_plan.h -- the pure function launch_gemm executes -- compiled with the host compiler
-(tests/gemm_plan_probe.cpp forms the model's launches the way fs2_runtime.hip does, shapes and null-ness of pointers only).
+"""Host-side checks of the GEMM plan (no GPU): csrc/gemm_plan.h -- the pure function launch_gemm executes -- and csrc/model_launches.h -- the forming of every
+named launch of the model, which fs2_runtime.hip executes -- compiled with the host compiler (tests/gemm_plan_probe.cpp describes a model and walks the header's lists).
 
 (a) the kernel family, tile height, split-K factor and ln_rows pass of every named launch of the default model, pinned for one utterance (c1) and
     for c3 in four precisions.  The expected values were read from kernel traces of the commit BEFORE the plan existed (rocprofv3 --kernel-trace of
@@ -9,7 +9,9 @@
     form, all plan onto gemm_row4_bf16" over row counts on both sides of the threshold, the forcing switches, two precisions and two decoder widths;
 (c) the plan of every frame-level launch is the same in every field for a row capacity of 1.0, 1.15 and 1.25 x the regime estimate (why the host- and
     the device-driven layout give equal bits);
-(d) every refusal of launch_gemm keeps its FS2_ERR_* code and message."""
+(d) every refusal of launch_gemm keeps its FS2_ERR_* code and message;
+(e) the pre-LN / concat_after block variants: the steps of a block, in order, are the launches run_stack_general made before the header existed, and every GEMM
+    among them plans."""
 import os
 import subprocess
 
@@ -205,10 +207,10 @@ def model_plans(probe):
 
 
 def test_gemm_plan_header_is_hip_free():
-    for h in ("gemm_plan.h", "gemm_args.h"):
+    for h in ("gemm_plan.h", "gemm_args.h", "model_launches.h"):
         src = open(os.path.join(CSRC, h)).read()
         incl = [l.split()[1] for l in src.split("\n") if l.startswith("#include")]
-        assert all(i.startswith("<") and "hip" not in i or i == '"gemm_args.h"' for i in incl), (h, incl)
+        assert all(i.startswith("<") and "hip" not in i or i in ('"gemm_args.h"', '"gemm_plan.h"') for i in incl), (h, incl)
 
 
 @pytest.mark.parametrize("regime", sorted(REGIMES))
@@ -263,11 +265,13 @@ def test_pinned_table_is_the_parent_trace(regime, mode):
 
 def test_planes_only_agrees_with_the_old_predicate(probe):
     rows = [l.split() for l in probe("sweep")]
-    assert len(rows) == 6 * 3 * 2 * 2 * 2
+    assert len(rows) == 3 * 6 * 3 * 2 * 2 * 2
+    assert {int(r[8]) for r in rows} == {0, 9, 10}      # plain, mx, mx4 FFN: the old predicate does not depend on the mode, nor may the answer
     assert {int(r[0]) for r in rows} == {1, 800, 16256, 16257, 36600, 78000}
     bad = [r for r in rows if not (r[5] == r[6] == r[7])]      # old predicate, plan at R = regime, plan at R = 1.25 x regime
     assert not bad, bad
     on = {(int(r[0]), int(r[1]), int(r[2]), r[3], int(r[4])) for r in rows if r[5] == "1"}
+    assert all(sum(1 for r in rows if r[5] == "1" and (int(r[0]), int(r[1]), int(r[2]), r[3], int(r[4])) == k) == 3 for k in on)
     # the threshold (r + 127) / 128 >= 128 flips between 16256 and 16257 rows; the default configuration (ddim 384, bf16x3, no switch) is in the sweep
     assert (16257, -1, -1, "bf16x3", 384) in on and (16256, -1, -1, "bf16x3", 384) not in on
     assert (800, 1, -1, "bf16x3", 384) in on and (78000, 0, -1, "bf16x3", 384) not in on and (78000, -1, 0, "bf16x3", 384) not in on
@@ -313,3 +317,30 @@ def test_refusals_keep_their_codes(probe):
     hdr = open(os.path.join(ROOT, "include", "fs2.h")).read()
     for name, val in (("ARG", ERR_ARG), ("HIP", ERR_HIP), ("STATE", ERR_STATE), ("UNSUPPORTED", ERR_UNSUPPORTED)):
         assert int(re.search(r"#define FS2_ERR_%s \((-\d+)\)" % name, hdr).group(1)) == val
+
+
+# The launches of one block in run_stack_general, written out by hand from the source of the commit before model_launches.h existed, in its order:
+# pre-LN puts ln1 / ln2 in front of the sub-layers (and names the GEMMs out / ffn2: no LayerNorm follows them), concat_after replaces the out-projection's
+# residual add by out, cat_x, cat_a.  (after_norm follows the last block of a pre-LN stack; the stack's runner launches it, it is no step of a block.)
+_LN, _AT, _G = "layernorm", "attention", "gemm"
+GENERAL_BLOCKS = {
+    (True, False): [("ln1", _LN), ("qkv", _G), ("attn", _AT), ("out", _G), ("ln2", _LN), ("ffn1", _G), ("ffn2", _G)],
+    (False, True): [("qkv", _G), ("attn", _AT), ("out", _G), ("cat_x", _G), ("cat_a", _G), ("ffn1", _G), ("ffn2", _G)],
+    (True, True): [("ln1", _LN), ("qkv", _G), ("attn", _AT), ("out", _G), ("cat_x", _G), ("cat_a", _G), ("ln2", _LN), ("ffn1", _G), ("ffn2", _G)],
+}
+# tests/test_oracle_golden.py's variants: (pre_ln, concat_after) of the encoder and of the decoder
+VARIANTS = {"pre_ln": ((True, False), (True, False)), "concat_after": ((False, True), (False, True)), "pre_ln_concat": ((True, True), (True, True)),
+            "enc_pre_ln_dec_concat": ((True, False), (False, True))}
+
+
+def test_block_variants_form_the_launches_of_run_stack_general(probe):
+    got = {}
+    for line in probe("variants", *REGIMES["c1"]):
+        variant, mode, name, kind, err = line.split()
+        got.setdefault((variant, mode), []).append((name, kind, int(err)))
+    assert set(got) == {(v, m) for v in VARIANTS for m in MODES}
+    for (variant, mode), steps in sorted(got.items()):
+        enc, dec = VARIANTS[variant]
+        want = [("enc." + n, k) for n, k in GENERAL_BLOCKS[enc]] + [("dec." + n, k) for n, k in GENERAL_BLOCKS[dec]]
+        assert [(n, k) for n, k, _ in steps] == want, (variant, mode)
+        assert all(err == 0 for _, _, err in steps), (variant, mode, steps)

@@ -1705,3 +1705,38 @@ def test_static_scale_arithmetic_under_heavy_tailed_weights(env, kind, fs2_optio
         assert errs["mix_mx"] <= bar, (kind, name, errs, scale)
         # mix_mx4 spends part of the budget by design (simulated: +3.7e-4 / +4.7e-4 under the LayerNorm / Student-t sets): its bar is the north star's 1e-3 at the plain model's mel scale
         assert errs["mix_mx4"] <= 1e-3 * max(1.0, scale / 4.0), (kind, name, errs, scale)
+
+
+@pytest.fixture(scope="module")
+def launch_cases():
+    """tools/forward_digest.py's cases (its models, its inputs), the names its launch_names() recorded on the parent commit, and the models built so far."""
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("forward_digest", os.path.join(root, "tools", "forward_digest.py"))
+    fd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fd)
+    with open(os.path.join(root, "profiles", "model_launches_names_parent.json")) as f:
+        parent = json.load(f)
+    return fd, parent, fd.make_inputs(), {}
+
+
+@pytest.mark.parametrize("row8", [0, 1])
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3", "mix_mx", "mix_mx4"])
+@pytest.mark.parametrize("block", ["default", "pre_ln_concat"])
+def test_launch_sequence_is_the_parents(launch_cases, block, precision, row8):
+    """csrc/model_launches.h forms every named launch of the model; before it existed fs2_runtime.hip did, in run_stack, run_stack_general, run_predictor,
+    run_predictors_fused and fs2_decode.  One teacher-forced forward of 3 utterances (5, 17, 33 phonemes): the ordered profile names equal the list recorded from
+    that commit (profiles/model_launches_names_parent.json, never regenerated from the tree under test) -- in every arithmetic, for the default and the
+    pre-LN + concat_after block, and with FS2_ROW8 = 1, where the row-complete and planes-only launches run at this size."""
+    fd, parent, inputs, models = launch_cases
+    if block not in models:
+        models[block] = fd.make_model(block)
+    got = fd.launch_names(models[block], inputs, precision, row8)
+    want = parent[fd.case_id(block, precision, row8)]
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            print("first difference at launch %d: got %s, parent %s" % (i, g, w))
+            break
+    assert got == want
+    assert len(want) > 40

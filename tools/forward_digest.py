@@ -1,0 +1,116 @@
+"""Digest of one small forward per launch-forming case: what a change of the host code that forms the model's launches must leave alone.
+
+For every case -- the default FFT block and the pre-LN + concat_after one, in fp32 / bf16x3 / mix_mx / mix_mx4, with the kernel choice automatic and with the
+row-complete kernels forced (FS2_ROW8 = 1: the planes-only regime at this size), plus the device-driven layout of the default block -- one teacher-forced
+forward of 3 utterances (5, 17 and 33 phonemes, synthetic weights):
+
+    python tools/forward_digest.py [--root TREE] [--names FILE.json]
+
+prints `<case> <sha256 over before, after, d, e, p>`; --names also writes the ordered profile names of each case's launches.  --root runs another checkout's
+package (built there) with this file's cases: run it on the parent commit twice and on the tree under test, on one machine; where the parent equals itself the
+tree must equal the parent (profiles/model_launches_digest.txt).  tests/test_gpu_parity.py compares launch_names() with the names recorded from the parent
+(profiles/model_launches_names_parent.json)."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+BLOCKS = {"default": {}, "pre_ln_concat": dict(encoder_normalize_before=True, decoder_normalize_before=True, encoder_concat_after=True, decoder_concat_after=True)}
+MODES = ("fp32", "bf16x3", "mix_mx", "mix_mx4")
+TLENS = [5, 17, 33]
+
+
+def case_id(block, precision, row8):
+    return "%s/%s/%s" % (block, precision, "row8" if row8 else "auto")
+
+
+def make_model(block):
+    import torch  # noqa: F401
+    from fastspeech2_amd import FeedForwardTransformer, default_hparams, N_PHONEME_SYMBOLS
+    from fastspeech2_amd.synthetic import portable_state_dict
+    hp = default_hparams()
+    for k, v in BLOCKS[block].items():
+        hp.model[k] = v
+    model = FeedForwardTransformer(N_PHONEME_SYMBOLS, hp.audio.num_mels, hp).eval()
+    model.load_state_dict(portable_state_dict(model.state_dict(), seed=3))
+    return model.to("cuda:0")
+
+
+def make_inputs():
+    from fastspeech2_amd.synthetic import make_batch
+    b = make_batch("c2", seed=11, B=len(TLENS), tlens=TLENS)      # (durations from the synthetic Gamma fit: about 8 frames per phoneme)
+    return {k: (v.cuda() if k in ("xs", "ds", "es", "ps") else v) for k, v in b.items()}
+
+
+def forward(model, b, precision, row8, profile=False):
+    """One teacher-forced forward -> (dict of outputs, ordered profile names or None).  FS2_ROW8 is restored to automatic afterwards."""
+    import torch
+    from fastspeech2_amd import _lib
+    want = ("before", "after", "e_outs", "p_outs")
+    model.precision = precision
+    _lib.set_option("FS2_ROW8", 1 if row8 else -1)
+    try:
+        with torch.no_grad():
+            r = model._run(b["xs"], b["ilens"], b["olens"], b["ds"], b["es"], b["ps"], is_inference=False, want=want)      # (creates the handle on first use)
+            names = None
+            if profile:
+                model.set_profiling(True)
+                try:
+                    r = model._run(b["xs"], b["ilens"], b["olens"], b["ds"], b["es"], b["ps"], is_inference=False, want=want)
+                    torch.cuda.synchronize()
+                    names = [n for n, *_ in model.get_profile()]
+                finally:
+                    model.set_profiling(False)
+        return {k: r[k] for k in want + ("d_log",)}, names
+    finally:
+        _lib.set_option("FS2_ROW8", -1)
+        model.precision = "fp32"
+
+
+def launch_names(model, b, precision, row8):
+    return forward(model, b, precision, row8, profile=True)[1]
+
+
+def digest(tensors):
+    import torch
+    h = hashlib.sha256()
+    for t in tensors:
+        torch.cuda.synchronize()
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package runs (default: this one)")
+    ap.add_argument("--names", help="write {case: [profile names]} here")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+    import fastspeech2_amd
+    print("# package:", os.path.dirname(os.path.abspath(fastspeech2_amd.__file__)))
+    b = make_inputs()
+    names = {}
+    for block in BLOCKS:
+        model = make_model(block)
+        for precision in MODES:
+            for row8 in (0, 1):
+                out, names[case_id(block, precision, row8)] = forward(model, b, precision, row8, profile=bool(args.names))
+                print(case_id(block, precision, row8), digest([out[k] for k in ("before", "after", "d_log", "e_outs", "p_outs")]), flush=True)
+            if block == "default":      # the device-driven layout (no host read-back between encode and decode): free-running decisions, given durations
+                model.precision = precision
+                with torch.no_grad():
+                    model.inference_batch(b["xs"], b["ilens"], d_override=b["ds"])
+                    res = model.inference_batch(b["xs"], b["ilens"], d_override=b["ds"], sync=False)
+                    ok = res.ok()
+                model.precision = "fp32"
+                print("%s/%s/device_layout" % (block, precision), digest([res[0], res[1]]) if ok else "capacity overflow", flush=True)
+    if args.names:
+        with open(args.names, "w") as f:
+            json.dump(names, f, indent=0, sort_keys=True)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
