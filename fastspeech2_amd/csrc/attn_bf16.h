@@ -22,11 +22,11 @@
 #pragma once
 #include "common.h"
 #include "gemm_bf16.h"
+#include "layout_rule.h"
 
 namespace fs2 {
 
-constexpr int kAttAlign = 8;    // utterance starts are multiples of this many rows: a 16-byte V^T load is 8 consecutive keys (rows).
-                                // (Round 1 used 32: an average of 12 more dead rows per utterance in every row-proportional kernel, 2.6 % at c3.)
+// (kAttAlign, the alignment of utterance starts that a 16-byte V^T load of 8 consecutive keys relies on, is layout_rule.h's)
 
 struct QkvSplitArgs {
     const float* qkv; int R; int Rvt; int D; int dk; float scale;
@@ -86,7 +86,7 @@ struct AttnB16Args {
     float* ctx; int ldc;                       // fp32 context [R][ldc] (or nullptr) ...
     void* ctxp; int ctxp_chunks;               // ... and / or split-bf16 planes, the A operand of the output projection (gemm_planes.h)
     const int* start; const int* len; const int* klen;
-    const int2* work;                          // (utterance, 128-query block) items, attn_f32.h: kAttBlk
+    const int2* work;                          // (utterance, 128-query block) items, layout_rule.h: kAttBlk
     const int* nwork;                          // device-driven layout: number of valid work items (the grid is a capacity), or nullptr
     int nitems;                                // host-driven layout: number of work items
     int D; int mask_q;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "gemm_args.h"
+#include "layout_rule.h"      // kGap, kMinGap, kTailRows, kAttAlign, kAttBlk, kXcds: the packed-row layout's constants
 
 namespace fs2 {
 
@@ -13,19 +14,15 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // (struct wrappers) larger than 64 bytes are not scalarised by hipcc and end up in scratch memory.
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kGap = 8;        // upper bound of the zero rows between packed sequences (capacity formulas); a model uses
-constexpr int kTailRows = 8;   // zero rows every layout appends behind its last utterance
-constexpr int kMinGap = 4;     // max(kMinGap, its largest conv halo (k - 1) / 2): 4 for the default 9-tap FFN (fs2_handle::gap)
 constexpr int kMaxHalo = 16;   // LDS rows reserved for conv halos (ktaps <= 17)
 constexpr int kBK = 32;        // K-chunk (channels per LDS stage) of the fp32 GEMMs
 constexpr int kLd = kBK + 4;   // LDS row stride in floats (16-B aligned, breaks the 128-B bank period)
 
-constexpr int kAttBQ = 64;   // queries per workgroup (4 waves x 16) of attn_f32 / attn_bf16
-constexpr int kAttBlk = 128; // queries per work-list item: one workgroup of attn_w32 (4 waves x 32), two of the 64-query kernels
+constexpr int kAttBQ = 64;   // queries per workgroup (4 waves x 16) of attn_f32 / attn_bf16; a work-list item is kAttBlk queries (layout_rule.h)
 
 // The 64-query kernels (attn_f32, attn_bf16) over the 128-query work list: grid.x = 2 x (items rounded up to a multiple of 8);
 // workgroup x serves half (x >> 3) & 1 of item 8 (x >> 4) + (x & 7), so x % 8 -- the XCD the workgroup runs on -- is the item's
-// position in the eight interleaved queues (fs2_runtime.hip: build_work_list) and the halves of an item are dispatched 8 apart.
+// position in the eight interleaved queues (layout_rule.h: Dealer) and the halves of an item are dispatched 8 apart.
 // Returns false when there is nothing to do; q0 = first query of the workgroup.
 inline unsigned att_grid64(int nitems) { return 2u * (unsigned)((nitems + 7) & ~7); }
 __device__ __forceinline__ bool att_item64(const int2* work, const int* nwork, int nitems, int& b, int& q0) {

@@ -1,144 +1,10 @@
-// HBM-bound kernels of the path: row metadata, embedding + positional encoding, duration post-op,
+// HBM-bound kernels of the path (the row metadata is layout.h's): embedding + positional encoding, duration post-op,
 // length regulator (prefix sum + expand), bucketize + embedding add, packed -> padded output copies.
 // All of them move whole rows with 16-byte accesses, one wavefront per row.
 #pragma once
 #include "common.h"
 
 namespace fs2 {
-
-// row_pos / row_seq for a gapped packed layout (start[] ascending).
-__global__ void build_row_meta(const int* start, const int* len, int B, int rpad, int* row_pos, int* row_seq) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= rpad) return;
-    int lo = 0, hi = B;   // first b with start[b] > row
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (start[mid] <= row) lo = mid + 1; else hi = mid;
-    }
-    const int b = lo - 1;
-    int pos = -1, seq = -1;
-    if (b >= 0 && row - start[b] < len[b]) { pos = row - start[b]; seq = b; }
-    row_pos[row] = pos;
-    row_seq[row] = seq;
-}
-
-// Frame-side layout built on the device from the frame counts the duration scan left there (device-driven mode of
-// fs2_decode: no host read-back).  Mirrors build_layout() / build_work_list() in fs2_runtime.hip exactly: 32-row aligned starts,
-// kGap zero rows between utterances, attention work list = (utterance, 64-query block) items in eight interleaved per-XCD queues,
-// utterances dealt longest-key-range first to the shortest queue, padding entries (-1, 0).
-// One workgroup.  dims = {rows used, work list length, overflow flags, longest utterance, valid frames}; pcum[b] = valid frames of the
-// utterances before b (row offset of utterance b in the packed output); 8 = kGap = kAttAlign, 128 = kAttBlk.
-__global__ __launch_bounds__(1024) void frame_layout_dev(const int* olens, int B, int compat, int masked, int row_cap, int work_cap,
-                                                         int lmax_cap, int pe_rows, int* start, int* len, int* klen, int* vlen,
-                                                         int* rank_tmp, int* woff_tmp, int* pcum, int2* work, int* dims, int* status = nullptr, int gap = 8) {
-    // The serial parts (row prefix with alignment, longest-first dealing to eight queues) run on one thread: their operands are staged
-    // in LDS first -- from global memory every iteration was a dependent round trip.  Round 2: 53 -> 28 us per call at B = 64 (one LDS
-    // atomic per wave instead of 1024 on one address; the dealing loop walks its operands front to back); what is left is seven
-    // barrier phases that each drain thread 0's global stores, and the launch.
-    constexpr int kStage = 4096;                      // utterances staged in LDS (beyond: the same code on the global arrays)
-    __shared__ int s_len[kStage], s_vlen[kStage], s_order[kStage];
-    __shared__ int s_max, s_min;
-    const int tid = threadIdx.x;
-    const bool staged = B <= kStage;
-    if (tid == 0) { s_max = 0; s_min = 0x7fffffff; }
-    __syncthreads();
-    int mx = 0, mn = 0x7fffffff;
-    for (int b = tid; b < B; b += 1024) { mx = max(mx, olens[b]); mn = min(mn, olens[b]); }
-    for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o)); mn = min(mn, __shfl_xor(mn, o)); }
-    if ((tid & 63) == 0) { atomicMax(&s_max, mx); atomicMin(&s_min, mn); }      // one LDS atomic per wave, not 1024 on one address
-    __syncthreads();
-    mx = s_max;
-    for (int b = tid; b < B; b += 1024) {
-        const int v = max(olens[b], 0);
-        const int l = compat ? mx : v;
-        vlen[b] = v;
-        len[b] = l;
-        klen[b] = compat ? (masked ? v : mx) : v;
-        if (staged) { s_vlen[b] = v; s_len[b] = l; }
-    }
-    for (int i = tid; i < work_cap; i += 1024) work[i] = make_int2(-1, 0);
-    __syncthreads();
-    // position of utterance b in the dealing order: longer key ranges first, ties in batch order
-    for (int b = tid; b < B; b += 1024) {
-        const int k = compat ? (masked ? max(olens[b], 0) : mx) : max(olens[b], 0);
-        int r = 0;
-        for (int j = 0; j < B; ++j) {
-            const int vj = staged ? s_vlen[j] : max(olens[j], 0);
-            const int kj = compat ? (masked ? vj : mx) : vj;
-            r += (kj > k) || (kj == k && j < b);
-        }
-        if (staged) s_order[r] = b; else rank_tmp[r] = b;
-    }
-    __syncthreads();
-    __shared__ int s_row, s_frames;
-    if (tid == 0) {
-        int row = gap;
-        int frames = 0;
-        for (int b = 0; b < B; ++b) {
-            row = (row + 7) & ~7;      // kAttAlign
-            start[b] = row;
-            row += (staged ? s_len[b] : len[b]) + gap;
-            pcum[b] = frames;
-            frames += staged ? s_vlen[b] : vlen[b];
-        }
-        s_row = row + 8; s_frames = frames;      // + kTailRows, as build_layout on the host
-    }
-    __syncthreads();
-    // blocks of 128 queries (kAttBlk) per utterance IN DEALING ORDER, so that the serial loop below walks two arrays front to back instead of
-    // chasing s_order[r] -> s_len[b] through LDS (two dependent round trips per utterance on one thread)
-    if (staged)
-        for (int r = tid; r < B; r += 1024) s_vlen[r] = (s_len[s_order[r]] + 127) >> 7;
-    __syncthreads();
-    if (tid == 0) {
-        const int row = s_row, frames = s_frames;
-        // (qlen is only ever indexed by unrolled constants: registers)
-        int qlen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int depth = 0;
-        for (int r = 0; r < B; ++r) {
-            const int b = staged ? s_order[r] : rank_tmp[r];
-            int j = 0, best = qlen[0];
-#pragma unroll
-            for (int t = 1; t < 8; ++t)
-                if (qlen[t] < best) { best = qlen[t]; j = t; }
-            woff_tmp[b] = best * 8 + j;           // list position of the utterance's first block; the next ones follow 8 apart
-            const int add = staged ? s_vlen[r] : ((len[b] + 127) >> 7);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) qlen[t] += (t == j) ? add : 0;
-            depth = max(depth, best + add);
-        }
-        int ovf = 0;
-        if (row > row_cap || depth * 8 > work_cap) ovf |= 1;
-        if (mx > lmax_cap) ovf |= 2;
-        if (mx > pe_rows) ovf |= 4;
-        if (s_min < 0) ovf |= 16;           // FS2_OVF_BAD_ID: dur_scan marked an utterance whose phoneme ids leave [0, idim)
-        else if (s_min <= 0) ovf |= 8;
-        dims[0] = row; dims[1] = ovf ? 0 : depth * 8; dims[2] = ovf; dims[3] = mx; dims[4] = frames; dims[5] = 0; dims[6] = 0; dims[7] = 0;
-        if (status) {     // the caller's copy of the same eight words
-            status[0] = row; status[1] = ovf ? 0 : depth * 8; status[2] = ovf; status[3] = mx; status[4] = frames; status[5] = 0; status[6] = 0; status[7] = 0;
-        }
-    }
-    __syncthreads();
-    if (dims[2] != 0) {           // a capacity is too small: leave an empty layout (all rows are gap rows, no work) so that
-        for (int b = tid; b < B; b += 1024) { start[b] = 8; len[b] = 0; klen[b] = 0; vlen[b] = 0; }    // nothing indexes out of range
-        return;
-    }
-    for (int b = tid; b < B; b += 1024) {
-        const int nq = (len[b] + 127) >> 7, o = woff_tmp[b];
-        for (int q = 0; q < nq; ++q) work[o + 8 * q] = make_int2(b, q);
-    }
-}
-
-// reduction_factor r > 1: the Postnet's row layout = the decoder's with every row expanded to r rows
-__global__ void scale_layout(const int* start, const int* len, const int* vlen, const int* dims, int B, int r, int* start2, int* len2,
-                             int* vlen2, int* dims2) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) { start2[b] = start[b] * r; len2[b] = len[b] * r; vlen2[b] = vlen[b] * r; }
-    if (b == 0 && dims != nullptr) {
-        dims2[0] = dims[0] * r;      // rows in use
-#pragma unroll
-        for (int i = 1; i < 8; ++i) dims2[i] = dims[i];
-    }
-}
 
 // h[row] = E[xs[b, t]] * xscale + alpha * pe[t]      (reference encoder.py:196, embedding.py:77-80,105-120)
 __global__ __launch_bounds__(256) void embed_pe(const int64_t* xs, int Tmax, const float* E, int idim, int D,

@@ -1,6 +1,6 @@
 // libfs2_hip.so -- runtime + C ABI (include/fs2.h) of the MI355X FastSpeech2 mel-generation path.
 // Orchestrates the kernels over the gapped packed row layout: gemm_planes.h / attn_bf16.h (split-bf16 and bf16 modes, activations as
-// planes), gemm_f32.h / attn_f32.h (exact fp32 mode), elementwise.h (HBM-bound steps, device-side layout).  Weight repacking at load
+// planes), gemm_f32.h / attn_f32.h (exact fp32 mode), elementwise.h (HBM-bound steps), layout.h (the layout, host- and device-built).  Weight repacking at load
 // time, workspace carving (no allocation inside a forward), host- or device-driven frame layout, per-launch hipEvent profiling.
 // Replaces the tensor work of reference fastspeech.py:169-243 (`FeedForwardTransformer._forward`).
 #include <hip/hip_runtime.h>
@@ -24,6 +24,8 @@
 #include "attn_f32.h"
 #include "common.h"
 #include "elementwise.h"
+#include "layout_rule.h"
+#include "layout.h"
 #include "gemm_bf16.h"
 #include "gemm_plan.h"
 #include "gemm_planes.h"
@@ -40,8 +42,6 @@ using namespace fs2;
 namespace {
 
 std::string g_create_error;
-
-constexpr int kXcds = 8;      // MI355X: 8 accelerator dies, workgroups of a launch are dealt to them round-robin
 
 // struct Options -- the A/B switches of the kernel choice -- lives in gemm_plan.h; it is read from the environment ONCE, here, when the library is first used.
 int env_int(const char* name, int dflt) {
@@ -197,20 +197,6 @@ struct DeviceGuard {
         if (err == hipSuccess && prev != dev) { err = hipSetDevice(dev); switched = (err == hipSuccess); }
     }
     ~DeviceGuard() { if (switched) hipSetDevice(prev); }
-};
-
-struct HostLayout {
-    int B = 0, R = 0, Rpad = 0;
-    std::vector<int> start, len, klen, vlen;
-    std::vector<int2> work;
-    int work_cap = -1;      // device-driven layout: R / Rpad / work_cap are capacities, the vectors stay empty
-    int nwork() const { return work_cap >= 0 ? work_cap : (int)work.size(); }
-};
-struct DevLayout {
-    int *start = nullptr, *len = nullptr, *klen = nullptr, *vlen = nullptr, *row_pos = nullptr, *row_seq = nullptr;
-    int2* work = nullptr;
-    int* dims = nullptr;    // device-driven layout: {rows used, work items, overflow flags, longest utterance, valid frames, 0, 0, 0}
-    int* pcum = nullptr;    // device-driven layout: valid frames before each utterance (packed-output row offsets)
 };
 
 struct ProfRec { std::string name; hipEvent_t e0, e1; double flops, bytes; };
@@ -592,49 +578,11 @@ int launch_attention_b16(fs2_handle* h, hipStream_t s, const char* name, const f
     return FS2_OK;
 }
 
-// ------------------------------------------------------------------ layouts
-// Attention work list = (utterance, 128-query block) items (kAttBlk: one workgroup of attn_w32, two of the 64-query kernels),
-// dispatched in list order.  Two goals:
-//  * XCD locality: workgroup i of a launch runs on XCD i % 8 (round-robin dispatch) and every XCD has its own L2.  All query
-//    blocks of one utterance stream the same K / V rows, so they are given to ONE XCD: the list is eight interleaved queues
-//    (entry 8 i + j = i-th item of queue j).  With the blocks of an utterance spread over all XCDs the K / V planes were
-//    fetched from HBM once per XCD: 830 MB per decoder-layer launch at c3 (PMC FETCH_SIZE), the whole 128 us of it.
-//  * balance: utterances go to the queues longest first, each to the currently shortest queue (LPT); queues are padded to
-//    the same length with (-1, 0) entries that exit at once.
-void build_work_list(const std::vector<int>& len, const std::vector<int>& klen, std::vector<int2>& work) {
-    const int B = (int)len.size();
-    std::vector<int> order(B);
-    for (int b = 0; b < B; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return klen[x] > klen[y]; });
-    std::vector<int2> q[kXcds];
-    for (int b : order) {
-        int j = 0;
-        for (int t = 1; t < kXcds; ++t) if (q[t].size() < q[j].size()) j = t;
-        for (int i = 0; i * kAttBlk < len[b]; ++i) q[j].push_back(make_int2(b, i));
-    }
-    size_t depth = 0;
-    for (int j = 0; j < kXcds; ++j) depth = std::max(depth, q[j].size());
-    work.assign(depth * kXcds, make_int2(-1, 0));
-    for (int j = 0; j < kXcds; ++j)
-        for (size_t i = 0; i < q[j].size(); ++i) work[i * kXcds + j] = q[j][i];
-}
+// ------------------------------------------------------------------ layouts (layout.h builds them, layout_rule.h places them in `meta`)
+static_assert(kOvfRows == FS2_OVF_ROWS && kOvfLmax == FS2_OVF_LMAX && kOvfPe == FS2_OVF_PE && kOvfEmpty == FS2_OVF_EMPTY && kOvfBadId == FS2_OVF_BAD_ID,
+              "layout_rule.h restates these");
 
-void build_layout(HostLayout& L, int B, const std::vector<int>& len, const std::vector<int>& klen, const std::vector<int>& vlen, int gap) {
-    L.B = B; L.len = len; L.klen = klen; L.vlen = vlen;
-    L.start.resize(B);
-    int row = gap;
-    for (int b = 0; b < B; ++b) {
-        row = round_up(row, kAttAlign);     // aligned starts: 16-byte aligned V^T key tiles (attn_bf16.h)
-        L.start[b] = row;
-        row += len[b] + gap;
-    }
-    row += kTailRows;        // zero rows behind the last utterance (attn_bf16.h: V^T vectors that straddle the last key)
-    L.R = row;
-    L.Rpad = round_up(row, 128);
-    build_work_list(len, klen, L.work);
-}
-
-size_t layout_dev_ints(const HostLayout& L) { return (size_t)7 * L.B + 2 * (size_t)L.Rpad + 2 * (size_t)L.nwork() + 64 + 16; }
+size_t layout_dev_ints(const HostLayout& L) { return (size_t)MetaDev::ints(L.B, L.Rpad, L.nwork()); }
 
 // uploads start/len/klen/vlen/work, then derives row_pos/row_seq on the device
 int upload_layout(fs2_handle* h, hipStream_t s, const HostLayout& L, int* dev, DevLayout& D) {
@@ -658,11 +606,10 @@ int upload_layout(fs2_handle* h, hipStream_t s, const HostLayout& L, int* dev, D
         src = pin;
     }
     HIP_TRY(h, hipMemcpyAsync(dev, src, host.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    D.start = dev; D.len = dev + L.B; D.klen = dev + 2 * L.B; D.vlen = dev + 3 * L.B;
-    D.work = reinterpret_cast<int2*>(dev + 4 * L.B);
-    int* rest = dev + 4 * L.B + 2 * L.work.size();
-    rest = reinterpret_cast<int*>(align_up(reinterpret_cast<size_t>(rest), 16));
-    D.row_pos = rest; D.row_seq = rest + L.Rpad;
+    const MetaHost m = MetaHost::at(L.B, L.Rpad, L.nwork());
+    D.start = dev + m.start; D.len = dev + m.len; D.klen = dev + m.klen; D.vlen = dev + m.vlen;
+    D.work = reinterpret_cast<int2*>(dev + m.work);
+    D.row_pos = dev + m.row_pos; D.row_seq = dev + m.row_seq;
     hipLaunchKernelGGL(build_row_meta, dim3((L.Rpad + 255) / 256), dim3(256), 0, s, D.start, D.len, L.B, L.Rpad, D.row_pos, D.row_seq);
     HIP_TRY(h, hipGetLastError());
     return FS2_OK;
@@ -671,18 +618,13 @@ int upload_layout(fs2_handle* h, hipStream_t s, const HostLayout& L, int* dev, D
 // device-driven variant: the layout arrays are produced by frame_layout_dev from the device frame counts
 int device_layout(fs2_handle* h, hipStream_t s, const HostLayout& L, int* dev, DevLayout& D, const int* olens32, int compat, int masked,
                   int lmax_cap, int pe_rows, int* status) {
-    D.start = dev; D.len = dev + L.B; D.klen = dev + 2 * L.B; D.vlen = dev + 3 * L.B;
-    int* rank_tmp = dev + 4 * L.B;
-    int* woff_tmp = dev + 5 * L.B;
-    D.pcum = dev + 6 * L.B;
-    int* rest = reinterpret_cast<int*>(align_up(reinterpret_cast<size_t>(dev + 7 * L.B), 16));
-    D.dims = rest; rest += 16;
-    D.work = reinterpret_cast<int2*>(rest);
-    rest += 2 * (size_t)L.nwork();
-    rest = reinterpret_cast<int*>(align_up(reinterpret_cast<size_t>(rest), 16));
-    D.row_pos = rest; D.row_seq = rest + L.Rpad;
-    hipLaunchKernelGGL(frame_layout_dev, dim3(1), dim3(1024), 0, s, olens32, L.B, compat, masked, L.R, L.nwork(), lmax_cap, pe_rows,
-                       D.start, D.len, D.klen, D.vlen, rank_tmp, woff_tmp, D.pcum, D.work, D.dims, status, h ? h->gap : kGap);
+    const MetaDev m = MetaDev::at(L.B, L.Rpad, L.nwork());
+    D.start = dev + m.start; D.len = dev + m.len; D.klen = dev + m.klen; D.vlen = dev + m.vlen;
+    D.pcum = dev + m.pcum; D.dims = dev + m.dims;
+    D.work = reinterpret_cast<int2*>(dev + m.work);
+    D.row_pos = dev + m.row_pos; D.row_seq = dev + m.row_seq;
+    hipLaunchKernelGGL(frame_layout_dev, dim3(1), dim3(kLayoutThreads), 0, s, olens32, L.B, compat, masked, L.R, L.nwork(), lmax_cap, pe_rows,
+                       D.start, D.len, D.klen, D.vlen, dev + m.rank, dev + m.woff, D.pcum, D.work, D.dims, status, h ? h->gap : kGap);
     hipLaunchKernelGGL(build_row_meta, dim3((L.Rpad + 255) / 256), dim3(256), 0, s, D.start, D.len, L.B, L.Rpad, D.row_pos, D.row_seq);
     HIP_TRY(h, hipGetLastError());
     return FS2_OK;
@@ -1089,63 +1031,46 @@ inline long regime_tokens_of(const fs2_batch& b, bool token_level) {
 }
 inline int regime_rows_of(const fs2_batch& b, bool token_level) {
     const long utts = b.regime_utterances > 0 ? b.regime_utterances : b.B;
-    return (int)std::min<long>((token_level ? 1 : 8) * regime_tokens_of(b, token_level) + utts * (kGap + kAttAlign) + kGap, INT32_MAX - 256);
+    return row_bound((token_level ? 1 : 8) * regime_tokens_of(b, token_level), utts);
 }
 
-void token_layout(const fs2_batch& b, HostLayout& L, int gap) {
-    std::vector<int> len(b.B), klen(b.B), vlen(b.B);
-    for (int i = 0; i < b.B; ++i) {
-        vlen[i] = klen[i] = (int)b.ilens[i];
-        len[i] = b.compat_padded ? b.Tmax : (int)b.ilens[i];
-    }
-    build_layout(L, b.B, len, klen, vlen, gap);
-}
-
-struct TokenPlan {   // offsets inside the token workspace
-    size_t total;
+struct TokenBufs {
+    int* meta; StackBufs sb; float *p0, *p1, *dlog_rows; int64_t* dint; int *cum, *o32;
+    float* kp; size_t kp_cap;
+    float* tokp;      // tok.proj's output rows (nullptr: this model or precision has none)
 };
 
 // carve the token workspace; if ws == nullptr only sizes it
-size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L, void* ws, size_t cap, int** meta, StackBufs* sb,
-                    float** p0, float** p1, float** dlog_rows, int64_t** dint, int** cum, int** olens32, bool* ok, float** kp = nullptr, size_t* kp_cap = nullptr, float** tokp = nullptr) {
+size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L, void* ws, size_t cap, TokenBufs* tb, bool* ok) {
     Bump bp(ws, cap);
     const size_t R = L.Rpad;
-    int* m = bp.take<int>(layout_dev_ints(L));
-    float* x0 = bp.take<float>(R * c.adim);
-    float* x1 = bp.take<float>(R * c.adim);
+    TokenBufs t;
+    t.meta = bp.take<int>(layout_dev_ints(L));
+    t.sb.x0 = bp.take<float>(R * c.adim);
+    t.sb.x1 = bp.take<float>(R * c.adim);
     const size_t eDp = att_width(c.adim, c.aheads);      // attention width: heads x padded head dim
-    float* qkv = bp.take<float>(R * 3 * eDp);
-    float* ctx = bp.take<float>(R * eDp);
-    float* hid = bp.take<float>(R * (size_t)round_up(c.eunits, 32));     // bf16 modes: hidden layer as planes (32-channel chunks)
-    __bf16* qkh = bp.take<__bf16>(R * 2 * eDp);
-    __bf16* qkl = bp.take<__bf16>(R * 2 * eDp);
-    __bf16* vth = bp.take<__bf16>(R * eDp);
-    __bf16* vtl = bp.take<__bf16>(R * eDp);
+    t.sb.qkv = bp.take<float>(R * 3 * eDp);
+    t.sb.ctx = bp.take<float>(R * eDp);
+    t.sb.hid = bp.take<float>(R * (size_t)round_up(c.eunits, 32));     // bf16 modes: hidden layer as planes (32-channel chunks)
+    t.sb.qkh = bp.take<__bf16>(R * 2 * eDp);
+    t.sb.qkl = bp.take<__bf16>(R * 2 * eDp);
+    t.sb.vth = bp.take<__bf16>(R * eDp);
+    t.sb.vtl = bp.take<__bf16>(R * eDp);
     const size_t pw = round_up(c.adim, 32);
-    float* x0p = bp.take<float>(R * pw);
-    float* x1p = bp.take<float>(R * pw);
-    float* xps = bp.take<float>(R * (size_t)round_up(std::max(c.adim, c.dur_chans), 32));
-    float* q0 = bp.take<float>(R * c.dur_chans);
-    float* q1 = bp.take<float>(R * c.dur_chans);
-    float* dl = bp.take<float>(R);
-    int64_t* di = bp.take<int64_t>((size_t)b.B * b.Tmax);
-    int* cu = bp.take<int>((size_t)b.B * b.Tmax);
-    int* o32 = bp.take<int>(b.B);
-    const size_t kcap = (size_t)4 * std::min<size_t>(R, kSplitRows) * 1024;
-    float* kpb = bp.take<float>(kcap);
+    t.sb.x0p = bp.take<float>(R * pw);
+    t.sb.x1p = bp.take<float>(R * pw);
+    t.sb.xps = bp.take<float>(R * (size_t)round_up(std::max(c.adim, c.dur_chans), 32));
+    t.p0 = bp.take<float>(R * c.dur_chans);
+    t.p1 = bp.take<float>(R * c.dur_chans);
+    t.dlog_rows = bp.take<float>(R);
+    t.dint = bp.take<int64_t>((size_t)b.B * b.Tmax);
+    t.cum = bp.take<int>((size_t)b.B * b.Tmax);
+    t.o32 = bp.take<int>(b.B);
+    t.kp_cap = (size_t)4 * std::min<size_t>(R, kSplitRows) * 1024;
+    t.kp = bp.take<float>(t.kp_cap);
     // tok.proj's output rows (taken last: every other offset is as it was; none in fp32, which never takes the path)
-    float* tkp = (tok_proj_cols(c) && b.precision != FS2_PREC_FP32) ? bp.take<float>(R * (size_t)tok_proj_cols(c)) : nullptr;
-    if (tokp) *tokp = tkp;
-    if (kp) *kp = kpb;
-    if (kp_cap) *kp_cap = kcap;
-    if (meta) *meta = m;
-    if (sb) { sb->x0 = x0; sb->x1 = x1; sb->qkv = qkv; sb->ctx = ctx; sb->hid = hid; sb->qkh = qkh; sb->qkl = qkl; sb->vth = vth; sb->vtl = vtl; sb->x0p = x0p; sb->x1p = x1p; sb->xps = xps; }
-    if (p0) *p0 = q0;
-    if (p1) *p1 = q1;
-    if (dlog_rows) *dlog_rows = dl;
-    if (dint) *dint = di;
-    if (cum) *cum = cu;
-    if (olens32) *olens32 = o32;
+    t.tokp = (tok_proj_cols(c) && b.precision != FS2_PREC_FP32) ? bp.take<float>(R * (size_t)tok_proj_cols(c)) : nullptr;
+    if (tb) *tb = t;
     if (ok) *ok = bp.ok();
     return align_up(bp.off, 256);
 }
@@ -1188,7 +1113,7 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
     f.before = bp.take<float>(R * rf * c.odim);
     f.after = bp.take<float>(R * rf * c.odim);
     if (rf > 1) {
-        f.meta2 = bp.take<int>(4 * (size_t)L.B + 2 * R * rf + 64);
+        f.meta2 = bp.take<int>((size_t)Meta2::ints(L.B, R * rf));
         f.pa2 = bp.take<float>(R * rf * c.postnet_chans);
         f.pb2 = bp.take<float>(R * rf * c.postnet_chans);
         f.xps2 = bp.take<float>(R * rf * (size_t)round_up(std::max(c.postnet_chans, c.odim), 32));
@@ -1201,18 +1126,6 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
     if (fb) *fb = f;
     if (ok) *ok = bp.ok();
     return align_up(bp.off, 256);
-}
-
-void frame_layout(const fs2_batch& b, const int64_t* olens, int masked, HostLayout& L, int gap) {
-    std::vector<int> len(b.B), klen(b.B), vlen(b.B);
-    int mx = 0;
-    for (int i = 0; i < b.B; ++i) mx = std::max(mx, (int)olens[i]);
-    for (int i = 0; i < b.B; ++i) {
-        vlen[i] = (int)olens[i];
-        len[i] = b.compat_padded ? mx : vlen[i];
-        klen[i] = b.compat_padded ? (masked ? vlen[i] : mx) : vlen[i];
-    }
-    build_layout(L, b.B, len, klen, vlen, gap);
 }
 
 template <typename T>
@@ -1422,7 +1335,7 @@ size_t fs2_token_workspace_bytes(const fs2_handle* h, const fs2_batch* b) {
     if (!h || !b || b->B <= 0 || !b->ilens) return 0;
     HostLayout L;
     token_layout(*b, L, h->gap);
-    return carve_tokens(h->cfg, *b, L, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return carve_tokens(h->cfg, *b, L, nullptr, 0, nullptr, nullptr);
 }
 
 int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
@@ -1444,12 +1357,14 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     const HostLayout& L = h->tok;
     if (L.len.size() && *std::max_element(L.len.begin(), L.len.end()) > h->enc.pe_rows)
         return fail(h, FS2_ERR_ARG, "sequence longer than the positional table (%d rows): extend `pe` and reload", h->enc.pe_rows);
-    int* meta; StackBufs sb; float *p0, *p1, *dlog_rows, *tokp; int64_t* dint; int* cum; int* o32; bool ok;
-    carve_tokens(c, b, L, io->workspace, io->workspace_bytes, &meta, &sb, &p0, &p1, &dlog_rows, &dint, &cum, &o32, &ok, &h->kp, &h->kp_cap, &tokp);
+    TokenBufs t; bool ok;
+    carve_tokens(c, b, L, io->workspace, io->workspace_bytes, &t, &ok);
     if (!ok) return fail(h, FS2_ERR_WORKSPACE, "fs2_encode: workspace too small");
+    h->kp = t.kp; h->kp_cap = t.kp_cap;
+    const StackBufs& sb = t.sb;
     const int tok_regime = regime_rows_of(b, /*token_level=*/true);
     h->cur_regime = tok_regime; h->cur_status = nullptr;
-    if ((rc = upload_layout(h, s, L, meta, h->dtok))) return rc;
+    if ((rc = upload_layout(h, s, L, t.meta, h->dtok))) return rc;
     const DevLayout& dl = h->dtok;
     const bool enc_pl = prec != FS2_PREC_FP32;   // activations also travel as planes (x0p holds those of x0 before and after the stack)
     {
@@ -1461,13 +1376,13 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     }
     const Rows rows{L.R, L.Rpad, dl.row_pos, dl.dims, tok_regime};
     if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, rows, L, dl, /*mask_q=*/1, sb, prec, /*x0p_ready=*/enc_pl && c.adim % 32 == 0, ffn_terms))) return rc;
-    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, p0, p1, dlog_rows, prec, enc_pl ? sb.x0p : nullptr, sb.xps))) return rc;
+    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, t.p0, t.p1, t.dlog_rows, prec, enc_pl ? sb.x0p : nullptr, sb.xps))) return rc;
     {
         Scope sc(h, s, "dur.post", 0, 0);
         const int n = b.B * b.Tmax;
-        hipLaunchKernelGGL(dur_finalize, dim3((n + 255) / 256), dim3(256), 0, s, dlog_rows, dl.start, dl.vlen, b.B, b.Tmax, io->d_log, dint, io->d_int);
+        hipLaunchKernelGGL(dur_finalize, dim3((n + 255) / 256), dim3(256), 0, s, t.dlog_rows, dl.start, dl.vlen, b.B, b.Tmax, io->d_log, t.dint, io->d_int);
         HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(dur_scan, dim3(b.B), dim3(256), 0, s, io->ds ? io->ds : dint, b.Tmax, dl.vlen, cum, io->olens, o32,
+        hipLaunchKernelGGL(dur_scan, dim3(b.B), dim3(256), 0, s, io->ds ? io->ds : t.dint, b.Tmax, dl.vlen, t.cum, io->olens, t.o32,
                            io->duration_alpha > 0.f ? io->duration_alpha : 1.f, io->xs, c.idim);
         HIP_TRY(h, hipGetLastError());
     }
@@ -1477,19 +1392,19 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     // tok.proj: the encoder rows times the stacked weights of the predictors' first convolution (one k = 1 product per tap) and of the decoder input layer, once
     // per token instead of once per frame (fs2_decode: var.gather0 / dec.in.gather).  One kernel whatever the batch (64-row tiles, N > 1024: never split-K).
     h->tokP = nullptr; h->tokP_conv = false;
-    if (enc_pl && h->tokw.N && tokp && opts().tokproj) {
+    if (enc_pl && h->tokw.N && t.tokp && opts().tokproj) {
         // the predictors' columns only where fs2_decode can use them (bit 0 and the fused predictors); else the launch is sliced to the input layer's columns
         // (a multiple of 128 rows into the weight images: whole tiles)
         const bool conv = (opts().tokproj & 1) && opts().fuse_var;
         const int n0 = conv ? 0 : 6 * c.var_chans;
         const Gemm g = gemm_rows_from(h->tokw, n0);
-        GemmArgs a = gemm_args(g, sb.x0, c.adim, L.R, dl.row_pos, tokp + n0, h->tokw.N);
+        GemmArgs a = gemm_args(g, sb.x0, c.adim, L.R, dl.row_pos, t.tokp + n0, h->tokw.N);
         a.Xp = sb.x0p; a.xp_scratch = sb.xps;
         a.kpart = h->kp; a.kpart_cap = 0;      // never split-K (no partial buffers allowed): one kernel whatever the batch or the slice
         if ((rc = launch_gemm(h, s, "tok.proj", a, opts().tokproj_f32 ? FS2_PREC_FP32 : prec))) return rc;
-        h->tokP = tokp; h->tokP_conv = conv;
+        h->tokP = t.tokp; h->tokP_conv = conv;
     }
-    h->enc_final = sb.x0; h->cum = cum; h->o32 = o32; h->enc_B = b.B; h->enc_Tmax = b.Tmax; h->enc_compat = b.compat_padded;
+    h->enc_final = sb.x0; h->cum = t.cum; h->o32 = t.o32; h->enc_B = b.B; h->enc_Tmax = b.Tmax; h->enc_compat = b.compat_padded;
     h->enc_ntok = 0;
     for (int i = 0; i < b.B; ++i) h->enc_ntok += (long)b.ilens[i];
     h->enc_ws = io->workspace;
@@ -1507,14 +1422,7 @@ size_t fs2_frame_workspace_bytes(const fs2_handle* h, const fs2_batch* b, const 
 // device-driven layout: every utterance start is rounded up to kAttAlign rows and followed by kGap zero rows
 int64_t fs2_row_capacity(const fs2_batch* b, int64_t total_frames_bound) {
     if (!b || b->B <= 0 || total_frames_bound <= 0) return 0;
-    return round_up((int)std::min<int64_t>(total_frames_bound + (int64_t)b->B * (kGap + kAttAlign) + kGap, INT32_MAX - 256), 128);
-}
-
-void capacity_layout(const fs2_batch& b, int64_t row_capacity, int lmax_cap, HostLayout& L) {
-    L.B = b.B; L.R = (int)row_capacity; L.Rpad = round_up((int)row_capacity, 128);
-    // eight LPT queues: none is longer than the mean plus one utterance's items
-    L.work_cap = kXcds * (((int)(row_capacity / kAttBlk) + b.B + kXcds - 1) / kXcds + lmax_cap / kAttBlk + 2);
-    L.start.clear(); L.len.clear(); L.klen.clear(); L.vlen.clear(); L.work.clear();
+    return rows_padded(row_bound(total_frames_bound, b->B));
 }
 
 size_t fs2_frame_workspace_bytes_cap(const fs2_handle* h, const fs2_batch* b, int64_t row_capacity, int32_t lmax_cap) {
@@ -1676,12 +1584,11 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
     const int R2 = R * rf;
     DevLayout dl2 = dl;
     if (rf > 1) {
-        int* m = f.meta2;
-        dl2.start = m; dl2.len = m + b.B; dl2.vlen = m + 2 * b.B; dl2.klen = dl2.len;
-        int* rest = reinterpret_cast<int*>(align_up(reinterpret_cast<size_t>(m + 3 * b.B), 16));
-        dl2.dims = dl.dims ? rest : nullptr; rest += 16;
         const int Rpad2 = L.Rpad * rf;
-        dl2.row_pos = rest; dl2.row_seq = rest + Rpad2;
+        const Meta2 m = Meta2::at(b.B, Rpad2);
+        dl2.start = f.meta2 + m.start; dl2.len = f.meta2 + m.len; dl2.vlen = f.meta2 + m.vlen; dl2.klen = dl2.len;
+        dl2.dims = dl.dims ? f.meta2 + m.dims : nullptr;
+        dl2.row_pos = f.meta2 + m.row_pos; dl2.row_seq = f.meta2 + m.row_seq;
         hipLaunchKernelGGL(scale_layout, dim3((b.B + 255) / 256), dim3(256), 0, s, dl.start, dl.len, dl.vlen, dl.dims, b.B, rf, dl2.start, dl2.len, dl2.vlen, dl2.dims);
         hipLaunchKernelGGL(build_row_meta, dim3((Rpad2 + 255) / 256), dim3(256), 0, s, dl2.start, dl2.len, b.B, Rpad2, dl2.row_pos, dl2.row_seq);
         HIP_TRY(h, hipGetLastError());

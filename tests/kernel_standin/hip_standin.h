@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <thread>
 #include <vector>
@@ -20,15 +21,18 @@
 #define __launch_bounds__(x)
 struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1) : x(a) {} };
 inline thread_local dim3 threadIdx, blockIdx, blockDim;
+struct int2 { int x, y; };
+inline int2 make_int2(int x, int y) { return int2{x, y}; }
+constexpr int kStandinWaves = 16;      // a workgroup of up to 1024 threads
 typedef void* hipStream_t;
 typedef int hipError_t;
 constexpr int hipSuccess = 0;
 inline hipError_t hipGetLastError() { return 0; }
 inline const char* hipGetErrorString(hipError_t) { return "?"; }
 inline std::barrier<>* g_block_bar;
-inline std::barrier<>* g_wave_bar[4];
+inline std::barrier<>* g_wave_bar[kStandinWaves];
 inline std::atomic<int> g_or{0};
-alignas(16) inline unsigned char g_shfl[4][64][16];
+alignas(16) inline unsigned char g_shfl[kStandinWaves][64][16];
 inline void __syncthreads() { g_block_bar->arrive_and_wait(); }
 inline int __syncthreads_or(int v) {
     if (v) g_or.store(1);
@@ -57,6 +61,16 @@ inline uint32_t atomicMin(uint32_t* p, uint32_t v) {
     while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
     return o;
 }
+inline int atomicMin(int* p, int v) {
+    int o = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return o;
+}
+inline int atomicMax(int* p, int v) {
+    int o = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return o;
+}
 inline uint32_t __float_as_uint(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 inline float __uint_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 inline float __fadd_rn(float a, float b) { volatile float r = a + b; return r; }
@@ -65,8 +79,10 @@ inline float __fmul_rn(float a, float b) { volatile float r = a * b; return r; }
 using std::min; using std::max; using std::isfinite;
 template <typename K, typename... A> void launch(K k, dim3 grid, dim3 blk, A... a) {
     for (unsigned b = 0; b < grid.x; ++b) {
-        std::barrier<> bb(blk.x), w0(64), w1(64), w2(64), w3(64);
-        g_block_bar = &bb; g_wave_bar[0] = &w0; g_wave_bar[1] = &w1; g_wave_bar[2] = &w2; g_wave_bar[3] = &w3;
+        std::barrier<> bb(blk.x);
+        std::deque<std::barrier<>> wb;
+        g_block_bar = &bb;
+        for (int w = 0; w < kStandinWaves; ++w) g_wave_bar[w] = &wb.emplace_back(64);
         std::vector<std::thread> ts;
         for (unsigned t = 0; t < blk.x; ++t)
             ts.emplace_back([=] { threadIdx = dim3(t); blockIdx = dim3(b); blockDim = blk; k(a...); });

@@ -542,6 +542,56 @@ def test_device_driven_layout_random_batches(env, seed):
         model.precision = "fp32"
 
 
+@pytest.mark.parametrize("B", [1, 9, 17])
+def test_device_driven_layout_status_equals_the_rule(env, B):
+    """What frame_layout_dev reports -- rows in use, work-list length, longest utterance, valid frames -- equals what the layout rule,
+    restated in Python (tests/test_layout_host.py: parent_layout), gives for the frame counts read back; the mels equal the host-driven
+    call's bit for bit.  Forced durations: utterance 0 crosses the 128-frame attention block (20 phonemes x 7 frames); from B = 9 on,
+    utterances 1 and 2 have equal frame counts (12 x 5 and 15 x 4) and the rest are ragged."""
+    from tests.test_layout_host import parent_layout
+    model = env[0]
+    rs = np.random.RandomState(40 + B)
+    il = [20, 12, 15][:B] + rs.randint(1, 40, size=max(B - 3, 0)).tolist()
+    per = [7, 5, 4][:B] + rs.randint(1, 9, size=max(B - 3, 0)).tolist()
+    T = max(il)
+    xs = torch.zeros(B, T, dtype=torch.long)
+    ds = torch.zeros(B, T, dtype=torch.long)
+    for b in range(B):
+        xs[b, :il[b]] = torch.from_numpy(rs.randint(1, 68, size=il[b]))
+        ds[b, :il[b]] = per[b]
+    xs, ds, il = xs.cuda(), ds.cuda(), torch.tensor(il)
+    c = model._cfg
+    gap = min(8, max(4, (max(c["ffn_kernel"], c["dur_kernel"], c["var_kernel"], c["postnet_filts"] if c["postnet_layers"] > 0 else 0) - 1) // 2))
+    model.precision = "bf16x3"
+    try:
+        with torch.no_grad():
+            ref, ol = model.inference_batch(xs, il, d_override=ds)
+            counts = ol.tolist()
+            assert counts[0] == 140 and (B < 3 or counts[1] == counts[2] == 60)
+            Lmax = max(counts)
+            r = model._run(xs, il, is_inference=True, want=("after",), d_override=ds, capacity=(sum(counts), Lmax))
+            st = r["status"].cpu().tolist()
+            want = parent_layout(counts, gap, 0, 0)
+            assert st[2] == 0, st
+            assert (st[0], st[1], st[3], st[4]) == (want["R"], len(want["work"]), Lmax, sum(counts)), (st, want["R"], len(want["work"]))
+            assert torch.equal(r["olens"].cpu(), ol) and torch.equal(r["after"][:, :Lmax], ref)
+    finally:
+        model.precision = "fp32"
+
+
+def test_workspace_sizes_are_the_parents():
+    """fs2_token_workspace_bytes, fs2_frame_workspace_bytes, fs2_row_capacity and fs2_frame_workspace_bytes_cap for three batches and two
+    configurations (default, reduction_factor = 2) equal the values recorded from the commit before csrc/layout_rule.h existed
+    (tools/layout_workspace_sizes.py --root; the queries need a handle, hence a device, but launch nothing)."""
+    import json
+    from tools import layout_workspace_sizes as W
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "layout_workspace_parent.json")) as f:
+        want = json.load(f)
+    got = W.sizes()
+    assert sorted(want) == sorted(W.CONFIGS) and all(len(want[c]) == 3 for c in want)
+    assert got == want
+
+
 def test_inference_second_call_uses_device_layout(env):
     """`inference(x)` (reference fastspeech.py:339-357): the first call learns the frames-per-phoneme ratio with the host-driven
     layout, later calls run sync-free inside capacities and read the frame count once at the end; same mel either way, and an
