@@ -23,8 +23,7 @@ constexpr int kAttBQ = 64;   // queries per workgroup (4 waves x 16) of attn_f32
 // The 64-query kernels (attn_f32, attn_bf16) over the 128-query work list: grid.x = 2 x (items rounded up to a multiple of 8);
 // workgroup x serves half (x >> 3) & 1 of item 8 (x >> 4) + (x & 7), so x % 8 -- the XCD the workgroup runs on -- is the item's
 // position in the eight interleaved queues (layout_rule.h: Dealer) and the halves of an item are dispatched 8 apart.
-// Returns false when there is nothing to do; q0 = first query of the workgroup.
-inline unsigned att_grid64(int nitems) { return 2u * (unsigned)((nitems + 7) & ~7); }
+// Returns false when there is nothing to do; q0 = first query of the workgroup.  (att_grid64, the grid's host arithmetic, is layout_rule.h's.)
 __device__ __forceinline__ bool att_item64(const int2* work, const int* nwork, int nitems, int& b, int& q0) {
     const int x = (int)blockIdx.x;
     const int item = ((x >> 4) << 3) | (x & 7);

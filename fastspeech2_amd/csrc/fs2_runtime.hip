@@ -22,6 +22,7 @@
 #include "attn_bf16.h"
 #include "attn_w32.h"
 #include "attn_f32.h"
+#include "attn_plan.h"
 #include "common.h"
 #include "elementwise.h"
 #include "layout_rule.h"
@@ -306,11 +307,12 @@ static_assert(kPlanErrArg == FS2_ERR_ARG && kPlanErrHip == FS2_ERR_HIP && kPlanE
               kPlanFp32 == FS2_PREC_FP32 && kPlanBf16x3 == FS2_PREC_BF16X3 && kPlanMaxHalo == kMaxHalo && kPlanBN == kB16BN && kPrecMixF16x2 == FS2_PREC_MIX_F16X2 &&
               kPrecMixF16x1 == FS2_PREC_MIX_F16X1 && kPrecMixMx == FS2_PREC_MIX_MX && kPrecMixMx4 == FS2_PREC_MIX_MX4, "gemm_plan.h and model_launches.h restate these");
 
-// One launcher for every GEMM kernel, keyed by the kernel: it owns the per-(kernel, device) flag of the LDS attribute.
-template <auto K>
-hipError_t launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, const GemmArgs& a) {
+// One launcher for every GEMM and attention kernel, keyed by the kernel: it owns the per-(kernel, device) flag of the LDS attribute.
+// lds_max: the most any launch of K asks for, where that is not the same for every launch (0: lds).
+template <auto K, class A>
+hipError_t launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, size_t lds_max = 0) {
     static LdsAttr attr;
-    allow_lds(reinterpret_cast<const void*>(K), lds, attr);
+    allow_lds(reinterpret_cast<const void*>(K), lds_max ? lds_max : lds, attr);
     hipLaunchKernelGGL(K, grid, block, lds, s, a);
     return hipGetLastError();
 }
@@ -323,7 +325,7 @@ hipError_t pick(int v, F&& f) {
     else return hipErrorInvalidValue;
 }
 // CV(X): the int that pick handed a generic lambda as its integral_constant parameter X, as a constant expression (a template argument).  A macro only
-// because `X.value` / `decltype(X)::value` of a lambda parameter is not usable as one by every compiler this builds with; it lives for run_plan alone.
+// because `X.value` / `decltype(X)::value` of a lambda parameter is not usable as one by every compiler this builds with; it lives for run_plan and run_attn_plan alone.
 #define CV(x) decltype(x)::value
 constexpr int row4_variant(int epi, int arith, int res) { return epi * 100 + arith * 10 + res; }      // gemm_row4_bf16's (EPI, ARITH, RES) as one case label
 
@@ -418,7 +420,6 @@ hipError_t run_plan(hipStream_t s, const GemmPlan& p, const GemmArgs& t) {
     }
     return hipErrorInvalidValue;
 }
-#undef CV
 
 // Plan (gemm_plan.h: which kernel, which tile, split-K, where the rows go), then execute: build the A planes if the producer did not, launch the
 // kernel on the arguments the plan implies, run ln_rows where the epilogue is a pass of its own.
@@ -466,114 +467,76 @@ int launch_gemm(fs2_handle* h, hipStream_t s, const char* name, GemmArgs a, int 
     return FS2_OK;
 }
 
-int launch_attention(fs2_handle* h, hipStream_t s, const char* name, const float* qkv, float* ctx, int D, int heads,
-                     const DevLayout& dl, int nwork, int mask_q, double flops, int dk_true = 0) {
-    const int dk = D / heads;      // (D = heads x padded head dim; dk_true: the model's head dim, for the softmax scale)
-    if (!dk_true) dk_true = dk;
-    AttnArgs a;
-    a.qkv = qkv; a.ld = 3 * D; a.ctx = ctx; a.ldc = D; a.start = dl.start; a.len = dl.len; a.klen = dl.klen;
-    a.work = dl.work; a.nwork = dl.dims ? dl.dims + 1 : nullptr; a.nitems = nwork; a.D = D; a.mask_q = mask_q; a.scale = 1.0f / sqrtf((float)dk_true);
-    if (nwork == 0) return FS2_OK;
-    Scope sc(h, s, name, flops, 0.0);
-    dim3 grid(att_grid64(nwork), heads);      // two 64-query workgroups per 128-query work item
-    if (dk == 128) {
-        static LdsAttr attr;
-        allow_lds(reinterpret_cast<const void*>(&attn_f32<128>), attn_lds_bytes<128>(), attr);
-        hipLaunchKernelGGL(attn_f32<128>, grid, dim3(256), attn_lds_bytes<128>(), s, a);
-    } else if (dk == 192) {
-        static LdsAttr attr;
-        allow_lds(reinterpret_cast<const void*>(&attn_f32<192>), attn_lds_bytes<192>(), attr);
-        hipLaunchKernelGGL(attn_f32<192>, grid, dim3(256), attn_lds_bytes<192>(), s, a);
-    } else if (dk == 64) {
-        static LdsAttr attr;
-        allow_lds(reinterpret_cast<const void*>(&attn_f32<64>), attn_lds_bytes<64>(), attr);
-        hipLaunchKernelGGL(attn_f32<64>, grid, dim3(256), attn_lds_bytes<64>(), s, a);
-    } else if (dk == 256) {
-        static LdsAttr attr;
-        allow_lds(reinterpret_cast<const void*>(&attn_f32<256>), attn_lds_bytes<256>(), attr);
-        hipLaunchKernelGGL(attn_f32<256>, grid, dim3(256), attn_lds_bytes<256>(), s, a);
-    } else {
-        return fail(h, FS2_ERR_UNSUPPORTED, "attention head dim %d not in {64,128,192,256} (the model path pads other head dims)", dk);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
-    return FS2_OK;
+// ------------------------------------------------------------------ self-attention: attn_plan.h decides, these run the decision
+static_assert(kPlanFp32 == FS2_PREC_FP32 && kPlanBf16x3 == FS2_PREC_BF16X3 && kPlanErrUnsupported == FS2_ERR_UNSUPPORTED && kAttBlk == 2 * kAttBQ, "attn_plan.h, att_grid64");
+
+// A self-attention launch: its pointers and the numbers the plan reads (c.qkv_rows and the plane distances: launch_attention takes them from the pointers).
+struct AttnIo {
+    const float* qkv = nullptr;                    // fp32 QKV rows [R, 3D]; nullptr: the projection has left the bf16 operands
+    float* ctx = nullptr; void* ctxp = nullptr;    // the context as fp32 rows [R, D] and / or (bf16 kernels) as planes
+    __bf16 *qkh = nullptr, *qkl = nullptr, *vth = nullptr, *vtl = nullptr;      // bf16 kernels: qk_hi/lo [Rvt][2D], vt_hi/lo [D][Rvt] (Rvt % 32 == 0)
+    const DevLayout* dl = nullptr;
+    int mask_q = 0; double flops = 0.0;
+    AttnCall c;
+    int *slow_count = nullptr, *slow_count2 = nullptr;      // attn_w32's counters of the handle and of the call in progress (launch_attention sets them)
+};
+
+// the layout fields AttnArgs and AttnB16Args share
+template <class A>
+void attn_layout_args(A& a, const AttnIo& io) {
+    const DevLayout& dl = *io.dl;
+    a.start = dl.start; a.len = dl.len; a.klen = dl.klen; a.work = dl.work;
+    a.nwork = dl.dims ? dl.dims + 1 : nullptr;      // device-driven layout: the count of valid items, next to the row count in dims
+    a.nitems = io.c.nwork; a.D = io.c.D; a.mask_q = io.mask_q;
 }
 
-template <int DK>
-hipError_t launch_attn_w32_t(hipStream_t s, dim3 grid, const AttnB16Args& a) {
-    static LdsAttr attr;
-    allow_lds(reinterpret_cast<const void*>(&attn_w32<DK>), attn_w32_lds_bytes<DK>(), attr);
-    hipLaunchKernelGGL((attn_w32<DK>), grid, dim3(256), attn_w32_lds_bytes<DK>(), s, a);
-    return hipGetLastError();
-}
-
-// attn_w32 (32 queries per wave, one wave per SIMD, 128-query workgroups) serves the split-bf16 launches whose grid fills the chip:
-// below kW32MinBlocks 128-query blocks per head a 128-query workgroup per CU leaves CUs idle and doubles the serial chain of an
-// utterance's key tiles per wave; the 64-query kernel keeps those (token-level launches, single utterances).  The choice is a
-// function of the regime row count (fs2_decode: derived from the phoneme count), like every other kernel-variant choice.
-constexpr int kW32MinBlocks = 64;
-bool use_attn_w32(int precision, int dk, long rows, unsigned long long qk_lo_bytes, unsigned long long vt_lo_bytes) {
-    if (precision != FS2_PREC_BF16X3 || (dk != 128 && dk != 192)) return false;
-    if (qk_lo_bytes >= (1ull << 31) || vt_lo_bytes >= (1ull << 31)) return false;      // the lo planes must sit within 2 GB behind the hi planes (32-bit DMA offsets)
-    if (opts().w32 >= 0) return opts().w32 != 0;
-    return (rows + kAttBlk - 1) / kAttBlk >= kW32MinBlocks;
-}
-
-template <int DK, int NSPLIT>
-hipError_t launch_attn_b16_t(hipStream_t s, dim3 grid, const AttnB16Args& a) {
-    static LdsAttr attr;
-    allow_lds(reinterpret_cast<const void*>(&attn_bf16<DK, NSPLIT>), attn_b16_lds_bytes<DK>(), attr);
-    hipLaunchKernelGGL((attn_bf16<DK, NSPLIT>), grid, dim3(256), attn_b16_lds_bytes<DK>(), s, a);
-    return hipGetLastError();
-}
-
-// qkv fp32 [R,3D] -> split planes -> attention.  planes: qk_hi/lo [Rvt][2D], vt_hi/lo [D][Rvt] (Rvt % 32 == 0)
-int launch_attention_b16(fs2_handle* h, hipStream_t s, const char* name, const float* qkv, float* ctx, int D, int heads, int R, int Rvt,
-                         const DevLayout& dl, int nwork, int mask_q, double flops, int precision, __bf16* qkh, __bf16* qkl, __bf16* vth,
-                         __bf16* vtl, void* ctxp = nullptr, int dk_true = 0) {
-    const int dk = D / heads;
-    if (!dk_true) dk_true = dk;
-    if (nwork == 0) return FS2_OK;
-    if (qkv != nullptr) {
-        char nm[112];
-        snprintf(nm, sizeof nm, "%s.split", name);
-        Scope sc(h, s, nm, 0.0, 4.0 * R * 3.0 * D * 2);
-        static LdsAttr attr;
-        allow_lds(reinterpret_cast<const void*>(&qkv_split), 32 * (1024 + 1) * 4, attr);
-        QkvSplitArgs q;
-        q.qkv = qkv; q.R = R; q.Rvt = Rvt; q.D = D; q.dk = dk; q.scale = 1.4426950408889634f / sqrtf((float)dk_true);   // log2(e)/sqrt(d_k): softmax in base 2
-        q.qk_hi = qkh; q.qk_lo = qkl; q.vt_hi = vth; q.vt_lo = vtl;
-        if (D > 1024) return fail(h, FS2_ERR_UNSUPPORTED, "attention dim %d > 1024", D);
-        hipLaunchKernelGGL(qkv_split, dim3(Rvt / 32), dim3(256), (size_t)32 * (D + 1) * 4, s, q);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", nm, hipGetErrorString(e));
+// The instantiation an attention plan names, on the arguments of the launch.  Instantiated in the order of the branches and of pick's values, like run_plan's.
+hipError_t run_attn_plan(hipStream_t s, const AttnPlan& p, const AttnIo& io) {
+    const dim3 grid(p.grid_x, p.grid_y);
+    const int D = io.c.D;
+    if (p.kernel == AttnKernel::F32) {
+        AttnArgs a;
+        attn_layout_args(a, io);
+        a.qkv = io.qkv; a.ld = 3 * D; a.ctx = io.ctx; a.ldc = D; a.scale = p.softmax_scale;
+        return pick<128, 192, 64, 256>(p.dk, [&](auto DK) { return launch_kernel<attn_f32<CV(DK)>>(grid, dim3(256), attn_lds_bytes<CV(DK)>(), s, a); });
     }
     AttnB16Args a;
-    a.qk_hi = qkh; a.qk_lo = qkl; a.ldqk = 2 * D; a.vt_hi = vth; a.vt_lo = vtl; a.Rvt = Rvt; a.ctx = ctx; a.ldc = D;
-    a.ctxp = ctxp; a.ctxp_chunks = D / 32;
-    a.start = dl.start; a.len = dl.len; a.klen = dl.klen; a.work = dl.work; a.nwork = dl.dims ? dl.dims + 1 : nullptr; a.nitems = nwork; a.D = D; a.mask_q = mask_q;
-    const ptrdiff_t qk_d = reinterpret_cast<const char*>(qkl) - reinterpret_cast<const char*>(qkh), vt_d = reinterpret_cast<const char*>(vtl) - reinterpret_cast<const char*>(vth);
-    a.qk_lo_bytes = (unsigned)qk_d; a.vt_lo_bytes = (unsigned)vt_d;
-    a.slow_count = h ? h->counters : nullptr; a.slow_count2 = (h && h->cur_status) ? h->cur_status + 5 : nullptr;
-    Scope sc(h, s, name, flops, 0.0);
-    hipError_t e;
-    // (the regime row count of the call in progress when there is one: derived from the phoneme count, it is the same number in the host-
-    //  and the device-driven layout of a batch, whose R -- rows in use vs row capacity -- differ)
-    const long regime = (h && h->cur_regime > 0) ? h->cur_regime : R;
-    if (qk_d > 0 && vt_d > 0 && use_attn_w32(precision, dk, regime, (unsigned long long)qk_d, (unsigned long long)vt_d)) {
-        dim3 grid(nwork, heads);
-        e = dk == 128 ? launch_attn_w32_t<128>(s, grid, a) : launch_attn_w32_t<192>(s, grid, a);
-        if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
-        return FS2_OK;
+    attn_layout_args(a, io);
+    a.qk_hi = io.qkh; a.qk_lo = io.qkl; a.ldqk = 2 * D; a.vt_hi = io.vth; a.vt_lo = io.vtl; a.Rvt = io.c.Rvt; a.ctx = io.ctx; a.ldc = D;
+    a.ctxp = io.ctxp; a.ctxp_chunks = D / 32; a.slow_count = io.slow_count; a.slow_count2 = io.slow_count2;
+    a.qk_lo_bytes = (unsigned)io.c.qk_lo_dist; a.vt_lo_bytes = (unsigned)io.c.vt_lo_dist;
+    if (p.kernel == AttnKernel::W32)
+        return pick<128, 192>(p.dk, [&](auto DK) { return launch_kernel<attn_w32<CV(DK)>>(grid, dim3(256), attn_w32_lds_bytes<CV(DK)>(), s, a); });
+    if (p.kernel == AttnKernel::B16)
+        return pick<128, 192, 64, 256>(p.dk, [&](auto DK) {
+            return pick<3, 1>(p.nsplit, [&](auto NS) { return launch_kernel<attn_bf16<CV(DK), CV(NS)>>(grid, dim3(256), attn_b16_lds_bytes<CV(DK)>(), s, a); });
+        });
+    return hipErrorInvalidValue;
+}
+#undef CV
+
+// Plan (attn_plan.h), then execute: qkv_split under "<name>.split" where the operands arrive as fp32 rows, the kernel under `name`.
+int launch_attention(fs2_handle* h, hipStream_t s, const char* name, AttnIo io) {
+    AttnCall& c = io.c;
+    c.qkv_rows = io.qkv != nullptr;
+    c.qk_lo_dist = reinterpret_cast<const char*>(io.qkl) - reinterpret_cast<const char*>(io.qkh);
+    c.vt_lo_dist = reinterpret_cast<const char*>(io.vtl) - reinterpret_cast<const char*>(io.vth);
+    io.slow_count = h ? h->counters : nullptr; io.slow_count2 = (h && h->cur_status) ? h->cur_status + 5 : nullptr;
+    const AttnPlan p = plan_attention(c, opts());
+    if (p.err) return fail(h, p.err, p.msg, p.m0);
+    if (p.kernel == AttnKernel::None) return FS2_OK;
+    if (p.split_pass) {
+        char nm[112];
+        snprintf(nm, sizeof nm, "%s.split", name);
+        Scope sc(h, s, nm, 0.0, 4.0 * c.R * 3.0 * c.D * 2);
+        QkvSplitArgs q;
+        q.qkv = io.qkv; q.R = c.R; q.Rvt = c.Rvt; q.D = c.D; q.dk = p.dk; q.scale = p.softmax_scale;
+        q.qk_hi = io.qkh; q.qk_lo = io.qkl; q.vt_hi = io.vth; q.vt_lo = io.vtl;
+        const hipError_t e = launch_kernel<qkv_split>(dim3(c.Rvt / 32), dim3(256), (size_t)32 * (c.D + 1) * 4, s, q, (size_t)32 * (1024 + 1) * 4);
+        if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", nm, hipGetErrorString(e));
     }
-    dim3 grid(att_grid64(nwork), heads);      // two 64-query workgroups per 128-query work item
-    const bool x3 = precision == FS2_PREC_BF16X3;
-    if (dk == 128) e = x3 ? launch_attn_b16_t<128, 3>(s, grid, a) : launch_attn_b16_t<128, 1>(s, grid, a);
-    else if (dk == 192) e = x3 ? launch_attn_b16_t<192, 3>(s, grid, a) : launch_attn_b16_t<192, 1>(s, grid, a);
-    else if (dk == 64) e = x3 ? launch_attn_b16_t<64, 3>(s, grid, a) : launch_attn_b16_t<64, 1>(s, grid, a);
-    else if (dk == 256) e = x3 ? launch_attn_b16_t<256, 3>(s, grid, a) : launch_attn_b16_t<256, 1>(s, grid, a);
-    else return fail(h, FS2_ERR_UNSUPPORTED, "attention head dim %d not in {64,128,192,256} (the model path pads other head dims)", dk);
+    Scope sc(h, s, name, io.flops, 0.0);
+    const hipError_t e = run_attn_plan(s, p, io);
     if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
     return FS2_OK;
 }
@@ -667,9 +630,8 @@ int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, in
             if (step.kind != StepKind::Attention) rc = launch_step(h, s, tag, step, prec);
             else {
                 snprintf(nm, sizeof nm, "%s.%s", tag, step.name);
-                if (!pl) rc = launch_attention(h, s, nm, step.a.X, step.a.Y, st.Dp, heads, dl, L.nwork(), mask_q, att_flops, st.dk);
-                else rc = launch_attention_b16(h, s, nm, step.a.X, step.a.Y, st.Dp, heads, r.R, r.Rpad, dl, L.nwork(), mask_q, att_flops, prec, (__bf16*)b.qkh, (__bf16*)b.qkl,
-                                               (__bf16*)b.vth, (__bf16*)b.vtl, step.a.Yp, st.dk);
+                rc = launch_attention(h, s, nm, AttnIo{step.a.X, step.a.Y, step.a.Yp, (__bf16*)b.qkh, (__bf16*)b.qkl, (__bf16*)b.vth, (__bf16*)b.vtl, &dl, mask_q, att_flops,
+                                                       AttnCall{st.Dp, heads, st.dk, prec, r.R, r.Rpad, h->cur_regime, L.nwork()}});
             }
             if (rc) return rc;
         }
@@ -1736,7 +1698,7 @@ int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int3
     std::vector<int2> work;
     int R = 0;
     for (int b = 0; b < B; ++b) {
-        for (int q = 0; q * kAttBlk < seq_len[b]; ++q) work.push_back(make_int2(b, q));
+        for (int q = 0; q < att_blocks(std::max(seq_len[b], 0)); ++q) work.push_back(make_int2(b, q));
         R = std::max(R, seq_start[b] + seq_len[b]);
         if (precision != FS2_PREC_FP32 && seq_start[b] % kAttAlign) return fail(nullptr, FS2_ERR_ARG, "bf16 attention needs sequence starts aligned to %d rows", kAttAlign);
     }
@@ -1750,28 +1712,24 @@ int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int3
     OP_TRY(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s));
     DevLayout dl;
     dl.start = dev; dl.len = dev + B; dl.klen = dev + 2 * B; dl.work = reinterpret_cast<int2*>(dev + 3 * B);
-    int rc;
-    if (precision == FS2_PREC_FP32) {
-        rc = launch_attention(nullptr, s, "op.attention", qkv, ctx, D, heads, dl, (int)work.size(), mask_q, 0.0);
-    } else {
-        const int Rvt = round_up(R + kTailRows, 128);      // (8-key V^T vectors that straddle the last key stay inside the planes)
+    AttnIo io{qkv, ctx, nullptr, nullptr, nullptr, nullptr, nullptr, &dl, mask_q, 0.0, AttnCall{D, heads, 0, precision, R, 0, 0, (int)work.size()}};
+    if (precision != FS2_PREC_FP32) {
+        const int Rvt = io.c.Rvt = round_up(R + kTailRows, 128);      // (8-key V^T vectors that straddle the last key stay inside the planes)
         __bf16* planes = nullptr;
         OP_TRY(tmp.alloc((void**)&planes, (size_t)Rvt * D * 6 * sizeof(__bf16)));
-        __bf16 *qkh = planes, *qkl = planes + (size_t)Rvt * 2 * D, *vth = qkl + (size_t)Rvt * 2 * D, *vtl = vth + (size_t)Rvt * D;
+        io.qkh = planes; io.qkl = planes + (size_t)Rvt * 2 * D; io.vth = io.qkl + (size_t)Rvt * 2 * D; io.vtl = io.vth + (size_t)Rvt * D;
         if (opts().op_att_planes > 0 && D % 32 == 0) {
-            // the model's output form: the kernels write the context as planes only (attn_w32: the LDS-staged epilogue), converted here
-            void* ctxp = nullptr;
-            OP_TRY(tmp.alloc(&ctxp, (size_t)Rvt * D * 4));
-            OP_TRY(hipMemsetAsync(ctxp, 0, (size_t)Rvt * D * 4, s));
-            rc = launch_attention_b16(nullptr, s, "op.attention", qkv, nullptr, D, heads, R, Rvt, dl, (int)work.size(), mask_q, 0.0, precision, qkh, qkl, vth, vtl, ctxp);
-            if (rc == FS2_OK) {
-                const int64_t n = (int64_t)R * (D / 4);
-                hipLaunchKernelGGL(planes_to_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctxp, D / 32, R, D, ctx, D);
-                OP_TRY(hipGetLastError());
-            }
-        } else {
-            rc = launch_attention_b16(nullptr, s, "op.attention", qkv, ctx, D, heads, R, Rvt, dl, (int)work.size(), mask_q, 0.0, precision, qkh, qkl, vth, vtl);
+            // the model's output form: the kernels write the context as planes only (attn_w32: the LDS-staged epilogue), converted below
+            io.ctx = nullptr;
+            OP_TRY(tmp.alloc(&io.ctxp, (size_t)Rvt * D * 4));
+            OP_TRY(hipMemsetAsync(io.ctxp, 0, (size_t)Rvt * D * 4, s));
         }
+    }
+    const int rc = launch_attention(nullptr, s, "op.attention", io);
+    if (rc == FS2_OK && io.ctxp) {
+        const int64_t n = (int64_t)R * (D / 4);
+        hipLaunchKernelGGL(planes_to_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, io.ctxp, D / 32, R, D, ctx, D);
+        OP_TRY(hipGetLastError());
     }
     return rc;      // (tmp drains the stream and frees)
 }

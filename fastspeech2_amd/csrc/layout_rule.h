@@ -54,6 +54,9 @@ LR_HD constexpr int rows_padded(int rows) { return lr_round_up(rows, kRowTile); 
 
 // ---- attention blocks of an utterance of len >= 0 rows
 LR_HD constexpr int att_blocks(int len) { return (int)((unsigned)(len + kAttBlk - 1) / (unsigned)kAttBlk); }
+// ---- grid.x of the 64-query kernels (attn_f32, attn_bf16) over a work list of nitems: 2 x (items rounded up to a multiple of kXcds) workgroups;
+// common.h: att_item64 says which half of which item workgroup x serves
+LR_HD constexpr unsigned att_grid64(int nitems) { return 2u * (unsigned)((nitems + kXcds - 1) & ~(kXcds - 1)); }
 
 // ---- dealing order: utterance a (key range ka) is dealt before utterance b (kb): longer key range first, ties in batch order.
 // A strict total order: the host sorts by it, the device counts for every utterance those dealt before it.

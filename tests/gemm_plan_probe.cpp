@@ -1,8 +1,11 @@
-// Host-compiled driver of csrc/gemm_plan.h and csrc/model_launches.h for tests/test_gemm_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
-//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr>      the plan of every named launch of the default model, in the four tested precisions
+// Host-compiled driver of csrc/gemm_plan.h, csrc/attn_plan.h and csrc/model_launches.h for tests/test_gemm_plan_host.py and tests/test_attn_plan_host.py
+// (g++ -std=c++17 -Wall -Werror, no HIP).
+//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr>      the plan of every named launch of the default model, attention included, in the four tested precisions
 //   probe variants <Rtok> <regime_tok> <Rfr> <regime_fr>   every step of the pre-LN / concat_after block variants, and whether its GEMMs plan
 //   probe sweep                                            the planes-only decision: the predicate fs2_decode used to restate against the plan's answer
 //   probe refusals                                         one argument set per refusal of plan_gemm
+//   probe attn_sweep                                       plan_attention over the regime threshold, the switch, the plane distances, the grid and the scales
+//   probe attn_refusals                                    the refusals of plan_attention
 // The launches are the ones model_launches.h forms, the header fs2_runtime.hip executes.  This file holds only data: a model described as the loader would leave it
 // (a marker pointer wherever it builds an image or the workspace has a buffer) and the walk over the header's step lists.
 #include <cstdio>
@@ -10,6 +13,7 @@
 #include <cstring>
 #include <string>
 
+#include "attn_plan.h"
 #include "model_launches.h"
 
 using namespace fs2;
@@ -88,6 +92,16 @@ const char* kernel_name(GemmKernel k) {
     return "?";
 }
 
+const char* attn_name(AttnKernel k) {
+    switch (k) {
+    case AttnKernel::None: return "none";
+    case AttnKernel::F32: return "attn_f32";
+    case AttnKernel::B16: return "attn_bf16";
+    case AttnKernel::W32: return "attn_w32";
+    }
+    return "?";
+}
+
 struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch, or collects the plans into `all` (capacity test)
     int prec, terms;
     Rows r;
@@ -113,9 +127,24 @@ struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch
             printf("%s %s %s %d %d %d\n", tag, name.c_str(), kernel_name(p.kernel), p.tile_rows(), p.ksplit, (int)p.rows_pass);
         }
     }
+    // the attention launch of a block as run_stack asks for it: the stack's width, heads and head dim, the call's rows and regime; the operands' lo planes lie
+    // one plane behind their hi planes (carve_tokens / carve_frames)
+    AttnCall attn_call(const Stack& st, const Step& s) const {
+        AttnCall c{st.Dp, st.Dp / padded_head_dim(st.dk), st.dk, prec, r.R, r.Rpad, r.regime_rows, att_blocks(r.R)};
+        c.qkv_rows = s.a.X != nullptr;
+        c.qk_lo_dist = 4LL * r.Rpad * st.Dp; c.vt_lo_dist = 2LL * r.Rpad * st.Dp;
+        return c;
+    }
     void stack(const char* name, const Stack& st, int D, const StackBufs& b, bool po) const {
         for (const Layer& ly : st.layers)
-            for (const Step& s : block_steps(st, ly, D, r, b, prec, terms, po, o)) emit(name, s);
+            for (const Step& s : block_steps(st, ly, D, r, b, prec, terms, po, o)) {
+                emit(name, s);
+                if (s.kind != StepKind::Attention || steps) continue;
+                const AttnPlan p = plan_attention(attn_call(st, s), o);
+                char line[96];
+                snprintf(line, sizeof line, "%s.%s %s %d %d %d\n", name, s.name, attn_name(p.kernel), p.dk, p.nsplit, (int)p.split_pass);
+                if (all) *all += line; else printf("%s %s", tag, line);
+            }
     }
     void predictor(const char* name, const Predictor& p, const void* Xp) const {
         for (size_t l = 0; l < p.conv.size(); ++l) emit(name, predictor_step(p, l, M, p.conv[0].C, r, M, M, M, prec, Xp, M));
@@ -241,6 +270,78 @@ int refusals() {
     return 0;
 }
 
+// ---- the attention plan (csrc/attn_plan.h) away from the model's shapes
+void show_attn(const char* what, const AttnCall& c, const Options& o) {
+    const AttnPlan p = plan_attention(c, o);
+    char msg[256] = "";
+    if (p.err) snprintf(msg, sizeof msg, p.msg, p.m0);
+    unsigned scale_bits;
+    memcpy(&scale_bits, &p.softmax_scale, 4);
+    printf("%s|%s|%d|%d|%u|%u|%d|%08x|%d|%s\n", what, attn_name(p.kernel), p.dk, p.nsplit, p.grid_x, p.grid_y, (int)p.split_pass, scale_bits, p.err, msg);
+}
+AttnCall attn_base(int prec, int dk, int heads = 2) {
+    AttnCall c{heads * dk, heads, 0, prec, 1024, 1024, 0, 8};
+    c.qk_lo_dist = c.vt_lo_dist = 1 << 20;
+    return c;
+}
+
+// what|kernel|dk|nsplit|grid_x|grid_y|split_pass|softmax_scale bits|err|message, `what` = the case's coordinates
+int attn_sweep() {
+    char what[128];
+    const struct { const char* name; int prec; } precs[] = {{"fp32", kFp32}, {"bf16x3", kBf16x3}, {"bf16", kBf16}};
+    // the threshold: regime rows x switch x precision x head dim, the regime given (R = 1 row) or left to R
+    for (int rows : {1, 8064, 8065, 8191, 8192, 8193, 37256})
+        for (int w32 = -1; w32 <= 1; ++w32)
+            for (const auto& pr : precs)
+                for (int dk : {64, 128, 192, 256})
+                    for (int by_R = 0; by_R <= 1; ++by_R) {
+                        AttnCall c = attn_base(pr.prec, dk);
+                        c.R = by_R ? rows : 1; c.regime_rows = by_R ? 0 : rows;
+                        Options o; o.w32 = w32;
+                        snprintf(what, sizeof what, "regime %d %d %s %d %d", rows, w32, pr.name, dk, by_R);
+                        show_attn(what, c, o);
+                    }
+    // the lo planes' distance: where everything else chooses attn_w32
+    for (long long d : {0LL, -256LL, (1LL << 31) - 1, 1LL << 31})
+        for (int which = 0; which <= 1; ++which) {
+            AttnCall c = attn_base(kBf16x3, 128);
+            (which ? c.vt_lo_dist : c.qk_lo_dist) = d;
+            Options o; o.w32 = 1;
+            snprintf(what, sizeof what, "dist %lld %d", d, which);
+            show_attn(what, c, o);
+        }
+    // the grid
+    for (int n = 0; n <= 33; ++n)
+        for (int k = 0; k < 3; ++k) {
+            AttnCall c = attn_base(k == 0 ? kFp32 : kBf16x3, 128);
+            c.nwork = n; c.qkv_rows = k != 2;      // (a split pass too has nothing to do without work)
+            Options o; o.w32 = k == 2;
+            snprintf(what, sizeof what, "grid %d %s", n, k == 0 ? "f32" : (k == 1 ? "b16" : "w32"));
+            show_attn(what, c, o);
+        }
+    // the scales: the model's head dim under a padded one
+    for (int dk_true : {64, 96, 128, 192})
+        for (const auto& pr : precs) {
+            AttnCall c = attn_base(pr.prec, padded_head_dim(dk_true));
+            c.dk_true = dk_true; c.qkv_rows = true;
+            snprintf(what, sizeof what, "scale %d %s", dk_true, pr.name);
+            show_attn(what, c, Options());
+        }
+    return 0;
+}
+
+int attn_refusals() {
+    const Options o;
+    AttnCall c = attn_base(kFp32, 96); c.qkv_rows = true; show_attn("head_dim_fp32", c, o);
+    c = attn_base(kBf16x3, 96); show_attn("head_dim_bf16x3", c, o);
+    c = attn_base(kBf16x3, 96); c.nwork = 0; show_attn("head_dim_no_work", c, o);
+    c = attn_base(kBf16x3, 264, 4); c.qkv_rows = true; show_attn("wide_split", c, o);                 // D = 1056: the refusal comes before the head dim's
+    c = attn_base(kBf16x3, 264, 4); show_attn("wide_operands_given", c, o);                           // ... and only the head dim's is left without a split pass
+    c = attn_base(kBf16x3, 192, 6); show_attn("wide_accepted", c, o);                                 // D = 1152, operands given
+    c = attn_base(kFp32, 192, 6); c.qkv_rows = true; show_attn("wide_fp32", c, o);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -248,6 +349,8 @@ int main(int argc, char** argv) {
     if (argc == 6 && !strcmp(argv[1], "variants")) return variants(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
     if (argc == 2 && !strcmp(argv[1], "sweep")) return sweep();
     if (argc == 2 && !strcmp(argv[1], "refusals")) return refusals();
-    fprintf(stderr, "usage: probe model|variants Rtok regime_tok Rfr regime_fr | sweep | refusals\n");
+    if (argc == 2 && !strcmp(argv[1], "attn_sweep")) return attn_sweep();
+    if (argc == 2 && !strcmp(argv[1], "attn_refusals")) return attn_refusals();
+    fprintf(stderr, "usage: probe model|variants Rtok regime_tok Rfr regime_fr | sweep | refusals | attn_sweep | attn_refusals\n");
     return 2;
 }

@@ -276,6 +276,28 @@ def test_attention_spiked_key_forces_rescale(precision, spike, fs2_option):
     assert err < (2e-5 if precision == "fp32" else 5e-4)
 
 
+@pytest.mark.parametrize("rows,blocks", [(8160, 64), (8032, 63)])
+def test_attention_automatic_choice_on_both_sides_of_the_w32_threshold(rows, blocks, fs2_option):
+    """The automatic kernel choice of split-bf16 attention (csrc/attn_plan.h: attn_w32 from kW32MinBlocks = 64 blocks of 128 queries on) gives the bits of the kernel
+    forced on at 64 blocks and of the kernel forced off at 63: one utterance from row 32 on, so that the operator's row count -- its regime -- is 8192 / 8064, the
+    smallest shapes on the two sides of the rule.  Whether the two forced kernels differ in any bit at this shape -- only then does the equality tell which
+    one ran -- is printed and recorded."""
+    from tests import ops_binding as ops
+    from tests.conftest import record_measurement
+    dev = _dev()
+    D, heads, start = 256, 2, 32
+    assert (start + rows + 127) // 128 == blocks
+    qkv = _rand(np.random.RandomState(rows), start + rows + 16, 3 * D, scale=2.0).to(dev)
+    out = {}
+    for w32 in (-1, 0, 1):
+        fs2_option("FS2_ATTN_W32", w32)
+        out[w32] = ops.attention(qkv, D, heads, [start], [rows], [rows], 0, precision="bf16x3").cpu().view(torch.int32)
+    forced_differ = not torch.equal(out[0], out[1])
+    print("attention, %d blocks: the forced kernels differ in some bit: %s" % (blocks, forced_differ))
+    record_measurement("attention_w32_threshold_%d_blocks_forced_kernels_differ" % blocks, float(forced_differ))
+    assert torch.equal(out[-1], out[1 if blocks >= 64 else 0])
+
+
 def test_length_regulator_known_answers(golden_dir):
     from tests import ops_binding as ops
     dev = _dev()

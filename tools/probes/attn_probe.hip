@@ -3,6 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DFS2_ATT_TIMING -I fastspeech2_amd/csrc tools/probes/attn_probe.hip -o tools/probes/attn_probe.bin
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "gemm_bf16.h"
 #include "attn_bf16.h"
