@@ -1689,6 +1689,21 @@ int fs2_op_conv_gemm(void* stream, const fs2_op_gemm_args* o) {
     return launch_gemm(nullptr, s, "op.conv_gemm", a, base_precision(o->precision));      // (tmp drains the stream and frees)
 }
 
+// Test hook (include/fs2.h): the launch path of the model -- plan_gemm, then launch_gemm -- on a caller-formed argument block; the plan goes back to the caller
+// first, so that a test knows which kernel its numbers came from.
+int fs2_op_launch_gemm(void* stream, const void* gemm_args, uint32_t args_size, int32_t precision, int32_t* plan_out, int32_t plan_cap) {
+    if (!gemm_args || !plan_out) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_gemm: null argument");
+    if (args_size != sizeof(GemmArgs)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_gemm: argument block of %u bytes, this library's GemmArgs has %zu", args_size, sizeof(GemmArgs));
+    if (plan_cap < FS2_GEMM_PLAN_FIELDS) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_gemm: plan_out holds %d fields, %d are written", plan_cap, FS2_GEMM_PLAN_FIELDS);
+    if (precision != FS2_PREC_FP32 && precision != FS2_PREC_BF16X3 && precision != FS2_PREC_BF16) return fail(nullptr, FS2_ERR_ARG, "unknown precision %d", precision);
+    GemmArgs a;
+    memcpy(&a, gemm_args, sizeof a);
+    const GemmPlan p = plan_gemm(a, precision, opts());
+    const int32_t fields[FS2_GEMM_PLAN_FIELDS] = {(int32_t)p.kernel, p.nsplit, p.nb, p.bm, p.mt, p.apart, p.epi, p.arith, p.res, p.ksplit, p.rows_pass, p.build_planes};
+    memcpy(plan_out, fields, sizeof fields);
+    return launch_gemm(nullptr, (hipStream_t)stream, "op.launch_gemm", a, precision);
+}
+
 int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int32_t heads, int32_t B, const int32_t* seq_start,
                      const int32_t* seq_len, const int32_t* seq_klen, int32_t mask_q, int32_t precision) {
     if (!qkv || !ctx || B <= 0) return fail(nullptr, FS2_ERR_ARG, "fs2_op_attention: bad arguments");
@@ -1722,7 +1737,7 @@ int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int3
             // the model's output form: the kernels write the context as planes only (attn_w32: the LDS-staged epilogue), converted below
             io.ctx = nullptr;
             OP_TRY(tmp.alloc(&io.ctxp, (size_t)Rvt * D * 4));
-            OP_TRY(hipMemsetAsync(io.ctxp, 0, (size_t)Rvt * D * 4, s));
+            OP_TRY(hipMemsetAsync(io.ctxp, 0xff, (size_t)Rvt * D * 4, s));      // (NaN in both halves: a query row the kernels leave unwritten shows in ctx)
         }
     }
     const int rc = launch_attention(nullptr, s, "op.attention", io);

@@ -244,6 +244,21 @@ typedef struct fs2_op_gemm_args {
 } fs2_op_gemm_args;
 int fs2_op_conv_gemm(void *stream, const fs2_op_gemm_args *a);
 
+/* TEST HOOK: plan and run ONE dense-layer launch from the library's own internal argument block (fs2::GemmArgs of
+ * csrc/gemm_args.h, copied from `gemm_args`), exactly as the model's launches are planned and run -- the way the kernel-level
+ * tests (tests/test_gpu_row_kernels.py) reach the kernels and epilogues the operator above cannot express: planes in and out,
+ * the residual as planes, the positional-encoding epilogue, the fused QKV split.  Nothing is allocated, converted or checked on
+ * the caller's behalf: the caller owns every buffer the block points to and its size (operand images, outputs, scratch, as the
+ * kernel the plan names reads and writes them).  The block is NOT a stable ABI -- it changes with the kernels -- which is why
+ * `args_size` must equal this library's sizeof(fs2::GemmArgs): FS2_ERR_ARG otherwise, as for a NULL `gemm_args` / `plan_out`,
+ * a `plan_cap` below FS2_GEMM_PLAN_FIELDS or a precision other than FS2_PREC_FP32 / _BF16X3 / _BF16.
+ * plan_out[0 .. FS2_GEMM_PLAN_FIELDS) receives the decision (csrc/gemm_plan.h: GemmPlan) before anything is launched: kernel
+ * (the GemmKernel enumerator), nsplit, nb, bm, mt, apart, epi, arith, res, ksplit, rows_pass, build_planes.  A launch the plan
+ * refuses returns the plan's error code and message and launches nothing. */
+#define FS2_GEMM_PLAN_FIELDS 12
+int fs2_op_launch_gemm(void *stream, const void *gemm_args, uint32_t args_size, int32_t precision, int32_t *plan_out,
+                       int32_t plan_cap);
+
 /* scaled-dot-product self-attention over packed sequences: qkv [R, 3*D] (q | k | v, head-major inside
  * each), ctx [R, D].  seq_start/len/klen: HOST [B]; in the bf16 modes seq_start must be a multiple of 8.  Keys >= klen
  * never reach the output whatever their rows hold (NaN included).  Query rows >= klen produce zeros when mask_q.

@@ -40,7 +40,7 @@ def attention(qkv, D, heads, starts, lens, klens, mask_q, precision="fp32"):
     L = _lib.lib()
     B = len(starts)
     qkv = qkv.contiguous()
-    ctx = torch.zeros(qkv.shape[0], D, device=qkv.device)
+    ctx = torch.full((qkv.shape[0], D), float("nan"), device=qkv.device)      # (a query row the kernels never write shows)
     arr = lambda v: (C.c_int32 * B)(*[int(i) for i in v])
     with torch.cuda.device(qkv.device):
         _lib.check(L.fs2_op_attention(_st(qkv.device), _p(qkv), _p(ctx), D, heads, B, arr(starts), arr(lens), arr(klens),

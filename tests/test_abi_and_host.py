@@ -127,6 +127,17 @@ def test_struct_size_mismatch_is_rejected(libpath):
     a = _lib.OpGemmArgs()
     a.struct_size = 8
     assert L.fs2_op_conv_gemm(None, ctypes.byref(a)) == -1 and b"struct_size" in L.fs2_last_error(None)
+    # the raw launch hook takes the library's internal argument block, which is no stable ABI: another size, a null argument, a short plan
+    # buffer or a precision that is no GEMM arithmetic is refused before the block is read
+    from tests.gemm_raw import GemmArgs
+    blk, plan = GemmArgs(), (ctypes.c_int32 * _lib.GEMM_PLAN_FIELDS)()
+    n = ctypes.sizeof(blk)
+    assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n - 8, 1, plan, len(plan)) == -1 and b"GemmArgs" in L.fs2_last_error(None)
+    assert L.fs2_op_launch_gemm(None, None, n, 1, plan, len(plan)) == -1 and b"null" in L.fs2_last_error(None)
+    assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, 1, None, len(plan)) == -1 and b"null" in L.fs2_last_error(None)
+    assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, 1, plan, len(plan) - 1) == -1 and b"plan_out" in L.fs2_last_error(None)
+    for precision in (-1, 3, 6):
+        assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, precision, plan, len(plan)) == -1 and b"precision" in L.fs2_last_error(None)
 
 
 def test_create_without_gpu_fails_loudly(libpath):

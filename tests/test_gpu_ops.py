@@ -207,11 +207,16 @@ ATT_TOL = {"fp32": 5e-6, "bf16x3": 7e-5, "bf16": 3.5e-2}
 # ".../planes": the kernels hand the context back as split-bf16 planes only, the form the model uses (attn_w32: the LDS-staged epilogue),
 # and the operator converts (FS2_OP_ATT_PLANES); hi + lo carries 16 mantissa bits: ~1.5e-5 on |ctx| <= 2
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16x3/w32", "bf16x3/planes", "bf16x3/w32/planes", "bf16"])
-@pytest.mark.parametrize("D,heads", [(256, 2), (384, 2)])
+# head dims 128 and 192 (the model's) and the other two plan_attention accepts, 64 and 256, at one, two and four heads: attn_w32 exists for 128 and 192
+# only, so "bf16x3/w32" at 64 / 256 must fall back to attn_bf16 and give its bits
+@pytest.mark.parametrize("D,heads", [(256, 2), (384, 2), (256, 4), (256, 1), (512, 2), (512, 4)])
 @pytest.mark.parametrize("mask_q", [0, 1])
 def test_attention(D, heads, mask_q, precision, fs2_option):
+    """Against float64.  The context buffer (fp32 rows, or the planes the kernels write in the ".../planes" forms) starts as NaN, so a query row a kernel
+    never wrote shows; the dead query rows of every utterance (mask_q, rows >= klen) must be exactly 0."""
     from tests import ops_binding as ops
     dev = _dev()
+    name, w32 = precision, "/w32" in precision
     if precision.startswith("bf16x3"):
         fs2_option("FS2_ATTN_W32", 1 if "/w32" in precision else 0)
         fs2_option("FS2_OP_ATT_PLANES", 1 if precision.endswith("/planes") else 0)
@@ -232,21 +237,27 @@ def test_attention(D, heads, mask_q, precision, fs2_option):
         live[s:s + kl] = True
     qkv[~live, D:] = float("nan")
     ctx = ops.attention(qkv.to(dev), D, heads, starts, lens, klens, mask_q, precision=precision).cpu()
-    assert torch.isfinite(ctx[live]).all(), "a dead key reached the output"
+    assert torch.isfinite(ctx[live]).all(), "a dead key reached the output, or a live query row was never written"
     dk = D // heads
+    if w32 and dk in (64, 256):          # no attn_w32 at this head dim: the plan falls back to attn_bf16
+        fs2_option("FS2_ATTN_W32", 0)
+        ctx0 = ops.attention(qkv.to(dev), D, heads, starts, lens, klens, mask_q, precision=precision).cpu()
+        assert torch.equal(ctx.view(torch.int32), ctx0.view(torch.int32)), "FS2_ATTN_W32 = 1 changed the bits at head dim %d" % dk      # (unwritten rows: the same NaN)
     worst = 0.0
     for s, l, kl in zip(starts, lens, klens):
-        q = qkv[s:s + l, :D].view(l, heads, dk).transpose(0, 1)
-        k, v = (qkv[s:s + kl, i * D:(i + 1) * D].view(kl, heads, dk).transpose(0, 1) for i in (1, 2))
+        q = qkv[s:s + l, :D].double().view(l, heads, dk).transpose(0, 1)
+        k, v = (qkv[s:s + kl, i * D:(i + 1) * D].double().view(kl, heads, dk).transpose(0, 1) for i in (1, 2))
         sc = q @ k.transpose(1, 2) / np.sqrt(dk)
         a = torch.softmax(sc, dim=-1)
         o = (a @ v).transpose(0, 1).reshape(l, D)
         if mask_q:
             o[kl:] = 0.0
-        worst = max(worst, float((ctx[s:s + l] - o).abs().max()))
-    print("attention %s max-abs %.2e" % (precision, worst))
+            if kl < l:
+                assert float(ctx[s + kl:s + l].abs().max()) == 0.0, "dead query rows of the utterance at row %d are not exactly zero" % s
+        worst = max(worst, float((ctx[s:s + l].double() - o).abs().max()))
+    print("attention %s d_k %d max-abs %.2e" % (name, dk, worst))
     from tests.conftest import record_measurement
-    record_measurement("attention_%s" % precision, worst)
+    record_measurement("attention_%s_dk%d" % (precision, dk), worst)
     assert worst < ATT_TOL[precision], "max-abs %g" % worst
 
 

@@ -308,8 +308,8 @@ def test_c2_one_wave_per_simd_row_kernel_against_the_8_wave_one(env, fs2_option)
     kernels forced at c2: the forward at both tile heights (FS2_MT4 = 4 | 5: 128 / 160 rows) must not differ in a single bit, and must stay within
     1e-4 of the forward with FS2_ROW4 = 0 (gemm_row8_bf16: fp32 residual) -- in split-bf16 and, with FFN2 kept on split-bf16 (FS2_FFN2_MX = 0), in
     mix_mx (out-proj epilogue writes mx planes: EPI 1; FFN2's residual comes out of them: RES 2).  Bit-identity of the kernel itself against
-    gemm_row8_bf16 on the same (reconstructed) residual is tools/probes/row_probe.hip's job (profiles/r06_row_probe.txt: 0 words differ in all
-    eight forms).  With FFN2 + LN2 in the mx arithmetic (gemm_row4.h ARITH = 2, the default of mix_mx where that kernel runs) the result is another
+    gemm_row8_bf16 on the same (reconstructed) residual, and each form against float64, is tests/test_gpu_row_kernels.py's job
+    (test_layernorm_forms_write_the_same_planes_bit_for_bit: the shipped library through fs2_op_launch_gemm).  With FFN2 + LN2 in the mx arithmetic (gemm_row4.h ARITH = 2, the default of mix_mx where that kernel runs) the result is another
     rounding of the same sums: within 5e-5 of the split-bf16 FFN2, the same at both tile heights bit for bit, and within the mode's tolerance of
     the oracle.  (The variance adaptor runs in front of the decoder: the bucket decisions of the runs compared here are the same.)"""
     model, sd, cfg, O = env
