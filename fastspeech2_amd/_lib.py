@@ -133,6 +133,7 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
+           "fs2_op_vocode_mel_workspace_bytes_geom", "fs2_op_griffin_lim_mel_geom", "fs2_op_vocode_mel_workspace_bytes_cap", "fs2_op_griffin_lim_mel_dev",
            "fs2_op_spsi_workspace_bytes_geom", "fs2_op_spsi_workspace_bytes_cap", "fs2_op_spsi_phase_geom", "fs2_op_spsi_phase_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
            "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align",
@@ -334,6 +335,16 @@ def lib():
     L.fs2_op_griffin_lim_dev.argtypes = [vp] + gp + [vp, i32, vp, i32, vp, i32, C.c_int64, vp, i32, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp, i32,
                                                      C.c_int64, vp, vp]
     L.fs2_op_griffin_lim_dev.restype = C.c_int
+    # the mel-constrained siblings: the same arguments with mel_basis after mel_pinv
+    L.fs2_op_vocode_mel_workspace_bytes_geom.argtypes = gp + [i32, i32p]
+    L.fs2_op_vocode_mel_workspace_bytes_geom.restype = C.c_size_t
+    L.fs2_op_griffin_lim_mel_geom.argtypes = [vp] + gp + [vp, i32, vp, vp, i32, i32p, i32p, i32, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp]
+    L.fs2_op_griffin_lim_mel_geom.restype = C.c_int
+    L.fs2_op_vocode_mel_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]
+    L.fs2_op_vocode_mel_workspace_bytes_cap.restype = C.c_size_t
+    L.fs2_op_griffin_lim_mel_dev.argtypes = [vp] + gp + [vp, i32, vp, vp, i32, vp, i32, C.c_int64, vp, i32, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp,
+                                                         i32, C.c_int64, vp, vp]
+    L.fs2_op_griffin_lim_mel_dev.restype = C.c_int
     L.fs2_op_spsi_workspace_bytes_geom.argtypes = gp + [i32, i32p]
     L.fs2_op_spsi_workspace_bytes_geom.restype = C.c_size_t
     L.fs2_op_spsi_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]

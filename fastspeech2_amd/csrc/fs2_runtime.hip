@@ -1948,6 +1948,40 @@ int fs2_op_griffin_lim_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win
                               momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status);
 }
 
+size_t fs2_op_vocode_mel_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
+    GlGeomHost gh;
+    GlPlan p;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_mel_workspace_bytes_geom", gh)) return 0;
+    return gl_plan(B, nullptr, lens, false, gh, p, false, true) == FS2_OK ? p.at.bytes : 0;
+}
+
+int fs2_op_griffin_lim_mel_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
+                                const float* mel_basis, int32_t B, const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed,
+                                const float* init_phase, void* workspace, size_t workspace_bytes, float* wav) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_mel_geom", gh)) return rc;
+    return gl_griffin_lim("fs2_op_griffin_lim_mel_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
+                          workspace, workspace_bytes, wav, true, mel_basis);
+}
+
+size_t fs2_op_vocode_mel_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
+    GlGeomHost gh;
+    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_mel_workspace_bytes_cap", gh)) return 0;
+    const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
+    return slots < 0 ? 0 : gl_layout(gh, (size_t)slots, B, frame_capacity, false, false, true).bytes;
+}
+
+int fs2_op_griffin_lim_mel_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
+                               const float* mel_basis, int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity,
+                               const int32_t* upstream_status, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase, void* workspace,
+                               size_t workspace_bytes, float* wav, int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
+    GlGeomHost gh;
+    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_mel_dev", gh)) return rc;
+    return gl_griffin_lim_dev("fs2_op_griffin_lim_mel_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status,
+                              n_iter, momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status, true,
+                              mel_basis);
+}
+
 size_t fs2_op_spsi_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
     GlGeomHost gh;
     if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_workspace_bytes_geom", gh)) return 0;

@@ -6,6 +6,8 @@
 //   ISTFT  x = OLA_f(w . irfft(C_f)) / wss, trimmed by N / 2 at both ends  (STFT.inverse, stft.py:112-151)
 //   STFT   X_f = rfft(w . frame_f) of the signal reflect-padded by N / 2   (STFT.transform, stft.py:80-110)
 //   GL     C = M . A / |A|, A = X - momentum / (1 + momentum) . T, T <- X   (griffin_lim, audio_processing.py:224-240; momentum 0 = reference)
+//          or, mel-constrained (fs2_op_griffin_lim_mel_geom / _dev; GlMelProj below), C = g . A with the
+//          per-bin gain g that makes the mel of |A| the caller's
 // Utterances with L < L_min = floor(N / 2H) + 2 (T <= N / 2) are too short for the reflect padding: their T samples are written as
 // zeros and no iteration touches them.
 //
@@ -343,12 +345,63 @@ __device__ inline float gl_wss(int p, int L, const float* win, int hop) {
 
 constexpr int kGlSigMax = gl_sig_max(kGlNfft, kGlHop, kGlTile);   // pre-trim samples a default tile's frames + halo span
 
+// ---- mel-constrained projection (PROJ = 1 of gl_iterate) ----
+// What the iteration reads beside the spectra: the caller's log-mel rows and mel basis [n_mels, bins], and the band tables
+// gl_band_tables writes from that basis once per call.  An empty record (all NULL) is what the plain projection passes.
+struct GlMelProj {
+    const float* mel;        // the call's src: log-mel rows [.., n_mels], indexed by GlTile::src_row0 as the prologue does
+    const float* basis;      // [n_mels, bins], non-negative
+    const int2* row_rng;     // [kGlMaxMels]: bins [x, y) outside which row c of the basis is zero
+    const int2* bin_rng;     // [bins]: mel rows [x, y) outside which column k is zero
+    const float* inv_w;      // [bins]: 1 / sum_c B[c, k] (from double), 0 where the column is zero
+    const float* band;       // [bins][kGlMaxMels]: band[b][c] = B[c, row_rng[c].x + b], 0 beyond the row's range: the rows of the basis
+                             // shifted to their first bin and transposed, so that lane c walks its band with coalesced loads
+};
+
+constexpr size_t gl_band_bytes(int n_bins) {
+    return kGlMaxMels * sizeof(int2) + (size_t)n_bins * (sizeof(int2) + sizeof(float) + kGlMaxMels * sizeof(float));
+}
+
+// (n_bins + 255) / 256 workgroups of 256 threads per call.  The ranges are the first and one past the last non-zero entry: a Slaney
+// basis gives contiguous bands (a bin lies in at most two), a dense basis full ranges; zeros inside a range only cost their multiply.
+// Rows: one wave per row (its lanes stride over the bins, a fixed butterfly joins them).  Bins: one thread per bin.
+__global__ __launch_bounds__(kGlThreads) void gl_band_tables(const float* basis, int nm, int nb, int2* row_rng, int2* bin_rng, float* inv_w,
+                                                             float* band) {
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    for (int c = blockIdx.x * 4 + wv; c < kGlMaxMels; c += gridDim.x * 4) {
+        const float* br = basis + (int64_t)c * nb;
+        int lo = nb, hi = 0;
+        if (c < nm)
+            for (int k = j; k < nb; k += 64)
+                if (br[k] != 0.f) { lo = min(lo, k); hi = max(hi, k + 1); }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+        if (hi == 0) lo = 0;
+        if (j == 0) row_rng[c] = make_int2(lo, hi);
+        for (int b = j; b < nb; b += 64) band[(int64_t)b * kGlMaxMels + c] = lo + b < hi ? br[lo + b] : 0.f;
+    }
+    const int k = blockIdx.x * kGlThreads + tid;
+    if (k < nb) {
+        int lo = 0, hi = 0;
+        double w = 0.0;
+        for (int c = 0; c < nm; ++c) {
+            const float b = basis[(int64_t)c * nb + k];
+            if (b != 0.f) { if (hi == 0) lo = c; hi = c + 1; }
+            w += (double)b;
+        }
+        bin_rng[k] = make_int2(lo, hi);
+        inv_w[k] = w > 0.0 ? (float)(1.0 / w) : 0.f;
+    }
+}
+
 // MODE 0: one Griffin-Lim iteration, C_in -> C_out for the tile's own frames.  MODE 1: the final ISTFT, writes the tile's samples
 // [hop f0, hop (f0 + F)) of the waveform (zeros for L < L_min).  HOP_C = 256 (with NFFT 1024): the default geometry, hop and tile as
 // constants and the signal in static LDS; HOP_C = 0: hop, F and the halo from g, the signal in dynamic LDS (g.sig_max floats).
-template <int NFFT, int HOP_C, int MODE, bool MOMENTUM>
+// PROJ 0: C = M . A / |A|.  PROJ 1 (MODE 0 only): C = g . A, the per-bin gain g that makes the mel of |A| the caller's (mp; M is
+// not read): a = |A|, y = B a, r = min(exp(mel) / max(y, 1e-12), 1e4), g = (B^T r) / (B^T 1), 0 where no filter covers the bin.
+template <int NFFT, int HOP_C, int MODE, bool MOMENTUM, int PROJ = 0>
 __global__ __launch_bounds__(kGlThreads) void gl_iterate(const GlTile* tiles, GlGeom g, const float2* gtw, const float* gwin, const float* M,
-                                                         const float2* Cin, float2* Cout, float2* Tm, float beta, float* wav) {
+                                                         const float2* Cin, float2* Cout, float2* Tm, float beta, float* wav, GlMelProj mp) {
     constexpr int N2 = NFFT / 2, V = N2 / 64, NB = N2 + 1;
     __shared__ float2 tw[NFFT];
     __shared__ float win[NFFT];
@@ -426,18 +479,82 @@ __global__ __launch_bounds__(kGlThreads) void gl_iterate(const GlTile* tiles, Gl
         }
         float2 X[V], xl;
         gl_frame_rfft<NFFT>(v, X, xl, scratch[wv], tw, j);
-        if (valid) {
-            const int64_t row = (int64_t)(t.ws_row0 + f) * NB;
+        if constexpr (PROJ == 0) {
+            if (valid) {
+                const int64_t row = (int64_t)(t.ws_row0 + f) * NB;
 #pragma unroll
-            for (int r = 0; r <= V; ++r) {
-                if (r == V && j) break;
-                const int k2 = r == V ? N2 : j + 64 * r;
-                const float2 x = r == V ? xl : X[r];
-                float2 a = x;
-                if (MOMENTUM) { const float2 tp = Tm[row + k2]; a = make_float2(x.x - beta * tp.x, x.y - beta * tp.y); Tm[row + k2] = x; }
-                const float mag = sqrtf(a.x * a.x + a.y * a.y);
-                const float m = M[row + k2];
-                Cout[row + k2] = mag > 0.f ? make_float2(m * (a.x / mag), m * (a.y / mag)) : make_float2(m, 0.f);
+                for (int r = 0; r <= V; ++r) {
+                    if (r == V && j) break;
+                    const int k2 = r == V ? N2 : j + 64 * r;
+                    const float2 x = r == V ? xl : X[r];
+                    float2 a = x;
+                    if (MOMENTUM) { const float2 tp = Tm[row + k2]; a = make_float2(x.x - beta * tp.x, x.y - beta * tp.y); Tm[row + k2] = x; }
+                    const float mag = sqrtf(a.x * a.x + a.y * a.y);
+                    const float m = M[row + k2];
+                    Cout[row + k2] = mag > 0.f ? make_float2(m * (a.x / mag), m * (a.y / mag)) : make_float2(m, 0.f);
+                }
+            }
+        } else {
+            // |A| of this wave's frame (N/2 + 1 floats) and the band ratios r (n_mels <= 128 floats) behind it, in the wave's own
+            // scratch: N/2 + 1 + 128 <= N for every NFFT.  A stays in registers.  nf is block-uniform and `valid` only predicates,
+            // so every wave meets the three barriers.
+            static_assert(NB + kGlMaxMels <= NFFT, "|A| and r share one wave's scratch");
+            float* am = reinterpret_cast<float*>(scratch[wv]);
+            float* rr = am + NB;
+            const int nm = g.n_mels;
+            const int64_t row = (int64_t)(t.ws_row0 + f) * NB;
+            float2 A[V], al = xl;
+            __syncthreads();                            // gl_frame_rfft's last reads of the scratch
+            if (valid) {
+#pragma unroll
+                for (int r = 0; r <= V; ++r) {
+                    if (r == V && j) break;
+                    const int k2 = r == V ? N2 : j + 64 * r;
+                    const float2 x = r == V ? xl : X[r];
+                    float2 a = x;
+                    if (MOMENTUM) { const float2 tp = Tm[row + k2]; a = make_float2(x.x - beta * tp.x, x.y - beta * tp.y); Tm[row + k2] = x; }
+                    if (r == V) al = a; else A[r] = a;
+                    am[k2] = sqrtf(a.x * a.x + a.y * a.y);
+                }
+            }
+            __syncthreads();
+            if (valid) {
+                // lane j: the bands j and j + 64, each over its own bins in increasing order, four steps of both in flight
+                const float* mrow = mp.mel + (int64_t)(t.src_row0 + f) * nm;
+                const int c0 = j, c1 = j + 64;
+                const int2 r0 = c0 < nm ? mp.row_rng[c0] : make_int2(0, 0), r1 = c1 < nm ? mp.row_rng[c1] : make_int2(0, 0);
+                const int n0 = r0.y - r0.x, n1 = r1.y - r1.x, nmax = max(n0, n1);
+                float y0 = 0.f, y1 = 0.f;
+                for (int b = 0; b < nmax; b += 4) {
+                    float q0[4], q1[4], a0[4], a1[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float* bp = mp.band + (int64_t)min(b + u, NB - 1) * kGlMaxMels;
+                        q0[u] = bp[c0]; q1[u] = bp[c1];
+                        a0[u] = am[min(r0.x + b + u, NB - 1)]; a1[u] = am[min(r1.x + b + u, NB - 1)];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (b + u < n0) y0 += q0[u] * a0[u];
+                        if (b + u < n1) y1 += q1[u] * a1[u];
+                    }
+                }
+                if (c0 < nm) rr[c0] = fminf(expf(mrow[c0]) / fmaxf(y0, 1e-12f), 1e4f);
+                if (c1 < nm) rr[c1] = fminf(expf(mrow[c1]) / fmaxf(y1, 1e-12f), 1e4f);
+            }
+            __syncthreads();
+            if (valid) {
+#pragma unroll
+                for (int r = 0; r <= V; ++r) {
+                    if (r == V && j) break;
+                    const int k2 = r == V ? N2 : j + 64 * r;
+                    const float2 a = r == V ? al : A[r];
+                    const int2 rg = mp.bin_rng[k2];
+                    float s = 0.f;
+                    for (int c = rg.x; c < rg.y; ++c) s += mp.basis[(int64_t)c * NB + k2] * rr[c];
+                    const float gk = s * mp.inv_w[k2];
+                    Cout[row + k2] = make_float2(gk * a.x, gk * a.y);
+                }
             }
         }
     }

@@ -1,5 +1,6 @@
 // Host side of the vocoder (kernels: griffin_lim.h): geometry, workspace layout, host plan, launch sequence and the argument checks
-// behind fs2_op_griffin_lim{,_geom,_dev}, fs2_op_stft{,_geom}, fs2_op_stft_pitch_geom and their workspace queries (include/fs2.h).
+// behind fs2_op_griffin_lim{,_geom,_dev}, fs2_op_griffin_lim_mel_{geom,dev}, fs2_op_stft{,_geom}, fs2_op_stft_pitch_geom and their workspace
+// queries (include/fs2.h).
 // The host-planned call, the device-driven call and the analysis STFT share one workspace layout (gl_layout), one check of the
 // synthesis arguments (gl_check_synthesis), one GlIterArgs builder (gl_iter_args) and one choice of instantiation (gl_dispatch).
 // Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up(), so the library
@@ -47,14 +48,15 @@ auto gl_dispatch(const GlGeomHost& gh, Fn&& f) {
 
 // Workspace of every vocoder call: tables, tile records, the device planner's per-utterance arrays (device-driven call only), then
 // (synthesis only) M, the two spectrum buffers and the momentum state over `frames` frames packed back to back, then (analysis with
-// pitch only) the window-autocorrelation table of gl_pitch.h.  Each region starts 256-byte aligned.
+// pitch only) the window-autocorrelation table of gl_pitch.h, then (mel-constrained synthesis only) the band tables of
+// gl_band_tables.  Each region starts 256-byte aligned.
 struct GlLayout {
-    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, off_acw = 0, bytes = 0;
+    size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, off_acw = 0, off_band = 0, bytes = 0;
 };
 
 // records: tile records (the exact tile count of a host plan, the slots of a device-driven call); planner_B: utterances the device
 // planner keeps its 4 ints each for, < 0: a host-planned call, no such region.  0 records / 0 utterances still reserve one.
-GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int64_t frames, bool analysis, bool pitch = false) {
+GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int64_t frames, bool analysis, bool pitch = false, bool band = false) {
     GlLayout l;
     size_t off = 0;
     auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
@@ -70,6 +72,7 @@ GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int6
         l.off_T = take(n * sizeof(float2));
     }
     if (pitch) l.off_acw = take(gl_pitch_lags(gh.n_fft) * sizeof(float));
+    if (band) l.off_band = take(gl_band_bytes(gh.n_bins));
     l.bytes = align_up(off, 256);
     return l;
 }
@@ -84,7 +87,7 @@ struct GlPlan {
 
 // analysis = false: lens are frame counts L_b, samples hop max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
 // frames T_b / hop + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
-int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p, bool pitch = false) {
+int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p, bool pitch = false, bool band = false) {
     if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
     const int hop = gh.hop, F = gh.g.F, nb = gh.n_bins;
     int64_t row = 0, wav = 0;
@@ -109,7 +112,7 @@ int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, co
     }
     p.frames = row;
     p.samples = wav;
-    p.at = gl_layout(gh, p.tiles.size(), -1, p.frames, analysis, pitch);
+    p.at = gl_layout(gh, p.tiles.size(), -1, p.frames, analysis, pitch, band);
     return FS2_OK;
 }
 
@@ -139,11 +142,15 @@ hipError_t gl_setup(hipStream_t s, const GlPlan& p, const GlGeomHost& gh, char* 
     return hipGetLastError();
 }
 
+// proj: the projection of an iteration (gl_iterate's PROJ): 0 onto M, 1 mel-constrained, with mp filled in
 struct GlIterArgs {
     const GlTile* tiles; const float2* tw; const float* win; const float* M; float2* C[2]; float2* Tm; float beta; float* wav;
+    int proj; GlMelProj mp;
 };
 
-GlIterArgs gl_iter_args(char* ws, const GlLayout& at, float momentum, float* wav) {
+// mel_basis != NULL: a mel-constrained call (its layout has the band region); src is then the call's log-mel source
+GlIterArgs gl_iter_args(char* ws, const GlLayout& at, float momentum, float* wav, const float* src = nullptr, const float* mel_basis = nullptr,
+                        int n_bins = 0) {
     GlIterArgs a{};
     a.tiles = (const GlTile*)(ws + at.off_tiles);
     a.tw = (const float2*)(ws + at.off_tw);
@@ -154,6 +161,15 @@ GlIterArgs gl_iter_args(char* ws, const GlLayout& at, float momentum, float* wav
     a.Tm = momentum > 0.f ? (float2*)(ws + at.off_T) : nullptr;
     a.beta = momentum / (1.f + momentum);
     a.wav = wav;
+    if (mel_basis) {
+        a.proj = 1;
+        a.mp.mel = src;
+        a.mp.basis = mel_basis;
+        a.mp.row_rng = (const int2*)(ws + at.off_band);
+        a.mp.bin_rng = a.mp.row_rng + kGlMaxMels;
+        a.mp.inv_w = (const float*)(a.mp.bin_rng + n_bins);
+        a.mp.band = a.mp.inv_w + n_bins;
+    }
     return a;
 }
 
@@ -168,29 +184,45 @@ hipError_t gl_run(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const f
     if (lds && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
     // Set on every eager call, not once per instantiation: the byte count follows the hop (<1024, 0> at hop 200 and at hop 300
     // differ).  Host work only, skipped while capturing: a captured call relies on the eager call before it.
-    if (lds && cap == hipStreamCaptureStatusNone)
+    if (lds && cap == hipStreamCaptureStatusNone) {
         for (const void* k : {(const void*)gl_iterate<NFFT, HOP_C, 0, false>, (const void*)gl_iterate<NFFT, HOP_C, 0, true>,
                               (const void*)gl_iterate<NFFT, HOP_C, 1, false>})
             if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        if (a.proj)
+            for (const void* k : {(const void*)gl_iterate<NFFT, HOP_C, 0, false, 1>, (const void*)gl_iterate<NFFT, HOP_C, 0, true, 1>})
+                if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+    }
     if (src_width == 80 && gh.n_mels == 80 && src_width != gh.n_bins)
         hipLaunchKernelGGL((gl_prologue<NFFT, 80>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
     else
         hipLaunchKernelGGL((gl_prologue<NFFT, 0>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
+    const GlMelProj none{};
+    if (a.proj && n_iter > 0)       // the band tables of this call's basis, read by the iterations only
+        hipLaunchKernelGGL(gl_band_tables, dim3((gh.n_bins + kGlThreads - 1) / kGlThreads), blk, 0, s, a.mp.basis, gh.n_mels, gh.n_bins,
+                           const_cast<int2*>(a.mp.row_rng), const_cast<int2*>(a.mp.bin_rng), const_cast<float*>(a.mp.inv_w),
+                           const_cast<float*>(a.mp.band));
     for (int it = 0; it < n_iter; ++it) {
-        if (a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
-        else hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav);
+        if (a.proj && a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true, 1>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, a.mp);
+        else if (a.proj) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false, 1>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, a.mp);
+        else if (a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, none);
+        else hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, none);
     }
-    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[n_iter & 1], a.C[(n_iter + 1) & 1], nullptr, 0.f, a.wav);
+    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[n_iter & 1], a.C[(n_iter + 1) & 1], nullptr, 0.f, a.wav, none);
     return hipGetLastError();
 }
 
-// what the host-planned and the device-driven synthesis check first, in this order
-int gl_check_synthesis(const char* who, const GlGeomHost& gh, int32_t src_width, const float* mel_pinv, int32_t n_iter, float momentum) {
+// what the host-planned and the device-driven synthesis check first, in this order (mel_proj: the mel-constrained entry points,
+// which have no use for a magnitude source and need the basis)
+int gl_check_synthesis(const char* who, const GlGeomHost& gh, int32_t src_width, const float* mel_pinv, int32_t n_iter, float momentum,
+                       bool mel_proj = false, const float* mel_basis = nullptr) {
     if (src_width != gh.n_mels && src_width != gh.n_bins)
         return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
                     gh.n_bins, gh.n_fft);
     if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
     if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
+    if (mel_proj && src_width != gh.n_mels)
+        return fail(nullptr, FS2_ERR_ARG, "%s: src_width %d is a magnitude source: there is no mel to constrain to (%d mel bins)", who, src_width, gh.n_mels);
+    if (mel_proj && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: null mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
     return FS2_OK;
 }
 
@@ -206,11 +238,11 @@ int gl_synthesize(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const f
 
 int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
                    const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
-                   void* workspace, size_t workspace_bytes, float* wav) {
-    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum)) return rc;
+                   void* workspace, size_t workspace_bytes, float* wav, bool mel_proj = false, const float* mel_basis = nullptr) {
+    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum, mel_proj, mel_basis)) return rc;
     if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
     GlPlan p;
-    if (int rc = gl_plan(B, starts, lens, false, gh, p)) return rc;
+    if (int rc = gl_plan(B, starts, lens, false, gh, p, false, mel_proj)) return rc;
     if (p.tiles.empty()) return FS2_OK;
     if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
     if (workspace_bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.at.bytes);
@@ -218,7 +250,8 @@ int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const fl
     char* ws = (char*)workspace;
     hipError_t e = gl_setup(s, p, gh, ws);
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
-    return gl_synthesize(s, gh, (unsigned)p.tiles.size(), src, src_width, mel_pinv, init_phase, seed, n_iter, gl_iter_args(ws, p.at, momentum, wav));
+    return gl_synthesize(s, gh, (unsigned)p.tiles.size(), src, src_width, mel_pinv, init_phase, seed, n_iter,
+                         gl_iter_args(ws, p.at, momentum, wav, src, mel_proj ? mel_basis : nullptr, gh.n_bins));
 }
 
 static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvfUpstream == FS2_OVF_UPSTREAM && kGlOvfNegative == FS2_OVF_NEG_LEN &&
@@ -229,8 +262,9 @@ static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvf
 int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
                        const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
                        float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav,
-                       int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
-    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum)) return rc;
+                       int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status, bool mel_proj = false,
+                       const float* mel_basis = nullptr) {
+    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum, mel_proj, mel_basis)) return rc;
     if (B < 1 || frame_capacity < 1 || src_stride < 0 || wav_stride < 0)
         return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d", who, B, (long long)frame_capacity, src_stride, wav_stride);
     if (frame_capacity > INT32_MAX / gh.n_bins || wav_capacity < 0 || wav_capacity > INT32_MAX || (int64_t)B * src_stride > INT32_MAX)
@@ -240,7 +274,7 @@ int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, cons
     if (!src || !lens_dev || !workspace || !sample_lens_dev || !status || (wav_capacity > 0 && !wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
     const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
     if (slots < 0) return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call", who);
-    const GlLayout at = gl_layout(gh, (size_t)slots, B, frame_capacity, false);
+    const GlLayout at = gl_layout(gh, (size_t)slots, B, frame_capacity, false, false, mel_proj);
     if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -260,7 +294,8 @@ int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, cons
         hipLaunchKernelGGL(gl_plan_fill, dim3((unsigned)std::min<int64_t>((wav_capacity + 1023) / 1024, 2048)), dim3(256), 0, s, pa, wav);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim plan: %s", hipGetErrorString(e));
-    return gl_synthesize(s, gh, (unsigned)n_slots, src, src_width, mel_pinv, init_phase, seed, n_iter, gl_iter_args(ws, at, momentum, wav));
+    return gl_synthesize(s, gh, (unsigned)n_slots, src, src_width, mel_pinv, init_phase, seed, n_iter,
+                         gl_iter_args(ws, at, momentum, wav, src, mel_proj ? mel_basis : nullptr, gh.n_bins));
 }
 
 int gl_stft_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,

@@ -923,7 +923,7 @@ class FeedForwardTransformer(nn.Module):
         cloned into static tensors of the graph, and ``run(new_xs, new_ds=None, **new_controls)`` copies new values (a number, or a
         tensor of the captured shape) into them before the replay; a control that was not captured cannot be given to ``run``.
 
-        ``vocoder`` (a ``GriffinLim``; ``vocoder_args``: its ``n_iter``, ``momentum``, ``seed``, ``init``): the graph also runs the device-driven
+        ``vocoder`` (a ``GriffinLim``; ``vocoder_args``: its ``n_iter``, ``momentum``, ``seed``, ``init``, ``constraint``): the graph also runs the device-driven
         vocoder on the mels (``vocoder(AsyncMels, sync=False, padded_out=True)``: the frame counts never leave the device), and
         ``run(new_xs)`` returns ``(wav [B, hop (Lcap - 1)] zero-padded, sample_lens_dev, status_dev)`` instead -- text to waveform
         in one graph launch.  ``status_dev`` is the vocoder's, with the mel status folded in: a mel overflow shows as

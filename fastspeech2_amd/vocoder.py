@@ -303,6 +303,15 @@ def _i32(a):
 
 
 INITS = ("seeded", "spsi")
+CONSTRAINTS = ("magnitude", "mel")
+
+
+def _check_constraint(constraint, magnitudes):
+    if constraint not in CONSTRAINTS:
+        raise ValueError("constraint must be one of %s, got %r" % (CONSTRAINTS, constraint))
+    if constraint == "mel" and magnitudes:
+        raise ValueError("constraint='mel' needs log-mel frames: with magnitudes=True there is no mel to constrain to")
+    return constraint == "mel"
 
 
 def _check_init(init, init_phase):
@@ -324,6 +333,8 @@ class GriffinLim:
         self.params, self.geometry = _audio_config(hp)
         self.device = torch.device(device) if device is not None else None
         B = mel_basis(**self.params)
+        if not (np.isfinite(B).all() and (B >= 0).all()):       # the mel-constrained projection divides by the column sums
+            raise ValueError("the mel basis of hp.audio must be finite and non-negative")
         self._basis_np = B
         self._pinv_np = np.linalg.pinv(B)          # [bins, n_mels], float64 on the host
         self._dev = {}
@@ -363,7 +374,7 @@ class GriffinLim:
         return mels.reshape(-1, W).contiguous().float(), init_phase, W, n_iter, momentum
 
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
-                 padded_out=False, init="seeded"):
+                 padded_out=False, init="seeded", constraint="magnitude"):
         """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
         with ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
         [.., n_fft / 2 + 1] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout
@@ -372,13 +383,20 @@ class GriffinLim:
         harmonic signals 10 iterations from it beat 20 from the seeded start.  ``momentum`` > 0: fast
         Griffin-Lim (0 = the reference).  Runs on the current stream of the input's device without synchronising.
 
+        ``constraint="magnitude"`` (default) projects every iteration onto the fixed ``M = max(pinv . exp(mel), 0)``.
+        ``constraint="mel"`` keeps the magnitudes of the current STFT and rescales them per mel band so that their mel is the
+        given one (fs2_op_griffin_lim_mel_geom / _dev): the waveform's log-mel then lies much closer to
+        ``mels``.  It needs log-mel frames (with ``magnitudes=True`` it raises) and composes with ``init``, ``init_phase``,
+        ``momentum`` and ``sync=False``; ``n_iter=0`` is the same in both.
+
         ``sync=True`` reads ``olens`` on the host (a CUDA ``olens`` is copied back, which waits for the GPU) and sizes the result
         from it.  ``sync=False``: the frame counts stay on the device -- ``olens`` must be a CUDA int64 tensor, or ``mels`` an
         :class:`AsyncMels` (``inference_batch(sync=False)``), whose mels, ``olens`` and status are taken -- and nothing waits for
         the GPU; see :meth:`_call_dev`.  Returns an :class:`AsyncWaveforms`."""
         _check_init(init, init_phase)
+        mel_proj = _check_constraint(constraint, magnitudes)
         if not sync:
-            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init)
+            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init, constraint)
         if capacity is not None or padded_out:
             raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
@@ -409,14 +427,19 @@ class GriffinLim:
         B = len(l_np)
         if init == "spsi":
             init_phase = self._spsi_host(src, W, s_np, l_np, magnitudes, False)[0]
-        ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_geom(*g, B, l_p))
+        query = lib.fs2_op_vocode_mel_workspace_bytes_geom if mel_proj else lib.fs2_op_vocode_workspace_bytes_geom
+        ws_bytes = int(query(*g, B, l_p))
         with torch.cuda.device(dev):
             pinv = self.constants(dev)[0] if not magnitudes else None
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_griffin_lim_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
-                                                   B, s_p, l_p, n_iter, momentum, int(seed) & 0xFFFFFFFF,
-                                                   init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
-                                                   wav.data_ptr()))
+            tail = (B, s_p, l_p, n_iter, momentum, int(seed) & 0xFFFFFFFF, init_phase.data_ptr() if init_phase is not None else None,
+                    ws.data_ptr(), ws_bytes, wav.data_ptr())
+            if mel_proj:
+                _lib.check(lib.fs2_op_griffin_lim_mel_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr(),
+                                                           self.constants(dev)[1].data_ptr(), *tail))
+            else:
+                _lib.check(lib.fs2_op_griffin_lim_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
+                                                       *tail))
         return Waveforms(wav, sample_lens)
 
 
@@ -522,14 +545,17 @@ class GriffinLim:
         slot[1] = _WavRecord(ev, slot[0])
         return slot[1]
 
-    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init="seeded"):
+    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init="seeded",
+                  constraint="magnitude"):
         """The device-driven call (include/fs2.h: fs2_op_griffin_lim_dev).  ``capacity``: bound on the batch's total frames (default:
         the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the waveform is
         sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only) [B, hop (Lcap - 1)].
         Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own call overflowed, give
         a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``.  ``init="spsi"``: the initial phase is computed on the device
-        from the same frame counts first (fs2_op_spsi_phase_dev), equally without a host read."""
+        from the same frame counts first (fs2_op_spsi_phase_dev), equally without a host read.  ``constraint="mel"``: the
+        mel-constrained projection (fs2_op_griffin_lim_mel_dev), as in :meth:`__call__`."""
         _check_init(init, init_phase)
+        mel_proj = _check_constraint(constraint, magnitudes)
         upstream = None
         if isinstance(mels, AsyncMels):
             if olens is not None:
@@ -578,17 +604,21 @@ class GriffinLim:
             sample_lens = torch.empty(B, dtype=torch.int64, device=dev)        # both written in full by the planner
             status = torch.empty(8, dtype=torch.int32, device=dev)
             lib = _lib.lib()
-            ws_bytes = int(lib.fs2_op_vocode_workspace_bytes_cap(*g, B, cap))
+            query = lib.fs2_op_vocode_mel_workspace_bytes_cap if mel_proj else lib.fs2_op_vocode_workspace_bytes_cap
+            ws_bytes = int(query(*g, B, cap))
             pinv = self.constants(dev)[0] if not magnitudes else None
             if init == "spsi":
                 init_phase = self._spsi_dev(src, W, olens, stride, cap, upstream, magnitudes, False)[0]
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_griffin_lim_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, B,
-                                                  olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
-                                                  n_iter, momentum, int(seed) & 0xFFFFFFFF,
-                                                  init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
-                                                  wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(),
-                                                  status.data_ptr()))
+            tail = (B, olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None, n_iter, momentum,
+                    int(seed) & 0xFFFFFFFF, init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
+                    wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(), status.data_ptr())
+            if mel_proj:
+                _lib.check(lib.fs2_op_griffin_lim_mel_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr(),
+                                                          self.constants(dev)[1].data_ptr(), *tail))
+            else:
+                _lib.check(lib.fs2_op_griffin_lim_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
+                                                      *tail))
             rec = None if torch.cuda.is_current_stream_capturing() else self._record(status, dev)
         return AsyncWaveforms(shaped, sample_lens, status, rec, bool(padded_out))
 

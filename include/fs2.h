@@ -397,6 +397,32 @@ int fs2_op_griffin_lim_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win
                            void *workspace, size_t workspace_bytes, float *wav, int32_t wav_stride, int64_t wav_capacity,
                            int64_t *sample_lens_dev, int32_t *status);
 
+/* ---- Mel-constrained Griffin-Lim: fs2_op_griffin_lim_geom / fs2_op_griffin_lim_dev with another
+ * projection inside an iteration.  The prologue (M = max(mel_pinv . exp(mel), 0), C0 = M . exp(i theta0)), the transforms, the
+ * momentum form A = X - momentum / (1 + momentum) . T, T <- X and the final ISTFT are unchanged; where the plain call sets
+ * C = M . A / |A|, these set, per frame with B = mel_basis [n_mels, bins] (non-negative) and mel the frame's log-mel row of src:
+ *   a[k] = |A[k]|;  y[c] = sum_k B[c,k] a[k];  r[c] = min(exp(mel[c]) / max(y[c], 1e-12), 1e4);
+ *   g[k] = (sum_c B[c,k] r[c]) / (sum_c B[c,k]), 0 where no filter covers bin k;  C[k] = g[k] A[k]
+ * so the mel of the magnitudes the next ISTFT starts from is the caller's.  n_iter = 0 gives the plain call's result bit for bit.
+ * Arguments are the plain siblings' plus mel_basis (device).  src_width must be n_mels: a magnitude source (src_width = bins) is
+ * FS2_ERR_ARG, as is a NULL mel_basis.  The workspace holds three band tables more than the plain call's (the queries below); an
+ * utterance's waveform is bit-identical alone or inside any batch, and in the host-planned and the device-driven form. ---- */
+
+size_t fs2_op_vocode_mel_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *lens);
+
+int fs2_op_griffin_lim_mel_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                                const float *mel_pinv, const float *mel_basis, int32_t B, const int32_t *starts, const int32_t *lens,
+                                int32_t n_iter, float momentum, uint32_t seed, const float *init_phase, void *workspace,
+                                size_t workspace_bytes, float *wav);
+
+size_t fs2_op_vocode_mel_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity);
+
+int fs2_op_griffin_lim_mel_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *src, int32_t src_width,
+                               const float *mel_pinv, const float *mel_basis, int32_t B, const int64_t *lens_dev, int32_t src_stride,
+                               int64_t frame_capacity, const int32_t *upstream_status, int32_t n_iter, float momentum, uint32_t seed,
+                               const float *init_phase, void *workspace, size_t workspace_bytes, float *wav, int32_t wav_stride,
+                               int64_t wav_capacity, int64_t *sample_lens_dev, int32_t *status);
+
 /* ---- Phase-continuity initial phase for Griffin-Lim (fastspeech2_amd/csrc/gl_spsi.h): Single Pass
  * Spectrogram Inversion (Beauregard, Harish and Wyse 2015) builds, from the magnitudes alone, angles to pass as `init_phase` to the
  * entry points above; from them Griffin-Lim needs fewer iterations than from the seeded random phase.  Geometries, src / src_width /

@@ -22,6 +22,12 @@ Every region is K steps between two device synchronisations; (b) and (c) are che
 
 --init seeded|spsi: the initial phase of every Griffin-Lim call of the runs above (default seeded; --n-iter as before).
 
+--constraint magnitude|mel: the projection of every Griffin-Lim iteration of the default run and of --pipeline (default magnitude;
+DESIGN.md section 14.10).  The default run also reports logmel_err = mean |log-mel(wav) - mels| over the batch (stft_magnitude on the GPU).
+
+--compare-constraint [--repeats R]: the vocoder call in both constraints on the same mels, at --n-iter and at 0 iterations, all four timed
+alternately over R rounds (median and max - min spread); per-iteration times, their ratio mel / magnitude, and logmel_err of both.
+
 --compare-init [--n-iter 10] [--repeats R] [--steps K] [--pipeline-workloads c3,c1]: the SPSI initial phase against the seeded one, per
 workload, every pair timed alternately over R rounds (median and max - min spread): (i) spsi_phase alone, (ii) the vocoder call
 (seeded, 30) against (spsi, --n-iter), (iii) the text -> wav step, synchronous and sync-free on three streams, for the same two
@@ -108,11 +114,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="steps per timed region of the --pipeline run")
     ap.add_argument("--precision", default="mix_mx4", help="the model's arithmetic mode in the --pipeline run (bench.py's default)")
     ap.add_argument("--init", default="seeded", choices=("seeded", "spsi"), help="initial phase of the Griffin-Lim calls")
+    ap.add_argument("--constraint", default="magnitude", choices=("magnitude", "mel"), help="projection of a Griffin-Lim iteration")
     ap.add_argument("--compare-init", action="store_true", help="(seeded, 30) against (spsi, --n-iter) (see the module docstring)")
+    ap.add_argument("--compare-constraint", action="store_true", help="both constraints alternately (see the module docstring)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "vocoder_bench needs a GPU"
+    if args.constraint != "magnitude" and (args.compare_init or args.geometry is not None or args.sample_rate is not None):
+        ap.error("--constraint belongs to the default run and to --pipeline (the --geometry run vocodes magnitudes)")
     if args.compare_init:
         return compare_init_main(args)
+    if args.compare_constraint:
+        return compare_constraint_main(args)
     if args.pipeline:
         return pipeline_main(args)
     if args.geometry is not None or args.sample_rate is not None:
@@ -121,7 +133,7 @@ def main():
     hp, mels, olens = c3_mels(args.workload)
     N, B = mels.shape[0], len(olens)
     gl = GriffinLim(hp)
-    run = lambda n: gl(mels, olens, n_iter=n, seed=0, init=args.init)
+    run = lambda n: gl(mels, olens, n_iter=n, seed=0, init=args.init, constraint=args.constraint)
     ms_call, reps = timed(lambda: run(args.n_iter), args.min_s)
     ms_zero, _ = timed(lambda: run(0), args.min_s)
     ms_iter = (ms_call - ms_zero) / max(args.n_iter, 1)
@@ -134,6 +146,8 @@ def main():
     Xh = stft_magnitude(out.wav, out.sample_lens)
     num = float(torch.linalg.norm(Mt - Xh)) if Xh.shape == Mt.shape else float("nan")
     sc_hip = num / float(torch.linalg.norm(Mt))
+    lm = stft_magnitude(out.wav, out.sample_lens, mel=True, hp=hp)
+    logmel_err = float((lm - mels).abs().mean()) if lm.shape == mels.shape else float("nan")
     # traffic / FLOP per iteration from shapes: C of (F + 6) / F frames in, M in, C out (+ halo), 2.4 real 1024-FFTs per frame
     F = 32
     tiles = sum(math.ceil(L / F) for L in olens if L >= 4)
@@ -143,7 +157,8 @@ def main():
     flop_iter = (halo_frames + N) * fft_flop + N * 513 * 12
     t_bytes = bytes_iter / (PEAK_HBM_TBS * 1e12) * 1e3
     t_flop = flop_iter / (PEAK_FP32_TFLOPS * 1e12) * 1e3
-    rec = dict(workload=args.workload, utterances=B, frames=N, tiles=tiles, n_iter=args.n_iter, init=args.init, samples=samples,
+    rec = dict(workload=args.workload, utterances=B, frames=N, tiles=tiles, n_iter=args.n_iter, init=args.init, constraint=args.constraint,
+               samples=samples, logmel_err=round(logmel_err, 5),
                audio_seconds=round(audio_s, 3), hip_ms_per_call=round(ms_call, 3), hip_ms_call_n_iter0=round(ms_zero, 3),
                hip_ms_per_iter=round(ms_iter, 4), hip_reps=reps, real_time_factor=round(audio_s / (ms_call / 1e3), 1),
                bytes_per_iter=bytes_iter, flop_per_iter=flop_iter,
@@ -179,8 +194,8 @@ def pipeline_main(args):
     model = model.cuda()
     model.precision = args.precision
     gl = GriffinLim(hp)
-    K, n_iter, init = args.steps, args.n_iter, args.init
-    rec = dict(mode="pipeline", precision=args.precision, n_iter=n_iter, init=init, steps_per_region=K, rounds=args.repeats, workloads={})
+    K, n_iter, init, con = args.steps, args.n_iter, args.init, args.constraint
+    rec = dict(mode="pipeline", precision=args.precision, n_iter=n_iter, init=init, constraint=con, steps_per_region=K, rounds=args.repeats, workloads={})
 
     def region(step, finish=None):
         torch.cuda.synchronize()
@@ -197,11 +212,11 @@ def pipeline_main(args):
             b = make_batch(workload)
             xs, il = b["xs"].cuda(), b["ilens"]
             mels, olens = model.inference_batch(xs, il, packed=True)          # (first call: synchronous, learns the capacities)
-            ref = gl(mels, olens, n_iter=n_iter, init=init)
+            ref = gl(mels, olens, n_iter=n_iter, init=init, constraint=con)
 
             def step_sync():
                 m, ol = model.inference_batch(xs, il, packed=True)
-                return gl(m, ol, n_iter=n_iter, init=init)
+                return gl(m, ol, n_iter=n_iter, init=init, constraint=con)
 
             rot = StepStreams(3)
             keep = []
@@ -209,12 +224,12 @@ def pipeline_main(args):
             def step_async():
                 with rot.next():
                     am = model.inference_batch(xs, il, packed=True, sync=False)
-                    keep.append((am, gl(am, n_iter=n_iter, sync=False, init=init)))
+                    keep.append((am, gl(am, n_iter=n_iter, sync=False, init=init, constraint=con)))
                 del keep[:-3]                                                   # (three steps in flight own their buffers)
 
             forms = {"sync": (step_sync, None), "async": (step_async, rot.join)}
             if workload == "c1":
-                run = model.capture_graph(xs, il, vocoder=gl, n_iter=n_iter, init=init)
+                run = model.capture_graph(xs, il, vocoder=gl, n_iter=n_iter, init=init, constraint=con)
                 forms["graph"] = (lambda: run(xs), None)
             for step, finish in forms.values():                                # warm-up of every form
                 region(step, finish)
@@ -240,6 +255,29 @@ def pipeline_main(args):
             if "graph" in forms:
                 out["graph_over_sync"] = round(out["graph_ms_per_step"] / out["sync_ms_per_step"], 4)
             rec["workloads"][workload] = out
+    print(json.dumps(rec))
+
+
+def compare_constraint_main(args):
+    from fastspeech2_amd.vocoder import GriffinLim, stft_magnitude
+    hp, mels, olens = c3_mels(args.workload)
+    gl = GriffinLim(hp)
+    rec = dict(mode="compare_constraint", workload=args.workload, utterances=len(olens), frames=int(mels.shape[0]), n_iter=args.n_iter, init=args.init,
+               rounds=args.repeats, min_s=args.min_s, note="mels of a randomly initialised model: not speech")
+    stat = lambda v: dict(median=round(float(np.median(v)), 4), spread=round(max(v) - min(v), 4), runs=[round(x, 4) for x in v])
+    ms = {(c, n): [] for c in ("magnitude", "mel") for n in (args.n_iter, 0)}
+    for _ in range(args.repeats):                                                # alternating: every setting once per round
+        for (c, n), v in ms.items():
+            v.append(timed(lambda: gl(mels, olens, n_iter=n, seed=0, init=args.init, constraint=c), args.min_s)[0])
+    per_iter = {}
+    for c in ("magnitude", "mel"):
+        rec[c + "_ms_per_call"], rec[c + "_ms_call_n_iter0"] = stat(ms[(c, args.n_iter)]), stat(ms[(c, 0)])
+        per_iter[c] = (rec[c + "_ms_per_call"]["median"] - rec[c + "_ms_call_n_iter0"]["median"]) / max(args.n_iter, 1)
+        rec[c + "_ms_per_iter"] = round(per_iter[c], 4)
+        w = gl(mels, olens, n_iter=args.n_iter, seed=0, init=args.init, constraint=c)
+        lm = stft_magnitude(w.wav, w.sample_lens, mel=True, hp=hp)
+        rec[c + "_logmel_err"] = round(float((lm - mels).abs().mean()), 5) if lm.shape == mels.shape else None
+    rec["mel_over_magnitude_per_iter"] = round(per_iter["mel"] / per_iter["magnitude"], 4)
     print(json.dumps(rec))
 
 
