@@ -1904,150 +1904,125 @@ int fs2_op_bucketize(void* stream, const float* x, int64_t n, const float* bins,
     return FS2_OK;
 }
 
+// The vocoder's entry points (griffin_lim_host.h): each fills one GlCall -- who, kind, geometry, batch, workspace, source, iteration,
+// output -- and hands it to gl_call; a query hands the same who-kind-geometry-batch to gl_workspace_bytes.
 size_t fs2_op_vocode_workspace_bytes(int32_t B, const int32_t* lens) { return fs2_op_vocode_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, lens); }
 
 size_t fs2_op_vocode_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
-    GlGeomHost gh;
-    GlPlan p;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, lens, false, gh, p) == FS2_OK ? p.at.bytes : 0;
+    return gl_workspace_bytes({"fs2_op_vocode_workspace_bytes_geom", GlKind::Synthesis, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, lens)});
 }
 
 int fs2_op_griffin_lim(void* stream, const float* src, int32_t src_width, const float* mel_pinv, int32_t B, const int32_t* starts,
                        const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase, void* workspace,
                        size_t workspace_bytes, float* wav) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(kGlNfft, kGlHop, kGlNfft, 80, "fs2_op_griffin_lim", gh)) return rc;
-    return gl_griffin_lim("fs2_op_griffin_lim", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
-                          workspace, workspace_bytes, wav);
+    return gl_call(stream, {"fs2_op_griffin_lim", GlKind::Synthesis, {kGlNfft, kGlHop, kGlNfft, 80}, gl_host_batch(B, starts, lens),
+                            {workspace, workspace_bytes}, {src, src_width, mel_pinv, nullptr}, {n_iter, momentum, seed, init_phase}, {wav}});
 }
 
 int fs2_op_griffin_lim_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
                             const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
                             void* workspace, size_t workspace_bytes, float* wav) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_geom", gh)) return rc;
-    return gl_griffin_lim("fs2_op_griffin_lim_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
-                          workspace, workspace_bytes, wav);
+    return gl_call(stream, {"fs2_op_griffin_lim_geom", GlKind::Synthesis, {n_fft, hop, win, n_mels}, gl_host_batch(B, starts, lens),
+                            {workspace, workspace_bytes}, {src, src_width, mel_pinv, nullptr}, {n_iter, momentum, seed, init_phase}, {wav}});
 }
 
 size_t fs2_op_vocode_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
-    GlGeomHost gh;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_workspace_bytes_cap", gh)) return 0;
-    const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
-    return slots < 0 ? 0 : gl_layout(gh, (size_t)slots, B, frame_capacity, false).bytes;
+    return gl_workspace_bytes({"fs2_op_vocode_workspace_bytes_cap", GlKind::Synthesis, {n_fft, hop, win, n_mels},
+                               gl_device_batch(B, nullptr, 0, frame_capacity, nullptr)});
 }
 
 int fs2_op_griffin_lim_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
                            int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
                            float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav, int32_t wav_stride,
                            int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_dev", gh)) return rc;
-    return gl_griffin_lim_dev("fs2_op_griffin_lim_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, n_iter,
-                              momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status);
+    return gl_call(stream, {"fs2_op_griffin_lim_dev", GlKind::Synthesis, {n_fft, hop, win, n_mels},
+                            gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status), {workspace, workspace_bytes},
+                            {src, src_width, mel_pinv, nullptr}, {n_iter, momentum, seed, init_phase},
+                            {wav, wav_stride, wav_capacity, sample_lens_dev, status}});
 }
 
 size_t fs2_op_vocode_mel_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
-    GlGeomHost gh;
-    GlPlan p;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_mel_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, lens, false, gh, p, false, true) == FS2_OK ? p.at.bytes : 0;
+    return gl_workspace_bytes({"fs2_op_vocode_mel_workspace_bytes_geom", GlKind::MelSynthesis, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, lens)});
 }
 
 int fs2_op_griffin_lim_mel_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
                                 const float* mel_basis, int32_t B, const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed,
                                 const float* init_phase, void* workspace, size_t workspace_bytes, float* wav) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_mel_geom", gh)) return rc;
-    return gl_griffin_lim("fs2_op_griffin_lim_mel_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, n_iter, momentum, seed, init_phase,
-                          workspace, workspace_bytes, wav, true, mel_basis);
+    return gl_call(stream, {"fs2_op_griffin_lim_mel_geom", GlKind::MelSynthesis, {n_fft, hop, win, n_mels}, gl_host_batch(B, starts, lens),
+                            {workspace, workspace_bytes}, {src, src_width, mel_pinv, mel_basis}, {n_iter, momentum, seed, init_phase}, {wav}});
 }
 
 size_t fs2_op_vocode_mel_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
-    GlGeomHost gh;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_vocode_mel_workspace_bytes_cap", gh)) return 0;
-    const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
-    return slots < 0 ? 0 : gl_layout(gh, (size_t)slots, B, frame_capacity, false, false, true).bytes;
+    return gl_workspace_bytes({"fs2_op_vocode_mel_workspace_bytes_cap", GlKind::MelSynthesis, {n_fft, hop, win, n_mels},
+                               gl_device_batch(B, nullptr, 0, frame_capacity, nullptr)});
 }
 
 int fs2_op_griffin_lim_mel_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
                                const float* mel_basis, int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity,
                                const int32_t* upstream_status, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase, void* workspace,
                                size_t workspace_bytes, float* wav, int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_griffin_lim_mel_dev", gh)) return rc;
-    return gl_griffin_lim_dev("fs2_op_griffin_lim_mel_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status,
-                              n_iter, momentum, seed, init_phase, workspace, workspace_bytes, wav, wav_stride, wav_capacity, sample_lens_dev, status, true,
-                              mel_basis);
+    return gl_call(stream, {"fs2_op_griffin_lim_mel_dev", GlKind::MelSynthesis, {n_fft, hop, win, n_mels},
+                            gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status), {workspace, workspace_bytes},
+                            {src, src_width, mel_pinv, mel_basis}, {n_iter, momentum, seed, init_phase},
+                            {wav, wav_stride, wav_capacity, sample_lens_dev, status}});
 }
 
 size_t fs2_op_spsi_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
-    GlGeomHost gh;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_workspace_bytes_geom", gh)) return 0;
-    const int64_t frames = spsi_host_frames("fs2_op_spsi_workspace_bytes_geom", gh, B, nullptr, lens);
-    return frames < 0 ? 0 : spsi_layout(gh.n_bins, B, frames).bytes;
+    return gl_workspace_bytes({"fs2_op_spsi_workspace_bytes_geom", GlKind::SpsiPhase, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, lens)});
 }
 
 size_t fs2_op_spsi_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
-    GlGeomHost gh;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_workspace_bytes_cap", gh)) return 0;
-    return spsi_caps_ok(gh, B, 0, frame_capacity) ? spsi_layout(gh.n_bins, B, frame_capacity).bytes : 0;
+    return gl_workspace_bytes({"fs2_op_spsi_workspace_bytes_cap", GlKind::SpsiPhase, {n_fft, hop, win, n_mels},
+                               gl_device_batch(B, nullptr, 0, frame_capacity, nullptr)});
 }
 
 int fs2_op_spsi_phase_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
                            int32_t B, const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes, float* phase, float* mag_out) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_phase_geom", gh)) return rc;
-    return spsi_phase_host("fs2_op_spsi_phase_geom", stream, gh, src, src_width, mel_pinv, B, starts, lens, workspace, workspace_bytes, phase, mag_out);
+    GlCall c{"fs2_op_spsi_phase_geom", GlKind::SpsiPhase, {n_fft, hop, win, n_mels}, gl_host_batch(B, starts, lens), {workspace, workspace_bytes},
+             {src, src_width, mel_pinv, nullptr}};
+    c.spsi = {phase, mag_out};
+    return gl_call(stream, c);
 }
 
 int fs2_op_spsi_phase_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* src, int32_t src_width, const float* mel_pinv,
                           int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, void* workspace,
                           size_t workspace_bytes, float* phase, float* mag_out) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_spsi_phase_dev", gh)) return rc;
-    return spsi_phase_dev("fs2_op_spsi_phase_dev", stream, gh, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, workspace,
-                          workspace_bytes, phase, mag_out);
+    GlCall c{"fs2_op_spsi_phase_dev", GlKind::SpsiPhase, {n_fft, hop, win, n_mels}, gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status),
+             {workspace, workspace_bytes}, {src, src_width, mel_pinv, nullptr}};
+    c.spsi = {phase, mag_out};
+    return gl_call(stream, c);
 }
 
 size_t fs2_op_stft_workspace_bytes(int32_t B, const int32_t* wav_lens) { return fs2_op_stft_workspace_bytes_geom(kGlNfft, kGlHop, kGlNfft, 80, B, wav_lens); }
 
 size_t fs2_op_stft_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* wav_lens) {
-    GlGeomHost gh;
-    GlPlan p;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, wav_lens, true, gh, p) == FS2_OK ? p.at.bytes : 0;
+    return gl_workspace_bytes({"fs2_op_stft_workspace_bytes_geom", GlKind::Analysis, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, wav_lens)});
 }
 
 int fs2_op_stft(void* stream, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens, void* workspace,
                 size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(kGlNfft, kGlHop, kGlNfft, 80, "fs2_op_stft", gh)) return rc;
-    return gl_stft_run("fs2_op_stft", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, nullptr);
+    GlCall c{"fs2_op_stft", GlKind::Analysis, {kGlNfft, kGlHop, kGlNfft, 80}, gl_host_batch(B, wav_starts, wav_lens), {workspace, workspace_bytes}, {wav}};
+    c.feat = {mag, mel_basis, logmel};
+    return gl_call(stream, c);
 }
 
 int fs2_op_stft_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* wav, int32_t B, const int32_t* wav_starts, const int32_t* wav_lens,
                      void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_geom", gh)) return rc;
-    return gl_stft_run("fs2_op_stft_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy);
+    GlCall c{"fs2_op_stft_geom", GlKind::Analysis, {n_fft, hop, win, n_mels}, gl_host_batch(B, wav_starts, wav_lens), {workspace, workspace_bytes}, {wav}};
+    c.feat = {mag, mel_basis, logmel, energy};
+    return gl_call(stream, c);
 }
 
 size_t fs2_op_stft_pitch_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* wav_lens) {
-    GlGeomHost gh;
-    GlPlan p;
-    if (gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_pitch_workspace_bytes_geom", gh)) return 0;
-    return gl_plan(B, nullptr, wav_lens, true, gh, p, true) == FS2_OK ? p.at.bytes : 0;
+    return gl_workspace_bytes({"fs2_op_stft_pitch_workspace_bytes_geom", GlKind::AnalysisPitch, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, wav_lens)});
 }
 
 int fs2_op_stft_pitch_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* wav, int32_t B, const int32_t* wav_starts,
                            const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy,
                            int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold, double octave_cost, float* f0, float* strength) {
-    GlGeomHost gh;
-    if (int rc = gl_geom(n_fft, hop, win, n_mels, "fs2_op_stft_pitch_geom", gh)) return rc;
-    return gl_stft_pitch_run("fs2_op_stft_pitch_geom", stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy,
-                             sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost, f0, strength);
+    GlCall c{"fs2_op_stft_pitch_geom", GlKind::AnalysisPitch, {n_fft, hop, win, n_mels}, gl_host_batch(B, wav_starts, wav_lens), {workspace, workspace_bytes}, {wav}};
+    c.feat = {mag, mel_basis, logmel, energy, {sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost}, f0, strength};
+    return gl_call(stream, c);
 }
 
 size_t fs2_op_targets_workspace_bytes(int32_t B) { return B < 0 ? 0 : tg_layout(B).bytes; }

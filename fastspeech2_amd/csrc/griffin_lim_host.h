@@ -1,10 +1,17 @@
-// Host side of the vocoder (kernels: griffin_lim.h): geometry, workspace layout, host plan, launch sequence and the argument checks
-// behind fs2_op_griffin_lim{,_geom,_dev}, fs2_op_griffin_lim_mel_{geom,dev}, fs2_op_stft{,_geom}, fs2_op_stft_pitch_geom and their workspace
-// queries (include/fs2.h).
-// The host-planned call, the device-driven call and the analysis STFT share one workspace layout (gl_layout), one check of the
-// synthesis arguments (gl_check_synthesis), one GlIterArgs builder (gl_iter_args) and one choice of instantiation (gl_dispatch).
+// Host side of the vocoder (kernels: griffin_lim.h, gl_spsi.h, gl_pitch.h): one description of a call, GlCall, and one path over it
+// (include/fs2.h).
+// A GlCall says what the call computes (GlKind), on which transform (GlGeomArgs), for which batch (GlBatch: host-planned or
+// device-driven), where it may work (GlWork), from what (GlSource), how it iterates (GlIter) and what it writes (GlWavOut, GlFeatures,
+// GlPhaseOut).  Every extern "C" entry point at the end of fs2_runtime.hip only fills one and hands it to gl_call (the calls) or
+// gl_workspace_bytes (the queries), which make the geometry first.  The kind alone decides which workspace regions exist and which
+// argument checks apply: the mel-constrained call is the plain call with another kind, pitch an optional part of the one analysis.
+// A query and the call it sizes go through the same sizing function with the same description -- gl_size (synthesis and analysis:
+// gl_plan and gl_layout), spsi_size (SPSI: spsi_layout) -- so they agree by construction.  Only the domain differs: a query answers a
+// size (or 0) where the call refuses in its own words, so the sizing of a device-driven batch fails without a text and the call gives it.
+// The order of the checks is part of the interface (the message names the check that fired): gl_synthesize, gl_analyze and
+// spsi_phase each state theirs.
 // Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up(), so the library
-// stays one translation unit; the extern "C" entry points are with the others at the end of fs2_runtime.hip.
+// stays one translation unit.
 
 // Geometry of a call: validated (n_fft, hop, win, n_mels) plus the tile rule (F, halo, tail frame, L_min, signal buffer) derived from it.
 struct GlGeomHost {
@@ -46,17 +53,69 @@ auto gl_dispatch(const GlGeomHost& gh, Fn&& f) {
     return f(integral_constant<int, 2048>{}, integral_constant<int, 0>{});
 }
 
-// Workspace of every vocoder call: tables, tile records, the device planner's per-utterance arrays (device-driven call only), then
-// (synthesis only) M, the two spectrum buffers and the momentum state over `frames` frames packed back to back, then (analysis with
-// pitch only) the window-autocorrelation table of gl_pitch.h, then (mel-constrained synthesis only) the band tables of
-// gl_band_tables.  Each region starts 256-byte aligned.
+// ---- the description of a call: plain aggregates, every part an entry point does not name is zero ----
+
+// What a call computes.  Synthesis projects every iteration onto the fixed M, MelSynthesis onto the magnitudes whose mel is the
+// source's (gl_iterate's PROJ = 1; it reads GlSource::mel_basis); Analysis is the STFT with its features, AnalysisPitch adds f0 and
+// strength; SpsiPhase is the initial phase of gl_spsi.h (a workspace of its own: spsi_layout).
+enum class GlKind { Synthesis, MelSynthesis, Analysis, AnalysisPitch, SpsiPhase };
+
+constexpr bool gl_is_analysis(GlKind k) { return k == GlKind::Analysis || k == GlKind::AnalysisPitch; }
+
+struct GlGeomArgs { int32_t n_fft, hop, win, n_mels; };
+
+// The batch in one of two forms.  Host-planned: starts and lens [B] on the host (synthesis: source rows and frame counts L_b;
+// analysis: waveform samples and sample counts T_b; starts may be NULL for a size query).  Device-driven (on_device): the frame counts
+// stay on the device, every size comes from the capacities, and upstream_status is the status of the producer of the frames, or NULL.
+struct GlBatch {
+    bool on_device; int32_t B;
+    const int32_t *starts, *lens;
+    const int64_t* lens_dev; int32_t src_stride; int64_t frame_capacity; const int32_t* upstream_status;
+};
+
+GlBatch gl_host_batch(int32_t B, const int32_t* starts, const int32_t* lens) { return {false, B, starts, lens, nullptr, 0, 0, nullptr}; }
+
+GlBatch gl_device_batch(int32_t B, const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status) {
+    return {true, B, nullptr, nullptr, lens_dev, src_stride, frame_capacity, upstream_status};
+}
+
+struct GlWork { void* ptr; size_t bytes; };
+
+// Rows of log-mel (src_width = n_mels, mapped to magnitudes with mel_pinv [bins, n_mels]) or of magnitudes (src_width = bins);
+// mel_basis [n_mels, bins]: what MelSynthesis constrains to.  The analysis reads src alone: its packed waveforms.
+struct GlSource { const float* src; int32_t src_width; const float *mel_pinv, *mel_basis; };
+
+struct GlIter { int32_t n_iter; float momentum; uint32_t seed; const float* init_phase; };
+
+// wav alone for a host-planned call (packed, sized by the caller from lens); the rest belongs to the device-driven one
+struct GlWavOut { float* wav; int32_t wav_stride; int64_t wav_capacity; int64_t* sample_lens_dev; int32_t* status; };
+
+struct GlPitchOptions { int32_t sample_rate; double f0_floor, f0_ceil, voicing_threshold, octave_cost; };
+
+// Outputs of the analysis, each optional; logmel needs mel_basis; pitch, f0 and strength belong to AnalysisPitch
+struct GlFeatures { float* mag; const float* mel_basis; float *logmel, *energy; GlPitchOptions pitch; float *f0, *strength; };
+
+struct GlPhaseOut { float *phase, *mag_out; };
+
+// who: the entry point, for the messages.  gh: made from geom by gl_call / gl_workspace_bytes before anything else is looked at.
+struct GlCall {
+    const char* who; GlKind kind; GlGeomArgs geom; GlBatch batch; GlWork work; GlSource source; GlIter iter; GlWavOut out;
+    GlFeatures feat; GlPhaseOut spsi; GlGeomHost gh;
+};
+
+// ---- sizing of the synthesis and the analysis ----
+
+// Their workspace: tables, tile records, the device planner's per-utterance arrays (device-driven call only), then (synthesis only)
+// M, the two spectrum buffers and the momentum state over `frames` frames packed back to back, then (AnalysisPitch only) the
+// window-autocorrelation table of gl_pitch.h, then (MelSynthesis only) the band tables of gl_band_tables.  Each region starts
+// 256-byte aligned.
 struct GlLayout {
     size_t off_tw = 0, off_win = 0, off_tiles = 0, off_plan = 0, off_M = 0, off_C0 = 0, off_C1 = 0, off_T = 0, off_acw = 0, off_band = 0, bytes = 0;
 };
 
 // records: tile records (the exact tile count of a host plan, the slots of a device-driven call); planner_B: utterances the device
 // planner keeps its 4 ints each for, < 0: a host-planned call, no such region.  0 records / 0 utterances still reserve one.
-GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int64_t frames, bool analysis, bool pitch = false, bool band = false) {
+GlLayout gl_layout(const GlGeomHost& gh, GlKind kind, size_t records, int64_t planner_B, int64_t frames) {
     GlLayout l;
     size_t off = 0;
     auto take = [&](size_t n) { off = align_up(off, 256); size_t o = off; off += n; return o; };
@@ -64,32 +123,36 @@ GlLayout gl_layout(const GlGeomHost& gh, size_t records, int64_t planner_B, int6
     l.off_win = take(gh.n_fft * sizeof(float));
     l.off_tiles = take(std::max<size_t>(records, 1) * sizeof(GlTile));
     if (planner_B >= 0) l.off_plan = take(std::max<size_t>((size_t)planner_B, 1) * 4 * sizeof(int));
-    if (!analysis) {
+    if (!gl_is_analysis(kind)) {
         const size_t n = (size_t)frames * gh.n_bins;
         l.off_M = take(n * sizeof(float));
         l.off_C0 = take(n * sizeof(float2));
         l.off_C1 = take(n * sizeof(float2));
         l.off_T = take(n * sizeof(float2));
     }
-    if (pitch) l.off_acw = take(gl_pitch_lags(gh.n_fft) * sizeof(float));
-    if (band) l.off_band = take(gl_band_bytes(gh.n_bins));
+    if (kind == GlKind::AnalysisPitch) l.off_acw = take(gl_pitch_lags(gh.n_fft) * sizeof(float));
+    if (kind == GlKind::MelSynthesis) l.off_band = take(gl_band_bytes(gh.n_bins));
     l.bytes = align_up(off, 256);
     return l;
 }
 
-// Host plan of fs2_op_griffin_lim / fs2_op_stft: the exact tile list and the workspace laid out for it.  frames[b] = L_b; tiles cover
-// utterances with L_b >= 2 (synthesis: they own samples) or every utterance with frames (analysis).
+// What a call launches over: `records` workgroups (= tile records) and the workspace laid out for them.  tiles: the exact tile list of
+// a host-planned batch (the planner kernels write the records of a device-driven one).
 struct GlPlan {
     std::vector<GlTile> tiles;
+    size_t records = 0;
     int64_t frames = 0, samples = 0;
     GlLayout at;
 };
 
-// analysis = false: lens are frame counts L_b, samples hop max(L_b - 1, 0).  analysis = true: lens are sample counts T_b,
-// frames T_b / hop + 1.  starts: source rows (synthesis) or waveform samples (analysis), may be NULL for the size query.
-int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, const GlGeomHost& gh, GlPlan& p, bool pitch = false, bool band = false) {
+// Host plan.  Synthesis: lens are frame counts L_b, samples hop max(L_b - 1, 0), tiles cover the utterances with L_b >= 2 (they own
+// samples).  Analysis: lens are sample counts T_b, frames T_b / hop + 1, tiles cover every utterance with frames.
+int gl_plan(const GlCall& c, GlPlan& p) {
+    const int B = c.batch.B;
+    const int32_t *starts = c.batch.starts, *lens = c.batch.lens;
+    const bool analysis = gl_is_analysis(c.kind);
     if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "vocoder: bad batch (B = %d)", B);
-    const int hop = gh.hop, F = gh.g.F, nb = gh.n_bins;
+    const int hop = c.gh.hop, F = c.gh.g.F, nb = c.gh.n_bins;
     int64_t row = 0, wav = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "vocoder: negative length / start of utterance %d", b);
@@ -110,9 +173,10 @@ int gl_plan(int B, const int32_t* starts, const int32_t* lens, bool analysis, co
         wav += T;
         if (row > INT32_MAX / nb || wav > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "vocoder: batch too large (%lld frames, %lld samples)", (long long)row, (long long)wav);
     }
+    p.records = p.tiles.size();
     p.frames = row;
     p.samples = wav;
-    p.at = gl_layout(gh, p.tiles.size(), -1, p.frames, analysis, pitch, band);
+    p.at = gl_layout(c.gh, c.kind, p.records, -1, p.frames);
     return FS2_OK;
 }
 
@@ -124,12 +188,28 @@ int64_t gl_cap_slots(const GlGeomHost& gh, int64_t B, int64_t frame_capacity) {
     return slots > INT32_MAX ? -1 : slots;
 }
 
+// The one sizing of the synthesis and the analysis, for the queries and the calls alike.  A host-planned batch is planned, and fails
+// with the plan's message.  A device-driven one has the layout of a host plan with every size taken from the capacities (gl_cap_slots
+// records, frame_capacity frames) plus the planner's per-utterance arrays; capacities out of range fail WITHOUT a message: the query
+// answers 0 and the call says it in its own words.  (B = 0, capacity 0 is a size here; the call refuses B < 1 before it asks.)
+int gl_size(const GlCall& c, GlPlan& p) {
+    if (!c.batch.on_device) return gl_plan(c, p);
+    const int64_t slots = gl_cap_slots(c.gh, c.batch.B, c.batch.frame_capacity);
+    if (slots < 0) return FS2_ERR_ARG;
+    p.records = (size_t)slots;
+    p.frames = c.batch.frame_capacity;
+    p.at = gl_layout(c.gh, c.kind, p.records, c.batch.B, p.frames);
+    return FS2_OK;
+}
+
+// ---- launches ----
+
 void gl_put_tables(hipStream_t s, const GlGeomHost& gh, const GlLayout& at, char* ws) {
     hipLaunchKernelGGL(gl_tables, dim3((gh.n_fft + 255) / 256), dim3(256), 0, s, (float2*)(ws + at.off_tw), (float*)(ws + at.off_win),
                        gh.n_fft, gh.win);
 }
 
-// tables + tile records into the workspace (kernel arguments, no host copy)
+// tables + tile records of a host plan into the workspace (kernel arguments, no host copy)
 hipError_t gl_setup(hipStream_t s, const GlPlan& p, const GlGeomHost& gh, char* ws) {
     gl_put_tables(s, gh, p.at, ws);
     for (size_t i = 0; i < p.tiles.size(); i += kGlTilesPerChunk) {
@@ -142,296 +222,305 @@ hipError_t gl_setup(hipStream_t s, const GlPlan& p, const GlGeomHost& gh, char* 
     return hipGetLastError();
 }
 
-// proj: the projection of an iteration (gl_iterate's PROJ): 0 onto M, 1 mel-constrained, with mp filled in
-struct GlIterArgs {
-    const GlTile* tiles; const float2* tw; const float* win; const float* M; float2* C[2]; float2* Tm; float beta; float* wav;
-    int proj; GlMelProj mp;
-};
+static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvfUpstream == FS2_OVF_UPSTREAM && kGlOvfNegative == FS2_OVF_NEG_LEN &&
+              kGlOvfWav == FS2_OVF_WAV, "griffin_lim.h restates the FS2_OVF_* bits");
 
-// mel_basis != NULL: a mel-constrained call (its layout has the band region); src is then the call's log-mel source
-GlIterArgs gl_iter_args(char* ws, const GlLayout& at, float momentum, float* wav, const float* src = nullptr, const float* mel_basis = nullptr,
-                        int n_bins = 0) {
-    GlIterArgs a{};
-    a.tiles = (const GlTile*)(ws + at.off_tiles);
-    a.tw = (const float2*)(ws + at.off_tw);
-    a.win = (const float*)(ws + at.off_win);
-    a.M = (const float*)(ws + at.off_M);
-    a.C[0] = (float2*)(ws + at.off_C0);
-    a.C[1] = (float2*)(ws + at.off_C1);
-    a.Tm = momentum > 0.f ? (float2*)(ws + at.off_T) : nullptr;
-    a.beta = momentum / (1.f + momentum);
-    a.wav = wav;
-    if (mel_basis) {
-        a.proj = 1;
-        a.mp.mel = src;
-        a.mp.basis = mel_basis;
-        a.mp.row_rng = (const int2*)(ws + at.off_band);
-        a.mp.bin_rng = a.mp.row_rng + kGlMaxMels;
-        a.mp.inv_w = (const float*)(a.mp.bin_rng + n_bins);
-        a.mp.band = a.mp.inv_w + n_bins;
-    }
-    return a;
+// tables, then the planner kernels of a device-driven call: they write the tile records, sample_lens and status, and fill the wav
+hipError_t gl_setup_on_device(hipStream_t s, const GlCall& c, const GlPlan& p, char* ws) {
+    const GlBatch& b = c.batch;
+    const GlWavOut& o = c.out;
+    gl_put_tables(s, c.gh, p.at, ws);
+    GlPlanArgs pa{};
+    pa.lens = b.lens_dev; pa.upstream = b.upstream_status;
+    pa.B = b.B; pa.hop = c.gh.hop; pa.F = c.gh.g.F;
+    pa.src_stride = b.src_stride; pa.wav_stride = o.wav_stride;
+    pa.frame_capacity = b.frame_capacity; pa.wav_capacity = o.wav_capacity;
+    int* plan = (int*)(ws + p.at.off_plan);
+    pa.row0 = plan; pa.wav0 = plan + b.B; pa.tile_end = plan + 2 * (size_t)b.B; pa.Lv = plan + 3 * (size_t)b.B;
+    pa.sample_lens = o.sample_lens_dev; pa.status = o.status;
+    const int n_slots = (int)p.records;          // >= B >= 1
+    hipLaunchKernelGGL(gl_plan_scan, dim3(1), dim3(kGlPlanThreads), 0, s, pa);
+    hipLaunchKernelGGL(gl_plan_emit, dim3((n_slots + 255) / 256), dim3(256), 0, s, pa, n_slots, (GlTile*)(ws + p.at.off_tiles));
+    if (o.wav_capacity > 0)
+        hipLaunchKernelGGL(gl_plan_fill, dim3((unsigned)std::min<int64_t>((o.wav_capacity + 1023) / 1024, 2048)), dim3(256), 0, s, pa, o.wav);
+    return hipGetLastError();
 }
 
-// prologue, n_iter fused iterations and the final ISTFT of one geometry (NFFT; HOP_C = 256: the default instantiation)
+// prologue, n_iter fused iterations and the final ISTFT of one geometry (NFFT; HOP_C = 256: the default instantiation) over the
+// tile records in place in ws: uploaded, or being written by the planner ahead on the stream
 template <int NFFT, int HOP_C>
-hipError_t gl_run(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const float* src, int src_width, const float* pinv,
-                  const float* init_phase, uint32_t seed, int n_iter, const GlIterArgs& a) {
-    const dim3 grid(n_tiles), blk(kGlThreads);
+hipError_t gl_run(hipStream_t s, const GlCall& c, const GlPlan& p, char* ws) {
+    // The instantiations of gl_iterate at this geometry, stated once: the iteration by [projection][momentum], and the final ISTFT.
+    using Iterate = decltype(&gl_iterate<NFFT, HOP_C, 0, false, 0>);
+    const Iterate iterate[2][2] = {{gl_iterate<NFFT, HOP_C, 0, false, 0>, gl_iterate<NFFT, HOP_C, 0, true, 0>},
+                                   {gl_iterate<NFFT, HOP_C, 0, false, 1>, gl_iterate<NFFT, HOP_C, 0, true, 1>}};
+    const Iterate final_istft = gl_iterate<NFFT, HOP_C, 1, false>;
+    const GlGeomHost& gh = c.gh;
+    const GlSource& in = c.source;
+    const GlLayout& at = p.at;
+    const int n_iter = c.iter.n_iter, proj = c.kind == GlKind::MelSynthesis;
+    const float momentum = c.iter.momentum, beta = momentum / (1.f + momentum);
+    const GlTile* tiles = (const GlTile*)(ws + at.off_tiles);
+    const float2* tw = (const float2*)(ws + at.off_tw);
+    const float* win = (const float*)(ws + at.off_win);
+    float* M = (float*)(ws + at.off_M);
+    float2* C[2] = {(float2*)(ws + at.off_C0), (float2*)(ws + at.off_C1)};
+    float2* Tm = momentum > 0.f ? (float2*)(ws + at.off_T) : nullptr;
+    GlMelProj mp{};                 // all zero for PROJ = 0
+    if (proj) {                     // the layout has the band region; src is the call's log-mel source
+        mp.mel = in.src;
+        mp.basis = in.mel_basis;
+        mp.row_rng = (const int2*)(ws + at.off_band);
+        mp.bin_rng = mp.row_rng + kGlMaxMels;
+        mp.inv_w = (const float*)(mp.bin_rng + gh.n_bins);
+        mp.band = mp.inv_w + gh.n_bins;
+    }
+    const dim3 grid((unsigned)p.records), blk(kGlThreads);
     const GlGeom g = gh.g;
     const size_t lds = gh.sig_bytes;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (lds && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
     // Set on every eager call, not once per instantiation: the byte count follows the hop (<1024, 0> at hop 200 and at hop 300
-    // differ).  Host work only, skipped while capturing: a captured call relies on the eager call before it.
+    // differ).  Host work only, skipped while capturing: a captured call relies on the eager call before it, which is why every plain
+    // instantiation gets it and not only the one this call launches (capture with momentum after an eager call without); the
+    // mel-constrained ones get it on a mel-constrained call.
     if (lds && cap == hipStreamCaptureStatusNone) {
-        for (const void* k : {(const void*)gl_iterate<NFFT, HOP_C, 0, false>, (const void*)gl_iterate<NFFT, HOP_C, 0, true>,
-                              (const void*)gl_iterate<NFFT, HOP_C, 1, false>})
-            if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
-        if (a.proj)
-            for (const void* k : {(const void*)gl_iterate<NFFT, HOP_C, 0, false, 1>, (const void*)gl_iterate<NFFT, HOP_C, 0, true, 1>})
-                if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        for (const Iterate k : {iterate[0][0], iterate[0][1], final_istft})
+            if (hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        if (proj)
+            for (const Iterate k : {iterate[1][0], iterate[1][1]})
+                if (hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
     }
-    if (src_width == 80 && gh.n_mels == 80 && src_width != gh.n_bins)
-        hipLaunchKernelGGL((gl_prologue<NFFT, 80>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
+    if (in.src_width == 80 && gh.n_mels == 80 && in.src_width != gh.n_bins)
+        hipLaunchKernelGGL((gl_prologue<NFFT, 80>), grid, blk, 0, s, tiles, g, in.src, in.src_width, in.mel_pinv, c.iter.init_phase, c.iter.seed, M, C[0], Tm);
     else
-        hipLaunchKernelGGL((gl_prologue<NFFT, 0>), grid, blk, 0, s, a.tiles, g, src, src_width, pinv, init_phase, seed, (float*)a.M, a.C[0], a.Tm);
+        hipLaunchKernelGGL((gl_prologue<NFFT, 0>), grid, blk, 0, s, tiles, g, in.src, in.src_width, in.mel_pinv, c.iter.init_phase, c.iter.seed, M, C[0], Tm);
+    if (proj && n_iter > 0)         // the band tables of this call's basis, read by the iterations only
+        hipLaunchKernelGGL(gl_band_tables, dim3((gh.n_bins + kGlThreads - 1) / kGlThreads), blk, 0, s, mp.basis, gh.n_mels, gh.n_bins,
+                           const_cast<int2*>(mp.row_rng), const_cast<int2*>(mp.bin_rng), const_cast<float*>(mp.inv_w), const_cast<float*>(mp.band));
+    const Iterate step = iterate[proj][Tm != nullptr];
+    for (int i = 0; i < n_iter; ++i)
+        hipLaunchKernelGGL(step, grid, blk, lds, s, tiles, g, tw, win, M, C[i & 1], C[(i + 1) & 1], Tm, beta, c.out.wav, mp);
     const GlMelProj none{};
-    if (a.proj && n_iter > 0)       // the band tables of this call's basis, read by the iterations only
-        hipLaunchKernelGGL(gl_band_tables, dim3((gh.n_bins + kGlThreads - 1) / kGlThreads), blk, 0, s, a.mp.basis, gh.n_mels, gh.n_bins,
-                           const_cast<int2*>(a.mp.row_rng), const_cast<int2*>(a.mp.bin_rng), const_cast<float*>(a.mp.inv_w),
-                           const_cast<float*>(a.mp.band));
-    for (int it = 0; it < n_iter; ++it) {
-        if (a.proj && a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true, 1>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, a.mp);
-        else if (a.proj) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false, 1>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, a.mp);
-        else if (a.Tm) hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, true>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, none);
-        else hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 0, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[it & 1], a.C[(it + 1) & 1], a.Tm, a.beta, a.wav, none);
-    }
-    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, a.tiles, g, a.tw, a.win, a.M, a.C[n_iter & 1], a.C[(n_iter + 1) & 1], nullptr, 0.f, a.wav, none);
+    hipLaunchKernelGGL((gl_iterate<NFFT, HOP_C, 1, false>), grid, blk, lds, s, tiles, g, tw, win, M, C[n_iter & 1], C[(n_iter + 1) & 1], nullptr, 0.f, c.out.wav, none);
     return hipGetLastError();
 }
 
-// what the host-planned and the device-driven synthesis check first, in this order (mel_proj: the mel-constrained entry points,
-// which have no use for a magnitude source and need the basis)
-int gl_check_synthesis(const char* who, const GlGeomHost& gh, int32_t src_width, const float* mel_pinv, int32_t n_iter, float momentum,
-                       bool mel_proj = false, const float* mel_basis = nullptr) {
+// ---- the synthesis ----
+
+// What every synthesis, and SPSI (whose GlIter is zero), checks first, in this order.  MelSynthesis has no use for a magnitude source
+// and needs the basis.
+int gl_check_synthesis(const GlCall& c) {
+    const char* who = c.who;
+    const GlGeomHost& gh = c.gh;
+    const int32_t src_width = c.source.src_width, n_iter = c.iter.n_iter;
+    const float momentum = c.iter.momentum;
+    const bool mel_proj = c.kind == GlKind::MelSynthesis;
     if (src_width != gh.n_mels && src_width != gh.n_bins)
         return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: src_width %d (%d mel bins or %d linear bins of the %d-point STFT)", who, src_width, gh.n_mels,
                     gh.n_bins, gh.n_fft);
-    if (src_width != gh.n_bins && !mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
+    if (src_width != gh.n_bins && !c.source.mel_pinv) return fail(nullptr, FS2_ERR_ARG, "%s: mel input needs mel_pinv [%d, %d]", who, gh.n_bins, gh.n_mels);
     if (n_iter < 0 || !(momentum >= 0.f) || !std::isfinite(momentum)) return fail(nullptr, FS2_ERR_ARG, "%s: n_iter %d, momentum %g", who, n_iter, momentum);
     if (mel_proj && src_width != gh.n_mels)
         return fail(nullptr, FS2_ERR_ARG, "%s: src_width %d is a magnitude source: there is no mel to constrain to (%d mel bins)", who, src_width, gh.n_mels);
-    if (mel_proj && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: null mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
+    if (mel_proj && !c.source.mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: null mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
     return FS2_OK;
 }
 
-// the launches of a synthesis whose tile records are in place (uploaded, or being written by the planner ahead on the stream)
-int gl_synthesize(hipStream_t s, const GlGeomHost& gh, unsigned n_tiles, const float* src, int32_t src_width, const float* mel_pinv,
-                  const float* init_phase, uint32_t seed, int32_t n_iter, const GlIterArgs& a) {
-    const hipError_t e = gl_dispatch(gh, [&](auto n, auto h) {
-        return gl_run<decltype(n)::value, decltype(h)::value>(s, gh, n_tiles, src, src_width, mel_pinv, init_phase, seed, n_iter, a);
-    });
+// The capacities and pointers of a device-driven synthesis, in the order its messages are known by
+int gl_check_device_batch(const GlCall& c) {
+    const char* who = c.who;
+    const GlBatch& b = c.batch;
+    const GlWavOut& o = c.out;
+    if (b.B < 1 || b.frame_capacity < 1 || b.src_stride < 0 || o.wav_stride < 0)
+        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d", who, b.B, (long long)b.frame_capacity, b.src_stride,
+                    o.wav_stride);
+    if (b.frame_capacity > INT32_MAX / c.gh.n_bins || o.wav_capacity < 0 || o.wav_capacity > INT32_MAX || (int64_t)b.B * b.src_stride > INT32_MAX)
+        return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call (%lld frames, %lld samples)", who, (long long)b.frame_capacity,
+                    (long long)o.wav_capacity);
+    if ((int64_t)b.B * o.wav_stride > o.wav_capacity)
+        return fail(nullptr, FS2_ERR_ARG, "%s: padded output of %d x %d samples in a wav of %lld", who, b.B, o.wav_stride, (long long)o.wav_capacity);
+    if (!c.source.src || !b.lens_dev || !c.work.ptr || !o.sample_lens_dev || !o.status || (o.wav_capacity > 0 && !o.wav))
+        return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    return FS2_OK;
+}
+
+// Synthesis and MelSynthesis, host-planned and device-driven.  Order of the checks -- host-planned: source and iteration arguments,
+// null starts / lens, the plan, "nobody owns a sample" (FS2_OK before any pointer is looked at), null pointers; device-driven: source
+// and iteration arguments, capacities, null pointers, the slots; for both the workspace last.
+int gl_synthesize(hipStream_t s, const GlCall& c) {
+    const char* who = c.who;
+    const bool on_device = c.batch.on_device;
+    if (int rc = gl_check_synthesis(c)) return rc;
+    GlPlan p;
+    if (on_device) {
+        if (int rc = gl_check_device_batch(c)) return rc;
+        if (gl_size(c, p)) return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call", who);
+    } else {
+        if (c.batch.B > 0 && (!c.batch.starts || !c.batch.lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+        if (int rc = gl_size(c, p)) return rc;
+        if (p.tiles.empty()) return FS2_OK;
+        if (!c.source.src || !c.out.wav || !c.work.ptr) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    }
+    if (c.work.bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, c.work.bytes, p.at.bytes);
+    char* ws = (char*)c.work.ptr;
+    hipError_t e = on_device ? gl_setup_on_device(s, c, p, ws) : gl_setup(s, p, c.gh, ws);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim %s: %s", on_device ? "plan" : "setup", hipGetErrorString(e));
+    e = gl_dispatch(c.gh, [&](auto n, auto h) { return gl_run<decltype(n)::value, decltype(h)::value>(s, c, p, ws); });
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim: %s", hipGetErrorString(e));
     return FS2_OK;
 }
 
-int gl_griffin_lim(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                   const int32_t* starts, const int32_t* lens, int32_t n_iter, float momentum, uint32_t seed, const float* init_phase,
-                   void* workspace, size_t workspace_bytes, float* wav, bool mel_proj = false, const float* mel_basis = nullptr) {
-    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum, mel_proj, mel_basis)) return rc;
-    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    GlPlan p;
-    if (int rc = gl_plan(B, starts, lens, false, gh, p, false, mel_proj)) return rc;
-    if (p.tiles.empty()) return FS2_OK;
-    if (!src || !wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    if (workspace_bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.at.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, gh, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim setup: %s", hipGetErrorString(e));
-    return gl_synthesize(s, gh, (unsigned)p.tiles.size(), src, src_width, mel_pinv, init_phase, seed, n_iter,
-                         gl_iter_args(ws, p.at, momentum, wav, src, mel_proj ? mel_basis : nullptr, gh.n_bins));
-}
-
-static_assert(kGlOvfRows == FS2_OVF_ROWS && kGlOvfLmax == FS2_OVF_LMAX && kGlOvfUpstream == FS2_OVF_UPSTREAM && kGlOvfNegative == FS2_OVF_NEG_LEN &&
-              kGlOvfWav == FS2_OVF_WAV, "griffin_lim.h restates the FS2_OVF_* bits");
-
-// The device-driven call: the layout of a host plan with every size taken from the capacities (gl_cap_slots records,
-// frame_capacity frames), plus the planner's per-utterance arrays.
-int gl_griffin_lim_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                       const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, int32_t n_iter,
-                       float momentum, uint32_t seed, const float* init_phase, void* workspace, size_t workspace_bytes, float* wav,
-                       int32_t wav_stride, int64_t wav_capacity, int64_t* sample_lens_dev, int32_t* status, bool mel_proj = false,
-                       const float* mel_basis = nullptr) {
-    if (int rc = gl_check_synthesis(who, gh, src_width, mel_pinv, n_iter, momentum, mel_proj, mel_basis)) return rc;
-    if (B < 1 || frame_capacity < 1 || src_stride < 0 || wav_stride < 0)
-        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d", who, B, (long long)frame_capacity, src_stride, wav_stride);
-    if (frame_capacity > INT32_MAX / gh.n_bins || wav_capacity < 0 || wav_capacity > INT32_MAX || (int64_t)B * src_stride > INT32_MAX)
-        return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call (%lld frames, %lld samples)", who, (long long)frame_capacity, (long long)wav_capacity);
-    if ((int64_t)B * wav_stride > wav_capacity)
-        return fail(nullptr, FS2_ERR_ARG, "%s: padded output of %d x %d samples in a wav of %lld", who, B, wav_stride, (long long)wav_capacity);
-    if (!src || !lens_dev || !workspace || !sample_lens_dev || !status || (wav_capacity > 0 && !wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    const int64_t slots = gl_cap_slots(gh, B, frame_capacity);
-    if (slots < 0) return fail(nullptr, FS2_ERR_ARG, "%s: capacities too large for one call", who);
-    const GlLayout at = gl_layout(gh, (size_t)slots, B, frame_capacity, false, false, mel_proj);
-    if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    gl_put_tables(s, gh, at, ws);
-    GlPlanArgs pa{};
-    pa.lens = lens_dev; pa.upstream = upstream_status;
-    pa.B = B; pa.hop = gh.hop; pa.F = gh.g.F;
-    pa.src_stride = src_stride; pa.wav_stride = wav_stride;
-    pa.frame_capacity = frame_capacity; pa.wav_capacity = wav_capacity;
-    int* plan = (int*)(ws + at.off_plan);
-    pa.row0 = plan; pa.wav0 = plan + B; pa.tile_end = plan + 2 * (size_t)B; pa.Lv = plan + 3 * (size_t)B;
-    pa.sample_lens = sample_lens_dev; pa.status = status;
-    const int n_slots = (int)slots;          // >= B >= 1
-    hipLaunchKernelGGL(gl_plan_scan, dim3(1), dim3(kGlPlanThreads), 0, s, pa);
-    hipLaunchKernelGGL(gl_plan_emit, dim3((n_slots + 255) / 256), dim3(256), 0, s, pa, n_slots, (GlTile*)(ws + at.off_tiles));
-    if (wav_capacity > 0)
-        hipLaunchKernelGGL(gl_plan_fill, dim3((unsigned)std::min<int64_t>((wav_capacity + 1023) / 1024, 2048)), dim3(256), 0, s, pa, wav);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "griffin_lim plan: %s", hipGetErrorString(e));
-    return gl_synthesize(s, gh, (unsigned)n_slots, src, src_width, mel_pinv, init_phase, seed, n_iter,
-                         gl_iter_args(ws, at, momentum, wav, src, mel_proj ? mel_basis : nullptr, gh.n_bins));
-}
-
-int gl_stft_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,
-                const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy) {
-    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
-    GlPlan p;
-    if (int rc = gl_plan(B, wav_starts, wav_lens, true, gh, p)) return rc;
-    if (p.tiles.empty() || (!mag && !logmel && !energy)) return FS2_OK;
-    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    if (workspace_bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.at.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    hipError_t e = gl_setup(s, p, gh, ws);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
-    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
-    const GlTile* tiles = (const GlTile*)(ws + p.at.off_tiles);
-    const float2* tw = (const float2*)(ws + p.at.off_tw);
-    const float* win = (const float*)(ws + p.at.off_win);
-    gl_dispatch(gh, [&](auto n, auto h) {
-        hipLaunchKernelGGL((gl_stft<decltype(n)::value, decltype(h)::value>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, mag, mel_basis, logmel, energy);
-    });
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft: %s", hipGetErrorString(e));
-    return FS2_OK;
-}
+// ---- the analysis ----
 
 // Lags of the pitch scan (gl_pitch.h): tmin = floor(sr / f0_ceil), tmax = ceil(sr / f0_floor), 2 <= tmin <= tmax <= win / 2 -- the
 // window's autocorrelation is divided by, and beyond half the window it is too small to.  Restated in vocoder.py: pitch_lags.
-int gl_pitch_args(const char* who, const GlGeomHost& gh, int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold,
-                  double octave_cost, GlPitch& out) {
-    if (sample_rate < 1 || !(f0_floor > 0.0) || !(f0_ceil >= f0_floor) || !std::isfinite(f0_ceil) || !std::isfinite(voicing_threshold) ||
-        !std::isfinite(octave_cost))
-        return fail(nullptr, FS2_ERR_ARG, "%s: sample_rate %d, f0_floor %g, f0_ceil %g, voicing_threshold %g, octave_cost %g", who, sample_rate, f0_floor,
-                    f0_ceil, voicing_threshold, octave_cost);
-    const double lo = std::floor((double)sample_rate / f0_ceil), hi = std::ceil((double)sample_rate / f0_floor);
+int gl_pitch_args(const char* who, const GlGeomHost& gh, const GlPitchOptions& o, GlPitch& out) {
+    if (o.sample_rate < 1 || !(o.f0_floor > 0.0) || !(o.f0_ceil >= o.f0_floor) || !std::isfinite(o.f0_ceil) || !std::isfinite(o.voicing_threshold) ||
+        !std::isfinite(o.octave_cost))
+        return fail(nullptr, FS2_ERR_ARG, "%s: sample_rate %d, f0_floor %g, f0_ceil %g, voicing_threshold %g, octave_cost %g", who, o.sample_rate, o.f0_floor,
+                    o.f0_ceil, o.voicing_threshold, o.octave_cost);
+    const double lo = std::floor((double)o.sample_rate / o.f0_ceil), hi = std::ceil((double)o.sample_rate / o.f0_floor);
     if (lo < 2.0 || hi > gh.win / 2)
         return fail(nullptr, FS2_ERR_UNSUPPORTED,
                     "%s: f0_floor %g .. f0_ceil %g at %d Hz need the lags %.0f .. %.0f, the window of %d samples allows 2 .. %d (lowest usable f0_floor "
-                    "%g Hz = 2 sample_rate / win, highest f0_ceil %g Hz)", who, f0_floor, f0_ceil, sample_rate, lo, hi, gh.win, gh.win / 2,
-                    2.0 * sample_rate / gh.win, sample_rate / 2.0);
+                    "%g Hz = 2 sample_rate / win, highest f0_ceil %g Hz)", who, o.f0_floor, o.f0_ceil, o.sample_rate, lo, hi, gh.win, gh.win / 2,
+                    2.0 * o.sample_rate / gh.win, o.sample_rate / 2.0);
     out.tmin = (int)lo; out.tmax = (int)hi;
-    out.sr = (float)sample_rate;
-    out.floor_over_sr = (float)(f0_floor / (double)sample_rate);
-    out.threshold = (float)voicing_threshold;
-    out.octave_cost = (float)octave_cost;
+    out.sr = (float)o.sample_rate;
+    out.floor_over_sr = (float)(o.f0_floor / (double)o.sample_rate);
+    out.threshold = (float)o.voicing_threshold;
+    out.octave_cost = (float)o.octave_cost;
     return FS2_OK;
 }
 
-// gl_stft_run with the pitch outputs: the same plan and tables plus the window-autocorrelation table, one gl_features launch.  Without
-// f0 and strength it is gl_stft_run (and needs no more workspace than it).
-int gl_stft_pitch_run(const char* who, void* stream, const GlGeomHost& gh, const float* wav, int32_t B, const int32_t* wav_starts,
-                      const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy,
-                      int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold, double octave_cost, float* f0, float* strength) {
+// Analysis and AnalysisPitch: one gl_stft launch, or with the pitch outputs the window-autocorrelation table and one gl_features
+// launch.  Order of the checks: the pitch options (AnalysisPitch; without f0 and strength it is then exactly Analysis and needs no
+// more workspace than it), null starts / lens, logmel without its basis, the plan, nothing to do (FS2_OK before any pointer is looked
+// at), null pointers, the workspace last.
+int gl_analyze(hipStream_t s, GlCall c) {
+    const char* who = c.who;
+    const GlGeomHost& gh = c.gh;
+    const GlFeatures& o = c.feat;
     GlPitch pp{};
-    if (int rc = gl_pitch_args(who, gh, sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost, pp)) return rc;
-    if (!f0 && !strength) return gl_stft_run(who, stream, gh, wav, B, wav_starts, wav_lens, workspace, workspace_bytes, mag, mel_basis, logmel, energy);
-    if (B > 0 && (!wav_starts || !wav_lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    if (logmel && !mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
+    if (c.kind == GlKind::AnalysisPitch) {
+        if (int rc = gl_pitch_args(who, gh, o.pitch, pp)) return rc;
+        if (!o.f0 && !o.strength) c.kind = GlKind::Analysis;
+    }
+    const bool pitch = c.kind == GlKind::AnalysisPitch;
+    if (c.batch.B > 0 && (!c.batch.starts || !c.batch.lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+    if (o.logmel && !o.mel_basis) return fail(nullptr, FS2_ERR_ARG, "%s: logmel needs mel_basis [%d, %d]", who, gh.n_mels, gh.n_bins);
     GlPlan p;
-    if (int rc = gl_plan(B, wav_starts, wav_lens, true, gh, p, true)) return rc;
-    if (p.tiles.empty()) return FS2_OK;
-    if (!wav || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    if (workspace_bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, p.at.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
+    if (int rc = gl_size(c, p)) return rc;
+    if (p.tiles.empty() || (!pitch && !o.mag && !o.logmel && !o.energy)) return FS2_OK;
+    const float* wav = c.source.src;
+    if (!wav || !c.work.ptr) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    if (c.work.bytes < p.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, c.work.bytes, p.at.bytes);
+    char* ws = (char*)c.work.ptr;
     hipError_t e = gl_setup(s, p, gh, ws);
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft setup: %s", hipGetErrorString(e));
     float* acw = (float*)(ws + p.at.off_acw);
-    hipLaunchKernelGGL(gl_pitch_table, dim3((gl_pitch_lags(gh.n_fft) + 7) / 8), dim3(256), 0, s, acw, gh.n_fft, gh.win);
-    const dim3 grid((unsigned)p.tiles.size()), blk(kGlThreads);
+    if (pitch) hipLaunchKernelGGL(gl_pitch_table, dim3((gl_pitch_lags(gh.n_fft) + 7) / 8), dim3(256), 0, s, acw, gh.n_fft, gh.win);
+    const dim3 grid((unsigned)p.records), blk(kGlThreads);
     const GlTile* tiles = (const GlTile*)(ws + p.at.off_tiles);
     const float2* tw = (const float2*)(ws + p.at.off_tw);
     const float* win = (const float*)(ws + p.at.off_win);
     gl_dispatch(gh, [&](auto n, auto h) {
-        hipLaunchKernelGGL((gl_features<decltype(n)::value, decltype(h)::value>), grid, blk, 0, s, tiles, gh.g, tw, win, acw, wav, mag, mel_basis, logmel,
-                           energy, pp, f0, strength);
+        constexpr int NFFT = decltype(n)::value, HOP_C = decltype(h)::value;
+        if (pitch)
+            hipLaunchKernelGGL((gl_features<NFFT, HOP_C>), grid, blk, 0, s, tiles, gh.g, tw, win, acw, wav, o.mag, o.mel_basis, o.logmel, o.energy, pp, o.f0,
+                               o.strength);
+        else
+            hipLaunchKernelGGL((gl_stft<NFFT, HOP_C>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, o.mag, o.mel_basis, o.logmel, o.energy);
     });
     e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "stft pitch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", pitch ? "stft pitch" : "stft", hipGetErrorString(e));
     return FS2_OK;
 }
 
-// ---- SPSI initial phase (kernels and launch sequences: gl_spsi.h): the argument checks behind fs2_op_spsi_phase_geom / _dev ----
-
-// what both forms check of the source first, by the rules of the synthesis (gl_check_synthesis)
-int spsi_check_source(const char* who, const GlGeomHost& gh, int32_t src_width, const float* mel_pinv) {
-    return gl_check_synthesis(who, gh, src_width, mel_pinv, 0, 0.f);
-}
+// ---- SPSI initial phase (kernels and launch sequences: gl_spsi.h) ----
 
 // frames of a host-planned batch (every utterance with L >= 1 is computed), or a failure code (< 0)
-int64_t spsi_host_frames(const char* who, const GlGeomHost& gh, int B, const int32_t* starts, const int32_t* lens) {
+int64_t spsi_host_frames(const GlCall& c) {
+    const char* who = c.who;
+    const int B = c.batch.B, rows_max = INT32_MAX / c.gh.n_bins;
+    const int32_t *starts = c.batch.starts, *lens = c.batch.lens;
     if (B < 0 || (B > 0 && !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d)", who, B);
     int64_t rows = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 0 || (starts && starts[b] < 0)) return fail(nullptr, FS2_ERR_ARG, "%s: negative length / start of utterance %d", who, b);
-        if (starts && (int64_t)starts[b] + lens[b] > INT32_MAX / gh.n_bins)
-            return fail(nullptr, FS2_ERR_ARG, "%s: utterance %d ends beyond row %d", who, b, INT32_MAX / gh.n_bins);
+        if (starts && (int64_t)starts[b] + lens[b] > rows_max) return fail(nullptr, FS2_ERR_ARG, "%s: utterance %d ends beyond row %d", who, b, rows_max);
         rows += lens[b];
-        if (rows > INT32_MAX / gh.n_bins) return fail(nullptr, FS2_ERR_ARG, "%s: batch too large (%lld frames)", who, (long long)rows);
+        if (rows > rows_max) return fail(nullptr, FS2_ERR_ARG, "%s: batch too large (%lld frames)", who, (long long)rows);
     }
     return rows;
 }
 
-int spsi_phase_host(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                    const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes, float* phase, float* mag_out) {
-    if (int rc = spsi_check_source(who, gh, src_width, mel_pinv)) return rc;
-    if (B > 0 && (!starts || !lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
-    const int64_t frames = spsi_host_frames(who, gh, B, starts, lens);
-    if (frames < 0) return (int)frames;
-    if (frames == 0) return FS2_OK;
-    if (!src || !phase || !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    const SpsiLayout at = spsi_layout(gh.n_bins, B, frames);
-    if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
-    const hipError_t e = spsi_run_host((hipStream_t)stream, gh.n_fft, gh.hop, src, src_width, mel_pinv, B, starts, lens, frames, (char*)workspace, at, phase, mag_out);
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FS2_OK;
-}
-
-// the capacities of a device-driven call, by the rules of gl_griffin_lim_dev
+// the capacities of a device-driven call, by the rules of the device-driven synthesis
 bool spsi_caps_ok(const GlGeomHost& gh, int64_t B, int64_t src_stride, int64_t frame_capacity) {
     return B >= 1 && frame_capacity >= 1 && src_stride >= 0 && frame_capacity <= INT32_MAX / gh.n_bins && B * src_stride <= INT32_MAX / gh.n_bins;
 }
 
-int spsi_phase_dev(const char* who, void* stream, const GlGeomHost& gh, const float* src, int32_t src_width, const float* mel_pinv, int32_t B,
-                   const int64_t* lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, void* workspace,
-                   size_t workspace_bytes, float* phase, float* mag_out) {
-    if (int rc = spsi_check_source(who, gh, src_width, mel_pinv)) return rc;
-    if (!spsi_caps_ok(gh, B, src_stride, frame_capacity))
-        return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d (B >= 1, 1 <= frame_capacity, rows * bins < 2^31)", who, B,
-                    (long long)frame_capacity, src_stride);
-    if (!src || !lens_dev || !workspace || !phase) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-    const SpsiLayout at = spsi_layout(gh.n_bins, B, frame_capacity);
-    if (workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
-    const hipError_t e = spsi_run_dev((hipStream_t)stream, gh.n_fft, gh.hop, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status,
-                                      (char*)workspace, at, phase, mag_out);
+struct SpsiSize {
+    int64_t frames = 0;
+    SpsiLayout at;
+};
+
+// The one sizing of SPSI, for the queries and the calls alike: the frames of a host-planned batch (failing with their message) or
+// the capacity of a device-driven one (out of range: no message, as in gl_size; B = 0 is no size here), and spsi_layout over them.
+int spsi_size(const GlCall& c, SpsiSize& z) {
+    const GlBatch& b = c.batch;
+    if (b.on_device && !spsi_caps_ok(c.gh, b.B, b.src_stride, b.frame_capacity)) return FS2_ERR_ARG;
+    z.frames = b.on_device ? b.frame_capacity : spsi_host_frames(c);
+    if (z.frames < 0) return (int)z.frames;
+    z.at = spsi_layout(c.gh.n_bins, b.B, z.frames);
+    return FS2_OK;
+}
+
+// Order of the checks: the source, by the rules of the synthesis; then host-planned: null starts / lens, the frames, no frames
+// (FS2_OK before any pointer is looked at), null pointers; device-driven: the capacities, null pointers; for both the workspace last.
+int spsi_phase(hipStream_t s, const GlCall& c) {
+    const char* who = c.who;
+    const GlGeomHost& gh = c.gh;
+    const GlSource& in = c.source;
+    const GlBatch& b = c.batch;
+    if (int rc = gl_check_synthesis(c)) return rc;
+    SpsiSize z;
+    if (b.on_device) {
+        if (spsi_size(c, z))
+            return fail(nullptr, FS2_ERR_ARG, "%s: B %d, frame_capacity %lld, src_stride %d (B >= 1, 1 <= frame_capacity, rows * bins < 2^31)", who, b.B,
+                        (long long)b.frame_capacity, b.src_stride);
+        if (!in.src || !b.lens_dev || !c.work.ptr || !c.spsi.phase) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    } else {
+        if (b.B > 0 && (!b.starts || !b.lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+        if (int rc = spsi_size(c, z)) return rc;
+        if (z.frames == 0) return FS2_OK;
+        if (!in.src || !c.spsi.phase || !c.work.ptr) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    }
+    if (c.work.bytes < z.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, c.work.bytes, z.at.bytes);
+    char* ws = (char*)c.work.ptr;
+    const hipError_t e = b.on_device ? spsi_run_dev(s, gh.n_fft, gh.hop, in.src, in.src_width, in.mel_pinv, b.B, b.lens_dev, b.src_stride, b.frame_capacity,
+                                                    b.upstream_status, ws, z.at, c.spsi.phase, c.spsi.mag_out)
+                                     : spsi_run_host(s, gh.n_fft, gh.hop, in.src, in.src_width, in.mel_pinv, b.B, b.starts, b.lens, z.frames, ws, z.at,
+                                                     c.spsi.phase, c.spsi.mag_out);
     if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return FS2_OK;
+}
+
+// ---- the one path ----
+
+int gl_call(void* stream, GlCall c) {
+    if (int rc = gl_geom(c.geom.n_fft, c.geom.hop, c.geom.win, c.geom.n_mels, c.who, c.gh)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (c.kind == GlKind::SpsiPhase) return spsi_phase(s, c);
+    return gl_is_analysis(c.kind) ? gl_analyze(s, c) : gl_synthesize(s, c);
+}
+
+// the workspace gl_call needs for the same description (only kind, geometry and batch are read), 0 on every failure
+size_t gl_workspace_bytes(GlCall c) {
+    GlPlan p;
+    SpsiSize z;
+    if (gl_geom(c.geom.n_fft, c.geom.hop, c.geom.win, c.geom.n_mels, c.who, c.gh)) return 0;
+    if (c.kind == GlKind::SpsiPhase) return spsi_size(c, z) == FS2_OK ? z.at.bytes : 0;
+    return gl_size(c, p) == FS2_OK ? p.at.bytes : 0;
 }

@@ -302,8 +302,41 @@ def _i32(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _host_batch(mels, olens, name="mels", have="have"):
+    """(L int64 [B] on the host, starts [B]) of a packed [N, W] or padded [B, Lmax, W] ``mels`` with host ``olens`` (None: one
+    utterance of N rows / every utterance Lmax frames).  ``name``, ``have``: how the messages call the argument."""
+    if mels.dim() == 2:
+        N = mels.shape[0]
+        L = _lens([N] if olens is None else olens)
+        if int(L.sum()) != N:
+            raise ValueError("packed %s: olens sum to %d, %s %s %d rows" % (name, int(L.sum()), name, have, N))
+        return L, np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
+    Bp, Lmax = mels.shape[0], mels.shape[1]
+    L = _lens([Lmax] * Bp if olens is None else olens, Bp)
+    if Bp and int(L.max()) > Lmax:
+        raise ValueError("padded %s: an olens entry exceeds Lmax = %d" % (name, Lmax))
+    return L, np.arange(Bp, dtype=np.int64) * Lmax
+
+
+def _device_batch(mels, olens):
+    """(olens contiguous [B], B, rows, stride, Lcap) of a packed (stride 0, Lcap None) or padded [B, Lcap, W] ``mels`` whose frame
+    counts ``olens`` stay on the device."""
+    olens = olens.reshape(-1).contiguous()
+    B = olens.numel()
+    if mels.dim() == 2:
+        return olens, B, mels.shape[0], 0, None
+    if mels.shape[0] != B:
+        raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
+    return olens, B, B * mels.shape[1], mels.shape[1], mels.shape[1]
+
+
 INITS = ("seeded", "spsi")
 CONSTRAINTS = ("magnitude", "mel")
+# (workspace query, call) of include/fs2.h by (device-driven, mel-constrained): the one place a synthesis picks its entry points
+_SYNTHESIS = {(False, False): ("fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom"),
+              (False, True): ("fs2_op_vocode_mel_workspace_bytes_geom", "fs2_op_griffin_lim_mel_geom"),
+              (True, False): ("fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev"),
+              (True, True): ("fs2_op_vocode_mel_workspace_bytes_cap", "fs2_op_griffin_lim_mel_dev")}
 
 
 def _check_constraint(constraint, magnitudes):
@@ -401,47 +434,35 @@ class GriffinLim:
             raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
         g = self.geometry
-        NB = g.n_bins
-        if mels.dim() == 2:
-            N = mels.shape[0]
-            L = _lens([N] if olens is None else olens)
-            if int(L.sum()) != N:
-                raise ValueError("packed mels: olens sum to %d, mels have %d rows" % (int(L.sum()), N))
-            starts = np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
-        else:
-            Bp, Lmax = mels.shape[0], mels.shape[1]
-            L = _lens([Lmax] * Bp if olens is None else olens, Bp)
-            if Bp and int(L.max()) > Lmax:
-                raise ValueError("padded mels: an olens entry exceeds Lmax = %d" % Lmax)
-            starts = np.arange(Bp, dtype=np.int64) * Lmax
-        dev = mels.device
+        L, starts = _host_batch(mels, olens)
         sample_lens = g.hop * torch.clamp(L - 1, min=0)
-        wav = torch.empty(int(sample_lens.sum()), dtype=torch.float32, device=dev)
+        wav = torch.empty(int(sample_lens.sum()), dtype=torch.float32, device=mels.device)
         if wav.numel() == 0:
             return Waveforms(wav, sample_lens)
-        if int(L.sum()) * NB >= 2 ** 31 or wav.numel() >= 2 ** 31:
+        if int(L.sum()) * g.n_bins >= 2 ** 31 or wav.numel() >= 2 ** 31:
             raise ValueError("batch too large for one call (%d frames)" % int(L.sum()))
-        lib = _lib.lib()
         s_np, s_p = _i32(starts)
         l_np, l_p = _i32(L.numpy())
         B = len(l_np)
         if init == "spsi":
             init_phase = self._spsi_host(src, W, s_np, l_np, magnitudes, False)[0]
-        query = lib.fs2_op_vocode_mel_workspace_bytes_geom if mel_proj else lib.fs2_op_vocode_workspace_bytes_geom
-        ws_bytes = int(query(*g, B, l_p))
-        with torch.cuda.device(dev):
-            pinv = self.constants(dev)[0] if not magnitudes else None
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            tail = (B, s_p, l_p, n_iter, momentum, int(seed) & 0xFFFFFFFF, init_phase.data_ptr() if init_phase is not None else None,
-                    ws.data_ptr(), ws_bytes, wav.data_ptr())
-            if mel_proj:
-                _lib.check(lib.fs2_op_griffin_lim_mel_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr(),
-                                                           self.constants(dev)[1].data_ptr(), *tail))
-            else:
-                _lib.check(lib.fs2_op_griffin_lim_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
-                                                       *tail))
+        self._synthesize((False, mel_proj), src, W, magnitudes, (B, l_p), (B, s_p, l_p), (n_iter, momentum, seed, init_phase), (wav.data_ptr(),))
         return Waveforms(wav, sample_lens)
 
+    def _synthesize(self, which, src, W, magnitudes, size, batch, iteration, out):
+        """Size and make the synthesis call ``which`` (a key of _SYNTHESIS) on checked arguments.  ``size``: what the query takes after
+        the geometry; ``batch``, ``out``: what the call takes before the iteration arguments and after the workspace."""
+        lib, g, dev = _lib.lib(), self.geometry, src.device
+        query, call = (getattr(lib, name) for name in _SYNTHESIS[which])
+        n_iter, momentum, seed, init_phase = iteration
+        ws_bytes = int(query(*g, *size))
+        with torch.cuda.device(dev):
+            source = (src.data_ptr(), W, None if magnitudes else self.constants(dev)[0].data_ptr())
+            if which[1]:
+                source += (self.constants(dev)[1].data_ptr(),)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(call(_stream(dev), *g, *source, *batch, n_iter, momentum, int(seed) & 0xFFFFFFFF,
+                            init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes, *out))
 
     def _spsi_host(self, src, W, starts_np, lens_np, magnitudes, want_mag):
         """fs2_op_spsi_phase_geom on checked arguments: (phase [rows, bins], M [rows, bins] or None), zeros where no utterance is."""
@@ -494,30 +515,12 @@ class GriffinLim:
         NB = self.geometry.n_bins
         shape = tuple(mels.shape[:-1]) + (NB,)
         if sync:
-            if mels.dim() == 2:
-                N = mels.shape[0]
-                L = _lens([N] if olens is None else olens)
-                if int(L.sum()) != N:
-                    raise ValueError("packed src: olens sum to %d, src has %d rows" % (int(L.sum()), N))
-                starts = np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
-            else:
-                Bp, Lmax = mels.shape[0], mels.shape[1]
-                L = _lens([Lmax] * Bp if olens is None else olens, Bp)
-                if Bp and int(L.max()) > Lmax:
-                    raise ValueError("padded src: an olens entry exceeds Lmax = %d" % Lmax)
-                starts = np.arange(Bp, dtype=np.int64) * Lmax
+            L, starts = _host_batch(mels, olens, "src", "has")
             if src.shape[0] * NB >= 2 ** 31:
                 raise ValueError("batch too large for one call (%d rows)" % src.shape[0])
             phase, mag = self._spsi_host(src, W, starts, L.numpy(), magnitudes, return_magnitudes)
         else:
-            olens = olens.reshape(-1).contiguous()
-            B = olens.numel()
-            if mels.dim() == 2:
-                rows, stride = mels.shape[0], 0
-            else:
-                if mels.shape[0] != B:
-                    raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
-                rows, stride = B * mels.shape[1], mels.shape[1]
+            olens, B, rows, stride, _ = _device_batch(mels, olens)
             if rows * NB >= 2 ** 31:
                 raise ValueError("batch too large for one call (%d rows)" % rows)
             if B == 0 or rows == 0:
@@ -575,19 +578,11 @@ class GriffinLim:
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes, olens)
         g = self.geometry
         NB = g.n_bins
-        olens = olens.reshape(-1).contiguous()
-        B = olens.numel()
-        if mels.dim() == 2:
-            rows, stride, Lcap = mels.shape[0], 0, None
-            if padded_out:
-                raise ValueError("padded_out needs padded mels [B, Lcap, %d] (the waveform's row length is hop * (Lcap - 1))" % W)
-            if capacity is not None and int(capacity) > rows:
-                raise ValueError("capacity %d exceeds the %d rows of the packed mels" % (int(capacity), rows))
-        else:
-            if mels.shape[0] != B:
-                raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
-            Lcap = mels.shape[1]
-            rows, stride = B * Lcap, Lcap
+        olens, B, rows, stride, Lcap = _device_batch(mels, olens)
+        if Lcap is None and padded_out:
+            raise ValueError("padded_out needs padded mels [B, Lcap, %d] (the waveform's row length is hop * (Lcap - 1))" % W)
+        if Lcap is None and capacity is not None and int(capacity) > rows:
+            raise ValueError("capacity %d exceeds the %d rows of the packed mels" % (int(capacity), rows))
         cap = rows if capacity is None else min(int(capacity), rows)
         dev = mels.device
         padded = bool(padded_out) and Lcap >= 2
@@ -603,22 +598,12 @@ class GriffinLim:
                                       None, bool(padded_out))
             sample_lens = torch.empty(B, dtype=torch.int64, device=dev)        # both written in full by the planner
             status = torch.empty(8, dtype=torch.int32, device=dev)
-            lib = _lib.lib()
-            query = lib.fs2_op_vocode_mel_workspace_bytes_cap if mel_proj else lib.fs2_op_vocode_workspace_bytes_cap
-            ws_bytes = int(query(*g, B, cap))
-            pinv = self.constants(dev)[0] if not magnitudes else None
             if init == "spsi":
                 init_phase = self._spsi_dev(src, W, olens, stride, cap, upstream, magnitudes, False)[0]
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            tail = (B, olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None, n_iter, momentum,
-                    int(seed) & 0xFFFFFFFF, init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes,
-                    wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(), status.data_ptr())
-            if mel_proj:
-                _lib.check(lib.fs2_op_griffin_lim_mel_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr(),
-                                                          self.constants(dev)[1].data_ptr(), *tail))
-            else:
-                _lib.check(lib.fs2_op_griffin_lim_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None,
-                                                      *tail))
+            self._synthesize((True, mel_proj), src, W, magnitudes, (B, cap),
+                             (B, olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None),
+                             (n_iter, momentum, seed, init_phase),
+                             (wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(), status.data_ptr()))
             rec = None if torch.cuda.is_current_stream_capturing() else self._record(status, dev)
         return AsyncWaveforms(shaped, sample_lens, status, rec, bool(padded_out))
 
