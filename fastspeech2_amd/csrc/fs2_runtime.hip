@@ -1704,6 +1704,36 @@ int fs2_op_launch_gemm(void* stream, const void* gemm_args, uint32_t args_size, 
     return launch_gemm(nullptr, (hipStream_t)stream, "op.launch_gemm", a, precision);
 }
 
+// Test hook (include/fs2.h): the weight repack of the mixed modes as fs2_load_weights runs it (make_gemm above: kw from max |w|, the scale image preset to
+// 127), into the caller's buffers -- no kernel instantiation of its own.
+int fs2_op_repack_weight(void* stream, const float* w, int32_t N, int32_t C, int32_t ktaps, int32_t format, void* image, size_t image_bytes,
+                         void* scale_image, size_t scale_bytes, int32_t* kw_out) {
+    if (!w || !image || !kw_out) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: null argument");
+    if (format != FS2_REPACK_MX && format != FS2_REPACK_MX4) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: unknown format %d", format);
+    if (N <= 0 || N % 128 != 0 || C <= 0 || C % 128 != 0 || ktaps < 1 || ktaps % 2 == 0 || ktaps - 1 > kMaxHalo)
+        return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: needs N %% 128 == 0, C %% 128 == 0 and an odd kernel size up to %d (N %d, C %d, k %d)", kMaxHalo + 1, N, C, ktaps);
+    const bool mx4 = format == FS2_REPACK_MX4;
+    const size_t bytes = mx4 ? mx4_image_bytes(N, C, ktaps) : mx_image_bytes(N, C, ktaps), sbytes = mx4 ? mx4_scale_image_bytes(N, C, ktaps) : 0;
+    if (image_bytes != bytes) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: image of %zu bytes, the format takes %zu", image_bytes, bytes);
+    if (mx4 && (!scale_image || scale_bytes != sbytes)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: scale image of %zu bytes, the format takes %zu", scale_image ? scale_bytes : (size_t)0, sbytes);
+    hipStream_t s = (hipStream_t)stream;
+    DevTmp tmp(s);
+    unsigned* scr = nullptr;
+    OP_TRY(tmp.alloc((void**)&scr, 16));
+    const int kw = fp8_scale_exponent(device_absmax(s, w, (int64_t)N * C * ktaps, scr));
+    *kw_out = kw;
+    if (mx4) {
+        OP_TRY(hipMemsetAsync(scale_image, 127, sbytes, s));
+        hipLaunchKernelGGL(repack_weight_mx4, dim3((unsigned)((bytes / 4 + 255) / 256)), dim3(256), 0, s, w, N, C, ktaps, N, reinterpret_cast<unsigned char*>(scale_image),
+                           reinterpret_cast<unsigned*>(image));
+    } else {
+        hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((bytes / 2 + 255) / 256)), dim3(256), 0, s, w, N, C, ktaps, N, kw, reinterpret_cast<unsigned short*>(image));
+    }
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipStreamSynchronize(s));
+    return FS2_OK;
+}
+
 int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int32_t heads, int32_t B, const int32_t* seq_start,
                      const int32_t* seq_len, const int32_t* seq_klen, int32_t mask_q, int32_t precision) {
     if (!qkv || !ctx || B <= 0) return fail(nullptr, FS2_ERR_ARG, "fs2_op_attention: bad arguments");

@@ -259,6 +259,20 @@ int fs2_op_conv_gemm(void *stream, const fs2_op_gemm_args *a);
 int fs2_op_launch_gemm(void *stream, const void *gemm_args, uint32_t args_size, int32_t precision, int32_t *plan_out,
                        int32_t plan_cap);
 
+/* TEST HOOK: the library's own weight repack of the mixed modes, run exactly as fs2_load_weights runs it, so that the
+ * kernel-level tests (tests/test_gpu_mx_kernels.py) can hold the images byte for byte against the CPU statement of the
+ * formats (tests/gemm_raw.py).  w: device fp32 [N][C][ktaps] (a convolution's weight; N % 128 == 0, C % 128 == 0, ktaps odd).
+ * format FS2_REPACK_MX: `image` receives the mx image [N][C / 32 units][tap][128 B] (csrc/gemm_mx.h: repack_weight_mx),
+ * `scale_image` is not touched.  FS2_REPACK_MX4: `image` receives the mx4 image [N][C / 64 + C / 128 units][tap][128 B] and
+ * `scale_image` its E8M0 scale image [N / 128][C / 128][tap][4][128][2] (repack_weight_mx4), preset to 127 as at load.
+ * `image_bytes` / `scale_bytes` must be exactly the images' sizes: FS2_ERR_ARG otherwise, before anything is launched.
+ * *kw_out: the exponent of the static weight scale fs2_load_weights derives from max |w| (the mx image is written under it; the
+ * mx4 image carries its scales itself).  Device pointers; the stream is drained before the call returns. */
+#define FS2_REPACK_MX 1
+#define FS2_REPACK_MX4 2
+int fs2_op_repack_weight(void *stream, const float *w, int32_t N, int32_t C, int32_t ktaps, int32_t format, void *image,
+                         size_t image_bytes, void *scale_image, size_t scale_bytes, int32_t *kw_out);
+
 /* scaled-dot-product self-attention over packed sequences: qkv [R, 3*D] (q | k | v, head-major inside
  * each), ctx [R, D].  seq_start/len/klen: HOST [B]; in the bf16 modes seq_start must be a multiple of 8.  Keys >= klen
  * never reach the output whatever their rows hold (NaN included).  Query rows >= klen produce zeros when mask_q.

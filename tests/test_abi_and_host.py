@@ -138,6 +138,23 @@ def test_struct_size_mismatch_is_rejected(libpath):
     assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, 1, plan, len(plan) - 1) == -1 and b"plan_out" in L.fs2_last_error(None)
     for precision in (-1, 3, 6):
         assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, precision, plan, len(plan)) == -1 and b"precision" in L.fs2_last_error(None)
+    # the repack hook: a null argument, an unknown format, a shape the formats do not exist for, or an image of another size is refused before anything is
+    # launched (the pointers are placeholders that nothing follows)
+    kw, p = ctypes.c_int32(7), ctypes.c_void_p(0x1000)
+    mx_bytes, mx4_bytes, sc_bytes = 256 * 12 * 3 * 128, 256 * 9 * 3 * 128, 2 * 3 * 3 * 1024
+    rp = lambda w, N, Cc, k, fmt, img, nb, sc, ns, out=kw: L.fs2_op_repack_weight(None, w, N, Cc, k, fmt, img, nb, sc, ns, ctypes.byref(out) if out is not None else None)
+    assert rp(None, 256, 384, 3, _lib.REPACK_MX, p, mx_bytes, None, 0) == -1 and b"null" in L.fs2_last_error(None)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX, None, mx_bytes, None, 0) == -1 and b"null" in L.fs2_last_error(None)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX, p, mx_bytes, None, 0, out=None) == -1 and b"null" in L.fs2_last_error(None)
+    for fmt in (0, 3):
+        assert rp(p, 256, 384, 3, fmt, p, mx_bytes, None, 0) == -1 and b"format" in L.fs2_last_error(None)
+    for N, Cc, k in ((200, 384, 3), (256, 320, 3), (256, 384, 4), (256, 384, 19), (0, 384, 3)):
+        assert rp(p, N, Cc, k, _lib.REPACK_MX, p, mx_bytes, None, 0) == -1 and b"128" in L.fs2_last_error(None)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX, p, mx_bytes - 128, None, 0) == -1 and b"image of" in L.fs2_last_error(None)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX4, p, mx_bytes, p, sc_bytes) == -1 and b"image of" in L.fs2_last_error(None)      # (the mx4 image is a quarter smaller)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX4, p, mx4_bytes, p, sc_bytes + 1024) == -1 and b"scale image" in L.fs2_last_error(None)
+    assert rp(p, 256, 384, 3, _lib.REPACK_MX4, p, mx4_bytes, None, sc_bytes) == -1 and b"scale image" in L.fs2_last_error(None)
+    assert kw.value == 7
 
 
 def test_create_without_gpu_fails_loudly(libpath):

@@ -7,7 +7,10 @@ is sent to a GPU.
     byte by byte, the pair values equal to bf16 / fp16 / e4m3 arithmetic stated independently;
 (c) the float64 reference against a plain F.linear + F.layer_norm fp32 statement;
 (d) the plan of every argument block the GPU tests send, from csrc/gemm_plan.h compiled for the host on the block's own bytes: the expected kernel,
-    epilogue, residual form and tile height, and no refusal."""
+    epilogue, residual form and tile height, and no refusal;
+(e) the formats of the mixed modes (tests/test_gpu_mx_kernels.py): the e2m1 codec, the scale rule against csrc/common.h compiled for the host, the byte positions
+    of the mx4 planes, their scale record, both weight images and the scale image written out again element by element, the formulas near the ideal product,
+    and DISCRIMINATION: every mutant of a formula -- what a kernel with one broken position rule would compute -- at 8 bars or more from it."""
 import ctypes
 import os
 import subprocess
@@ -157,20 +160,205 @@ def test_operands_are_exact_pairs_on_the_tested_distributions():
 
 def test_every_block_the_gpu_tests_send_plans_onto_the_expected_kernel(probe, tmp_path):
     launches = G.all_launches()
-    assert len(launches) == 4 * len(G.LN_CASES) + sum(len(r) for r in G.QKV_RUNS.values()) and len({l[0] for l in launches}) == len(launches)
+    n_mixed = len(G.CONV_ARITHS) * len(G.CONV_CASES) * len(G.CONV_OUTS) + 2 * len(G.EPI4_CASES) + 3 * len(G.FFN2_CASES)
+    assert len(launches) == 4 * len(G.LN_CASES) + sum(len(r) for r in G.QKV_RUNS.values()) + n_mixed and len({l[0] for l in launches}) == len(launches)
     path = tmp_path / "blocks.txt"
     with open(path, "w") as f:
         for name, opts, block, _ in launches:
-            f.write("%s 1 %s %s\n" % (name, ",".join("%s=%d" % kv for kv in sorted(opts.items())), bytes(block).hex()))
+            f.write("%s 1 %s %s\n" % (name, ",".join("%s=%d" % kv for kv in sorted(opts.items())) or "-", bytes(block).hex()))
     fields = ("kernel",) + G.Plan._fields[1:] + ("err",)
     got = {l[0]: dict(zip(fields, [l[1]] + [int(v) for v in l[2:]])) for l in probe("plans", path)}
     assert sorted(got) == sorted(l[0] for l in launches)
     for name, _, _, want in launches:
         assert got[name]["err"] == 0, (name, got[name])
         assert {k: got[name][k] for k in want} == want, (name, got[name])
-        assert got[name]["nsplit"] == 3 and got[name]["ksplit"] == 1 and not got[name]["rows_pass"] and not got[name]["build_planes"], (name, got[name])
+        # (the conv in the mx arithmetics has one MFMA term per unit kind: its plan says nsplit 1, and the block's expectation names it)
+        assert got[name]["nsplit"] == want.get("nsplit", 3) and got[name]["ksplit"] == 1 and not got[name]["rows_pass"] and not got[name]["build_planes"], (name, got[name])
     # every instantiation family the issue names is reached: both heights of the four row4 forms, the QKV passes on it, gemm_qkv8_bf16 whole and apart
     reached = {(g["kernel"], g["epi"], g["res"], g["mt"], g["apart"]) for g in got.values()}
-    for epi, res in ((0, 1), (0, 2), (1, 1), (2, 3)):
+    for epi, res in ((0, 1), (0, 2), (1, 1), (2, 3), (4, 1)):
         assert {("row4", epi, res, 4, 0), ("row4", epi, res, 5, 0)} <= reached
+    # ... and the launches of the mixed modes: the conv on mx and on mx4 operands, FFN2 + LN2 in the mx arithmetic at both heights
+    assert {(g["kernel"], g["arith"], g["bm"]) for g in got.values() if g["kernel"].startswith("pl_mx")} == {("pl_mx4", 3, 256), ("pl_mx", 2, 64)}
+    assert {("row4", 0, 2, 2, m) for m in (4, 5)} <= {(g["kernel"], g["epi"], g["arith"], g["res"], g["mt"]) for g in got.values()}
     assert {("qkv4", 3, 0, 4, 0), ("qkv4", 3, 0, 5, 0)} | {("qkv8", -1, 0, m, s) for m in (2, 3) for s in (0, 1)} | {("row8", -1, 0, 2, 0), ("row8", -1, 0, 3, 0)} <= reached
+
+
+# ------------------------------------------------------------------ the mx / mx4 formats (tests/test_gpu_mx_kernels.py)
+def test_bars_of_the_mixed_mode_launches_respect_the_ceiling():
+    assert set(G.MX_BAR) == {"conv_mx4", "conv_mx", "ffn2_mx", "epi4"} and all(0 < b <= G.MX_CEILING for b in G.MX_BAR.values())
+
+
+def test_e2m1_codec_rounds_to_nearest_even_and_saturates():
+    codes = torch.arange(16, dtype=torch.uint8)
+    vals = G.e2m1_decode(codes)
+    assert vals.tolist() == [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0]
+    assert torch.equal(G.e2m1_encode(vals), codes)                                      # (the sign of a zero is kept: code 8)
+    # nearest: a fine grid against the brute-force nearest code; the seven midpoints go to the code with the even mantissa bit
+    x = torch.arange(-8.0, 8.0, 1.0 / 64, dtype=torch.float64)
+    x = x[~G.e2m1_on_tie(x)]
+    near = (x.unsqueeze(1) - vals[:8].unsqueeze(0) * torch.sign(x).unsqueeze(1)).abs().argmin(1)
+    assert torch.equal((G.e2m1_encode(x) & 7).long(), near) and torch.equal(G.e2m1_encode(x) >> 3, (x < 0).to(torch.uint8))
+    ties = torch.tensor([0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0], dtype=torch.float64)
+    assert G.e2m1_encode(ties).tolist() == [0, 2, 2, 4, 4, 6, 6] and G.e2m1_encode(-ties).tolist() == [8, 10, 10, 12, 12, 14, 14]
+    assert G.e2m1_encode(torch.tensor([6.0, 7.0, 1e30, -1e30])).tolist() == [7, 7, 7, 15]
+    assert int(G.e2m1_on_tie(ties).sum()) == 7 and not bool(G.e2m1_on_tie(vals).any())
+
+
+def test_mx4_scale_rule_matches_the_compiled_header(tmp_path):
+    """mx4_scale_byte / mx4_inv_scale of csrc/common.h, compiled for the host, on every binade edge, its neighbours, zero, denormals and the clamped ends."""
+    exe = str(tmp_path / "mx_format_probe")
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--offload-host-only", "-std=c++17", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "mx_format_probe.cpp"), "-o", exe], check=True)
+    bits = [0, 1, 0x007FFFFF, 0x7F7FFFFF]
+    for e in list(range(1, 255, 7)) + [41, 42, 43, 201, 202, 203, 127]:
+        bits += [(e << 23) - 1, e << 23, (e << 23) + 1, (e << 23) | 0x400000]
+    out = subprocess.run([exe] + ["%08x" % b for b in bits], check=True, capture_output=True, text=True).stdout.split()
+    got_byte, got_inv = [int(v) for v in out[1::3]], [int(v, 16) for v in out[2::3]]
+    m = torch.tensor(np.array(bits, dtype=np.uint32).view(np.float32))
+    eb = G.mx4_scale_byte(m)
+    assert eb.tolist() == got_byte and int(eb.min()) == 40 and int(eb.max()) == 200
+    assert G.mx4_inv_scale(eb).float().view(torch.int32).tolist() == got_inv
+    # the rule: m / 2^(byte - 127) lies in [4, 8) wherever the clamp does not act
+    free = (eb > 40) & (eb < 200)
+    q = m.double()[free] * G.mx4_inv_scale(eb[free])
+    assert bool(((q >= 4) & (q < 8)).all())
+    assert G.fp8_scale_exponent(448.0) == 0 and G.fp8_scale_exponent(1.0) == 8 and G.fp8_scale_exponent(8.0) == 5 and G.fp8_scale_exponent(0.0) == 0
+    assert G.scale_byte4(113) == 0x71717171 and G.scale_byte4(0) == 0x01010101
+
+
+def test_mx4_planes_round_trip_and_byte_positions():
+    rs = np.random.RandomState(3)
+    rows, Cc, ka = 5, 384, 3
+    x = torch.from_numpy(rs.uniform(-1, 1, size=(rows, Cc)).astype(np.float32)) * G._gain(rs, Cc)
+    x[3] = 0.0                                                                            # a row of zeros: the clamped scale byte
+    t = G.split_mx4(x, ka)
+    planes, rec = G.encode_mx4(t, fill=0xEE)
+    assert planes.shape == (rows, 4 * Cc) and rec.shape == (rows, 32) and planes.dtype == rec.dtype == torch.uint8
+    hb = t.h.view(torch.int16).numpy().view(np.uint16)
+    raw = planes.numpy()
+    for r in range(rows):
+        for c in range(Cc):
+            assert int(raw[r, 2 * c]) | (int(raw[r, 2 * c + 1]) << 8) == int(hb[r, c])
+            q, j = c & ~3, c & 3                                                          # the four channels c & ~3 .. + 3 own bytes 2 C + (c & ~3) .. + 3
+            assert (int(raw[r, 2 * Cc + q + (j >> 1)]) >> (4 * (j & 1))) & 15 == int(t.r4[r, c])          # ra4 ra4 | ra4 ra4
+            assert (int(raw[r, 2 * Cc + q + 2 + (j >> 1)]) >> (4 * (j & 1))) & 15 == int(t.h4[r, c])      # ah4 ah4 | ah4 ah4
+            assert raw[r, 3 * Cc + c] == t.e8[r, c]
+        for S in range(Cc // 16):
+            u, sl = S // 8, S % 8
+            assert int(rec[r, 8 * u + 2 * (sl & 3) + (sl >> 2)]) == int(t.sb[r, S]) - 11
+    assert sorted(G.slot_pos(S) for S in range(24)) == list(range(24)) and bool((rec[:, 24:] == 0xEE).all())
+    assert t.sb[3].tolist() == [40] * 24 and not bool(planes[3].any())
+    back = G.decode_mx4(planes, rec, rows, Cc)
+    for a, b in zip(t, back):
+        assert torch.equal(a.view(torch.int16) if a.dtype == torch.float16 else a, b.view(torch.int16) if b.dtype == torch.float16 else b)
+    # the parts: under the slot's scale the fp16 part lands in e2m1's range with the slot maximum in [4, 8) -> code 6 or 7; both parts within half a step
+    inv = G.mx4_inv_scale(t.sb).repeat_interleave(16, dim=1)
+    hs, rsd = t.h.double() * inv, (x - t.h.float()).double() * 2048.0 * inv
+    live = torch.ones(rows, dtype=torch.bool)
+    live[3] = False
+    assert int((G.e2m1_decode(t.h4).abs().reshape(rows, -1, 16).amax(2)[live]).min()) >= 4
+    for v, code in ((hs, t.h4), (rsd, t.r4)):
+        err = (G.e2m1_decode(code) - v.clamp(-6, 6)).abs()
+        assert bool((err <= torch.where(v.abs() >= 4, 1.0, torch.where(v.abs() >= 2, 0.5, 0.25))).all())
+    assert float((x - t.h.float()).abs().max()) * 2.0 ** (ka + 11) <= 448.0
+
+
+def test_weight_images_byte_positions_and_scale_image():
+    rs = np.random.RandomState(4)
+    N, Cc, k = 256, 384, 3
+    w = G.repack_weights(N, Cc, k, 4)
+    kw = G.fp8_scale_exponent(float(w.abs().max()))
+    assert float(w.abs().max()) * 2.0 ** kw <= 448.0 < float(w.abs().max()) * 2.0 ** (kw + 1)
+    t3, t4 = G.split_mx3(w, kw), G.split_mx4(w, 0, slot_dim=1)
+    img3 = G.image_w_mx(t3).numpy()
+    img4, sc = G.image_w_mx4(t4)
+    img4, sc = img4.numpy(), sc.numpy()
+    assert img3.shape == (N, Cc // 32, k, 128) and img4.shape == (N, Cc // 64 + Cc // 128, k, 128) and sc.shape == (N // 128, Cc // 128, k, 4, 128, 2)
+    assert t4.sb.shape == (N, Cc // 16, k) and len(torch.unique(t4.sb)) > 4              # the blocks take different scale bytes
+    hb = t3.h.view(torch.int16).numpy().view(np.uint16)
+    nmain, ncross = Cc // 64, Cc // 128
+    for n, c, tap in [(int(rs.randint(N)), int(rs.randint(Cc)), int(rs.randint(k))) for _ in range(3000)] + [(0, 0, 0), (N - 1, Cc - 1, k - 1), (128, 127, 1), (127, 128, 1)]:
+        for img in (img3, img4):                                                          # fp16 channels: unit c / 64, two bytes at 2 (c % 64)
+            assert int(img[n, c // 64, tap, 2 * (c % 64)]) | (int(img[n, c // 64, tap, 2 * (c % 64) + 1]) << 8) == int(hb[n, c, tap])
+        assert img3[n, nmain + c // 128, tap, c % 128] == t3.a8[n, c, tap]                # wh8 meets ra8: the first C / 128 units behind the fp16 ones
+        assert img3[n, nmain + ncross + c // 128, tap, c % 128] == t3.r8[n, c, tap]       # rw8 meets ah8
+        q, j = (c % 128) & ~3, c & 3
+        assert (int(img4[n, nmain + c // 128, tap, q + (j >> 1)]) >> (4 * (j & 1))) & 15 == int(t4.h4[n, c, tap])          # wh4 where the planes hold ra4
+        assert (int(img4[n, nmain + c // 128, tap, q + 2 + (j >> 1)]) >> (4 * (j & 1))) & 15 == int(t4.r4[n, c, tap])      # rw4 where they hold ah4
+        sl = (c % 128) // 16
+        assert sc[n // 128, c // 128, tap, sl & 3, n % 128, sl >> 2] == int(t4.sb[n, c // 16, tap])
+    # the value: fp16 + both reduced copies state w to the precision of their formats
+    assert float((G.e4m3_value(t3.a8) * 2.0 ** -kw - t3.h.double()).abs().max()) <= 2.0 ** -4 * float(w.abs().max())
+    assert float((G.e4m3_value(t3.r8) * 2.0 ** -(kw + 11) - (w - t3.h.float()).double()).abs().max()) <= 2.0 ** -4 * 2.0 ** -11 * float(w.abs().max())
+
+
+def test_formulas_state_the_product_to_the_precision_of_the_formats():
+    """The float64 formulas are the kernels', not the ideal product -- but they must be NEAR it: against F.conv1d / F.linear of the fp32 values in float64 the mx
+    formula drops ra.rw (2^-22) and keeps 2^-4 of the cross terms (2^-15 per product), the mx4 formula keeps about a quarter of them (2^-13 per product)."""
+    for arith, tol in (("mx", 2.0 ** -14), ("mx4", 2.0 ** -11)):
+        o = G.ConvOperands(arith, 3, 256, 256, "model")
+        a = o.x.h.double() + (G.e4m3_value(o.x.r8) * 2.0 ** -(o.ka + 11) if arith == "mx" else G.e4m3_value(o.x.e8) * 2.0 ** -(o.ka + 11))
+        if arith == "mx":
+            w = o.w.h.double() + G.e4m3_value(o.w.r8) * 2.0 ** -(o.kw + 11)
+        else:
+            w = o.w.h.double() + G.e2m1_decode(o.w.r4) * G.pow2(o.w.sb - 127).repeat_interleave(16, dim=1) * 2.0 ** -11
+        want = torch.relu(F.conv1d(a[:o.R].t().unsqueeze(0), w, o.bias.double(), padding=1)[0].t()) * (o.pos[:o.R] >= 0).unsqueeze(1)
+        scale = float(F.conv1d(a[:o.R].abs().t().unsqueeze(0), w.abs(), None, padding=1).max())      # Sum |a| |w|: what a relative error per product scales with
+        assert float((o.ref - want).abs().max()) <= tol * scale, (arith, float((o.ref - want).abs().max()), scale)
+        assert float(o.ref[o.pos[:o.R] < 0].abs().max()) == 0.0 and float(o.ref.min()) == 0.0 and float(o.ref.max()) > 0.5
+
+
+def _discrimination(ops):
+    worst = {}
+    for m in ops.mutants():
+        worst[m] = float((ops.mutant(m) - ops.ref).abs().max())
+    return worst
+
+
+@pytest.mark.parametrize("arith", G.CONV_ARITHS)
+@pytest.mark.parametrize("case", G.CONV_CASES, ids=["k%d-N%d-R%d" % c for c in G.CONV_CASES])
+def test_conv_formula_tells_every_mutant_apart(arith, case):
+    """On the coherent operands every mutant of the formula -- cross terms dropped, the two scale bytes of a lane's pair swapped, the scale image's g index off by
+    one, ra4 / ah4 nibble pairs swapped (mx: the ra8 and ah8 units swapped) -- lies at least 8 bars from the formula: a kernel that passes the bar is none of them."""
+    ops = G.ConvOperands(arith, *case, "coherent")
+    worst = _discrimination(ops)
+    print(arith, case, worst)
+    assert set(worst) == set(G.MX4_MUTANTS if arith == "mx4" else G.MX_MUTANTS)
+    # (the bar the GPU test applies to this launch's fp32 rows; read back from mx planes an output carries 2^-14 |ref| of rounding on top: a mutant must clear that too)
+    assert min(worst.values()) >= 8 * G.MX_BAR["conv_" + arith] and min(worst.values()) >= 2 * (G.MX_BAR["conv_" + arith] + 2.0 ** -14 * float(ops.ref.abs().max())), worst
+
+
+@pytest.mark.parametrize("case", G.FFN2_CASES, ids=["C%d-R%d-rm%d" % c for c in G.FFN2_CASES])
+def test_ffn2_formula_tells_every_mutant_apart(case):
+    """... and for FFN2 + LN2 in the mx arithmetic; with the residual from mx4 planes also the residual bytes taken from 2 C (the cross units) instead of 3 C."""
+    ops = G.Ffn2Operands(*case, "coherent")
+    worst = _discrimination(ops)
+    print(case, worst)
+    assert ("resid_at_2c" in worst) == (case[2] == 2)
+    assert min(worst.values()) >= 8 * G.MX_BAR["ffn2_mx"], worst
+
+
+@pytest.mark.parametrize("case", G.EPI4_CASES, ids=["%s-R%d-C%d" % c for c in G.EPI4_CASES])
+def test_epi4_operands_leave_few_slots_on_a_binade_edge(case):
+    """From the reference alone: slots whose maximum lies within the bar of a power of two (where a kernel inside the bar may take either neighbouring scale byte) stay
+    below 1 % of all slots; gamma spreads the slots of a row over several bytes."""
+    ops = G.LnOperands(*case)
+    bar = G.MX_BAR["epi4"] + 2.0 ** -14 * ops.ref.abs()
+    lo, hi = G.epi4_scale_bounds(ops.ref, bar)
+    assert bool((hi - lo >= 0).all()) and int((hi - lo).max()) <= 1
+    print("edge slots: %d of %d" % (int((hi != lo).sum()), lo.numel()))
+    assert int((hi != lo).sum()) < 0.01 * lo.numel()
+    live = ops.pos[:ops.R] >= 0
+    assert int((lo[live].max(1).values - lo[live].min(1).values).min()) >= 4              # 80-fold gamma: at least 2^4 between the slots of every live row
+    assert bool((lo[~live] == 40).all()) and bool((hi[~live] == 40).all())
+    assert float(ops.ref.abs().max()) * 2.0 ** -11 * 2.0 ** (G.KA_OUT + 11) <= 448.0       # the e4m3 residual under 2^ka stays finite
+
+
+def test_e4m3_cells_contain_what_rounds_to_them():
+    rs = np.random.RandomState(5)
+    v = torch.from_numpy(rs.uniform(-300, 300, size=20000).astype(np.float32)) * torch.from_numpy(2.0 ** rs.randint(-12, 1, size=20000).astype(np.float32))
+    b = G.e4m3_of(v)
+    lo, hi = G.e4m3_cell(b)
+    assert bool(((v.double() >= lo) & (v.double() <= hi)).all())
+    assert bool((hi - lo <= 32.0).all()) and bool((lo <= G.e4m3_value(b)).all()) and bool((G.e4m3_value(b) <= hi).all())
