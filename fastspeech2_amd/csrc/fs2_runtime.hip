@@ -32,6 +32,7 @@
 #include "gemm_planes.h"
 #include "gemm_row4.h"
 #include "model_launches.h"
+#include "call_plan.h"
 #include "gemm_mx.h"
 #include "gemm_f32.h"
 #include "griffin_lim.h"
@@ -221,23 +222,13 @@ struct fs2_handle {
     Gemm tokw; float *TEd = nullptr, *TPd = nullptr;
     Gemm feat;
     std::vector<Gemm> post;
-    // state carried from encode to decode
-    bool encoded = false;
-    HostLayout tok;
-    DevLayout dtok;
-    float* enc_final = nullptr;
-    float* tokP = nullptr;     // tok.proj's output of the encoded batch [token rows, tokw.N] (nullptr: not computed)
-    bool tokP_conv = false;    // ... its predictor columns were computed too (else only the input layer's)
-    int* cum = nullptr;
-    int* o32 = nullptr;        // device frame counts (int32) left by the duration scan
-    int enc_B = 0, enc_Tmax = 0, enc_compat = 0;
-    long enc_ntok = 0;         // phonemes of the encoded batch (basis of the frame-level kernel-variant choice)
+    Encoded left;              // state carried from encode to decode (call_plan.h)
+    HostLayout tok;            // fs2_encode's host layout (kept for its storage)
     float* kp = nullptr; size_t kp_cap = 0;   // split-K scratch of the call in progress (carved from its workspace)
     int cur_regime = 0;        // regime_rows of the call in progress (0: the launch's own row count)
     int* counters = nullptr;   // device int[16], zeroed at creation: [0] = waves of attn_w32 that left the fast path (fs2_get_counter)
     int* cur_status = nullptr; // device-driven layout: the status words of the call in progress ([5] counts the same event for that call alone)
     int gap = kGap;            // zero rows between packed utterances: max(kMinGap, largest conv halo of this model)
-    void* enc_ws = nullptr;
     std::vector<void*> graph_pinned;   // host staging owned by captured graphs (see upload_layout)
     // profiling
     bool prof = false;
@@ -970,37 +961,28 @@ void free_weights(fs2_handle* h) {
     h->loaded = false;
 }
 
-int check_batch(fs2_handle* h, const fs2_batch& b) {
-    if (b.B <= 0 || b.Tmax <= 0 || !b.ilens) return fail(h, FS2_ERR_ARG, "batch: B=%d Tmax=%d ilens=%p", b.B, b.Tmax, (const void*)b.ilens);
-    for (int i = 0; i < b.B; ++i)
-        if (b.ilens[i] <= 0 || b.ilens[i] > b.Tmax) return fail(h, FS2_ERR_ARG, "ilens[%d]=%lld outside [1,%d]", i, (long long)b.ilens[i], b.Tmax);
-    if (b.precision < FS2_PREC_FP32 || b.precision > FS2_PREC_MIX_MX4) return fail(h, FS2_ERR_ARG, "unknown precision mode %d", b.precision);
-    if (b.regime_tokens < 0 || b.regime_utterances < 0 || (b.regime_tokens > 0) != (b.regime_utterances > 0))
-        return fail(h, FS2_ERR_ARG, "batch: regime_tokens=%lld / regime_utterances=%d must be given together (0 / 0 = this call's own batch)", (long long)b.regime_tokens, b.regime_utterances);
-    return FS2_OK;
-}
-
-// The row counts the kernel-variant choices are functions of (fs2.h: fs2_batch.regime_*): ESTIMATES of the packed rows of the batch the variants
-// are chosen for -- this call's own, or the larger one the caller names -- at token level (one row per phoneme) and at frame level (8 frames per
-// phoneme; LJSpeech: 7.9), plus the alignment and gap rows of every utterance.  Functions of (phonemes, utterances) only: the host knows both in
-// the host- and in the device-driven layout, and a shard that names the whole batch gets the whole batch's numbers.  Any value gives correct
-// results; the same value gives the same kernels, hence the same bits.
-inline long regime_tokens_of(const fs2_batch& b, bool token_level) {
-    if (b.regime_tokens > 0) return (long)b.regime_tokens;
-    long n = 0;
-    for (int i = 0; i < b.B; ++i) n += (token_level && b.compat_padded) ? (long)b.Tmax : (long)b.ilens[i];      // (padded-batch semantics: the encoder runs on Tmax rows per utterance)
-    return n;
-}
-inline int regime_rows_of(const fs2_batch& b, bool token_level) {
-    const long utts = b.regime_utterances > 0 ? b.regime_utterances : b.B;
-    return row_bound((token_level ? 1 : 8) * regime_tokens_of(b, token_level), utts);
-}
-
 struct TokenBufs {
     int* meta; StackBufs sb; float *p0, *p1, *dlog_rows; int64_t* dint; int *cum, *o32;
     float* kp; size_t kp_cap;
     float* tokp;      // tok.proj's output rows (nullptr: this model or precision has none)
 };
+
+// The buffers of an FFT-block stack, x0 to xps: contiguous and in this order in both workspaces.  D: the stack's width, Dp: its attention width; hid, x0p, x1p, xps:
+// floats per row of those buffers (what else they hold: at the callers).
+void carve_stack(Bump& bp, size_t R, size_t D, size_t Dp, size_t hid, size_t x0p, size_t x1p, size_t xps, StackBufs& sb) {
+    sb.x0 = bp.take<float>(R * D);
+    sb.x1 = bp.take<float>(R * D);
+    sb.qkv = bp.take<float>(R * 3 * Dp);
+    sb.ctx = bp.take<float>(R * Dp);
+    sb.hid = bp.take<float>(R * hid);
+    sb.qkh = bp.take<__bf16>(R * 2 * Dp);
+    sb.qkl = bp.take<__bf16>(R * 2 * Dp);
+    sb.vth = bp.take<__bf16>(R * Dp);
+    sb.vtl = bp.take<__bf16>(R * Dp);
+    sb.x0p = bp.take<float>(R * x0p);
+    sb.x1p = bp.take<float>(R * x1p);
+    sb.xps = bp.take<float>(R * xps);
+}
 
 // carve the token workspace; if ws == nullptr only sizes it
 size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L, void* ws, size_t cap, TokenBufs* tb, bool* ok) {
@@ -1008,27 +990,16 @@ size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L
     const size_t R = L.Rpad;
     TokenBufs t;
     t.meta = bp.take<int>(layout_dev_ints(L));
-    t.sb.x0 = bp.take<float>(R * c.adim);
-    t.sb.x1 = bp.take<float>(R * c.adim);
-    const size_t eDp = att_width(c.adim, c.aheads);      // attention width: heads x padded head dim
-    t.sb.qkv = bp.take<float>(R * 3 * eDp);
-    t.sb.ctx = bp.take<float>(R * eDp);
-    t.sb.hid = bp.take<float>(R * (size_t)round_up(c.eunits, 32));     // bf16 modes: hidden layer as planes (32-channel chunks)
-    t.sb.qkh = bp.take<__bf16>(R * 2 * eDp);
-    t.sb.qkl = bp.take<__bf16>(R * 2 * eDp);
-    t.sb.vth = bp.take<__bf16>(R * eDp);
-    t.sb.vtl = bp.take<__bf16>(R * eDp);
     const size_t pw = round_up(c.adim, 32);
-    t.sb.x0p = bp.take<float>(R * pw);
-    t.sb.x1p = bp.take<float>(R * pw);
-    t.sb.xps = bp.take<float>(R * (size_t)round_up(std::max(c.adim, c.dur_chans), 32));
+    // (attention width: heads x padded head dim; bf16 modes: the hidden layer as planes, 32-channel chunks)
+    carve_stack(bp, R, c.adim, att_width(c.adim, c.aheads), round_up(c.eunits, 32), pw, pw, round_up(std::max(c.adim, c.dur_chans), 32), t.sb);
     t.p0 = bp.take<float>(R * c.dur_chans);
     t.p1 = bp.take<float>(R * c.dur_chans);
     t.dlog_rows = bp.take<float>(R);
     t.dint = bp.take<int64_t>((size_t)b.B * b.Tmax);
     t.cum = bp.take<int>((size_t)b.B * b.Tmax);
     t.o32 = bp.take<int>(b.B);
-    t.kp_cap = (size_t)4 * std::min<size_t>(R, kSplitRows) * 1024;
+    t.kp_cap = kpart_floats(R);
     t.kp = bp.take<float>(t.kp_cap);
     // tok.proj's output rows (taken last: every other offset is as it was; none in fp32, which never takes the path)
     t.tokp = (tok_proj_cols(c) && b.precision != FS2_PREC_FP32) ? bp.take<float>(R * (size_t)tok_proj_cols(c)) : nullptr;
@@ -1057,19 +1028,9 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
     f.p_rows = bp.take<float>(R);
     f.vp = bp.take<float>(R * 2 * (size_t)c.var_chans);
     f.vs = bp.take<float>(R * 2 * (size_t)c.var_chans);
-    f.sb.x0 = bp.take<float>(R * c.ddim);
-    f.sb.x1 = bp.take<float>(R * c.ddim);
-    const size_t dDp = att_width(c.ddim, c.aheads);
-    f.sb.qkv = bp.take<float>(R * 3 * dDp);
-    f.sb.ctx = bp.take<float>(R * dDp);
-    f.sb.hid = bp.take<float>(R * (size_t)std::max(round_up(c.dunits, 32), 2 * c.postnet_chans));
-    f.sb.qkh = bp.take<__bf16>(R * 2 * dDp);
-    f.sb.qkl = bp.take<__bf16>(R * 2 * dDp);
-    f.sb.vth = bp.take<__bf16>(R * dDp);
-    f.sb.vtl = bp.take<__bf16>(R * dDp);
-    f.sb.x0p = bp.take<float>(R * (size_t)round_up(std::max(c.ddim, c.postnet_chans), 32));
-    f.sb.x1p = bp.take<float>(R * (size_t)round_up(std::max(std::max(c.adim, c.ddim), c.postnet_chans), 32));    // also holds the length-regulator output's planes
-    f.sb.xps = bp.take<float>(R * (size_t)round_up(std::max(std::max(c.adim, c.ddim), std::max(std::max(c.var_chans, c.postnet_chans), c.odim)), 32));
+    // (hid: also the Postnet's ping-pong rows; x0p / x1p: also the Postnet's planes, x1p the length-regulator output's too; xps: of every launch that builds its planes)
+    carve_stack(bp, R, c.ddim, att_width(c.ddim, c.aheads), std::max(round_up(c.dunits, 32), 2 * c.postnet_chans), round_up(std::max(c.ddim, c.postnet_chans), 32),
+                round_up(std::max(std::max(c.adim, c.ddim), c.postnet_chans), 32), round_up(std::max(std::max(c.adim, c.ddim), std::max(std::max(c.var_chans, c.postnet_chans), c.odim)), 32), f.sb);
     f.sb.xs4 = bp.take<unsigned char>(R * 32 + 64);      // mx4: one scale byte per (row, 16-channel slot of a cross unit), 32 per row
     const size_t rf = (size_t)std::max(c.reduction_factor, 1);
     f.before = bp.take<float>(R * rf * c.odim);
@@ -1083,7 +1044,7 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
     f.qe = bp.take<int>(R);
     f.qp = bp.take<int>(R);
     f.lri = bp.take<int>(R);
-    f.kp_cap = (size_t)4 * std::min<size_t>(R, kSplitRows) * 1024;
+    f.kp_cap = kpart_floats(R);
     f.kp = bp.take<float>(f.kp_cap);
     if (fb) *fb = f;
     if (ok) *ok = bp.ok();
@@ -1091,15 +1052,12 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
 }
 
 template <typename T>
-int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, const int* limit, int B, int Lout, T* dst, T fill,
-           const int* ovf = nullptr, bool* ovf_handled = nullptr) {
+int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, const int* limit, int B, int Lout, T* dst, T fill, const int* ovf = nullptr) {
     const int64_t total = (int64_t)B * Lout * W;
-    if (ovf_handled) *ovf_handled = false;
     if (total == 0) return FS2_OK;
     if constexpr (std::is_same<T, float>::value) {
-        if (W % 4 == 0 && fill == 0.f && (reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) % 16 == 0) {
+        if (fill == 0.f && unpack_vec(W, src, dst)) {      // (looks at the overflow flags itself: call_plan.h)
             hipLaunchKernelGGL(unpack_rows4, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, src, W / 4, start, limit, B, Lout, dst, ovf);
-            if (ovf_handled) *ovf_handled = true;
             HIP_TRY(h, hipGetLastError());
             return FS2_OK;
         }
@@ -1127,6 +1085,111 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 
 // ---------------------------------------------------------------------------------- pitch / energy control, per-phoneme means
 #include "prosody.h"
+
+// ------------------------------------------------------------------ pieces of fs2_decode (call_plan.h: DecodePlan says which of them run)
+// (behind the operator headers: decode_outputs is the first to instantiate unpack<T>, and the kernels of the code object stand in the order of first instantiation)
+// what var.gather0 and dec.in.gather share: the token-level products and the frame rows that gather them
+TokGatherArgs tok_gather_args(const fs2_handle* h, const FrameBufs& f, const DevLayout& dl, int R) {
+    TokGatherArgs tg;
+    memset(&tg, 0, sizeof tg);
+    tg.P = h->left.tokP; tg.ldp = h->tokw.N; tg.tok_start = h->left.start; tg.lri = f.lri; tg.row_pos = dl.row_pos; tg.row_seq = dl.row_seq; tg.R = R;
+    tg.chans = h->cfg.var_chans; tg.bias = h->var2.c0.bias; tg.ln_g = h->var2.ln0g; tg.ln_b = h->var2.ln0b; tg.vp = f.vp;
+    return tg;
+}
+
+// dec.in.gather: bucket search + embedding add + decoder input layer as one row kernel over the token-level products
+int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, TokGatherArgs tg, const FrameBufs& f, bool po) {
+    const fs2_config& c = h->cfg;
+    tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
+    tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
+    tg.qe_rows = f.qe; tg.qp_rows = f.qp; tg.ln_g2 = h->dec_in_lng; tg.ln_b2 = h->dec_in_lnb;
+    tg.pe = h->dec.pe; tg.pe_alpha = h->dec.alpha; tg.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
+    tg.x0 = po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
+    Scope sc(h, s, "dec.in.gather", 0, 4.0 * tg.R * c.ddim * (po ? 2.0 : 3.0));
+    hipLaunchKernelGGL(dec_in_gather, dim3((tg.R + 3) / 4), dim3(256), 0, s, tg);
+    HIP_TRY(h, hipGetLastError());
+    return FS2_OK;
+}
+
+// dec.in.pe, the TorchScript twin: the decoder input is just x (* sqrt(d)) + alpha * pe   (encoder.py:138-141)
+int dec_in_pe_launch(fs2_handle* h, hipStream_t s, const FrameBufs& f, const DevLayout& dl, int R, bool planes) {
+    const fs2_config& c = h->cfg;
+    Scope sc(h, s, "dec.in.pe", 0.0, 8.0 * R * c.ddim);
+    HIP_TRY(h, hipMemcpyAsync(f.sb.x0, f.hfr, (size_t)R * c.ddim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    GemmArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = c.ddim; a.R = R; a.row_pos = dl.row_pos; a.Y = f.sb.x0; a.ldy = c.ddim;
+    a.pe = h->dec.pe; a.pe_ld = c.ddim; a.pe_alpha = h->dec.alpha; a.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
+    if (planes) { a.Yp = f.sb.x0p; a.yp_chunks = c.ddim / 32; }
+    hipLaunchKernelGGL(ln_rows, dim3((R + 3) / 4), dim3(256), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return FS2_OK;
+}
+
+// reduction_factor r (reference fastspeech.py:153,228-230): feat_out emits r mel frames per decoder frame; its [R, odim r] output
+// IS the [R r, odim] row image the Postnet runs on (decoder row i -> rows i r .. i r + r - 1, gap rows stay zero rows), so only the
+// row metadata is rebuilt at the finer rate.  r = 1 uses the decoder's own metadata and buffers.
+int mel_layout(fs2_handle* h, hipStream_t s, const FrameBufs& f, const DevLayout& dl, int B, int Rpad, int rf, DevLayout& dl2) {
+    dl2 = dl;
+    if (rf == 1) return FS2_OK;
+    const int Rpad2 = Rpad * rf;
+    const Meta2 m = Meta2::at(B, Rpad2);
+    dl2.start = f.meta2 + m.start; dl2.len = f.meta2 + m.len; dl2.vlen = f.meta2 + m.vlen; dl2.klen = dl2.len;
+    dl2.dims = dl.dims ? f.meta2 + m.dims : nullptr;
+    dl2.row_pos = f.meta2 + m.row_pos; dl2.row_seq = f.meta2 + m.row_seq;
+    hipLaunchKernelGGL(scale_layout, dim3((B + 255) / 256), dim3(256), 0, s, dl.start, dl.len, dl.vlen, dl.dims, B, rf, dl2.start, dl2.len, dl2.vlen, dl2.dims);
+    hipLaunchKernelGGL(build_row_meta, dim3((Rpad2 + 255) / 256), dim3(256), 0, s, dl2.start, dl2.len, B, Rpad2, dl2.row_pos, dl2.row_seq);
+    HIP_TRY(h, hipGetLastError());
+    return FS2_OK;
+}
+
+// The outputs of fs2_decode, all under the profile name "unpack": the packed rows to the caller's padded [B, Lmax] buffers, the mel also back to back
+// (after_packed), and in the device-driven layout NaN over the mel outputs whose writer does not look at the overflow flags itself (p.poison_*).
+// dl2 / mel_after: the layout and the rows of the final mel (mel outputs hold Lmax * reduction_factor frames per utterance).
+int decode_outputs(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, const DecodePlan& p, const FrameBufs& f, const DevLayout& dl, const DevLayout& dl2, int R, const float* mel_after) {
+    const fs2_config& c = h->cfg;
+    const int B = io->batch.B, Lmax = io->Lmax, rf = p.rf;
+    int rc;
+    Scope sc(h, s, "unpack", 0, 4.0 * R * c.odim * 4);
+    const int* lim_len = dl.len;    // every stored row (pads carry real values in compat mode)
+    const int* lim_msk = p.ep_stored ? dl.len : dl.vlen;
+    const int* ovf = p.devlay ? dl.dims + 2 : nullptr;
+    if (io->after && (rc = unpack<float>(h, s, mel_after, c.odim, dl2.start, dl2.len, B, Lmax * rf, io->after, 0.f, ovf))) return rc;
+    if (io->before && (rc = unpack<float>(h, s, f.before, c.odim, dl2.start, dl2.len, B, Lmax * rf, io->before, 0.f, ovf))) return rc;
+    if (io->e_out && (rc = unpack<float>(h, s, f.e_rows, 1, dl.start, lim_msk, B, Lmax, io->e_out, 0.f))) return rc;
+    if (io->p_out && (rc = unpack<float>(h, s, f.p_rows, 1, dl.start, lim_msk, B, Lmax, io->p_out, 0.f))) return rc;
+    if (io->qe && (rc = unpack<int>(h, s, f.qe, 1, dl.start, lim_len, B, Lmax, io->qe, -1))) return rc;
+    if (io->qp && (rc = unpack<int>(h, s, f.qp, 1, dl.start, lim_len, B, Lmax, io->qp, -1))) return rc;
+    if (io->lr_index && (rc = unpack<int>(h, s, f.lri, 1, dl.start, dl.vlen, B, Lmax, io->lr_index, -1))) return rc;
+    if (io->dec_out && (rc = unpack<float>(h, s, f.sb.x0, c.ddim, dl.start, lim_len, B, Lmax, io->dec_out, 0.f))) return rc;
+    if (io->after_packed) {
+        if (c.odim % 4) return fail(h, FS2_ERR_UNSUPPORTED, "after_packed needs odim %% 4 == 0");
+        const int* dcum;
+        if (p.devlay) {
+            dcum = dl.pcum;      // built by frame_layout_dev; the caller's buffer holds row_capacity rows (>= the frames)
+        } else {
+            std::vector<int> cum(B);
+            int run = 0;
+            for (int i = 0; i < B; ++i) { cum[i] = run; run += (int)io->olens[i]; }
+            int* up = f.qe;    // the bucket-index rows are already unpacked: reuse their storage for the offsets
+            HIP_TRY(h, hipMemcpyAsync(up, cum.data(), cum.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            dcum = up;
+        }
+        // (r > 1: the rows are mel frames -- the Postnet's layout dl2, r rows per decoder row -- and the offsets r times the decoder-frame sums)
+        const int R2 = R * rf;
+        const int64_t n = (int64_t)R2 * (c.odim / 4);
+        hipLaunchKernelGGL(pack_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mel_after, c.odim, dl2.row_pos, dl2.row_seq, dl2.vlen, dcum, R2, io->after_packed,
+                           p.packed_ovf ? ovf : (const int*)nullptr, rf);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (p.poison()) {
+        const int64_t mel = (int64_t)B * Lmax * rf * c.odim;
+        hipLaunchKernelGGL(poison_on_overflow, dim3(256), dim3(256), 0, s, dl.dims, io->after, p.poison_after ? mel : (int64_t)0, io->after_packed,
+                           p.poison_packed ? io->row_capacity * rf * c.odim : (int64_t)0, io->before, p.poison_before ? mel : (int64_t)0);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return FS2_OK;
+}
 
 }  // namespace
 
@@ -1200,7 +1263,7 @@ int fs2_load_weights(fs2_handle* h, const fs2_tensor_desc* t, int32_t n, void* s
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipStreamSynchronize(s));   // nothing may still be reading the old weights
     free_weights(h);
-    h->encoded = false;
+    h->left = Encoded();
     const fs2_config& c = h->cfg;
     Loader L{h, s, {}, FS2_OK};
     for (int i = 0; i < n; ++i) if (t[i].name) L.m[t[i].name] = &t[i];
@@ -1245,7 +1308,7 @@ int fs2_load_weights(fs2_handle* h, const fs2_tensor_desc* t, int32_t n, void* s
         h->dec_in_lng = L.copy("decoder.embed.1.weight", {c.ddim});
         h->dec_in_lnb = L.copy("decoder.embed.1.bias", {c.ddim});
     }
-    h->tokw = Gemm(); h->TEd = h->TPd = nullptr; h->tokP = nullptr;
+    h->tokw = Gemm(); h->TEd = h->TPd = nullptr;
     if (tok_proj_cols(c) && h->var2.ok && !L.rc) load_tok_proj(L, h);
     h->feat = L.gemm({"feat_out.weight"}, {"feat_out.bias"}, c.odim * std::max(c.reduction_factor, 1), c.ddim, 1, true);
     h->post.clear();
@@ -1300,25 +1363,20 @@ size_t fs2_token_workspace_bytes(const fs2_handle* h, const fs2_batch* b) {
     return carve_tokens(h->cfg, *b, L, nullptr, 0, nullptr, nullptr);
 }
 
+// Four steps: checks, layout and carve, plan, then the launches, which branch on the plan's fields only.
 int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     if (!h || !io) return fail(h, FS2_ERR_ARG, "fs2_encode: null argument");
     ABI_CHECK(h, "fs2_encode", io, fs2_encode_io);
     if (!h->loaded) return fail(h, FS2_ERR_STATE, "fs2_encode: weights not loaded");
-    int rc = check_batch(h, io->batch);
-    if (rc) return rc;
-    if (!io->xs || !io->olens || !io->workspace) return fail(h, FS2_ERR_ARG, "fs2_encode: xs/olens/workspace must be given");
-    if (io->duration_alpha < 0.f) return fail(h, FS2_ERR_ARG, "fs2_encode: duration_alpha %g must be > 0 (0 = 1.0)", (double)io->duration_alpha);
+    if (const Refusal r = check_encode(*io, h->enc.pe_rows); r.err) return fail(h, r.err, "%s", r.msg);
     DeviceGuard g(h->cfg.device);
     HIP_TRY(h, g.err);
     hipStream_t s = (hipStream_t)stream;
     const fs2_config& c = h->cfg;
     const fs2_batch& b = io->batch;
-    const int prec = base_precision(b.precision), ffn_terms = ffn_f16_terms(b.precision);
-    h->encoded = false;
+    h->left = Encoded();
     token_layout(b, h->tok, h->gap);
     const HostLayout& L = h->tok;
-    if (L.len.size() && *std::max_element(L.len.begin(), L.len.end()) > h->enc.pe_rows)
-        return fail(h, FS2_ERR_ARG, "sequence longer than the positional table (%d rows): extend `pe` and reload", h->enc.pe_rows);
     TokenBufs t; bool ok;
     carve_tokens(c, b, L, io->workspace, io->workspace_bytes, &t, &ok);
     if (!ok) return fail(h, FS2_ERR_WORKSPACE, "fs2_encode: workspace too small");
@@ -1326,19 +1384,20 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     const StackBufs& sb = t.sb;
     const int tok_regime = regime_rows_of(b, /*token_level=*/true);
     h->cur_regime = tok_regime; h->cur_status = nullptr;
-    if ((rc = upload_layout(h, s, L, t.meta, h->dtok))) return rc;
-    const DevLayout& dl = h->dtok;
-    const bool enc_pl = prec != FS2_PREC_FP32;   // activations also travel as planes (x0p holds those of x0 before and after the stack)
+    const EncodePlan p = plan_encode(c, opts(), b.precision, h->tokw.N, t.tokp != nullptr);
+    int rc;
+    DevLayout dl;
+    if ((rc = upload_layout(h, s, L, t.meta, dl))) return rc;
     {
         Scope sc(h, s, "enc.embed", 0, 4.0 * L.R * c.adim * 2);
         hipLaunchKernelGGL(embed_pe, dim3((L.R + 3) / 4), dim3(256), 0, s, io->xs, b.Tmax, h->enc_embed, c.idim, c.adim, h->enc.pe,
                            h->enc.alpha, c.use_scaled_pos_enc ? 1.0f : sqrtf((float)c.adim), dl.row_pos, dl.row_seq, L.R, sb.x0,
-                           enc_pl && c.adim % 32 == 0 ? sb.x0p : nullptr);
+                           p.embed_planes ? sb.x0p : nullptr);
         HIP_TRY(h, hipGetLastError());
     }
     const Rows rows{L.R, L.Rpad, dl.row_pos, dl.dims, tok_regime};
-    if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, rows, L, dl, /*mask_q=*/1, sb, prec, /*x0p_ready=*/enc_pl && c.adim % 32 == 0, ffn_terms))) return rc;
-    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, t.p0, t.p1, t.dlog_rows, prec, enc_pl ? sb.x0p : nullptr, sb.xps))) return rc;
+    if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, rows, L, dl, /*mask_q=*/1, sb, p.prec, /*x0p_ready=*/p.embed_planes, p.ffn_terms))) return rc;
+    if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, t.p0, t.p1, t.dlog_rows, p.prec, p.planes ? sb.x0p : nullptr, sb.xps))) return rc;
     {
         Scope sc(h, s, "dur.post", 0, 0);
         const int n = b.B * b.Tmax;
@@ -1351,26 +1410,14 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     if (io->enc_out) {
         if ((rc = unpack<float>(h, s, sb.x0, c.adim, dl.start, dl.vlen, b.B, b.Tmax, io->enc_out, 0.f))) return rc;
     }
-    // tok.proj: the encoder rows times the stacked weights of the predictors' first convolution (one k = 1 product per tap) and of the decoder input layer, once
-    // per token instead of once per frame (fs2_decode: var.gather0 / dec.in.gather).  One kernel whatever the batch (64-row tiles, N > 1024: never split-K).
-    h->tokP = nullptr; h->tokP_conv = false;
-    if (enc_pl && h->tokw.N && t.tokp && opts().tokproj) {
-        // the predictors' columns only where fs2_decode can use them (bit 0 and the fused predictors); else the launch is sliced to the input layer's columns
-        // (a multiple of 128 rows into the weight images: whole tiles)
-        const bool conv = (opts().tokproj & 1) && opts().fuse_var;
-        const int n0 = conv ? 0 : 6 * c.var_chans;
-        const Gemm g = gemm_rows_from(h->tokw, n0);
-        GemmArgs a = gemm_args(g, sb.x0, c.adim, L.R, dl.row_pos, t.tokp + n0, h->tokw.N);
-        a.Xp = sb.x0p; a.xp_scratch = sb.xps;
-        a.kpart = h->kp; a.kpart_cap = 0;      // never split-K (no partial buffers allowed): one kernel whatever the batch or the slice
-        if ((rc = launch_gemm(h, s, "tok.proj", a, opts().tokproj_f32 ? FS2_PREC_FP32 : prec))) return rc;
-        h->tokP = t.tokp; h->tokP_conv = conv;
+    if (p.tok_proj) {      // (call_plan.h: EncodePlan)
+        if ((rc = launch_step(h, s, nullptr, tok_proj_step(h->tokw, p.tok_n0, sb.x0, c.adim, rows, sb.x0p, sb.xps, t.tokp, h->kp), p.tok_prec))) return rc;
     }
-    h->enc_final = sb.x0; h->cum = t.cum; h->o32 = t.o32; h->enc_B = b.B; h->enc_Tmax = b.Tmax; h->enc_compat = b.compat_padded;
-    h->enc_ntok = 0;
-    for (int i = 0; i < b.B; ++i) h->enc_ntok += (long)b.ilens[i];
-    h->enc_ws = io->workspace;
-    h->encoded = true;
+    Encoded& e = h->left;
+    e.B = b.B; e.Tmax = b.Tmax; e.compat = b.compat_padded; e.ws = io->workspace;
+    e.rows = sb.x0; e.tokP = p.tok_proj ? t.tokp : nullptr; e.tokP_conv = p.tok_conv;
+    e.start = dl.start; e.vlen = dl.vlen; e.cum = t.cum; e.o32 = t.o32;
+    e.valid = true;
     return FS2_OK;
 }
 
@@ -1399,61 +1446,26 @@ int fs2_decode(fs2_handle* h, void* stream, const fs2_decode_io* io) { return fs
 int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const fs2_prosody* ctl) {
     if (!h || !io) return fail(h, FS2_ERR_ARG, "fs2_decode: null argument");
     ABI_CHECK(h, "fs2_decode", io, fs2_decode_io);
-    // control of the predicted pitch / energy (prosody.h): refused as a whole before anything is launched
-    ProsodyTrack ctl_p{}, ctl_e{};
-    if (ctl) {
-        ABI_CHECK(h, "fs2_decode_ctl", ctl, fs2_prosody);
-        ctl_p = ProsodyTrack{ctl->pitch_scale, ctl->pitch_shift, ctl->pitch_scale_cols, ctl->pitch_shift_cols};
-        ctl_e = ProsodyTrack{ctl->energy_scale, ctl->energy_shift, ctl->energy_scale_cols, ctl->energy_shift_cols};
-    }
-    const bool ctl_pitch = ctl_p.scale || ctl_p.shift, ctl_energy = ctl_e.scale || ctl_e.shift;
-    if (ctl_pitch || ctl_energy) {
-        const int T = io->batch.Tmax;
-        const struct { const float* p; int cols; const char* name; } given[4] = {{ctl_p.scale, ctl_p.scale_cols, "pitch_scale"}, {ctl_p.shift, ctl_p.shift_cols, "pitch_shift"},
-                                                                                  {ctl_e.scale, ctl_e.scale_cols, "energy_scale"}, {ctl_e.shift, ctl_e.shift_cols, "energy_shift"}};
-        for (const auto& g : given)
-            if (g.p && g.cols != 1 && g.cols != T) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: %s_cols = %d is neither 1 (per utterance) nor Tmax = %d (per phoneme)", g.name, g.cols, T);
-        if (ctl_pitch && io->ps) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: pitch control together with given pitches (io->ps): control acts on predictions");
-        if (ctl_energy && io->es) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: energy control together with given energies (io->es): control acts on predictions");
-        if (io->batch.compat_padded) return fail(h, FS2_ERR_ARG, "fs2_decode_ctl: control has per-utterance semantics only (batch.compat_padded must be 0)");
-    }
-    if (!h->encoded) return fail(h, FS2_ERR_STATE, "fs2_decode called without a preceding fs2_encode");
-    const fs2_batch& b = io->batch;
-    int rc = check_batch(h, b);
-    if (rc) return rc;
-    if (b.B != h->enc_B || b.Tmax != h->enc_Tmax || b.compat_padded != h->enc_compat || io->token_workspace != h->enc_ws)
-        return fail(h, FS2_ERR_STATE, "fs2_decode: batch does not match the preceding fs2_encode");
-    const bool devlay = io->olens == nullptr && io->row_capacity > 0;
-    if ((!io->olens && !devlay) || !io->workspace || (!io->after && !io->after_packed))
-        return fail(h, FS2_ERR_ARG, "fs2_decode: olens (or row_capacity) / workspace / after (or after_packed) must be given");
+    if (ctl) ABI_CHECK(h, "fs2_decode_ctl", ctl, fs2_prosody);
+    if (const Refusal r = check_decode(*io, ctl, h->left, h->cfg.idim, h->dec.pe_rows); r.err) return fail(h, r.err, "%s", r.msg);
     const fs2_config& c = h->cfg;
-    if (devlay) {
-        if (!io->status) return fail(h, FS2_ERR_ARG, "fs2_decode: the device-driven layout needs a status buffer");
-        if (io->row_capacity > INT32_MAX - 256 || io->Lmax <= 0) return fail(h, FS2_ERR_ARG, "row_capacity %lld / Lmax %d", (long long)io->row_capacity, io->Lmax);
-    } else {
-        int mx = 0;
-        for (int i = 0; i < b.B; ++i) {
-            if (io->olens[i] == -1) return fail(h, FS2_ERR_ARG, "utterance %d holds a phoneme id outside [0, %d) (fs2_encode marks it with the frame count -1)", i, h->cfg.idim);
-            if (io->olens[i] <= 0) return fail(h, FS2_ERR_ARG, "olens[%d]=%lld", i, (long long)io->olens[i]);
-            mx = std::max(mx, (int)io->olens[i]);
-        }
-        if (io->Lmax < mx) return fail(h, FS2_ERR_ARG, "Lmax %d < longest utterance %d", io->Lmax, mx);
-        if (mx > h->dec.pe_rows) return fail(h, FS2_ERR_ARG, "utterance of %d frames exceeds the positional table (%d rows): extend `pe` and reload", mx, h->dec.pe_rows);
-    }
+    const fs2_batch& b = io->batch;
+    const Encoded& enc = h->left;
     DeviceGuard g(c.device);
     HIP_TRY(h, g.err);
     hipStream_t s = (hipStream_t)stream;
-    const int prec = base_precision(b.precision), ffn_terms = ffn_f16_terms(b.precision);
+    DecodeAsk ask = decode_ask(*io, ctl);
     HostLayout L;
-    if (devlay) capacity_layout(b, io->row_capacity, io->Lmax, L);
+    if (ask.devlay) capacity_layout(b, io->row_capacity, io->Lmax, L);
     else frame_layout(b, io->olens, io->masked, L, h->gap);
     FrameBufs f; bool ok;
     carve_frames(c, L, io->workspace, io->workspace_bytes, &f, &ok);
     if (!ok) return fail(h, FS2_ERR_WORKSPACE, "fs2_decode: workspace too small");
     h->kp = f.kp; h->kp_cap = f.kp_cap;
+    int rc;
     DevLayout dl;
-    if (devlay) {
-        if ((rc = device_layout(h, s, L, f.meta, dl, h->o32, b.compat_padded, io->masked, io->Lmax, h->dec.pe_rows, io->status))) return rc;
+    if (ask.devlay) {
+        if ((rc = device_layout(h, s, L, f.meta, dl, enc.o32, b.compat_padded, io->masked, io->Lmax, h->dec.pe_rows, io->status))) return rc;
     } else if ((rc = upload_layout(h, s, L, f.meta, dl))) return rc;
     const int R = L.R;
     // Kernel variants with different summation orders (LayerNorm fused into the row-complete GEMM or not) are chosen from a row
@@ -1461,156 +1473,71 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
     // the same ESTIMATE instead (regime_rows_of): 8 frames per phoneme plus the per-utterance alignment rows -- of this batch, or of
     // the larger batch the caller says this one is a shard of (fs2_batch.regime_*).
     const int regime_rows = regime_rows_of(b, /*token_level=*/false);
-    h->cur_regime = regime_rows; h->cur_status = devlay ? io->status : nullptr;
+    h->cur_regime = regime_rows; h->cur_status = ask.devlay ? io->status : nullptr;
     const Rows rows{R, L.Rpad, dl.row_pos, dl.dims, regime_rows};
-    // bf16 modes: the length-regulator output (and later its sum with the pitch / energy embeddings) is also written as planes,
-    // in x1p (free until the decoder stack's first LayerNorm): the A operand of both variance predictors and of the decoder input layer
-    void* hfr_planes = (prec != FS2_PREC_FP32 && c.adim % 32 == 0) ? f.sb.x1p : nullptr;
-    const bool need_e = (io->es == nullptr) || io->e_out, need_p = (io->ps == nullptr) || io->p_out;
-    const bool fused_var = need_e && need_p && prec != FS2_PREC_FP32 && h->var2.ok && hfr_planes && opts().fuse_var;
-    // Multiply before expanding (FS2_TOKPROJ; a function of the model, the precision and which outputs are asked for -- never of the batch): the predictors' first
-    // layer (bit 0; where the fused predictors run) and the decoder input layer (bit 1) gather fs2_encode's token-level products; with both nothing reads the
-    // expanded rows, which are then not built.
-    const int tokproj = (prec != FS2_PREC_FP32 && h->tokP && c.decoder_input_layer) ? (opts().tokproj & ((fused_var && h->tokP_conv) ? 3 : 2)) : 0;
-    TokGatherArgs tg;
-    memset(&tg, 0, sizeof tg);
-    tg.P = h->tokP; tg.ldp = h->tokw.N; tg.tok_start = h->dtok.start; tg.lri = f.lri; tg.row_pos = dl.row_pos; tg.row_seq = dl.row_seq; tg.R = R;
-    tg.chans = c.var_chans; tg.bias = h->var2.c0.bias; tg.ln_g = h->var2.ln0g; tg.ln_b = h->var2.ln0b; tg.vp = f.vp;
-    if (tokproj == 3) {
+    DecIn dec_in;
+    if (c.decoder_input_layer) dec_in = DecIn{&h->dec_in, h->dec_in_lng, h->dec_in_lnb, c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim)};
+    const float* mel_after = c.postnet_layers > 0 ? f.after : f.before;
+    ask.R = R; ask.after_vec = unpack_vec(c.odim, mel_after, io->after); ask.before_vec = unpack_vec(c.odim, f.before, io->before);
+    const DecodePlan p = plan_decode(c, opts(), b.precision, ask, enc, h->var2.ok, dec_in, h->dec, rows, f.sb);
+    const int prec = p.prec;
+
+    void* hfr_planes = p.hfr_planes ? f.sb.x1p : nullptr;
+    const TokGatherArgs tg = tok_gather_args(h, f, dl, R);
+    if (p.tokproj == 3) {
         Scope sc(h, s, "lr.index", 0, 4.0 * R);
-        hipLaunchKernelGGL(lr_index_only, dim3((R + 255) / 256), dim3(256), 0, s, h->cum, b.Tmax, h->dtok.vlen, dl.row_pos, dl.row_seq, dl.vlen, R, f.lri);
+        hipLaunchKernelGGL(lr_index_only, dim3((R + 255) / 256), dim3(256), 0, s, enc.cum, b.Tmax, enc.vlen, dl.row_pos, dl.row_seq, dl.vlen, R, f.lri);
         HIP_TRY(h, hipGetLastError());
     } else {   // length regulator
         Scope sc(h, s, "lr.expand", 0, 4.0 * R * c.adim * 2);
-        hipLaunchKernelGGL(lr_expand, dim3((R + 3) / 4), dim3(256), 0, s, h->enc_final, c.adim, h->dtok.start, h->dtok.vlen, h->cum, b.Tmax,
+        hipLaunchKernelGGL(lr_expand, dim3((R + 3) / 4), dim3(256), 0, s, enc.rows, c.adim, enc.start, enc.vlen, enc.cum, b.Tmax,
                            dl.row_pos, dl.row_seq, 0, dl.vlen, R, f.hfr, f.lri, hfr_planes);
         HIP_TRY(h, hipGetLastError());
     }
-    if (fused_var) {
-        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, rows, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (tokproj & 1) ? &tg : nullptr))) return rc;
+    if (p.fused_var) {
+        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, rows, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (p.tokproj & 1) ? &tg : nullptr))) return rc;
     } else {
-        if (need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, rows, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps))) return rc;
-        if (need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, rows, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps))) return rc;
+        if (p.need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, rows, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps))) return rc;
+        if (p.need_p && (rc = run_predictor(h, s, "pitch", h->pitch, f.hfr, c.adim, rows, f.t0, f.t1, f.p_rows, prec, hfr_planes, f.sb.xps))) return rc;
     }
-    if (ctl_pitch || ctl_energy) {   // the predictions become the controlled values in place: both consumers below, and e_out / p_out, see those
-        Scope sc(h, s, "var.control", 2.0 * R * (ctl_pitch + ctl_energy), 4.0 * R * (3.0 + 3.0 * (ctl_pitch + ctl_energy)));
+    if (p.control) {   // the predictions become the controlled values in place: both consumers below, and e_out / p_out, see those
+        const ProsodyTrack ctl_p{ctl->pitch_scale, ctl->pitch_shift, ctl->pitch_scale_cols, ctl->pitch_shift_cols};
+        const ProsodyTrack ctl_e{ctl->energy_scale, ctl->energy_shift, ctl->energy_scale_cols, ctl->energy_shift_cols};
+        const int n = ask.ctl_pitch + ask.ctl_energy;
+        Scope sc(h, s, "var.control", 2.0 * R * n, 4.0 * R * (3.0 + 3.0 * n));
         hipLaunchKernelGGL(prosody_apply, dim3((R + 255) / 256), dim3(256), 0, s, f.p_rows, f.e_rows, dl.row_pos, dl.row_seq, f.lri, R, b.B, b.Tmax, ctl_p, ctl_e);
         HIP_TRY(h, hipGetLastError());
     }
-    if (!(tokproj & 2)) {
+    if (!(p.tokproj & 2)) {
         Scope sc(h, s, "var.embed", 0, 4.0 * R * c.adim * 4);
         hipLaunchKernelGGL(bucket_embed, dim3((R + 3) / 4), dim3(256), 0, s, f.hfr, c.adim, dl.row_pos, dl.row_seq, R, io->es, io->es_stride,
                            io->ps, io->ps_stride, f.e_rows, f.p_rows, h->ebins, h->pbins, c.n_bins - 1, h->Te, h->Tp, f.qe, f.qp, hfr_planes);
         HIP_TRY(h, hipGetLastError());
     }
-    const bool dec_pl = prec != FS2_PREC_FP32;
-    // Planes-only residual stream: where the decoder's LayerNorm-fused launches run on gemm_row4_bf16 they write planes and nothing else and read their residual
-    // from planes (gemm_row4.h: RES) -- the fp32 rows x0 / x1 are not written at all.
-    DecIn dec_in;
-    if (c.decoder_input_layer) dec_in = DecIn{&h->dec_in, h->dec_in_lng, h->dec_in_lnb, c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim)};
-    const bool po = dec_pl && planes_only(dec_in, h->dec, c.ddim, rows, f.sb, prec, ffn_terms, opts());
-    if (tokproj & 2) {   // bucket search + embedding add + decoder input layer as one row kernel over the token-level products
-        tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
-        tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
-        tg.qe_rows = f.qe; tg.qp_rows = f.qp; tg.ln_g2 = h->dec_in_lng; tg.ln_b2 = h->dec_in_lnb;
-        tg.pe = h->dec.pe; tg.pe_alpha = h->dec.alpha; tg.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
-        tg.x0 = po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
-        Scope sc(h, s, "dec.in.gather", 0, 4.0 * R * c.ddim * (po ? 2.0 : 3.0));
-        hipLaunchKernelGGL(dec_in_gather, dim3((R + 3) / 4), dim3(256), 0, s, tg);
-        HIP_TRY(h, hipGetLastError());
+    if (p.tokproj & 2) {
+        if ((rc = dec_in_gather_launch(h, s, io, tg, f, p.po))) return rc;
     } else if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
-        if ((rc = launch_step(h, s, nullptr, dec_in_step(dec_in, h->dec, f.hfr, c.adim, hfr_planes, rows, f.sb, prec, po), prec))) return rc;
-    } else {                       // TorchScript twin: the decoder input is just x (* sqrt(d)) + alpha * pe   (encoder.py:138-141)
-        Scope sc(h, s, "dec.in.pe", 0.0, 8.0 * R * c.ddim);
-        HIP_TRY(h, hipMemcpyAsync(f.sb.x0, f.hfr, (size_t)R * c.ddim * sizeof(float), hipMemcpyDeviceToDevice, s));
-        GemmArgs a;
-        memset(&a, 0, sizeof a);
-        a.N = c.ddim; a.R = R; a.row_pos = dl.row_pos; a.Y = f.sb.x0; a.ldy = c.ddim;
-        a.pe = h->dec.pe; a.pe_ld = c.ddim; a.pe_alpha = h->dec.alpha; a.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
-        if (dec_pl) { a.Yp = f.sb.x0p; a.yp_chunks = c.ddim / 32; }
-        hipLaunchKernelGGL(ln_rows, dim3((R + 3) / 4), dim3(256), 0, s, a);
-        HIP_TRY(h, hipGetLastError());
-    }
-    const int mask_q = (b.compat_padded && io->masked) ? 1 : 0;
-    if ((rc = run_stack(h, s, "dec", h->dec, c.ddim, c.aheads, rows, L, dl, mask_q, f.sb, prec, /*x0p_ready=*/dec_pl, ffn_terms, po))) return rc;
-    if (po && io->dec_out) {      // the API hands the decoder output out as fp32 rows: rebuilt from the planes (hi + lo) only when asked for
+        if ((rc = launch_step(h, s, nullptr, dec_in_step(dec_in, h->dec, f.hfr, c.adim, hfr_planes, rows, f.sb, prec, p.po), prec))) return rc;
+    } else if ((rc = dec_in_pe_launch(h, s, f, dl, R, p.planes))) return rc;
+    if ((rc = run_stack(h, s, "dec", h->dec, c.ddim, c.aheads, rows, L, dl, p.mask_q, f.sb, prec, /*x0p_ready=*/p.planes, p.ffn_terms, p.po))) return rc;
+    if (p.po && io->dec_out) {      // the API hands the decoder output out as fp32 rows: rebuilt from the planes (hi + lo) only when asked for
         Scope sc(h, s, "dec.out.rows", 0.0, 8.0 * R * c.ddim);
         const int64_t n = (int64_t)R * (c.ddim / 4);
         hipLaunchKernelGGL(planes_to_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f.sb.x0p, c.ddim / 32, R, c.ddim, f.sb.x0, c.ddim);
         HIP_TRY(h, hipGetLastError());
     }
-    // reduction_factor r (reference fastspeech.py:153,228-230): feat_out emits r mel frames per decoder frame; its [R, odim r] output
-    // IS the [R r, odim] row image the Postnet runs on (decoder row i -> rows i r .. i r + r - 1, gap rows stay zero rows), so only the
-    // row metadata is rebuilt at the finer rate.  r = 1 uses the decoder's own metadata and buffers.
-    const int rf = std::max(c.reduction_factor, 1);
-    const int R2 = R * rf;
-    DevLayout dl2 = dl;
-    if (rf > 1) {
-        const int Rpad2 = L.Rpad * rf;
-        const Meta2 m = Meta2::at(b.B, Rpad2);
-        dl2.start = f.meta2 + m.start; dl2.len = f.meta2 + m.len; dl2.vlen = f.meta2 + m.vlen; dl2.klen = dl2.len;
-        dl2.dims = dl.dims ? f.meta2 + m.dims : nullptr;
-        dl2.row_pos = f.meta2 + m.row_pos; dl2.row_seq = f.meta2 + m.row_seq;
-        hipLaunchKernelGGL(scale_layout, dim3((b.B + 255) / 256), dim3(256), 0, s, dl.start, dl.len, dl.vlen, dl.dims, b.B, rf, dl2.start, dl2.len, dl2.vlen, dl2.dims);
-        hipLaunchKernelGGL(build_row_meta, dim3((Rpad2 + 255) / 256), dim3(256), 0, s, dl2.start, dl2.len, b.B, Rpad2, dl2.row_pos, dl2.row_seq);
-        HIP_TRY(h, hipGetLastError());
-    }
+    const int rf = p.rf;
+    DevLayout dl2;      // the Postnet's and the mel outputs' layout: rf rows per decoder row
+    if ((rc = mel_layout(h, s, f, dl, b.B, L.Rpad, rf, dl2))) return rc;
     // planes hand-off through the tail: decoder -> feat_out (fp32 mel + planes of it) -> Postnet convs ping-pong x0p / x1p
-    const bool post_pl = dec_pl && c.postnet_layers > 1 && rf == 1;     // (r > 1: feat_out's planes would be in the decoder-row layout)
-    if ((rc = launch_step(h, s, nullptr, feat_out_step(h->feat, rows, f.sb, f.before, prec, post_pl), prec))) return rc;
+    if ((rc = launch_step(h, s, nullptr, feat_out_step(h->feat, rows, f.sb, f.before, prec, p.post_pl), prec))) return rc;
     if (c.postnet_layers > 0) {
-        const Rows rows2{R2, L.Rpad * rf, dl2.row_pos, dl2.dims, 0};
+        const Rows rows2{R * rf, L.Rpad * rf, dl2.row_pos, dl2.dims, 0};
         const PostBufs pb{f.before, f.after, rf > 1 ? f.pa2 : f.sb.hid, rf > 1 ? f.pb2 : f.sb.hid + (size_t)L.Rpad * c.postnet_chans, rf > 1 ? f.xps2 : f.sb.xps};
         for (int l = 0; l < c.postnet_layers; ++l)
-            if ((rc = launch_step(h, s, nullptr, postnet_step(h->post, l, c.odim, rows2, pb, f.sb, post_pl, ffn_terms, opts()), prec))) return rc;
+            if ((rc = launch_step(h, s, nullptr, postnet_step(h->post, l, c.odim, rows2, pb, f.sb, p.post_pl, p.ffn_terms, opts()), prec))) return rc;
     }
-    const float* mel_after = c.postnet_layers > 0 ? f.after : f.before;
-    {
-        Scope sc(h, s, "unpack", 0, 4.0 * R * c.odim * 4);
-        const int* lim_len = dl.len;    // every stored row (pads carry real values in compat mode)
-        const int* lim_msk = (b.compat_padded && !io->masked) ? dl.len : dl.vlen;
-        // device-driven layout: the kernels that write the mel outputs look at the overflow flags themselves and write NaN when a
-        // capacity was too small (nobody can mistake the outputs of such a call for silence); poison_on_overflow covers the rest
-        const int* ovf = devlay ? dl.dims + 2 : nullptr;
-        bool after_done = false, before_done = false, packed_done = false;
-        // (mel outputs hold Lmax * reduction_factor frames per utterance)
-        if (io->after && (rc = unpack<float>(h, s, mel_after, c.odim, dl2.start, dl2.len, b.B, io->Lmax * rf, io->after, 0.f, ovf, &after_done))) return rc;
-        if (io->before && (rc = unpack<float>(h, s, f.before, c.odim, dl2.start, dl2.len, b.B, io->Lmax * rf, io->before, 0.f, ovf, &before_done))) return rc;
-        if (io->e_out && (rc = unpack<float>(h, s, f.e_rows, 1, dl.start, lim_msk, b.B, io->Lmax, io->e_out, 0.f))) return rc;
-        if (io->p_out && (rc = unpack<float>(h, s, f.p_rows, 1, dl.start, lim_msk, b.B, io->Lmax, io->p_out, 0.f))) return rc;
-        if (io->qe && (rc = unpack<int>(h, s, f.qe, 1, dl.start, lim_len, b.B, io->Lmax, io->qe, -1))) return rc;
-        if (io->qp && (rc = unpack<int>(h, s, f.qp, 1, dl.start, lim_len, b.B, io->Lmax, io->qp, -1))) return rc;
-        if (io->lr_index && (rc = unpack<int>(h, s, f.lri, 1, dl.start, dl.vlen, b.B, io->Lmax, io->lr_index, -1))) return rc;
-        if (io->dec_out && (rc = unpack<float>(h, s, f.sb.x0, c.ddim, dl.start, lim_len, b.B, io->Lmax, io->dec_out, 0.f))) return rc;
-        if (io->after_packed) {
-            if (c.odim % 4) return fail(h, FS2_ERR_UNSUPPORTED, "after_packed needs odim %% 4 == 0");
-            const int* dcum;
-            if (devlay) {
-                dcum = dl.pcum;      // built by frame_layout_dev; the caller's buffer holds row_capacity rows (>= the frames)
-            } else {
-                std::vector<int> cum(b.B);
-                int run = 0;
-                for (int i = 0; i < b.B; ++i) { cum[i] = run; run += (int)io->olens[i]; }
-                int* up = f.qe;    // the bucket-index rows are already unpacked: reuse their storage for the offsets
-                HIP_TRY(h, hipMemcpyAsync(up, cum.data(), cum.size() * sizeof(int), hipMemcpyHostToDevice, s));
-                dcum = up;
-            }
-            // (r > 1: the rows are mel frames -- the Postnet's layout dl2, r rows per decoder row -- and the offsets r times the decoder-frame sums)
-            const int64_t n = (int64_t)R2 * (c.odim / 4);
-            hipLaunchKernelGGL(pack_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mel_after, c.odim, dl2.row_pos, dl2.row_seq, dl2.vlen, dcum, R2, io->after_packed,
-                               (devlay && R == io->row_capacity) ? ovf : (const int*)nullptr, rf);
-            HIP_TRY(h, hipGetLastError());
-            packed_done = devlay && R == io->row_capacity;
-        }
-        const bool need_poison = devlay && ((io->after && !after_done) || (io->before && !before_done) || (io->after_packed && !packed_done));
-        if (need_poison) {
-            hipLaunchKernelGGL(poison_on_overflow, dim3(256), dim3(256), 0, s, dl.dims, io->after, (io->after && !after_done) ? (int64_t)b.B * io->Lmax * rf * c.odim : (int64_t)0,
-                               io->after_packed, (io->after_packed && !packed_done) ? io->row_capacity * rf * c.odim : (int64_t)0, io->before,
-                               (io->before && !before_done) ? (int64_t)b.B * io->Lmax * rf * c.odim : (int64_t)0);
-            HIP_TRY(h, hipGetLastError());
-        }
-    }
-    return FS2_OK;
+    return decode_outputs(h, s, io, p, f, dl, dl2, R, mel_after);
 }
 
 // ---------------------------------------------------------------------------------- single operators

@@ -1,6 +1,8 @@
 // The model's GEMM launches, stated once: the weight descriptors, and for every named launch of the model the arguments it is made with, as short lists of steps.
-// fs2_runtime.hip executes the lists (run_stack, run_predictor, run_predictors_fused, the tail of fs2_decode), the planes-only decision of fs2_decode asks them
-// (planes_only), tests/gemm_plan_probe.cpp walks them on the CPU.  HIP-free like gemm_plan.h: integers and pointers nobody follows here.
+// fs2_runtime.hip executes the lists (run_stack, run_predictor, run_predictors_fused, tok.proj and the tail of fs2_decode), tests/gemm_plan_probe.cpp walks them on
+// the CPU.  Who decides what: this header HOW a launch is made (its arguments; gemm_plan.h / attn_plan.h then choose the kernel), call_plan.h WHICH launches a call
+// consists of -- the booleans the functions here take (po, post_pl, layer0, the tok.proj slice) are fields of its plans, and plan_decode asks planes_only below for po.
+// HIP-free like gemm_plan.h: integers and pointers nobody follows here (DESIGN.md sections 7.1 and 7.3).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -276,6 +278,15 @@ inline Steps<3> fused_predictor_steps(const FusedPredictors& v, const Predictor&
     a.dot_w = v.lin_w; a.dot_b = v.lin_b; a.dot_out = e_rows; a.dot_gstride = (int)(p_rows - e_rows);
     out.add(StepKind::Gemm, a, "var.conv1");
     return out;
+}
+
+// tok.proj (fs2_encode; call_plan.h: EncodePlan): the encoder rows X / Xp times the columns [n0, N) of the stacked k = 1 weight, into the same columns of P [R, tokw.N].
+// kpart without ksplit: the launch names the call's scratch but allows no partial buffers -- never split-K: one kernel whatever the batch or the slice.
+inline Step tok_proj_step(const Gemm& tokw, int n0, const float* X, int ldx, const Rows& r, const void* Xp, void* xps, float* P, float* kpart) {
+    GemmArgs a = gemm_args(gemm_rows_from(tokw, n0), X, ldx, r.R, r.row_pos, P + n0, tokw.N);
+    a.Xp = Xp; a.xp_scratch = xps;
+    a.kpart = kpart; a.kpart_cap = 0;
+    return make_step(StepKind::Gemm, a, "tok.proj");
 }
 
 // ------------------------------------------------------------------ the decoder's input layer and tail

@@ -1,20 +1,27 @@
-// Host-compiled driver of csrc/gemm_plan.h, csrc/attn_plan.h and csrc/model_launches.h for tests/test_gemm_plan_host.py and tests/test_attn_plan_host.py
-// (g++ -std=c++17 -Wall -Werror, no HIP).
-//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr>      the plan of every named launch of the default model, attention included, in the four tested precisions
+// Host-compiled driver of csrc/gemm_plan.h, csrc/attn_plan.h, csrc/model_launches.h and csrc/call_plan.h for tests/test_gemm_plan_host.py, tests/test_attn_plan_host.py
+// and tests/test_call_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
+//   probe model <Rtok> <regime_tok> <Rfr> <regime_fr> <case>   the plan of every GEMM and attention launch of a teacher-forced forward of the default model, in the four tested precisions
+//   probe names <block> <mode> <case> <tokens,frames>..    the ordered profile names of one forward (rows: layout_rule.h), sub-launches (.planes, .rows, .split) included
+//   probe decisions                                        every field of EncodePlan / DecodePlan over the inputs they are functions of
+//   probe call_refusals                                    one argument set per refusal of check_encode / check_decode, and one per pair the entry points test in sequence
 //   probe variants <Rtok> <regime_tok> <Rfr> <regime_fr>   every step of the pre-LN / concat_after block variants, and whether its GEMMs plan
 //   probe sweep                                            the planes-only decision: the predicate fs2_decode used to restate against the plan's answer
 //   probe refusals                                         one argument set per refusal of plan_gemm
 //   probe attn_sweep                                       plan_attention over the regime threshold, the switch, the plane distances, the grid and the scales
 //   probe attn_refusals                                    the refusals of plan_attention
-// The launches are the ones model_launches.h forms, the header fs2_runtime.hip executes.  This file holds only data: a model described as the loader would leave it
-// (a marker pointer wherever it builds an image or the workspace has a buffer) and the walk over the header's step lists.
+// <case>: key=value,... (or -): the options tokproj, tokproj_f32, fuse_var, row8; the model's rf (reduction_factor), post (postnet_layers), in (decoder input layer); the call's
+// es, ps, e_out, p_out, dec_out, after, before, packed, ctl, devlay (0 / 1), tokp (the token workspace has tok.proj's buffer).  Default: the default options, a teacher-forced forward.
+// The launches are the ones model_launches.h forms and call_plan.h decides on, the headers fs2_runtime.hip executes: encode() and decode() below are its two entry points
+// without the kernels, branching on the same plan fields.  This file holds only data: a model described as the loader would leave it (a marker pointer wherever it builds
+// an image or the workspace has a buffer) and the walk over the headers' step lists.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "attn_plan.h"
-#include "model_launches.h"
+#include "call_plan.h"
 
 using namespace fs2;
 
@@ -38,7 +45,7 @@ Gemm gemm(int C, int ktaps, int N, bool mx = false, bool f16 = false) {
 GemmArgs base(int C, int ktaps, int N, int R, bool y) { return gemm_args(gemm(C, ktaps, N), M, C, R, nullptr, y ? M : nullptr, N); }      // (the refusal cases start from it)
 
 struct Model { int adim = 256, ddim = 384, heads = 2, eunits = 1024, dunits = 1024, kffn = 9, odim = 80, post_layers = 5, post_chans = 256, post_k = 5,
-               dur_chans = 256, dur_k = 3, var_chans = 256, var_k = 3, layers = 4;
+               dur_chans = 256, dur_k = 3, var_chans = 256, var_k = 3, layers = 4, rf = 1, input_layer = 1;
                bool enc_pre_ln = false, enc_concat = false, dec_pre_ln = false, dec_concat = false; };
 
 Stack stack(int D, int heads, int units, int k, int layers, bool pre_ln, bool concat) {
@@ -58,16 +65,19 @@ Predictor predictor(int cin, int chans, int k) {
     return p;
 }
 struct Built {
-    Stack enc, dec; Predictor dur, energy, pitch; FusedPredictors var2; Gemm dec_in, feat; std::vector<Gemm> post;
+    Stack enc, dec; Predictor dur, energy, pitch; FusedPredictors var2; Gemm dec_in, feat, tokw; std::vector<Gemm> post; fs2_config cfg;
     explicit Built(const Model& m)
         : enc(stack(m.adim, m.heads, m.eunits, m.kffn, m.layers, m.enc_pre_ln, m.enc_concat)), dec(stack(m.ddim, m.heads, m.dunits, m.kffn, m.layers, m.dec_pre_ln, m.dec_concat)),
-          dur(predictor(m.adim, m.dur_chans, m.dur_k)), energy(predictor(m.adim, m.var_chans, m.var_k)), pitch(energy), dec_in(gemm(m.adim, 1, m.ddim)), feat(gemm(m.ddim, 1, m.odim)) {
+          dur(predictor(m.adim, m.dur_chans, m.dur_k)), energy(predictor(m.adim, m.var_chans, m.var_k)), pitch(energy), dec_in(gemm(m.adim, 1, m.ddim)), feat(gemm(m.ddim, 1, m.odim * m.rf)), cfg() {
         var2.ok = m.var_chans % 128 == 0;
         var2.c0 = gemm(m.adim, m.var_k, 2 * m.var_chans); var2.c1 = gemm(m.var_chans, m.var_k, 2 * m.var_chans);
         var2.ln0g = var2.ln0b = var2.ln1g = var2.ln1b = var2.lin_w = var2.lin_b = M;
         for (int l = 0; l < m.post_layers; ++l) post.push_back(gemm(l ? m.post_chans : m.odim, m.post_k, l == m.post_layers - 1 ? m.odim : m.post_chans, true));
+        if (m.input_layer && var2.ok) tokw = gemm(m.adim, 1, 6 * m.var_chans + m.ddim);      // (load_tok_proj)
+        cfg.idim = 68; cfg.odim = m.odim; cfg.adim = m.adim; cfg.ddim = m.ddim; cfg.aheads = m.heads; cfg.var_chans = m.var_chans; cfg.postnet_layers = m.post_layers;
+        cfg.reduction_factor = m.rf; cfg.decoder_input_layer = m.input_layer; cfg.use_scaled_pos_enc = 1;
     }
-    DecIn in() const { return DecIn{&dec_in, M, M, 1.f}; }
+    DecIn in() const { return cfg.decoder_input_layer ? DecIn{&dec_in, M, M, 1.f} : DecIn(); }
 };
 const StackBufs kTokBufs{M, M, M, M, M, M, M, M, M, M, M, M, nullptr}, kFrameBufs{M, M, M, M, M, M, M, M, M, M, M, M, MB};      // (carve_tokens / carve_frames: only the frames have xs4)
 
@@ -108,16 +118,25 @@ struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch
     const char* tag;
     Options o;
     std::string* all = nullptr;
+    int nwork = -1;          // the attention work list's items (-1: att_blocks(R), one utterance's)
+    int gemm_prec = -1;      // the precision of the next emit() where it is not the call's (tok.proj under FS2_TOKPROJ_F32)
     bool steps = false;      // print every step with its kind and the plan's refusal code instead
+    bool names = false;      // print the profile names instead: every launch's, the sub-launches launch_gemm / launch_attention / run_stack add included
+    void mark(const char* name) const { if (names) printf("%s\n", name); }      // a launch that is no step of model_launches.h
     void emit(const char* stack, const Step& st) const {
         const std::string name = std::string(stack ? stack : "") + (stack ? "." : "") + st.name;
+        if (names && st.kind == StepKind::LayerNorm) printf("%s\n", name.c_str());
         if (steps && st.kind != StepKind::Gemm) printf("%s %s %s 0\n", tag, name.c_str(), st.kind == StepKind::Attention ? "attention" : "layernorm");
         if (st.kind != StepKind::Gemm) return;
         GemmArgs a = st.a;
-        call_defaults(a, M, (size_t)4 * std::min(r.Rpad, kSplitRows) * 1024, r.regime_rows);      // the call's split-K scratch (carve_tokens / carve_frames: 4 slabs) and regime
-        const GemmPlan p = plan_gemm(a, prec, o);
+        call_defaults(a, M, kpart_floats(r.Rpad), r.regime_rows);      // the call's split-K scratch (carve_tokens / carve_frames) and regime
+        const GemmPlan p = plan_gemm(a, gemm_prec >= 0 ? gemm_prec : prec, o);
         char line[256];
-        if (all) {
+        if (names) {      // launch_gemm's scopes
+            if (p.build_planes) printf("%s.planes\n", name.c_str());
+            printf("%s\n", name.c_str());
+            if (p.rows_pass) printf("%s.rows\n", name.c_str());
+        } else if (all) {
             snprintf(line, sizeof line, "%s %s ns%d nb%d bm%d mt%d k1%d ap%d epi%d ar%d res%d ks%d y%d bp%d rp%d err%d\n", name.c_str(), kernel_name(p.kernel), p.nsplit, p.nb, p.bm, p.mt,
                      (int)p.k1, p.apart, p.epi, p.arith, p.res, p.ksplit, (int)p.y, (int)p.build_planes, (int)p.rows_pass, p.err);
             *all += line;
@@ -130,12 +149,14 @@ struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch
     // the attention launch of a block as run_stack asks for it: the stack's width, heads and head dim, the call's rows and regime; the operands' lo planes lie
     // one plane behind their hi planes (carve_tokens / carve_frames)
     AttnCall attn_call(const Stack& st, const Step& s) const {
-        AttnCall c{st.Dp, st.Dp / padded_head_dim(st.dk), st.dk, prec, r.R, r.Rpad, r.regime_rows, att_blocks(r.R)};
+        AttnCall c{st.Dp, st.Dp / padded_head_dim(st.dk), st.dk, prec, r.R, r.Rpad, r.regime_rows, nwork >= 0 ? nwork : att_blocks(r.R)};
         c.qkv_rows = s.a.X != nullptr;
         c.qk_lo_dist = 4LL * r.Rpad * st.Dp; c.vt_lo_dist = 2LL * r.Rpad * st.Dp;
         return c;
     }
-    void stack(const char* name, const Stack& st, int D, const StackBufs& b, bool po) const {
+    // run_stack: the blocks' steps, the planes of the stack's input where its producer left none, after_norm behind a pre-LN stack
+    void stack(const char* name, const Stack& st, int D, const StackBufs& b, bool po, bool x0p_ready = true) const {
+        if (names && prec != kFp32 && !st.pre_ln && !x0p_ready) printf("%s.in.planes\n", name);
         for (const Layer& ly : st.layers)
             for (const Step& s : block_steps(st, ly, D, r, b, prec, terms, po, o)) {
                 emit(name, s);
@@ -143,54 +164,307 @@ struct Call {      // one fs2_encode / fs2_decode: prints a line per GEMM launch
                 const AttnPlan p = plan_attention(attn_call(st, s), o);
                 char line[96];
                 snprintf(line, sizeof line, "%s.%s %s %d %d %d\n", name, s.name, attn_name(p.kernel), p.dk, p.nsplit, (int)p.split_pass);
-                if (all) *all += line; else printf("%s %s", tag, line);
+                if (names) {      // launch_attention's scopes
+                    if (p.kernel != AttnKernel::None && p.split_pass) printf("%s.%s.split\n", name, s.name);
+                    if (p.kernel != AttnKernel::None) printf("%s.%s\n", name, s.name);
+                } else if (all) *all += line;
+                else printf("%s %s", tag, line);
             }
+        if (names && st.pre_ln) printf("%s.after_norm\n", name);
     }
     void predictor(const char* name, const Predictor& p, const void* Xp) const {
         for (size_t l = 0; l < p.conv.size(); ++l) emit(name, predictor_step(p, l, M, p.conv[0].C, r, M, M, M, prec, Xp, M));
     }
 };
 
-void encode(const Built& m, const Call& c) {
-    c.stack("enc", m.enc, m.enc.layers[0].out.N, kTokBufs, false);
-    c.predictor("dur", m.dur, c.prec != kFp32 ? M : nullptr);
+// fs2_encode without the kernels
+void encode(const Built& m, Call c, const EncodePlan& p) {
+    c.prec = p.prec; c.terms = p.ffn_terms;
+    c.mark("enc.embed");
+    c.stack("enc", m.enc, m.cfg.adim, kTokBufs, false, p.embed_planes);
+    c.predictor("dur", m.dur, p.planes ? M : nullptr);
+    c.mark("dur.post");
+    if (p.tok_proj) {
+        c.gemm_prec = p.tok_prec;
+        c.emit(nullptr, tok_proj_step(m.tokw, p.tok_n0, M, m.cfg.adim, c.r, M, M, M, M));
+    }
 }
 
-void decode(const Built& m, const Call& c) {
-    const bool pl = c.prec != kFp32;
-    const int D = m.dec_in.N;
-    if (pl && m.var2.ok && c.o.fuse_var) { for (const Step& s : fused_predictor_steps(m.var2, m.energy, m.pitch, true, M, m.dec_in.C, c.r, M, M, M, M, M, M, c.o)) c.emit(nullptr, s); }
-    else { c.predictor("energy", m.energy, pl ? M : nullptr); c.predictor("pitch", m.pitch, pl ? M : nullptr); }
-    const bool po = pl && planes_only(m.in(), m.dec, D, c.r, kFrameBufs, c.prec, c.terms, c.o);
-    c.emit(nullptr, dec_in_step(m.in(), m.dec, M, m.dec_in.C, pl ? M : nullptr, c.r, kFrameBufs, c.prec, po));
-    c.stack("dec", m.dec, D, kFrameBufs, po);
-    const bool post_pl = pl && m.post.size() > 1;
-    c.emit(nullptr, feat_out_step(m.feat, c.r, kFrameBufs, M, c.prec, post_pl));
-    Rows r2 = c.r; r2.regime_rows = 0;
-    for (int l = 0; l < (int)m.post.size(); ++l) c.emit(nullptr, postnet_step(m.post, l, m.feat.N, r2, PostBufs{M, M, M, M, M}, kFrameBufs, post_pl, c.terms, c.o));
+// fs2_decode without the kernels
+void decode(const Built& m, Call c, const DecodePlan& p, const DecodeAsk& ask) {
+    c.prec = p.prec; c.terms = p.ffn_terms;
+    const int D = m.cfg.ddim;
+    const void* hfr_planes = p.hfr_planes ? M : nullptr;
+    c.mark(p.tokproj == 3 ? "lr.index" : "lr.expand");
+    if (p.fused_var) {
+        if (p.tokproj & 1) c.mark("var.gather0");
+        for (const Step& s : fused_predictor_steps(m.var2, m.energy, m.pitch, !(p.tokproj & 1), M, m.cfg.adim, c.r, hfr_planes, M, M, M, M, M, c.o)) c.emit(nullptr, s);
+    } else {
+        if (p.need_e) c.predictor("energy", m.energy, hfr_planes);
+        if (p.need_p) c.predictor("pitch", m.pitch, hfr_planes);
+    }
+    if (p.control) c.mark("var.control");
+    if (!(p.tokproj & 2)) c.mark("var.embed");
+    if (p.tokproj & 2) c.mark("dec.in.gather");
+    else if (m.cfg.decoder_input_layer) c.emit(nullptr, dec_in_step(m.in(), m.dec, M, m.cfg.adim, hfr_planes, c.r, kFrameBufs, p.prec, p.po));
+    else c.mark("dec.in.pe");
+    c.stack("dec", m.dec, D, kFrameBufs, p.po, p.planes);
+    if (p.po && ask.dec_out) c.mark("dec.out.rows");
+    c.emit(nullptr, feat_out_step(m.feat, c.r, kFrameBufs, M, p.prec, p.post_pl));
+    const Rows r2{c.r.R * p.rf, c.r.Rpad * p.rf, nullptr, nullptr, 0};
+    for (int l = 0; l < (int)m.post.size(); ++l) c.emit(nullptr, postnet_step(m.post, l, m.cfg.odim, r2, PostBufs{M, M, M, M, M}, kFrameBufs, p.post_pl, p.ffn_terms, c.o));
+    c.mark("unpack");
 }
 
 Rows rows_of(int R, int regime) { return Rows{R, round_up(R, 128), nullptr, nullptr, regime}; }
 
 const struct { const char* name; int prec, terms; } kModes[] = {{"fp32", kFp32, 0}, {"bf16x3", kBf16x3, 0}, {"mix_mx", kBf16x3, kFfnMx}, {"mix_mx4", kBf16x3, kFfnMx4}};
 
-int model(int Rtok, int reg_tok, int Rfr, int reg_fr) {
-    const Built m{Model()};
+int mode_precision(const char* name) {      // include/fs2.h's value of a tested mode (-1: none of them)
+    const struct { const char* name; int precision; } k[] = {{"fp32", FS2_PREC_FP32}, {"bf16x3", FS2_PREC_BF16X3}, {"mix_mx", FS2_PREC_MIX_MX}, {"mix_mx4", FS2_PREC_MIX_MX4}};
+    for (const auto& m : k) if (!strcmp(m.name, name)) return m.precision;
+    return -1;
+}
+
+// A case: the options, the model's variations and what the call gives and asks for (see the head of this file).  Default: a teacher-forced forward that asks
+// for before, after, e_out and p_out (tools/forward_digest.py).
+struct Case {
+    Options o; Model m; DecodeAsk ask; bool tokp = true;
+    Case() { ask.es = ask.ps = ask.e_out = ask.p_out = ask.after = ask.before = true; }
+    bool parse(const char* text) {
+        if (!strcmp(text, "-")) return true;
+        std::string t(text);
+        for (size_t at = 0; at < t.size();) {
+            const size_t end = std::min(t.find(',', at), t.size()), eq = t.find('=', at);
+            if (eq == std::string::npos || eq > end) return false;
+            const std::string key = t.substr(at, eq - at);
+            const int v = atoi(t.substr(eq + 1, end - eq - 1).c_str());
+            if (key == "tokproj") o.tokproj = v; else if (key == "tokproj_f32") o.tokproj_f32 = v; else if (key == "fuse_var") o.fuse_var = v; else if (key == "row8") o.row8 = v;
+            else if (key == "rf") m.rf = v; else if (key == "post") m.post_layers = v;
+            else if (key == "in") { m.input_layer = v; if (!v) m.adim = m.ddim; }      // (no input layer: the decoder runs at the encoder's width)
+            else if (key == "es") ask.es = v; else if (key == "ps") ask.ps = v; else if (key == "e_out") ask.e_out = v; else if (key == "p_out") ask.p_out = v;
+            else if (key == "dec_out") ask.dec_out = v; else if (key == "after") ask.after = v; else if (key == "before") ask.before = v; else if (key == "packed") ask.after_packed = v;
+            else if (key == "ctl") ask.ctl_pitch = v; else if (key == "devlay") ask.devlay = v; else if (key == "tokp") tokp = v;
+            else return false;
+            at = end + 1;
+        }
+        return true;
+    }
+};
+
+// what the encode of a case leaves behind, as far as plan_decode reads it
+Encoded left_by(const EncodePlan& p) {
+    Encoded e;
+    e.valid = true; e.tokP = p.tok_proj ? M : nullptr; e.tokP_conv = p.tok_conv;
+    return e;
+}
+
+// one forward: fs2_encode on the token rows, fs2_decode on the frame rows (the outputs unpack_rows4 can take are given aligned; a capacity is the rows)
+void forward(const Built& m, const Case& k, int precision, Call c, const Rows& tok, const Rows& fr, int nwork_tok = -1, int nwork_fr = -1) {
+    const EncodePlan ep = plan_encode(m.cfg, k.o, precision, m.tokw.N, k.tokp && precision != FS2_PREC_FP32);
+    c.r = tok; c.nwork = nwork_tok;
+    if (!c.all) encode(m, c, ep);
+    DecodeAsk ask = k.ask;
+    ask.R = fr.R; ask.row_capacity = fr.R; ask.after_vec = ask.before_vec = true;
+    const DecodePlan dp = plan_decode(m.cfg, k.o, precision, ask, left_by(ep), m.var2.ok, m.in(), m.dec, fr, kFrameBufs);
+    c.r = fr; c.nwork = nwork_fr;
+    decode(m, c, dp, ask);
+}
+
+int model(int Rtok, int reg_tok, int Rfr, int reg_fr, const char* text) {
+    Case k;
+    if (!k.parse(text)) return 2;
+    const Built m{k.m};
     for (const auto& md : kModes) {
-        Call c{md.prec, md.terms, rows_of(Rtok, reg_tok), md.name, Options()};
-        encode(m, c);
-        c.r = rows_of(Rfr, reg_fr);
-        decode(m, c);
+        const Call c{md.prec, md.terms, Rows(), md.name, k.o};
+        forward(m, k, mode_precision(md.name), c, rows_of(Rtok, reg_tok), rows_of(Rfr, reg_fr));
         // the plan does not depend on the row capacity (device-driven layout: 15-25 % above the rows in use)
         std::string plans[3];
         const double caps[3] = {1.0, 1.15, 1.25};
         for (int i = 0; i < 3; ++i) {
-            Call k = c;
-            k.r = rows_of((int)(reg_fr * caps[i]), reg_fr); k.all = &plans[i];
-            decode(m, k);
+            Call q = c;
+            q.all = &plans[i];
+            forward(m, k, mode_precision(md.name), q, Rows(), rows_of((int)(reg_fr * caps[i]), reg_fr));
         }
         printf("%s capacity_independent %d\n", md.name, (int)(plans[0] == plans[1] && plans[0] == plans[2] && !plans[0].empty()));
     }
+    return 0;
+}
+
+// ---- the rows of a batch: layout_rule.h's walk and dealing, as layout.h's build_layout applies them on the host (per-utterance semantics)
+struct BatchRows { int R = 0, Rpad = 0, nwork = 0; };
+BatchRows rows_of_batch(const std::vector<int64_t>& len, int gap) {
+    int row = gap;
+    for (int64_t l : len) row = row_after(row_start(row), (int)l, gap);
+    BatchRows out;
+    out.R = rows_used(row); out.Rpad = rows_padded(out.R);
+    std::vector<int> order(len.size());
+    for (size_t i = 0; i < len.size(); ++i) order[i] = (int)i;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return dealt_before((int)len[x], x, (int)len[y], y); });
+    Dealer deal;
+    for (int b : order) deal.place(att_blocks((int)len[b]));
+    out.nwork = deal.items();
+    return out;
+}
+
+// the ordered profile names of one forward of the utterances given as tokens,frames
+int names(const char* block, const char* mode, const char* text, int n, char** utts) {
+    Case k;
+    const int precision = mode_precision(mode);
+    if (!k.parse(text) || precision < 0 || n < 1) return 2;
+    if (!strcmp(block, "pre_ln_concat")) k.m.enc_pre_ln = k.m.enc_concat = k.m.dec_pre_ln = k.m.dec_concat = true;
+    else if (strcmp(block, "default")) return 2;
+    const Built m{k.m};
+    std::vector<int64_t> tokens, frames;
+    int64_t total = 0, longest = 0;
+    for (int i = 0; i < n; ++i) {
+        long long t = 0, f = 0;
+        if (sscanf(utts[i], "%lld,%lld", &t, &f) != 2) return 2;
+        tokens.push_back(t); frames.push_back(f); total += f; longest = std::max<int64_t>(longest, f);
+    }
+    fs2_batch b{};
+    b.B = n; b.ilens = tokens.data(); b.precision = precision;
+    for (int64_t t : tokens) b.Tmax = std::max(b.Tmax, (int)t);
+    int p = std::max(std::max(k.m.kffn, k.m.dur_k), k.m.var_k);      // fs2_create: the zero rows between utterances are the largest conv halo of the model
+    if (k.m.post_layers > 0) p = std::max(p, k.m.post_k);
+    const int gap = std::min(kGap, std::max(kMinGap, (p - 1) / 2));
+    const BatchRows tok = rows_of_batch(tokens, gap);
+    BatchRows fr = rows_of_batch(frames, gap);
+    if (k.ask.devlay) {      // the capacities of `total` frames, the longest utterance's as the per-utterance one (fs2_row_capacity, capacity_layout)
+        fr.R = fr.Rpad = rows_padded(row_bound(total, n));
+        fr.nwork = work_capacity(fr.R, n, (int)longest);
+    }
+    Call c{0, 0, Rows(), "", k.o};
+    c.names = true;
+    forward(m, k, precision, c, Rows{tok.R, tok.Rpad, nullptr, nullptr, regime_rows_of(b, true)}, Rows{fr.R, fr.Rpad, nullptr, nullptr, regime_rows_of(b, false)}, tok.nwork, fr.nwork);
+    return 0;
+}
+
+// ---- every field of the two plans over the inputs they are functions of: `coordinates | fields`
+int decisions() {
+    const char* modes[] = {"fp32", "bf16x3", "mix_mx", "mix_mx4"};
+    const Rows fr = rows_of(896, 664);      // one utterance: the planes-only regime is there only when FS2_ROW8 forces it
+    for (const char* mode : modes)
+        for (int tokproj = 0; tokproj <= 3; ++tokproj)
+            for (int fuse = 0; fuse <= 1; ++fuse)
+                for (int row8 : {-1, 1})
+                    for (int in = 0; in <= 1; ++in)
+                        for (int rf = 1; rf <= 2; ++rf)
+                            for (int post : {0, 1, 5})
+                                for (int tokp = 0; tokp <= 1; ++tokp) {
+                                    Case k;
+                                    k.o.tokproj = tokproj; k.o.fuse_var = fuse; k.o.row8 = row8; k.m.rf = rf; k.m.post_layers = post; k.m.input_layer = in; k.tokp = tokp;
+                                    k.m.adim = k.m.ddim;      // (one width, so that a model without an input layer is the same model otherwise)
+                                    const Built m{k.m};
+                                    const int precision = mode_precision(mode);
+                                    const EncodePlan e = plan_encode(m.cfg, k.o, precision, m.tokw.N, tokp && precision != FS2_PREC_FP32);
+                                    printf("enc %s tokproj=%d fuse=%d row8=%d in=%d rf=%d post=%d tokp=%d | prec=%d ffn_terms=%d planes=%d embed_planes=%d tok_proj=%d tok_conv=%d tok_n0=%d tok_prec=%d\n",
+                                           mode, tokproj, fuse, row8, in, rf, post, tokp, e.prec, e.ffn_terms, (int)e.planes, (int)e.embed_planes, (int)e.tok_proj, (int)e.tok_conv, e.tok_n0, e.tok_prec);
+                                    for (int given = 0; given < 4; ++given)
+                                        for (int asked = 0; asked < 4; ++asked)
+                                            for (int devlay = 0; devlay <= 1; ++devlay) {
+                                                DecodeAsk a;
+                                                a.es = given & 1; a.ps = given & 2; a.e_out = asked & 1; a.p_out = asked & 2; a.after = true; a.devlay = devlay;
+                                                a.R = a.row_capacity = fr.R; a.after_vec = true;
+                                                const DecodePlan d = plan_decode(m.cfg, k.o, precision, a, left_by(e), m.var2.ok, m.in(), m.dec, fr, kFrameBufs);
+                                                printf("dec %s tokproj=%d fuse=%d row8=%d in=%d rf=%d post=%d tokp=%d es=%d ps=%d e_out=%d p_out=%d devlay=%d | prec=%d ffn_terms=%d devlay=%d planes=%d "
+                                                       "hfr_planes=%d need_e=%d need_p=%d fused_var=%d tokproj=%d control=%d po=%d mask_q=%d rf=%d post_pl=%d ep_stored=%d\n",
+                                                       mode, tokproj, fuse, row8, in, rf, post, tokp, (int)a.es, (int)a.ps, (int)a.e_out, (int)a.p_out, devlay, d.prec, d.ffn_terms, (int)d.devlay,
+                                                       (int)d.planes, (int)d.hfr_planes, (int)d.need_e, (int)d.need_p, (int)d.fused_var, d.tokproj, (int)d.control, (int)d.po, d.mask_q, d.rf,
+                                                       (int)d.post_pl, (int)d.ep_stored);
+                                            }
+                                }
+    // what the batch semantics, the control and the outputs decide: nothing above depends on them, nor they on anything above but the layout
+    const Built m{Model()};
+    for (int bits = 0; bits < 1 << 11; ++bits) {
+        DecodeAsk a;
+        a.devlay = bits & 1; a.after = bits & 2; a.before = bits & 4; a.after_packed = bits & 8; a.after_vec = bits & 16; a.before_vec = bits & 32;
+        a.compat = (bits >> 6) & 1; a.masked = (bits >> 7) & 1; a.ctl_pitch = bits & 256; a.ctl_energy = bits & 512;
+        a.row_capacity = 1024; a.R = (bits & 1024) ? 1024 : 896;
+        const DecodePlan d = plan_decode(m.cfg, Options(), FS2_PREC_BF16X3, a, Encoded(), m.var2.ok, m.in(), m.dec, fr, kFrameBufs);
+        printf("out devlay=%d after=%d before=%d packed=%d after_vec=%d before_vec=%d compat=%d masked=%d ctl_pitch=%d ctl_energy=%d rows_are_capacity=%d | control=%d mask_q=%d ep_stored=%d "
+               "packed_ovf=%d poison_after=%d poison_before=%d poison_packed=%d poison=%d\n", (int)a.devlay, (int)a.after, (int)a.before, (int)a.after_packed, (int)a.after_vec, (int)a.before_vec,
+               a.compat, a.masked, (int)a.ctl_pitch, (int)a.ctl_energy, (int)(a.R == a.row_capacity), (int)d.control, d.mask_q, (int)d.ep_stored, (int)d.packed_ovf, (int)d.poison_after,
+               (int)d.poison_before, (int)d.poison_packed, (int)d.poison());
+    }
+    return 0;
+}
+
+// ---- the refusals of the two entry points: what|err|message.  `a+b`: both conditions hold and the one the entry point tests first answers.
+constexpr int kPe = 512;      // rows of both positional tables in the cases below
+int call_refusals() {
+    static const int64_t ilens[3] = {5, 17, 33}, olens[3] = {40, 136, 264};
+    auto batch = [&] { fs2_batch b{}; b.B = 3; b.Tmax = 33; b.ilens = ilens; b.precision = FS2_PREC_BF16X3; return b; };
+    auto show = [](const char* what, const Refusal& r) { printf("%s|%d|%s\n", what, r.err, r.msg); };
+    {
+        auto io = [&] { fs2_encode_io e{}; e.batch = batch(); e.xs = reinterpret_cast<const int64_t*>(M); e.olens = reinterpret_cast<int64_t*>(M); e.workspace = M; return e; };
+        auto enc = [&](const char* what, const fs2_encode_io& e, int pe = kPe) { show(what, check_encode(e, pe)); };
+        static const int64_t zero_len[3] = {5, 0, 33}, long_len[3] = {5, 17, 34};
+        fs2_encode_io e = io(); enc("enc.accepted", e);
+        e = io(); e.batch.B = 0; enc("enc.batch_empty", e);
+        e = io(); e.batch.Tmax = 0; enc("enc.batch_tmax", e);
+        e = io(); e.batch.ilens = nullptr; e.batch.precision = 99; enc("enc.batch_ilens+precision", e);
+        e = io(); e.batch.ilens = zero_len; enc("enc.ilens_zero", e);
+        e = io(); e.batch.ilens = long_len; e.batch.precision = 99; enc("enc.ilens_long+precision", e);
+        e = io(); e.batch.precision = -1; enc("enc.precision_low", e);
+        e = io(); e.batch.precision = 7; e.batch.regime_tokens = 5; enc("enc.precision+regime", e);
+        e = io(); e.batch.regime_tokens = 5; e.xs = nullptr; enc("enc.regime_tokens_alone+xs", e);
+        e = io(); e.batch.regime_utterances = 2; enc("enc.regime_utterances_alone", e);
+        e = io(); e.batch.regime_tokens = -1; e.batch.regime_utterances = -1; enc("enc.regime_negative", e);
+        e = io(); e.batch.regime_tokens = 4528; e.batch.regime_utterances = 64; enc("enc.regime_accepted", e);
+        e = io(); e.xs = nullptr; e.duration_alpha = -1.f; enc("enc.xs+alpha", e);
+        e = io(); e.olens = nullptr; enc("enc.olens", e);
+        e = io(); e.workspace = nullptr; enc("enc.workspace", e);
+        e = io(); e.duration_alpha = -0.5f; enc("enc.alpha+pe", e, 32);
+        e = io(); enc("enc.pe", e, 32);
+        e = io(); enc("enc.pe_exact", e, 33);
+        e = io(); e.batch.Tmax = 40; e.batch.compat_padded = 1; enc("enc.pe_padded_batch", e, 39);      // every utterance is stored at Tmax rows
+    }
+    auto left = [&] { Encoded e; e.valid = true; e.B = 3; e.Tmax = 33; e.ws = M; return e; };
+    auto io = [&] { fs2_decode_io d{}; d.batch = batch(); d.olens = olens; d.Lmax = 264; d.token_workspace = M; d.workspace = M; d.after = M; return d; };
+    auto dev = [&] { fs2_decode_io d = io(); d.olens = nullptr; d.row_capacity = 1024; d.status = reinterpret_cast<int32_t*>(M); return d; };
+    auto ctl = [&] { fs2_prosody p{}; p.pitch_scale = M; p.pitch_scale_cols = 1; return p; };
+    auto dec = [&](const char* what, const fs2_decode_io& d, const fs2_prosody* p = nullptr, const Encoded* e = nullptr, int pe = kPe) {
+        const Encoded dflt = left();
+        show(what, check_decode(d, p, e ? *e : dflt, 68, pe));
+    };
+    static const int64_t bad_id[3] = {40, -1, 0}, empty[3] = {40, 0, 264}, negative[3] = {40, -2, 264};
+    const Encoded none;
+    fs2_decode_io d = io(); dec("dec.accepted", d);
+    d = dev(); dec("dec.devlay_accepted", d);
+    fs2_prosody p = ctl(); d = io(); dec("dec.ctl_accepted", d, &p);
+    p = ctl(); p.pitch_scale_cols = 33; d = io(); dec("dec.ctl_per_phoneme_accepted", d, &p);
+    p = fs2_prosody{}; p.pitch_scale_cols = 7; d = io(); dec("dec.ctl_neutral_cols_ignored", d, &p);
+    p = ctl(); p.pitch_scale_cols = 2; d = io(); d.ps = M; dec("dec.ctl_pitch_scale_cols+ps", d, &p);
+    p = ctl(); p.pitch_shift = M; p.pitch_shift_cols = 0; p.energy_scale = M; p.energy_scale_cols = 5; d = io(); dec("dec.ctl_pitch_shift_cols+energy_scale_cols", d, &p);
+    p = fs2_prosody{}; p.energy_scale = M; p.energy_scale_cols = 34; d = io(); dec("dec.ctl_energy_scale_cols", d, &p);
+    p = fs2_prosody{}; p.energy_shift = M; p.energy_shift_cols = 3; d = io(); d.es = M; dec("dec.ctl_energy_shift_cols+es", d, &p);
+    p = ctl(); p.energy_shift = M; p.energy_shift_cols = 1; d = io(); d.ps = M; d.es = M; dec("dec.ctl_ps+es", d, &p);
+    p = ctl(); d = io(); d.es = M; dec("dec.ctl_pitch_with_es_accepted", d, &p);
+    p = fs2_prosody{}; p.energy_shift = M; p.energy_shift_cols = 1; d = io(); d.es = M; d.batch.compat_padded = 1; dec("dec.ctl_es+compat", d, &p);
+    p = ctl(); d = io(); d.batch.compat_padded = 1; dec("dec.ctl_compat+no_encode", d, &p, &none);
+    d = io(); d.batch.B = 0; dec("dec.no_encode+batch", d, nullptr, &none);
+    d = io(); d.batch.B = 0; dec("dec.batch_empty", d);
+    d = io(); d.batch.precision = 99; d.batch.Tmax = 34; dec("dec.precision+pairing", d);
+    d = io(); d.batch.B = 2; dec("dec.pairing_B", d);
+    d = io(); d.batch.Tmax = 34; dec("dec.pairing_Tmax", d);
+    { Encoded e = left(); e.compat = 1; d = io(); dec("dec.pairing_compat", d, nullptr, &e); }
+    d = io(); d.token_workspace = MB + 4; d.workspace = nullptr; dec("dec.pairing_workspace+workspace", d);
+    d = io(); d.olens = nullptr; dec("dec.olens", d);
+    d = io(); d.workspace = nullptr; dec("dec.workspace", d);
+    d = io(); d.after = nullptr; dec("dec.after", d);
+    d = io(); d.after = nullptr; d.after_packed = M; dec("dec.after_packed_accepted", d);
+    d = dev(); d.status = nullptr; d.after = nullptr; dec("dec.after+status", d);
+    d = dev(); d.status = nullptr; d.Lmax = 0; dec("dec.status+Lmax", d);
+    d = dev(); d.Lmax = 0; dec("dec.devlay_Lmax", d);
+    d = dev(); d.row_capacity = (long long)INT32_MAX - 255; dec("dec.row_capacity", d);
+    d = dev(); d.row_capacity = (long long)INT32_MAX - 256; dec("dec.row_capacity_accepted", d);
+    d = io(); d.olens = bad_id; dec("dec.bad_id+empty", d);
+    d = io(); d.olens = empty; d.Lmax = 10; dec("dec.empty+Lmax", d);
+    d = io(); d.olens = negative; dec("dec.negative", d);
+    d = io(); d.Lmax = 263; dec("dec.Lmax+pe", d, nullptr, nullptr, 200);
+    d = io(); dec("dec.pe", d, nullptr, nullptr, 263);
+    d = io(); dec("dec.pe_exact", d, nullptr, nullptr, 264);
     return 0;
 }
 
@@ -207,7 +481,7 @@ int variants(int Rtok, int reg_tok, int Rfr, int reg_fr) {
             c.steps = true;
             c.stack("enc", m.enc, mm.adim, kTokBufs, false);
             c.r = rows_of(Rfr, reg_fr);
-            c.stack("dec", m.dec, mm.ddim, kFrameBufs, c.prec != kFp32 && planes_only(m.in(), m.dec, mm.ddim, c.r, kFrameBufs, c.prec, c.terms, c.o));
+            c.stack("dec", m.dec, mm.ddim, kFrameBufs, plan_decode(m.cfg, c.o, mode_precision(md.name), DecodeAsk(), Encoded(), m.var2.ok, m.in(), m.dec, c.r, kFrameBufs).po);
         }
     return 0;
 }
@@ -345,12 +619,16 @@ int attn_refusals() {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc == 6 && !strcmp(argv[1], "model")) return model(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
+    if (argc == 7 && !strcmp(argv[1], "model")) return model(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), argv[6]);
+    if (argc >= 6 && !strcmp(argv[1], "names")) return names(argv[2], argv[3], argv[4], argc - 5, argv + 5);
+    if (argc == 2 && !strcmp(argv[1], "decisions")) return decisions();
+    if (argc == 2 && !strcmp(argv[1], "call_refusals")) return call_refusals();
     if (argc == 6 && !strcmp(argv[1], "variants")) return variants(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
     if (argc == 2 && !strcmp(argv[1], "sweep")) return sweep();
     if (argc == 2 && !strcmp(argv[1], "refusals")) return refusals();
     if (argc == 2 && !strcmp(argv[1], "attn_sweep")) return attn_sweep();
     if (argc == 2 && !strcmp(argv[1], "attn_refusals")) return attn_refusals();
-    fprintf(stderr, "usage: probe model|variants Rtok regime_tok Rfr regime_fr | sweep | refusals | attn_sweep | attn_refusals\n");
+    fprintf(stderr, "usage: probe model Rtok regime_tok Rfr regime_fr case | variants Rtok regime_tok Rfr regime_fr | names block mode case tokens,frames.. | decisions | call_refusals | "
+                    "sweep | refusals | attn_sweep | attn_refusals\n");
     return 2;
 }

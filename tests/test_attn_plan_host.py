@@ -13,7 +13,7 @@ import re
 import numpy as np
 import pytest
 
-from tests.test_gemm_plan_host import ERR_UNSUPPORTED, MODES, REGIMES, ROOT, probe  # noqa: F401  (probe: the fixture)
+from tests.test_gemm_plan_host import ERR_UNSUPPORTED, MODES, REGIMES, ROOT, TRACED_CASE, probe  # noqa: F401  (probe: the fixture)
 
 HEADS = 2      # of the default model (tests/gemm_plan_probe.cpp: Model)
 
@@ -35,7 +35,7 @@ ATTN_PINNED = {
 @pytest.mark.parametrize("mode", MODES)
 def test_pinned_attention_plans(probe, regime, mode):
     got = {"enc.attn": [], "dec.attn": []}
-    for line in probe("model", *REGIMES[regime]):
+    for line in probe("model", *REGIMES[regime], TRACED_CASE):
         f = line.split()
         if f[0] == mode and f[1] in got:
             got[f[1]].append((f[2], int(f[3]), int(f[4]), int(f[5])))

@@ -1790,3 +1790,27 @@ def test_launch_sequence_is_the_parents(launch_cases, block, precision, row8):
             break
     assert got == want
     assert len(want) > 40
+
+
+@pytest.mark.parametrize("case", ["default/bf16x3/tokproj0", "default/bf16x3/tokproj1", "default/bf16x3/tokproj2", "default/mix_mx4/tokproj0", "default/mix_mx4/tokproj1",
+                                  "default/mix_mx4/tokproj2", "default/bf16x3/fuse_var0", "default/bf16x3/free_running", "default/bf16x3/pitch_control", "rf2/fp32/teacher",
+                                  "rf2/bf16x3/teacher", "default/bf16x3/device_packed"])
+def test_launch_sequence_is_the_parents_call_cases(launch_cases, case):
+    """test_launch_sequence_is_the_parents for the cases the per-call decisions (csrc/call_plan.h) depend on and its 16 do not reach: every FS2_TOKPROJ value,
+    FS2_FUSE_VAR = 0, a free-running forward, per-phoneme pitch control, reduction_factor = 2 and the device-driven layout with the packed output
+    (tools/forward_digest.py: CALL_CASES).  The names were recorded from the commit before the call plan existed (profiles/call_plan_names_parent.json)."""
+    import json
+    fd, _, inputs, models = launch_cases
+    assert sorted(fd.CALL_CASES) == sorted(test_launch_sequence_is_the_parents_call_cases.pytestmark[0].args[1])
+    which = fd.CALL_CASES[case][0]
+    if which not in models:
+        models[which] = fd.make_rf2_model() if which == "rf2" else fd.make_model(which)
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "call_plan_names_parent.json")) as f:
+        want = json.load(f)[case]
+    got = fd.call_launch_names(models[which], inputs, case)
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            print("first difference at launch %d: got %s, parent %s" % (i, g, w))
+            break
+    assert got == want
+    assert len(want) > 40
