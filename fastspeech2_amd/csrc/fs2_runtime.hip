@@ -13,6 +13,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <list>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -34,6 +35,7 @@
 #include "model_launches.h"
 #include "call_plan.h"
 #include "gemm_mx.h"
+#include "weight_plan.h"
 #include "gemm_f32.h"
 #include "griffin_lim.h"
 #include "gl_pitch.h"
@@ -664,20 +666,83 @@ __global__ void pad_heads(const float* src, int rows, int cols, int dk, int dkp,
     else dst[((size_t)(r / dk) * dkp + r % dk) * cols + c] = src[i];
 }
 
+// What build_weight reads besides the plan: the tensors of every part (w: at the first column of a concat half), the BatchNorm statistics, and the two launch
+// arguments that differ between its callers.
+struct WeightSrc {
+    const float* w[3] = {};
+    const float* bias[3] = {};
+    const float *bn_g = nullptr, *bn_b = nullptr, *bn_m = nullptr, *bn_v = nullptr;
+    float bn_eps = 1e-5f;
+    bool wb_f16 = false;      // the "split-bf16" image holds fp16 (fs2_op_conv_gemm in the fp16 arithmetic)
+};
+
+// The one executor of a weight plan (weight_plan.h): the images the plan gives bytes, from `alloc(image, bytes)` (nullptr: it has recorded the failure), filled on
+// stream s.  kw is measured here, from the source the plan names; scratch: 16 bytes for that (needed where the plan has an mx source).  Every repack kernel is
+// launched here and nowhere else.
+template <class Alloc>
+bool build_weight(hipStream_t s, const WeightAsk& a, const WeightPlan& p, const WeightSrc& src, unsigned* scratch, Alloc&& alloc, Gemm& g) {
+    g.N = p.N; g.C = a.C; g.ktaps = a.ktaps; g.Cpad = p.Cpad;
+    void* img[kWeightImages] = {};
+    for (int i = 0; i < kWeightImages; ++i)
+        if (p.bytes[i] && !(img[i] = alloc((WeightImage)i, p.bytes[i]))) return false;
+    g.w = (float*)img[kImgW]; g.wb = img[kImgWb]; g.wf = img[kImgWf]; g.wm = img[kImgWm]; g.wm4 = img[kImgWm4]; g.ws4 = (unsigned char*)img[kImgWs4]; g.bias = (float*)img[kImgBias];
+    for (int i : {kImgW, kImgWb, kImgWf})
+        if (img[i]) hipMemsetAsync(img[i], 0, p.bytes[i], s);
+    const int k = a.ktaps, Neach = a.Neach;
+    // kw from max |w| of `from` ([.][C][k], or the fp32 image with rows of ld floats: BatchNorm folded in), then the mx and mx4 images of it
+    auto mx_images = [&](const float* from, int64_t count, int ld) {
+        g.kw = fp8_scale_exponent(device_absmax(s, from, count, scratch));
+        if (g.wm)
+            hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((p.bytes[kImgWm] / 2 + 255) / 256)), dim3(256), 0, s, from, p.N, a.C, k, p.Npad, g.kw,
+                               reinterpret_cast<unsigned short*>(g.wm), ld);
+        if (g.wm4) {      // (fp4 cross terms, one scale byte per 16-channel block: preset to 127 = 2^0)
+            hipMemsetAsync(g.ws4, 127, p.bytes[kImgWs4], s);
+            hipLaunchKernelGGL(repack_weight_mx4, dim3((unsigned)((p.bytes[kImgWm4] / 4 + 255) / 256)), dim3(256), 0, s, from, p.N, a.C, k, p.Npad, g.ws4, reinterpret_cast<unsigned*>(g.wm4));
+        }
+    };
+    // (the measurement waits for the stream: from the tensor it runs first, so that the repacks below are still running while the host looks up the next layer)
+    if (p.mx_src == MxSource::Tensor) mx_images(src.w[0], (int64_t)Neach * a.C * k, 0);
+    for (int part = 0; part < a.parts; ++part) {      // (the parts are whole row ranges of the fp32 and bf16 images: each is repacked as a layer of Npad = Neach rows)
+        const int64_t tb = (int64_t)Neach * k * p.nchunks * 32, total = (int64_t)Neach * k * p.Cpad;
+        for (int f16 = 0; f16 <= 1; ++f16)
+            if (void* dst = f16 ? g.wf : g.wb)
+                hipLaunchKernelGGL(repack_weight_bf16, dim3((unsigned)((tb + 255) / 256)), dim3(256), 0, s, src.w[part], Neach, a.C, k, Neach, p.nchunks, src.bn_g, src.bn_v,
+                                   src.bn_eps, reinterpret_cast<__bf16*>(dst) + (size_t)part * Neach * k * p.nchunks * 64, f16 || src.wb_f16 ? 1 : 0, a.src_cols);
+        if (g.w)
+            hipLaunchKernelGGL(repack_weight, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src.w[part], Neach, a.C, k, Neach, p.Cpad, src.bn_g, src.bn_v, src.bn_eps,
+                               g.w + (size_t)part * Neach * k * p.Cpad, a.src_cols);
+    }
+    // (from the fp32 image just made; the layer's operand is a tanh output: |x| <= 1 is the a-priori bound of kPostKa)
+    if (p.mx_src == MxSource::Folded) mx_images(g.w, (int64_t)p.Npad * k * p.Cpad, p.Cpad);
+    if (g.bias && a.bias)
+        for (int part = 0; part < a.parts; ++part) hipMemcpyAsync(g.bias + (size_t)part * Neach, src.bias[part], Neach * sizeof(float), hipMemcpyDeviceToDevice, s);
+    else if (g.bias)
+        hipLaunchKernelGGL(bn_fold_bias, dim3((Neach + 255) / 256), dim3(256), 0, s, src.bn_g, src.bn_b, src.bn_m, src.bn_v, src.bn_eps, Neach, g.bias);
+    return true;
+}
+
 struct Loader {
     fs2_handle* h; hipStream_t s;
     std::map<std::string, const fs2_tensor_desc*> m;
     int rc = FS2_OK;
     unsigned* absmax_scratch = nullptr;
-    std::vector<fs2_tensor_desc*> synth;      // head-padded copies of projection weights (padded_tensor): descriptors + device memory, released with the loader
-    std::vector<std::string*> synth_names;
-    std::vector<void*> synth_mem;
+    // tensors of the loader's own making, looked up like the caller's (head-padded projection weights, tok.proj's stacked weight): released with the loader
+    struct Synth { fs2_tensor_desc desc; std::string name; float* mem; };
+    std::list<Synth> synth;
     ~Loader() {
         if (absmax_scratch) hipFree(absmax_scratch);
-        if (!synth_mem.empty()) hipStreamSynchronize(s);
-        for (void* p : synth_mem) hipFree(p);
-        for (auto* d : synth) delete d;
-        for (auto* n : synth_names) delete n;
+        if (!synth.empty()) hipStreamSynchronize(s);
+        for (Synth& t : synth) hipFree(t.mem);
+    }
+    // Registers `name`: a tensor of n floats of device memory, described like `like` (the caller sets the shape).  nullptr on error.
+    Synth* add_synth(const std::string& name, const fs2_tensor_desc& like, size_t n) {
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return nullptr; }
+        synth.push_back(Synth{like, name, p});
+        Synth& t = synth.back();
+        t.desc.name = t.name.c_str(); t.desc.data = p;
+        m[t.name] = &t.desc;
+        return &t;
     }
     // Registers "<name>#pad": the tensor `name` ([D, C] weight, or [D] bias when C == 0) with every head's dk rows (pad_cols: columns)
     // moved to a block of dkp, zeros in between.  Returns the new name ("" on error).
@@ -686,35 +751,41 @@ struct Loader {
         if (!d) return "";
         const int Dp = heads * dkp;
         const size_t n = C ? (pad_cols ? (size_t)D * Dp : (size_t)Dp * C) : (size_t)Dp;
-        float* p = nullptr;
-        if (hipMalloc((void**)&p, n * sizeof(float)) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return ""; }
-        synth_mem.push_back(p);
-        hipMemsetAsync(p, 0, n * sizeof(float), s);
+        Synth* t = add_synth(name + "#pad", *d, n);
+        if (!t) return "";
+        fs2_tensor_desc* nd = &t->desc;
+        hipMemsetAsync(t->mem, 0, n * sizeof(float), s);
         const int rows = pad_cols ? D : heads * dk, cols = C ? (pad_cols ? heads * dk : C) : 1;
-        hipLaunchKernelGGL(pad_heads, dim3((unsigned)(((size_t)rows * cols + 255) / 256)), dim3(256), 0, s, (const float*)d->data, rows, cols, dk, dkp, pad_cols ? 1 : 0, p);
-        auto* nd = new fs2_tensor_desc(*d);
-        auto* nn = new std::string(name + "#pad");
-        nd->name = nn->c_str(); nd->data = p;
+        hipLaunchKernelGGL(pad_heads, dim3((unsigned)(((size_t)rows * cols + 255) / 256)), dim3(256), 0, s, (const float*)d->data, rows, cols, dk, dkp, pad_cols ? 1 : 0, t->mem);
         if (C) { nd->shape[0] = pad_cols ? D : Dp; nd->shape[1] = pad_cols ? Dp : C; } else nd->shape[0] = Dp;
-        synth.push_back(nd); synth_names.push_back(nn);
-        m[*nn] = nd;
-        return *nn;
+        return t->name;
     }
-    const fs2_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) {
+    const fs2_tensor_desc* get(const std::string& name, const int64_t* shape, int ndim) {
         auto it = m.find(name);
         if (it == m.end()) { if (!rc) rc = fail(h, FS2_ERR_WEIGHT, "missing tensor %s", name.c_str()); return nullptr; }
         const fs2_tensor_desc* d = it->second;
-        bool ok = d->ndim == (int)shape.size();
-        int i = 0;
-        for (int64_t v : shape) { if (ok && d->shape[i] != v) ok = false; ++i; }
+        bool ok = d->ndim == ndim;
+        for (int i = 0; ok && i < ndim; ++i) ok = d->shape[i] == shape[i];
         if (!ok) { if (!rc) rc = fail(h, FS2_ERR_WEIGHT, "tensor %s has the wrong shape", name.c_str()); return nullptr; }
         return d;
     }
-    float* dalloc(size_t n) {
+    const fs2_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) { return get(name, shape.begin(), (int)shape.size()); }
+    const float* data(const std::string& name, const int64_t* shape, int ndim) {
+        const fs2_tensor_desc* d = get(name, shape, ndim);
+        return d ? (const float*)d->data : nullptr;
+    }
+    // the one allocation of weight memory: owned by the handle (free_weights); msg: what a failure says
+    void* take(size_t bytes, const std::string& msg) {
         void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of %zu floats failed", n); return nullptr; }
+        if (hipMalloc(&p, bytes) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "%s", msg.c_str()); return nullptr; }
         h->allocs.push_back(p);
-        return (float*)p;
+        return p;
+    }
+    float* dalloc(size_t n) { return (float*)take(std::max<size_t>(n, 1) * sizeof(float), "hipMalloc of " + std::to_string(n) + " floats failed"); }
+    void* image(WeightImage i, size_t bytes) {
+        static const char* const what[kWeightImages] = {nullptr, "bf16 weights", "the mx weight image", "the mx4 weight image", "the mx4 weight image", "fp16 weights", nullptr};
+        static_assert(kImgWb == 1 && kImgWm == 2 && kImgWm4 == 3 && kImgWs4 == 4 && kImgWf == 5, "the messages follow the images");
+        return what[i] ? take(bytes, std::string("hipMalloc of ") + what[i] + " failed") : dalloc(bytes / sizeof(float));
     }
     float* copy(const std::string& name, std::initializer_list<int64_t> shape) {
         const fs2_tensor_desc* d = get(name, shape);
@@ -738,104 +809,25 @@ struct Loader {
         }
         return p;
     }
-    // parts: weights stacked along N (q|k|v); each [n_i, C, k] (k omitted for Linear)
-    // col_off / src_cols: take columns [col_off, col_off + C) of a Linear weight stored [Neach, src_cols] (concat_linear halves)
-    Gemm gemm(std::vector<std::string> wnames, std::vector<std::string> bnames, int Neach, int C, int k, bool linear,
-              const std::string& bn_prefix = "", bool f16_image = false, int col_off = 0, int src_cols = 0, bool mx_k1 = false) {
+    // The layer `ask` describes, from the tensors named: one weight (and bias, where the ask has one) per part; bn_prefix: the BatchNorm folded in, where it has one.
+    // The plan says which images it gets and which shapes the tensors must have; the memory is the handle's.
+    Gemm gemm(const WeightAsk& ask, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames = {}, const std::string& bn_prefix = "") {
+        const WeightPlan p = plan_weight(ask);
+        WeightSrc src;
+        bool ok = true;
+        if (ask.bn) {
+            src.bn_g = data(bn_prefix + ".weight", &p.vec_len, 1); src.bn_b = data(bn_prefix + ".bias", &p.vec_len, 1);
+            src.bn_m = data(bn_prefix + ".running_mean", &p.vec_len, 1); src.bn_v = data(bn_prefix + ".running_var", &p.vec_len, 1);
+            ok = src.bn_g && src.bn_b && src.bn_m && src.bn_v;
+        }
+        for (int part = 0; ok && part < ask.parts; ++part) {
+            src.w[part] = data(wnames[part], p.w_shape, p.w_ndim);
+            if ((ok = src.w[part] != nullptr)) src.w[part] += ask.col_off;
+        }
+        for (int part = 0; ok && ask.bias && part < ask.parts; ++part) ok = (src.bias[part] = data(bnames[part], &p.vec_len, 1)) != nullptr;
+        if (ok && p.mx_src != MxSource::None && !absmax_scratch && hipMalloc((void**)&absmax_scratch, 16) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); ok = false; }
         Gemm g;
-        const int parts = (int)wnames.size();
-        g.N = Neach * parts; g.C = C; g.ktaps = k; g.Cpad = round_up(C, kBK);
-        const int Npad = round_up(g.N, 128);
-        g.w = dalloc((size_t)Npad * k * g.Cpad);
-        if (!g.w) return g;
-        hipMemsetAsync(g.w, 0, (size_t)Npad * k * g.Cpad * sizeof(float), s);
-        const float *bg = nullptr, *bb = nullptr, *bm = nullptr, *bv = nullptr;
-        if (!bn_prefix.empty()) {
-            const fs2_tensor_desc *dg = get(bn_prefix + ".weight", {Neach}), *db = get(bn_prefix + ".bias", {Neach}),
-                                  *dm = get(bn_prefix + ".running_mean", {Neach}), *dv = get(bn_prefix + ".running_var", {Neach});
-            if (!dg || !db || !dm || !dv) return g;
-            bg = (const float*)dg->data; bb = (const float*)db->data; bm = (const float*)dm->data; bv = (const float*)dv->data;
-        }
-        const int nchunks = g.Cpad / 32;
-        const size_t wb_elems = (size_t)Npad * k * nchunks * 64;
-        {
-            void* pb = nullptr;
-            if (hipMalloc(&pb, wb_elems * 2) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of bf16 weights failed"); return g; }
-            h->allocs.push_back(pb);
-            g.wb = pb;
-            hipMemsetAsync(pb, 0, wb_elems * 2, s);
-        }
-        if (((f16_image && k > 1 && !linear) || (mx_k1 && k == 1 && !src_cols)) && parts == 1 && g.N % 128 == 0 && C % 128 == 0 && bn_prefix.empty()) {      // "mx" mode: its weight image (gemm_mx.h)
-            const fs2_tensor_desc* d = (k == 1 && linear) ? get(wnames[0], {Neach, C}) : get(wnames[0], {Neach, C, k});
-            if (!d) return g;
-            if (!absmax_scratch && hipMalloc((void**)&absmax_scratch, 16) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return g; }
-            g.kw = fp8_scale_exponent(device_absmax(s, (const float*)d->data, (int64_t)Neach * C * k, absmax_scratch));
-            const size_t bytes = mx_image_bytes(Npad, C, k);
-            void* pm = nullptr;
-            if (hipMalloc(&pm, bytes) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of the mx weight image failed"); return g; }
-            h->allocs.push_back(pm);
-            g.wm = pm;
-            hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((bytes / 2 + 255) / 256)), dim3(256), 0, s, (const float*)d->data, g.N, C, k, Npad, g.kw,
-                               reinterpret_cast<unsigned short*>(pm));
-            if (k > 1) {      // the mx4 image of the same convolution (fp4 cross terms, one scale byte per output channel)
-                const size_t b4 = mx4_image_bytes(Npad, C, k), bs = mx4_scale_image_bytes(Npad, C, k);
-                void *p4 = nullptr, *ps = nullptr;
-                if (hipMalloc(&p4, b4) != hipSuccess || hipMalloc(&ps, bs) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of the mx4 weight image failed"); return g; }
-                h->allocs.push_back(p4); h->allocs.push_back(ps);
-                g.wm4 = p4; g.ws4 = reinterpret_cast<unsigned char*>(ps);
-                hipMemsetAsync(ps, 127, bs, s);
-                hipLaunchKernelGGL(repack_weight_mx4, dim3((unsigned)((b4 / 4 + 255) / 256)), dim3(256), 0, s, (const float*)d->data, g.N, C, k, Npad, g.ws4,
-                                   reinterpret_cast<unsigned*>(p4));
-            }
-        }
-        if (f16_image) {
-            void* pf = nullptr;
-            if (hipMalloc(&pf, wb_elems * 2) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of fp16 weights failed"); return g; }
-            h->allocs.push_back(pf);
-            g.wf = pf;
-            hipMemsetAsync(pf, 0, wb_elems * 2, s);
-        }
-        for (int p = 0; p < parts; ++p) {
-            const fs2_tensor_desc* d = src_cols ? get(wnames[p], {Neach, src_cols}) : (linear ? get(wnames[p], {Neach, C}) : get(wnames[p], {Neach, C, k}));
-            if (!d) return g;
-            const float* wsrc = (const float*)d->data + col_off;
-            {
-                const int64_t tb = (int64_t)Neach * k * nchunks * 32;
-                hipLaunchKernelGGL(repack_weight_bf16, dim3((unsigned)((tb + 255) / 256)), dim3(256), 0, s, wsrc, Neach, C, k,
-                                   Neach, nchunks, bg, bv, 1e-5f, reinterpret_cast<__bf16*>(g.wb) + (size_t)p * Neach * k * nchunks * 64, 0, src_cols);
-                if (g.wf)
-                    hipLaunchKernelGGL(repack_weight_bf16, dim3((unsigned)((tb + 255) / 256)), dim3(256), 0, s, wsrc, Neach, C, k,
-                                       Neach, nchunks, bg, bv, 1e-5f, reinterpret_cast<__bf16*>(g.wf) + (size_t)p * Neach * k * nchunks * 64, 1, src_cols);
-            }
-            const int64_t total = (int64_t)Neach * k * g.Cpad;
-            hipLaunchKernelGGL(repack_weight, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wsrc, Neach, C, k,
-                               Neach, g.Cpad, bg, bv, 1e-5f, g.w + (size_t)p * Neach * k * g.Cpad, src_cols);
-        }
-        if (!bn_prefix.empty() && k > 1 && parts == 1 && g.N % 128 == 0 && C % 128 == 0) {
-            // mx image of a BatchNorm-folded convolution (the Postnet's 512 -> 512 layers), from the library's own folded fp32 image; its operand is a tanh output:
-            // |x| <= 1 is the a-priori bound of the static activation scale (kPostKa)
-            if (!absmax_scratch && hipMalloc((void**)&absmax_scratch, 16) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return g; }
-            g.kw = fp8_scale_exponent(device_absmax(s, g.w, (int64_t)Npad * k * g.Cpad, absmax_scratch));
-            const size_t bytes = mx_image_bytes(Npad, C, k);
-            void* pm = nullptr;
-            if (hipMalloc(&pm, bytes) != hipSuccess) { if (!rc) rc = fail(h, FS2_ERR_HIP, "hipMalloc of the mx weight image failed"); return g; }
-            h->allocs.push_back(pm);
-            g.wm = pm;
-            hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((bytes / 2 + 255) / 256)), dim3(256), 0, s, g.w, g.N, C, k, Npad, g.kw, reinterpret_cast<unsigned short*>(pm), g.Cpad);
-        }
-        if (!bnames.empty()) {
-            g.bias = dalloc(g.N);
-            if (!g.bias) return g;
-            for (int p = 0; p < parts; ++p) {
-                const fs2_tensor_desc* d = get(bnames[p], {Neach});
-                if (!d) return g;
-                hipMemcpyAsync(g.bias + (size_t)p * Neach, d->data, Neach * sizeof(float), hipMemcpyDeviceToDevice, s);
-            }
-        } else if (bg) {
-            g.bias = dalloc(g.N);
-            if (!g.bias) return g;
-            hipLaunchKernelGGL(bn_fold_bias, dim3((Neach + 255) / 256), dim3(256), 0, s, bg, bb, bm, bv, 1e-5f, Neach, g.bias);
-        }
+        if (ok) build_weight(s, ask, p, src, absmax_scratch, [this](WeightImage i, size_t bytes) { return image(i, bytes); }, g);
         return g;
     }
 };
@@ -852,9 +844,9 @@ void load_stack(Loader& L, Stack& st, const std::string& pre, int nlayers, int D
         const std::string p = pre + ".encoders_." + std::to_string(i);
         Layer& ly = st.layers[i];
         if (st.Dp == D) {
-            ly.qkv = L.gemm({p + ".self_attn.linear_q.weight", p + ".self_attn.linear_k.weight", p + ".self_attn.linear_v.weight"},
-                            {p + ".self_attn.linear_q.bias", p + ".self_attn.linear_k.bias", p + ".self_attn.linear_v.bias"}, D, D, 1, true);
-            ly.out = L.gemm({p + ".self_attn.linear_out.weight"}, {p + ".self_attn.linear_out.bias"}, D, D, 1, true);
+            ly.qkv = L.gemm(ask_qkv(D, D), {p + ".self_attn.linear_q.weight", p + ".self_attn.linear_k.weight", p + ".self_attn.linear_v.weight"},
+                            {p + ".self_attn.linear_q.bias", p + ".self_attn.linear_k.bias", p + ".self_attn.linear_v.bias"});
+            ly.out = L.gemm(ask_attn_out(D, D), {p + ".self_attn.linear_out.weight"}, {p + ".self_attn.linear_out.bias"});
         } else {      // head dim padded to a kernel size: zero rows in W_q / W_k / W_v (and their biases), zero columns in W_out
             std::vector<std::string> wn, bn;
             for (const char* t : {"q", "k", "v"}) {
@@ -863,32 +855,26 @@ void load_stack(Loader& L, Stack& st, const std::string& pre, int nlayers, int D
             }
             const std::string wo = L.padded_tensor(p + ".self_attn.linear_out.weight", heads, st.dk, dkp, D, D, true);
             if (L.rc) return;
-            ly.qkv = L.gemm(wn, bn, st.Dp, D, 1, true);
-            ly.out = L.gemm({wo}, {p + ".self_attn.linear_out.bias"}, D, st.Dp, 1, true);
+            ly.qkv = L.gemm(ask_qkv(D, st.Dp), wn, bn);
+            ly.out = L.gemm(ask_attn_out(D, st.Dp), {wo}, {p + ".self_attn.linear_out.bias"});
         }
-        ly.w1 = L.gemm({p + ".feed_forward.w_1.weight"}, {p + ".feed_forward.w_1.bias"}, units, D, k, L.h->cfg.ffn_kernel == 1 && L.m.count(p + ".feed_forward.w_1.weight") && L.m[p + ".feed_forward.w_1.weight"]->ndim == 2,
-                        "", /*f16_image=*/k > 1);
-        {
-            const bool lin2 = L.m.count(p + ".feed_forward.w_2.weight") && L.m[p + ".feed_forward.w_2.weight"]->ndim == 2;
-            // (mx image of w_2 where the one-wave-per-SIMD row kernel exists for this width: gemm_row4.h is instantiated for N = 384)
-            ly.w2 = L.gemm({p + ".feed_forward.w_2.weight"}, {p + ".feed_forward.w_2.bias"}, D, units, 1, lin2, "", false, 0, 0, /*mx_k1=*/k > 1 && D == 384);
-        }
+        // (a Linear FFN hands in 2-d tensors, a Conv1d one 3-d tensors even for one tap)
+        auto two_d = [&](const std::string& name) { auto it = L.m.find(name); return it != L.m.end() && it->second->ndim == 2; };
+        const WeightAsk w1 = ask_ffn_w1(D, units, k, k == 1 && two_d(p + ".feed_forward.w_1.weight"));
+        ly.w1 = L.gemm(w1, {p + ".feed_forward.w_1.weight"}, {p + ".feed_forward.w_1.bias"});
+        ly.w2 = L.gemm(ask_ffn_w2(w1, two_d(p + ".feed_forward.w_2.weight")), {p + ".feed_forward.w_2.weight"}, {p + ".feed_forward.w_2.bias"});
         if (concat) {
-            ly.cat_x = L.gemm({p + ".concat_linear.weight"}, {p + ".concat_linear.bias"}, D, D, 1, true, "", false, /*col_off=*/0, /*src_cols=*/2 * D);
-            ly.cat_a = L.gemm({p + ".concat_linear.weight"}, {}, D, D, 1, true, "", false, /*col_off=*/D, /*src_cols=*/2 * D);
+            ly.cat_x = L.gemm(ask_concat_half(D, 0), {p + ".concat_linear.weight"}, {p + ".concat_linear.bias"});
+            ly.cat_a = L.gemm(ask_concat_half(D, 1), {p + ".concat_linear.weight"});
         }
         ly.ln1g = L.copy(p + ".norm1.weight", {D}); ly.ln1b = L.copy(p + ".norm1.bias", {D});
-        if (ly.w1.wm && ly.ln1g && ly.ln1b && L.absmax_scratch) {      // a-priori bound of the LayerNorm output that feeds the FFN conv
+        if (ly.w1.wm && ly.ln1g && ly.ln1b) {      // a-priori bound of the LayerNorm output that feeds the FFN conv
             const float gm = device_absmax(L.s, ly.ln1g, D, L.absmax_scratch), bm = device_absmax(L.s, ly.ln1b, D, L.absmax_scratch);
             const float xmax = std::sqrt((float)D) * gm + bm;
             ly.ka = fp8_scale_exponent(xmax);
-            if (ly.w2.wm) {      // the hidden layer's bound: l1 norms of w_1's rows (the fp32 tensor the caller handed in is still there during the load)
-                const fs2_tensor_desc* dw = L.m.count(p + ".feed_forward.w_1.weight") ? L.m[p + ".feed_forward.w_1.weight"] : nullptr;
-                if (dw) ly.kh = fp8_scale_exponent(device_row_l1_bound(L.s, (const float*)dw->data, ly.w1.bias, units, D * k, xmax, L.absmax_scratch));
-                else ly.w2.wm = nullptr;
-            }
+            // the hidden layer's bound: l1 norms of w_1's rows (the fp32 tensor the caller handed in is still there during the load)
+            if (ly.w2.wm) ly.kh = fp8_scale_exponent(device_row_l1_bound(L.s, (const float*)L.m[p + ".feed_forward.w_1.weight"]->data, ly.w1.bias, units, D * k, xmax, L.absmax_scratch));
         }
-        else ly.w2.wm = nullptr;
         ly.ln2g = L.copy(p + ".norm2.weight", {D}); ly.ln2b = L.copy(p + ".norm2.bias", {D});
     }
     auto it = L.m.find(pe_pre + ".pe");
@@ -905,7 +891,7 @@ void load_predictor(Loader& L, Predictor& p, const std::string& pre, int nlayers
     p.conv.clear(); p.lng.clear(); p.lnb.clear();
     for (int l = 0; l < nlayers; ++l) {
         const std::string c = pre + ".conv." + std::to_string(l);
-        p.conv.push_back(L.gemm({c + ".0.weight"}, {c + ".0.bias"}, chans, l == 0 ? idim : chans, k, false));
+        p.conv.push_back(L.gemm(ask_predictor_conv(l == 0 ? idim : chans, chans, k), {c + ".0.weight"}, {c + ".0.bias"}));
         p.lng.push_back(L.copy(c + ".2.layer_norm.weight", {chans}));
         p.lnb.push_back(L.copy(c + ".2.layer_norm.bias", {chans}));
     }
@@ -931,19 +917,15 @@ void load_tok_proj(Loader& L, fs2_handle* h) {
     const fs2_tensor_desc* wsrc[2] = {L.get("energy_predictor.predictor.conv.0.0.weight", {ch, c.adim, 3}), L.get("pitch_predictor.predictor.conv.0.0.weight", {ch, c.adim, 3})};
     const fs2_tensor_desc* win = L.get("decoder.embed.0.weight", {c.ddim, c.adim});
     if (!wsrc[0] || !wsrc[1] || !win) return;
-    float* stk = nullptr;
-    if (hipMalloc((void**)&stk, (size_t)Nt * c.adim * sizeof(float)) != hipSuccess) { if (!L.rc) L.rc = fail(h, FS2_ERR_HIP, "hipMalloc failed"); return; }
-    L.synth_mem.push_back(stk);
+    Loader::Synth* t = L.add_synth("tok_proj#stack", *win, (size_t)Nt * c.adim);
+    if (!t) return;
+    t->desc.ndim = 2; t->desc.shape[0] = Nt; t->desc.shape[1] = c.adim;
+    float* stk = t->mem;
     for (int tap = 0; tap < 3; ++tap)
         for (int g = 0; g < 2; ++g)
             hipLaunchKernelGGL(conv_tap_rows, dim3((ch * c.adim + 255) / 256), dim3(256), 0, s, (const float*)wsrc[g]->data, ch, c.adim, 3, tap, stk + (size_t)(tap * 2 + g) * ch * c.adim);
     hipMemcpyAsync(stk + (size_t)6 * ch * c.adim, win->data, (size_t)c.ddim * c.adim * sizeof(float), hipMemcpyDeviceToDevice, s);
-    auto* nd = new fs2_tensor_desc(*win);
-    auto* nn = new std::string("tok_proj#stack");
-    nd->name = nn->c_str(); nd->data = stk; nd->ndim = 2; nd->shape[0] = Nt; nd->shape[1] = c.adim;
-    L.synth.push_back(nd); L.synth_names.push_back(nn);
-    L.m[*nn] = nd;
-    h->tokw = L.gemm({*nn}, {}, Nt, c.adim, 1, true);
+    h->tokw = L.gemm(ask_tok_proj(c.adim, Nt), {t->name});
     h->TPd = L.dalloc((size_t)c.n_bins * c.ddim);
     h->TEd = L.dalloc((size_t)c.n_bins * c.ddim);
     if (L.rc || !h->TPd || !h->TEd || !h->Te || !h->Tp) { h->tokw = Gemm(); return; }
@@ -1280,8 +1262,8 @@ int fs2_load_weights(fs2_handle* h, const fs2_tensor_desc* t, int32_t n, void* s
     if (c.var_layers == 2 && c.var_chans % 128 == 0 && c.adim % 32 == 0) {
         const std::string e = "energy_predictor.predictor", q = "pitch_predictor.predictor";
         FusedPredictors& v = h->var2;
-        v.c0 = L.gemm({e + ".conv.0.0.weight", q + ".conv.0.0.weight"}, {e + ".conv.0.0.bias", q + ".conv.0.0.bias"}, c.var_chans, c.adim, c.var_kernel, false);
-        v.c1 = L.gemm({e + ".conv.1.0.weight", q + ".conv.1.0.weight"}, {e + ".conv.1.0.bias", q + ".conv.1.0.bias"}, c.var_chans, c.var_chans, c.var_kernel, false);
+        v.c0 = L.gemm(ask_fused_predictor_conv(c.adim, c.var_chans, c.var_kernel), {e + ".conv.0.0.weight", q + ".conv.0.0.weight"}, {e + ".conv.0.0.bias", q + ".conv.0.0.bias"});
+        v.c1 = L.gemm(ask_fused_predictor_conv(c.var_chans, c.var_chans, c.var_kernel), {e + ".conv.1.0.weight", q + ".conv.1.0.weight"}, {e + ".conv.1.0.bias", q + ".conv.1.0.bias"});
         v.ln0g = L.copy2(e + ".conv.0.2.layer_norm.weight", q + ".conv.0.2.layer_norm.weight", {c.var_chans});
         v.ln0b = L.copy2(e + ".conv.0.2.layer_norm.bias", q + ".conv.0.2.layer_norm.bias", {c.var_chans});
         v.ln1g = L.copy2(e + ".conv.1.2.layer_norm.weight", q + ".conv.1.2.layer_norm.weight", {c.var_chans});
@@ -1304,19 +1286,19 @@ int fs2_load_weights(fs2_handle* h, const fs2_tensor_desc* t, int32_t n, void* s
         }
     }
     if (c.decoder_input_layer) {
-        h->dec_in = L.gemm({"decoder.embed.0.weight"}, {"decoder.embed.0.bias"}, c.ddim, c.adim, 1, true);
+        h->dec_in = L.gemm(ask_dec_in(c.adim, c.ddim), {"decoder.embed.0.weight"}, {"decoder.embed.0.bias"});
         h->dec_in_lng = L.copy("decoder.embed.1.weight", {c.ddim});
         h->dec_in_lnb = L.copy("decoder.embed.1.bias", {c.ddim});
     }
     h->tokw = Gemm(); h->TEd = h->TPd = nullptr;
     if (tok_proj_cols(c) && h->var2.ok && !L.rc) load_tok_proj(L, h);
-    h->feat = L.gemm({"feat_out.weight"}, {"feat_out.bias"}, c.odim * std::max(c.reduction_factor, 1), c.ddim, 1, true);
+    h->feat = L.gemm(ask_feat_out(c.ddim, c.odim * std::max(c.reduction_factor, 1)), {"feat_out.weight"}, {"feat_out.bias"});
     h->post.clear();
     for (int l = 0; l < c.postnet_layers; ++l) {
         const std::string p = "postnet.postnet." + std::to_string(l);
         const int ic = (l == 0) ? c.odim : c.postnet_chans;
         const int oc = (l == c.postnet_layers - 1) ? c.odim : c.postnet_chans;
-        h->post.push_back(L.gemm({p + ".0.weight"}, {}, oc, ic, c.postnet_filts, false, c.use_batch_norm ? p + ".1" : std::string()));
+        h->post.push_back(L.gemm(ask_postnet(ic, oc, c.postnet_filts, c.use_batch_norm != 0), {p + ".0.weight"}, {}, p + ".1"));
     }
     if (L.rc) { free_weights(h); return L.rc; }
     HIP_TRY(h, hipGetLastError());
@@ -1565,26 +1547,22 @@ int fs2_op_conv_gemm(void* stream, const fs2_op_gemm_args* o) {
     const bool mx = o->precision == FS2_PREC_MIX_MX || o->precision == FS2_PREC_MIX_MX4;   // THIS operator in the fp16 + block-scaled-fp8 arithmetic (convolutions, C % 128 == 0; the fp4 form exists inside the model only: its operand comes with row scales from a LayerNorm epilogue)
     const int f16t = mx ? 1 : ffn_f16_terms(o->precision);      // mixed modes: THIS operator on fp16 operands with 2 / 1 MFMAs per fragment pair
     hipStream_t s = (hipStream_t)stream;
-    Gemm g; g.N = o->N; g.C = o->C; g.ktaps = o->ktaps; g.Cpad = round_up(o->C, kBK);
-    const int Npad = round_up(o->N, 128);
-    const int nchunks = g.Cpad / 32;
-    const size_t wn = (size_t)Npad * o->ktaps * g.Cpad;
+    const WeightAsk ask = ask_conv_op(o->N, o->C, o->ktaps, mx);
+    const WeightPlan wp = plan_weight(ask);
+    if (mx && !wp.has(kImgWm)) return fail(nullptr, FS2_ERR_UNSUPPORTED, "the mx arithmetic needs a convolution with C %% 128 == 0 and N %% 128 == 0");
     DevTmp tmp(s);
-    OP_TRY(tmp.alloc((void**)&g.w, wn * sizeof(float)));
-    OP_TRY(tmp.alloc((void**)&g.wb, wn * 4));
+    unsigned* scr = nullptr;      // (device_absmax)
+    if (mx) OP_TRY(tmp.alloc((void**)&scr, 16));
+    WeightSrc src;
+    src.w[0] = o->w; src.bn_eps = 0.f; src.wb_f16 = f16t != 0;
+    Gemm g;
+    hipError_t werr = hipSuccess;
+    if (!build_weight(s, ask, wp, src, scr, [&](WeightImage, size_t bytes) { void* p = nullptr; werr = tmp.alloc(&p, bytes); return p; }, g)) OP_TRY(werr);
     float* scratch = nullptr;
     OP_TRY(tmp.alloc((void**)&scratch, (size_t)o->R * o->N * sizeof(float)));
     void* xps = nullptr;          // planes of x for the bf16 modes (gemm_planes.h)
     if (o->precision != FS2_PREC_FP32) OP_TRY(tmp.alloc((void**)&xps, (size_t)o->R * g.Cpad * sizeof(float)));
     int* rp = nullptr;
-    hipMemsetAsync(g.w, 0, wn * sizeof(float), s);
-    hipMemsetAsync(g.wb, 0, wn * 4, s);
-    const int64_t total = (int64_t)o->N * o->ktaps * g.Cpad;
-    hipLaunchKernelGGL(repack_weight, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, o->w, o->N, o->C, o->ktaps, o->N, g.Cpad,
-                       (const float*)nullptr, (const float*)nullptr, 0.f, g.w);
-    const int64_t tb = (int64_t)o->N * o->ktaps * nchunks * 32;
-    hipLaunchKernelGGL(repack_weight_bf16, dim3((unsigned)((tb + 255) / 256)), dim3(256), 0, s, o->w, o->N, o->C, o->ktaps, o->N, nchunks,
-                       (const float*)nullptr, (const float*)nullptr, 0.f, reinterpret_cast<__bf16*>(g.wb), f16t ? 1 : 0);
     g.bias = const_cast<float*>(o->bias);
     GemmArgs a = gemm_args(g, o->x, o->C, o->R, nullptr, o->y, o->N);
     a.scratch = scratch;
@@ -1601,17 +1579,9 @@ int fs2_op_conv_gemm(void* stream, const fs2_op_gemm_args* o) {
     a.act_post = o->act_post; a.dot_w = o->dot_w; a.dot_b = o->dot_b; a.dot_out = o->dot_out;
     a.xp_scratch = xps;
     a.f16_terms = mx ? 0 : f16t;
-    if (mx) {
-        if (o->ktaps < 3 || Npad != o->N || o->C % 128 != 0) return fail(nullptr, FS2_ERR_UNSUPPORTED, "the mx arithmetic needs a convolution with C %% 128 == 0 and N %% 128 == 0");
-        unsigned* scr = nullptr;
-        OP_TRY(tmp.alloc((void**)&scr, 16));
+    if (mx) {      // (the activation scale is measured from x itself: the operator has no LayerNorm to bound it)
         const int ka = fp8_scale_exponent(device_absmax(s, o->x, (int64_t)o->R * o->C, scr));
-        const int kw = fp8_scale_exponent(device_absmax(s, o->w, (int64_t)o->N * o->C * o->ktaps, scr));
-        void* wm = nullptr;
-        const size_t bytes = mx_image_bytes(Npad, o->C, o->ktaps);
-        OP_TRY(tmp.alloc(&wm, bytes));
-        hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((bytes / 2 + 255) / 256)), dim3(256), 0, s, o->w, o->N, o->C, o->ktaps, Npad, kw, reinterpret_cast<unsigned short*>(wm));
-        a.mx = 1; a.Wb = wm; a.yp_scale = exp2f((float)ka); a.mx_scale = scale_byte4(127 - ka - 11); a.mx_scale_b = scale_byte4(127 - kw);
+        a.mx = 1; a.Wb = g.wm; a.yp_scale = exp2f((float)ka); a.mx_scale = scale_byte4(127 - ka - 11); a.mx_scale_b = scale_byte4(127 - g.kw);
     }
     return launch_gemm(nullptr, s, "op.conv_gemm", a, base_precision(o->precision));      // (tmp drains the stream and frees)
 }
@@ -1631,8 +1601,8 @@ int fs2_op_launch_gemm(void* stream, const void* gemm_args, uint32_t args_size, 
     return launch_gemm(nullptr, (hipStream_t)stream, "op.launch_gemm", a, precision);
 }
 
-// Test hook (include/fs2.h): the weight repack of the mixed modes as fs2_load_weights runs it (make_gemm above: kw from max |w|, the scale image preset to
-// 127), into the caller's buffers -- no kernel instantiation of its own.
+// Test hook (include/fs2.h): the weight repack of the mixed modes as fs2_load_weights runs it -- build_weight, the loader's executor: kw from max |w|, the scale
+// image preset to 127 -- on the plan of that one image, into the caller's buffers.
 int fs2_op_repack_weight(void* stream, const float* w, int32_t N, int32_t C, int32_t ktaps, int32_t format, void* image, size_t image_bytes,
                          void* scale_image, size_t scale_bytes, int32_t* kw_out) {
     if (!w || !image || !kw_out) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: null argument");
@@ -1640,22 +1610,19 @@ int fs2_op_repack_weight(void* stream, const float* w, int32_t N, int32_t C, int
     if (N <= 0 || N % 128 != 0 || C <= 0 || C % 128 != 0 || ktaps < 1 || ktaps % 2 == 0 || ktaps - 1 > kMaxHalo)
         return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: needs N %% 128 == 0, C %% 128 == 0 and an odd kernel size up to %d (N %d, C %d, k %d)", kMaxHalo + 1, N, C, ktaps);
     const bool mx4 = format == FS2_REPACK_MX4;
-    const size_t bytes = mx4 ? mx4_image_bytes(N, C, ktaps) : mx_image_bytes(N, C, ktaps), sbytes = mx4 ? mx4_scale_image_bytes(N, C, ktaps) : 0;
+    const WeightPlan wp = plan_image_alone(N, C, ktaps, mx4);
+    const size_t bytes = wp.bytes[mx4 ? kImgWm4 : kImgWm], sbytes = wp.bytes[kImgWs4];
     if (image_bytes != bytes) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: image of %zu bytes, the format takes %zu", image_bytes, bytes);
     if (mx4 && (!scale_image || scale_bytes != sbytes)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_repack_weight: scale image of %zu bytes, the format takes %zu", scale_image ? scale_bytes : (size_t)0, sbytes);
     hipStream_t s = (hipStream_t)stream;
     DevTmp tmp(s);
     unsigned* scr = nullptr;
     OP_TRY(tmp.alloc((void**)&scr, 16));
-    const int kw = fp8_scale_exponent(device_absmax(s, w, (int64_t)N * C * ktaps, scr));
-    *kw_out = kw;
-    if (mx4) {
-        OP_TRY(hipMemsetAsync(scale_image, 127, sbytes, s));
-        hipLaunchKernelGGL(repack_weight_mx4, dim3((unsigned)((bytes / 4 + 255) / 256)), dim3(256), 0, s, w, N, C, ktaps, N, reinterpret_cast<unsigned char*>(scale_image),
-                           reinterpret_cast<unsigned*>(image));
-    } else {
-        hipLaunchKernelGGL(repack_weight_mx, dim3((unsigned)((bytes / 2 + 255) / 256)), dim3(256), 0, s, w, N, C, ktaps, N, kw, reinterpret_cast<unsigned short*>(image));
-    }
+    WeightSrc src;
+    src.w[0] = w;
+    Gemm g;
+    build_weight(s, ask_conv_op(N, C, ktaps, true), wp, src, scr, [&](WeightImage i, size_t) { return i == kImgWs4 ? scale_image : image; }, g);
+    *kw_out = g.kw;
     OP_TRY(hipGetLastError());
     OP_TRY(hipStreamSynchronize(s));
     return FS2_OK;

@@ -26,11 +26,9 @@
 // Any odd kernel size up to 17 taps, C % 128 == 0, N % 128 == 0.
 #pragma once
 #include "gemm_planes.h"
+#include "weight_plan.h"      // the sizes of the images: mx_image_bytes, mx4_image_bytes, mx4_scale_image_bytes
 
 namespace fs2 {
-
-// bytes of the mx weight image: Npad rows x (C / 32 units) x ktaps x 128 B  (= the split-bf16 image's size)
-__host__ __device__ inline size_t mx_image_bytes(int Npad, int C, int ktaps) { return (size_t)Npad * (C / 32) * ktaps * 128; }
 
 // weights [N][ldw or C][k] fp32 -> mx image [Npad][unit][tap][128 B]; kw: exponent of the static weight scale (|w| 2^kw <= 448).
 // repacked_ld > 0: the source is the library's own fp32 image [Npad][k][repacked_ld] (repack_weight: BatchNorm already folded in -- the Postnet's convolutions).
@@ -67,13 +65,7 @@ __global__ void repack_weight_mx(const float* w, int N, int C, int k, int Npad, 
 }
 
 // ---- mx4 (gemm_planes.h: ARITH = 3; precision mode mix_mx4): the weight image with both cross terms in e2m1 and ONE scale per output channel.
-// units per (n, tap): C/64 of fp16 channels, then C/128 cross units (layout: gemm_planes.h)
-__host__ __device__ inline size_t mx4_image_bytes(int Npad, int C, int ktaps) { return (size_t)Npad * (C / 64 + C / 128) * ktaps * 128; }
-
-// bytes of the weight scale image: per (N tile of 128 output channels, cross unit, tap) 1 KB = [g = 0 .. 3][n = 0 .. 127][2]: byte 0 = the E8M0 scale of the
-// 16-byte slot g of that weight row (16 channels, both terms: the block lane (n, g) hands the first scaled MFMA of a cross-unit step), byte 1 = of slot 4 + g
-// (the second MFMA's).  One LDS-DMA piece per step; a lane's four output channels are eight contiguous bytes.
-__host__ __device__ inline size_t mx4_scale_image_bytes(int Npad, int C, int ktaps) { return (size_t)(Npad / 128) * (C / 128) * ktaps * 1024; }
+// units per (n, tap): C/64 of fp16 channels, then C/128 cross units (layout: gemm_planes.h); the scale image: weight_plan.h, mx4_scale_image_bytes
 
 // weights [N][C][k] fp32 -> mx4 image [Npad][unit][tap][128 B] + its scale image; one 4-byte word (four channels of one part) per thread.
 // The scale of a 16-channel block (one 16-byte slot: four consecutive threads) follows the OCP rule from the block's own largest |fp16(w)|: a weight

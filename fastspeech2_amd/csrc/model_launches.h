@@ -19,14 +19,14 @@ namespace fs2 {
 // The mixed precisions of include/fs2.h (fs2_runtime.hip static_asserts that they agree; kPlanFp32 / kPlanBf16x3 are gemm_plan.h's).
 constexpr int kPrecMixF16x2 = 3, kPrecMixF16x1 = 4, kPrecMixMx = 5, kPrecMixMx4 = 6;
 
-struct Gemm {          // one repacked Linear / Conv1d
+struct Gemm {          // one repacked Linear / Conv1d; which images it holds: weight_plan.h
     float* w = nullptr;      // [Npad][ktaps][Cpad]
     void* wb = nullptr;      // split-bf16 image [Npad][ktaps][Cpad/32][hi 32 | lo 32]
     void* wf = nullptr;      // the same image in fp16 (FFN w_1 only): operand of the two- / one-term arithmetic modes
     void* wm = nullptr;      // weight image of the "mx" mode (gemm_mx.h; FFN w_1 convolutions with C % 128 == 0 and N % 128 == 0) ...
     int kw = 0;              // ... and the exponent of its static scale: |w| 2^kw <= 448
     void* wm4 = nullptr;     // weight image of the "mx4" mode (gemm_planes.h ARITH = 3: both cross terms in e2m1) ...
-    unsigned char* ws4 = nullptr;      // ... and its scale image: one E8M0 byte per 16-channel block of every weight row (gemm_mx.h: mx4_scale_image_bytes)
+    unsigned char* ws4 = nullptr;      // ... and its scale image: one E8M0 byte per 16-channel block of every weight row (weight_plan.h: mx4_scale_image_bytes)
     float* bias = nullptr;   // [N] or null
     int N = 0, C = 0, Cpad = 0, ktaps = 1;
 };

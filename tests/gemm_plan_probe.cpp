@@ -1,5 +1,5 @@
-// Host-compiled driver of csrc/gemm_plan.h, csrc/attn_plan.h, csrc/model_launches.h and csrc/call_plan.h for tests/test_gemm_plan_host.py, tests/test_attn_plan_host.py
-// and tests/test_call_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
+// Host-compiled driver of csrc/gemm_plan.h, csrc/attn_plan.h, csrc/model_launches.h, csrc/call_plan.h and csrc/weight_plan.h for tests/test_gemm_plan_host.py,
+// tests/test_attn_plan_host.py, tests/test_call_plan_host.py and tests/test_weight_plan_host.py (g++ -std=c++17 -Wall -Werror, no HIP).
 //   probe model <Rtok> <regime_tok> <Rfr> <regime_fr> <case>   the plan of every GEMM and attention launch of a teacher-forced forward of the default model, in the four tested precisions
 //   probe names <block> <mode> <case> <tokens,frames>..    the ordered profile names of one forward (rows: layout_rule.h), sub-launches (.planes, .rows, .split) included
 //   probe decisions                                        every field of EncodePlan / DecodePlan over the inputs they are functions of
@@ -9,11 +9,13 @@
 //   probe refusals                                         one argument set per refusal of plan_gemm
 //   probe attn_sweep                                       plan_attention over the regime threshold, the switch, the plane distances, the grid and the scales
 //   probe attn_refusals                                    the refusals of plan_attention
+//   probe weights <model>                                  every layer of a model as the loader asks for it, with the plan's answer: the byte size of every image
+//   probe weight_sweep                                     plan_weight over the asks: `coordinates | fields`
 // <case>: key=value,... (or -): the options tokproj, tokproj_f32, fuse_var, row8; the model's rf (reduction_factor), post (postnet_layers), in (decoder input layer); the call's
 // es, ps, e_out, p_out, dec_out, after, before, packed, ctl, devlay (0 / 1), tokp (the token workspace has tok.proj's buffer).  Default: the default options, a teacher-forced forward.
 // The launches are the ones model_launches.h forms and call_plan.h decides on, the headers fs2_runtime.hip executes: encode() and decode() below are its two entry points
-// without the kernels, branching on the same plan fields.  This file holds only data: a model described as the loader would leave it (a marker pointer wherever it builds
-// an image or the workspace has a buffer) and the walk over the headers' step lists.
+// without the kernels, branching on the same plan fields.  This file holds only data: a model described as the loader leaves it -- the asks of weight_plan.h's
+// constructors, a marker pointer wherever plan_weight gives an image bytes or the workspace has a buffer -- and the walk over the headers' step lists.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +24,7 @@
 
 #include "attn_plan.h"
 #include "call_plan.h"
+#include "weight_plan.h"
 
 using namespace fs2;
 
@@ -34,46 +37,89 @@ constexpr int kFp32 = kPlanFp32, kBf16x3 = kPlanBf16x3, kBf16 = 2;
 
 int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
-// a layer as the Loader leaves it: the split-bf16 image always, the others by its rules (mx: the layer is one the mx image is built for when the shape allows)
-Gemm gemm(int C, int ktaps, int N, bool mx = false, bool f16 = false) {
+// a layer as the loader leaves it: an image wherever the plan gives it bytes
+Gemm gemm(const WeightAsk& ask) {
+    const WeightPlan p = plan_weight(ask);
     Gemm g;
-    g.w = M; g.wb = M; g.C = C; g.Cpad = round_up(C, 32); g.ktaps = ktaps; g.N = N;
-    if (f16) g.wf = M;
-    if (mx && C % 128 == 0 && N % 128 == 0) { g.wm = M; if (ktaps > 1 && f16) { g.wm4 = M; g.ws4 = MB; } }
+    g.C = ask.C; g.Cpad = p.Cpad; g.ktaps = ask.ktaps; g.N = p.N;
+    if (p.has(kImgW)) g.w = M;
+    if (p.has(kImgWb)) g.wb = M;
+    if (p.has(kImgWf)) g.wf = M;
+    if (p.has(kImgWm)) g.wm = M;
+    if (p.has(kImgWm4)) g.wm4 = M;
+    if (p.has(kImgWs4)) g.ws4 = MB;
+    if (p.has(kImgBias)) g.bias = M;
     return g;
 }
-GemmArgs base(int C, int ktaps, int N, int R, bool y) { return gemm_args(gemm(C, ktaps, N), M, C, R, nullptr, y ? M : nullptr, N); }      // (the refusal cases start from it)
+GemmArgs base(int C, int ktaps, int N, int R, bool y) {      // (the refusal cases start from it: a plain layer without a bias)
+    return gemm_args(gemm(ask_of(1, N, C, ktaps, ktaps == 1, false)), M, C, R, nullptr, y ? M : nullptr, N);
+}
 
+// hp.model as far as the launches and the weights depend on it; the defaults are default_hparams()'
 struct Model { int adim = 256, ddim = 384, heads = 2, eunits = 1024, dunits = 1024, kffn = 9, odim = 80, post_layers = 5, post_chans = 256, post_k = 5,
-               dur_chans = 256, dur_k = 3, var_chans = 256, var_k = 3, layers = 4, rf = 1, input_layer = 1;
-               bool enc_pre_ln = false, enc_concat = false, dec_pre_ln = false, dec_concat = false; };
+               dur_chans = 256, dur_k = 3, dur_layers = 2, var_chans = 256, var_k = 3, elayers = 4, dlayers = 4, rf = 1, input_layer = 1;
+               bool enc_pre_ln = false, enc_concat = false, dec_pre_ln = false, dec_concat = false, use_batch_norm = true, linear_ffn = false; };
 
-Stack stack(int D, int heads, int units, int k, int layers, bool pre_ln, bool concat) {
+// The model's layers in the loader's order (fs2_load_weights), each with the ask the loader forms for it.
+struct NamedAsk { std::string name; WeightAsk ask; };
+std::vector<NamedAsk> model_asks(const Model& m) {
+    std::vector<NamedAsk> out;
+    auto stack = [&](const char* tag, int D, int units, int layers, bool concat) {
+        const int Dp = att_width(D, m.heads);
+        const WeightAsk w1 = ask_ffn_w1(D, units, m.kffn, m.linear_ffn);
+        for (int i = 0; i < layers; ++i) {
+            const std::string p = std::string(tag) + "." + std::to_string(i) + ".";
+            out.push_back({p + "qkv", ask_qkv(D, Dp)}); out.push_back({p + "out", ask_attn_out(D, Dp)});
+            out.push_back({p + "w1", w1}); out.push_back({p + "w2", ask_ffn_w2(w1, m.linear_ffn)});
+            if (concat) { out.push_back({p + "cat_x", ask_concat_half(D, 0)}); out.push_back({p + "cat_a", ask_concat_half(D, 1)}); }
+        }
+    };
+    auto predictor = [&](const char* tag, int layers, int chans, int k) {
+        for (int l = 0; l < layers; ++l) out.push_back({std::string(tag) + ".conv" + std::to_string(l), ask_predictor_conv(l ? chans : m.adim, chans, k)});
+    };
+    stack("enc", m.adim, m.eunits, m.elayers, m.enc_concat);
+    stack("dec", m.ddim, m.dunits, m.dlayers, m.dec_concat);
+    predictor("dur", m.dur_layers, m.dur_chans, m.dur_k); predictor("energy", 2, m.var_chans, m.var_k); predictor("pitch", 2, m.var_chans, m.var_k);
+    const bool fused = m.var_chans % 128 == 0 && m.adim % 32 == 0;      // (FusedPredictors: two layers)
+    if (fused) { out.push_back({"var.c0", ask_fused_predictor_conv(m.adim, m.var_chans, m.var_k)}); out.push_back({"var.c1", ask_fused_predictor_conv(m.var_chans, m.var_chans, m.var_k)}); }
+    if (m.input_layer) out.push_back({"dec_in", ask_dec_in(m.adim, m.ddim)});
+    if (m.input_layer && fused && m.var_k == 3 && m.ddim % 32 == 0) out.push_back({"tokw", ask_tok_proj(m.adim, 6 * m.var_chans + m.ddim)});      // (tok_proj_cols)
+    out.push_back({"feat", ask_feat_out(m.ddim, m.odim * m.rf)});
+    for (int l = 0; l < m.post_layers; ++l)
+        out.push_back({"post." + std::to_string(l), ask_postnet(l ? m.post_chans : m.odim, l == m.post_layers - 1 ? m.odim : m.post_chans, m.post_k, m.use_batch_norm)});
+    return out;
+}
+
+Stack stack(int D, int heads, int units, int k, int layers, bool pre_ln, bool concat, bool linear_ffn) {
     Stack st;
     st.dk = D / heads; st.Dp = att_width(D, heads); st.pre_ln = pre_ln; st.concat = concat; st.pe = M; st.after_g = st.after_b = M;
     Layer ly;
-    ly.qkv = gemm(D, 1, 3 * st.Dp); ly.out = gemm(st.Dp, 1, D); ly.w1 = gemm(D, k, units, k > 1, k > 1); ly.w2 = gemm(units, 1, D, k > 1 && D == 384);
-    if (concat) ly.cat_x = ly.cat_a = gemm(D, 1, D);
+    const WeightAsk w1 = ask_ffn_w1(D, units, k, linear_ffn);
+    ly.qkv = gemm(ask_qkv(D, st.Dp)); ly.out = gemm(ask_attn_out(D, st.Dp)); ly.w1 = gemm(w1); ly.w2 = gemm(ask_ffn_w2(w1, linear_ffn));
+    if (concat) { ly.cat_x = gemm(ask_concat_half(D, 0)); ly.cat_a = gemm(ask_concat_half(D, 1)); }
     ly.ln1g = ly.ln1b = ly.ln2g = ly.ln2b = M;
     st.layers.assign(layers, ly);
     return st;
 }
 Predictor predictor(int cin, int chans, int k) {
     Predictor p;
-    p.conv = {gemm(cin, k, chans), gemm(chans, k, chans)};
+    p.conv = {gemm(ask_predictor_conv(cin, chans, k)), gemm(ask_predictor_conv(chans, chans, k))};
     p.lng = p.lnb = {M, M}; p.lin_w = p.lin_b = M;
     return p;
 }
 struct Built {
     Stack enc, dec; Predictor dur, energy, pitch; FusedPredictors var2; Gemm dec_in, feat, tokw; std::vector<Gemm> post; fs2_config cfg;
     explicit Built(const Model& m)
-        : enc(stack(m.adim, m.heads, m.eunits, m.kffn, m.layers, m.enc_pre_ln, m.enc_concat)), dec(stack(m.ddim, m.heads, m.dunits, m.kffn, m.layers, m.dec_pre_ln, m.dec_concat)),
-          dur(predictor(m.adim, m.dur_chans, m.dur_k)), energy(predictor(m.adim, m.var_chans, m.var_k)), pitch(energy), dec_in(gemm(m.adim, 1, m.ddim)), feat(gemm(m.ddim, 1, m.odim * m.rf)), cfg() {
+        : enc(stack(m.adim, m.heads, m.eunits, m.kffn, m.elayers, m.enc_pre_ln, m.enc_concat, m.linear_ffn)),
+          dec(stack(m.ddim, m.heads, m.dunits, m.kffn, m.dlayers, m.dec_pre_ln, m.dec_concat, m.linear_ffn)),
+          dur(predictor(m.adim, m.dur_chans, m.dur_k)), energy(predictor(m.adim, m.var_chans, m.var_k)), pitch(energy), dec_in(gemm(ask_dec_in(m.adim, m.ddim))),
+          feat(gemm(ask_feat_out(m.ddim, m.odim * m.rf))), cfg() {
         var2.ok = m.var_chans % 128 == 0;
-        var2.c0 = gemm(m.adim, m.var_k, 2 * m.var_chans); var2.c1 = gemm(m.var_chans, m.var_k, 2 * m.var_chans);
+        var2.c0 = gemm(ask_fused_predictor_conv(m.adim, m.var_chans, m.var_k)); var2.c1 = gemm(ask_fused_predictor_conv(m.var_chans, m.var_chans, m.var_k));
         var2.ln0g = var2.ln0b = var2.ln1g = var2.ln1b = var2.lin_w = var2.lin_b = M;
-        for (int l = 0; l < m.post_layers; ++l) post.push_back(gemm(l ? m.post_chans : m.odim, m.post_k, l == m.post_layers - 1 ? m.odim : m.post_chans, true));
-        if (m.input_layer && var2.ok) tokw = gemm(m.adim, 1, 6 * m.var_chans + m.ddim);      // (load_tok_proj)
+        for (int l = 0; l < m.post_layers; ++l)
+            post.push_back(gemm(ask_postnet(l ? m.post_chans : m.odim, l == m.post_layers - 1 ? m.odim : m.post_chans, m.post_k, m.use_batch_norm)));
+        if (m.input_layer && var2.ok) tokw = gemm(ask_tok_proj(m.adim, 6 * m.var_chans + m.ddim));      // (load_tok_proj)
         cfg.idim = 68; cfg.odim = m.odim; cfg.adim = m.adim; cfg.ddim = m.ddim; cfg.aheads = m.heads; cfg.var_chans = m.var_chans; cfg.postnet_layers = m.post_layers;
         cfg.reduction_factor = m.rf; cfg.decoder_input_layer = m.input_layer; cfg.use_scaled_pos_enc = 1;
     }
@@ -231,6 +277,15 @@ int mode_precision(const char* name) {      // include/fs2.h's value of a tested
 struct Case {
     Options o; Model m; DecodeAsk ask; bool tokp = true;
     Case() { ask.es = ask.ps = ask.e_out = ask.p_out = ask.after = ask.before = true; }
+    bool model_key(const std::string& key, int v) {      // hp.model's other settings (probe weights)
+        const struct { const char* key; int* at; } ints[] = {{"adim", &m.adim}, {"ddim", &m.ddim}, {"aheads", &m.heads}, {"eunits", &m.eunits}, {"dunits", &m.dunits}, {"kffn", &m.kffn},
+            {"elayers", &m.elayers}, {"dlayers", &m.dlayers}, {"dur_layers", &m.dur_layers}, {"post_chans", &m.post_chans}, {"var_chans", &m.var_chans}};
+        const struct { const char* key; bool* at; } bools[] = {{"linear_ffn", &m.linear_ffn}, {"bn", &m.use_batch_norm}, {"enc_pre_ln", &m.enc_pre_ln}, {"enc_concat", &m.enc_concat},
+            {"dec_pre_ln", &m.dec_pre_ln}, {"dec_concat", &m.dec_concat}};
+        for (const auto& k : ints) if (key == k.key) { *k.at = v; return true; }
+        for (const auto& k : bools) if (key == k.key) { *k.at = v != 0; return true; }
+        return false;
+    }
     bool parse(const char* text) {
         if (!strcmp(text, "-")) return true;
         std::string t(text);
@@ -245,7 +300,7 @@ struct Case {
             else if (key == "es") ask.es = v; else if (key == "ps") ask.ps = v; else if (key == "e_out") ask.e_out = v; else if (key == "p_out") ask.p_out = v;
             else if (key == "dec_out") ask.dec_out = v; else if (key == "after") ask.after = v; else if (key == "before") ask.before = v; else if (key == "packed") ask.after_packed = v;
             else if (key == "ctl") ask.ctl_pitch = v; else if (key == "devlay") ask.devlay = v; else if (key == "tokp") tokp = v;
-            else return false;
+            else if (!model_key(key, v)) return false;
             at = end + 1;
         }
         return true;
@@ -474,7 +529,7 @@ int variants(int Rtok, int reg_tok, int Rfr, int reg_fr) {
         {"pre_ln", true, false, true, false}, {"concat_after", false, true, false, true}, {"pre_ln_concat", true, true, true, true}, {"enc_pre_ln_dec_concat", true, false, false, true}};
     for (const auto& v : kVariants)
         for (const auto& md : kModes) {
-            Model mm; mm.layers = 1; mm.enc_pre_ln = v.enc_pre_ln; mm.enc_concat = v.enc_concat; mm.dec_pre_ln = v.dec_pre_ln; mm.dec_concat = v.dec_concat;
+            Model mm; mm.elayers = mm.dlayers = 1; mm.enc_pre_ln = v.enc_pre_ln; mm.enc_concat = v.enc_concat; mm.dec_pre_ln = v.dec_pre_ln; mm.dec_concat = v.dec_concat;
             const Built m{mm};
             const std::string tag = std::string(v.name) + " " + md.name;
             Call c{md.prec, md.terms, rows_of(Rtok, reg_tok), tag.c_str(), Options()};
@@ -616,6 +671,51 @@ int attn_refusals() {
     return 0;
 }
 
+// ---- the weight plan (csrc/weight_plan.h)
+void show_plan(const WeightPlan& p) {
+    printf("N=%d Npad=%d Cpad=%d nchunks=%d w=%zu wb=%zu wf=%zu wm=%zu wm4=%zu ws4=%zu bias=%zu mx_src=%s shape=%d:%lld,%lld,%lld vec=%lld\n", p.N, p.Npad, p.Cpad, p.nchunks,
+           p.bytes[kImgW], p.bytes[kImgWb], p.bytes[kImgWf], p.bytes[kImgWm], p.bytes[kImgWm4], p.bytes[kImgWs4], p.bytes[kImgBias],
+           p.mx_src == MxSource::None ? "none" : (p.mx_src == MxSource::Tensor ? "tensor" : "folded"), p.w_ndim, (long long)p.w_shape[0], (long long)p.w_shape[1],
+           (long long)p.w_shape[2], (long long)p.vec_len);
+}
+
+// every layer of a model in the loader's order: `name parts Neach C ktaps | plan`, then the bytes of all images together
+int weights(const char* text) {
+    Case k;
+    if (!k.parse(text)) return 2;
+    size_t total = 0;
+    for (const NamedAsk& l : model_asks(k.m)) {
+        printf("%s parts=%d Neach=%d C=%d k=%d | ", l.name.c_str(), l.ask.parts, l.ask.Neach, l.ask.C, l.ask.ktaps);
+        const WeightPlan p = plan_weight(l.ask);
+        show_plan(p);
+        total += p.total_bytes();
+    }
+    printf("total %zu\n", total);
+    return 0;
+}
+
+int weight_sweep() {
+    const struct { bool f16, mx_conv, mx4, mx_k1; } roles[] = {{false, false, false, false}, {true, false, false, false}, {false, true, false, false}, {false, false, true, false},
+                                                             {false, false, false, true}, {false, true, true, false}, {true, true, true, false}, {true, true, true, true}};
+    for (int parts : {1, 3})
+        for (int N : {31, 32, 33, 127, 128, 129, 256})
+            for (int C : {31, 32, 33, 127, 128, 129, 256, 384})
+                for (int ktaps : {1, 3, 9})
+                    for (int linear = 0; linear <= 1; ++linear)
+                        for (int bn = 0; bn <= 1; ++bn)
+                            for (int slice = 0; slice <= 1; ++slice)
+                                for (int bias = 0; bias <= 1; ++bias)
+                                    for (const auto& r : roles) {
+                                        WeightAsk a = ask_of(parts, N, C, ktaps, linear, bias);
+                                        a.bn = bn; a.f16 = r.f16; a.mx_conv = r.mx_conv; a.mx4 = r.mx4; a.mx_k1 = r.mx_k1;
+                                        if (slice) { a.col_off = C; a.src_cols = 2 * C; }
+                                        printf("parts=%d Neach=%d C=%d k=%d linear=%d bn=%d col_off=%d src_cols=%d bias=%d f16=%d mx_conv=%d mx4=%d mx_k1=%d | ", parts, N, C, ktaps, linear, bn,
+                                               a.col_off, a.src_cols, bias, (int)r.f16, (int)r.mx_conv, (int)r.mx4, (int)r.mx_k1);
+                                        show_plan(plan_weight(a));
+                                    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -628,7 +728,9 @@ int main(int argc, char** argv) {
     if (argc == 2 && !strcmp(argv[1], "refusals")) return refusals();
     if (argc == 2 && !strcmp(argv[1], "attn_sweep")) return attn_sweep();
     if (argc == 2 && !strcmp(argv[1], "attn_refusals")) return attn_refusals();
+    if (argc == 3 && !strcmp(argv[1], "weights")) return weights(argv[2]);
+    if (argc == 2 && !strcmp(argv[1], "weight_sweep")) return weight_sweep();
     fprintf(stderr, "usage: probe model Rtok regime_tok Rfr regime_fr case | variants Rtok regime_tok Rfr regime_fr | names block mode case tokens,frames.. | decisions | call_refusals | "
-                    "sweep | refusals | attn_sweep | attn_refusals\n");
+                    "sweep | refusals | attn_sweep | attn_refusals | weights case | weight_sweep\n");
     return 2;
 }

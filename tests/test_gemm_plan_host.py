@@ -211,7 +211,7 @@ def model_plans(probe):
 
 
 def test_gemm_plan_header_is_hip_free():
-    for h in ("gemm_plan.h", "gemm_args.h", "model_launches.h", "attn_plan.h", "layout_rule.h", "call_plan.h"):
+    for h in ("gemm_plan.h", "gemm_args.h", "model_launches.h", "attn_plan.h", "layout_rule.h", "call_plan.h", "weight_plan.h"):
         src = open(os.path.join(CSRC, h)).read()
         incl = [l.split()[1] for l in src.split("\n") if l.startswith("#include")]
         ours = ('"gemm_args.h"', '"gemm_plan.h"', '"layout_rule.h"', '"attn_plan.h"', '"model_launches.h"', '"../../include/fs2.h"')      # (fs2.h: plain C over stddef.h / stdint.h)

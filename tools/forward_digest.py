@@ -11,7 +11,9 @@ utterances and the default block, the cases the per-call decisions of csrc/call_
 FS2_FUSE_VAR = 0, a free-running forward, per-phoneme pitch control, reduction_factor = 2, the device-driven layout with the packed output): `<case> <sha256
 over the outputs it asks for>`, their names to --call-names (profiles/call_plan_names_parent.json, profiles/call_plan_digest.txt).  --root runs another checkout's
 package (built there) with this file's cases: run it on the parent commit twice and on the tree under test, on one machine; where the parent equals itself the
-tree must equal the parent (profiles/model_launches_digest.txt).  tests/test_gpu_parity.py compares launch_names() with the names recorded from the parent
+tree must equal the parent (profiles/model_launches_digest.txt).  LOAD_CASES adds, on the same utterances, the configurations that reach the branches of the weight
+loader (csrc/weight_plan.h) the cases above do not -- a Linear FFN, no BatchNorm, a 3-tap FFN, padded heads, concat_after on padded heads, a 256-wide decoder -- in fp32,
+bf16x3 and mix_mx4, and the default block after a second fs2_load_weights on the same handle (profiles/weight_plan_digest.txt).  tests/test_gpu_parity.py compares launch_names() with the names recorded from the parent
 (profiles/model_launches_names_parent.json)."""
 import argparse
 import hashlib
@@ -153,6 +155,44 @@ def call_launch_names(model, b, case):
     return call_forward(model, b, case, profile=True)[1]
 
 
+# ---- the cases of the weight loader: id -> (configuration, precision, second load).  The configurations are tests/test_gpu_parity.py's VARIANTS of the same names
+# (tests/test_weight_plan_host.py holds the two together).
+LOAD_VARIANTS = {
+    "linear_ffn": dict(positionwise_layer_type="linear", positionwise_conv_kernel_size=1),
+    "no_batchnorm": dict(use_batch_norm=False),
+    "conv_k3_ffn": dict(positionwise_conv_kernel_size=3, duration_predictor_layers=3),
+    "aheads8": dict(aheads=8),
+    "aheads4_pre_ln_concat": dict(aheads=4, decoder_normalize_before=True, decoder_concat_after=True),
+    "ddim256_arch": dict(ddim=256, dunits=1024, elayers=2, dlayers=3, postnet_layers=3),
+}
+LOAD_MODES = ("fp32", "bf16x3", "mix_mx4")
+LOAD_CASES = {"%s/%s/load" % (v, m): (v, m, False) for v in LOAD_VARIANTS for m in LOAD_MODES}
+LOAD_CASES.update({"default/%s/reload" % m: ("default", m, True) for m in LOAD_MODES})
+
+
+def make_load_model(variant):
+    from fastspeech2_amd import FeedForwardTransformer, default_hparams, N_PHONEME_SYMBOLS
+    from fastspeech2_amd.synthetic import portable_state_dict
+    hp = default_hparams()
+    for k, v in LOAD_VARIANTS.get(variant, {}).items():
+        hp.model[k] = v
+    model = FeedForwardTransformer(N_PHONEME_SYMBOLS, hp.audio.num_mels, hp).eval()
+    model.load_state_dict(portable_state_dict(model.state_dict(), seed=3))
+    return model.to("cuda:0")
+
+
+def load_forward(model, b, case):
+    """One teacher-forced forward of a LOAD_CASES entry -> list of output tensors; a reload case runs one forward, has the weights loaded again and runs the next."""
+    _, precision, reload = LOAD_CASES[case]
+    out, _ = forward(model, b, precision, 0)
+    if reload:
+        generation = model._weights_generation
+        model.refresh_weights()
+        out, _ = forward(model, b, precision, 0)
+        assert model._weights_generation == generation + 1, "no second fs2_load_weights"
+    return [out[k] for k in ("before", "after", "d_log", "e_outs", "p_outs")]
+
+
 def digest(tensors):
     import torch
     h = hashlib.sha256()
@@ -192,6 +232,15 @@ def main():
     for case in CALL_CASES:
         out, call_names[case] = call_forward(models[CALL_CASES[case][0]], b, case, profile=bool(args.call_names))
         print(case, digest(out), flush=True)
+    load_models = {}
+    for case in LOAD_CASES:
+        variant = LOAD_CASES[case][0]
+        if variant not in load_models:
+            load_models = {variant: make_load_model(variant)}      # (one model at a time on the device)
+        try:
+            print(case, digest(load_forward(load_models[variant], b, case)), flush=True)
+        except fastspeech2_amd._lib.Fs2LibraryError as e:      # (a refusal of the library is an answer too: the same one from both trees)
+            print(case, "refused: %s" % e, flush=True)
     for path, what in ((args.names, names), (args.call_names, call_names)):
         if path:
             with open(path, "w") as f:
