@@ -16,9 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import _i32, _lens, _stream
 from .dtw import FEATURES, _pairs
 from .losses import DeviceRecords
-from .vocoder import _i32, _lens, _stream
 
 TERMS = _lib.ALIGN_TERMS
 # index of a record (include/fs2.h)

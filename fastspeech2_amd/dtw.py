@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import _i32, _lens, _require_cuda, _stream
 from .losses import DeviceRecords, _rows
-from .vocoder import _i32, _lens, _require_cuda, _stream
 
 TERMS = _lib.DTW_TERMS
 # index of a record (include/fs2.h)

@@ -21,6 +21,8 @@ from torch import nn
 
 from . import _lib
 from . import prosody as _prosody
+from ._host import _stream
+from ._run_plan import PackedOut, plan_run
 
 __all__ = ["FeedForwardTransformer", "AsyncMels", "Fs2CapacityError", "StepStreams"]
 
@@ -258,8 +260,22 @@ def _require_device(t):
                            "move the module and its inputs to a HIP device)" % t.device)
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _host_lens(lens):
+    return torch.as_tensor(lens).detach().to("cpu", torch.int64)
+
+
+_LOSS_PATH_R = ("loss path with reduction_factor > 1 (the reference's own length handling for it is commented "
+                "out, fastspeech.py:275-276); _forward / inference are implemented")
+
+
+def _teacher_targets(xs, ds, es, ps):
+    """The targets of a teacher-forced pass: ``ds`` (on the device), ``ds`` cut to ``xs``'s width, and the float32 tracks on the device."""
+    return ds, ds[:, : xs.shape[1]], es.to(xs.device).float(), ps.to(xs.device).float()
+
+
+def _require_alpha(alpha):
+    if not float(alpha) > 0.0:
+        raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -486,170 +502,59 @@ class FeedForwardTransformer(nn.Module):
             raise NotImplementedError(
                 "training (autograd / dropout / BatchNorm batch statistics) is outside the scope of this MI355X "
                 "inference path: call model.eval() and wrap calls in torch.no_grad()")
+        # 1. the plan (_run_plan.py): every refusal that plain values decide, before a handle, an allocation or a launch
         dev = xs.device
+        B, Tmax = xs.shape
+        il = _host_lens(ilens).contiguous()                   # host lengths (reference: .tolist())
+        durations = d_override if is_inference else ds
+        rows = Lcap = 0
+        if capacity is not None:
+            total_cap, Lcap = int(capacity[0]), int(capacity[1])
+            rows = int(_lib.lib().fs2_row_capacity(C.byref(_lib.Batch(B, Tmax, None, 0, 0)), total_cap))      # (a function of B and the bound alone)
+        plan = plan_run(
+            B, Tmax, il.numel(), self.reduction_factor, self.odim, self._cfg["adim"], self._cfg["ddim"], is_inference, compat, want,
+            has_ds=ds is not None, has_es=es is not None, has_ps=ps is not None, has_d_override=d_override is not None, has_olens=olens is not None,
+            durations_shape=None if durations is None else tuple(durations.shape), capacity=capacity, rows=rows, regime=regime,
+            controlled=bool(prosody) and any(v is not None for v in prosody.values()),
+            packed_out=None if packed_out is None else PackedOut(packed_out.is_contiguous(), packed_out.dtype, packed_out.device == dev,
+                                                                 tuple(packed_out.shape)),
+            device=dev, overlap_encoder=self.overlap_encoder,
+            capturing=capacity is not None and self.overlap_encoder and torch.cuda.is_current_stream_capturing())
+        # 2. the inputs as the library takes them
         # (overlap_encoder: whatever copy these conversions need -- a column-sliced shard of a batch is not contiguous -- must run on the stream the
         #  encoder runs on; on the current stream it would queue behind the previous call's kernels while the side stream reads the result at once)
-        in_stream = self.input_stream(dev) if capacity is not None else torch.cuda.current_stream(dev)
-        with torch.cuda.stream(in_stream):
+        with torch.cuda.stream(self.input_stream(dev) if plan.device else torch.cuda.current_stream(dev)):
             xs = xs.contiguous().long()
-        B, Tmax = xs.shape
-        ctl = None
-        if prosody and any(v is not None for v in prosody.values()):
-            if compat:
-                raise ValueError("pitch / energy control has per-utterance semantics only (batch_semantics='padded_compat')")
-            if not is_inference:
-                raise ValueError("pitch / energy control acts on predictions: the teacher-forced pass quantises the es / ps it is given")
-            with torch.cuda.stream(in_stream):
-                ctl = _prosody.normalize_controls(B, Tmax, dev, **prosody)
-        il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).contiguous()   # host lengths (reference: .tolist())
-        if il.numel() != B:
-            raise ValueError("ilens has %d entries for a batch of %d" % (il.numel(), B))
-        prec = _lib.PRECISIONS[self.precision]
-        L = self._ensure_ready(dev, Tmax)
-        h = self._handle
-        il_arr = (C.c_int64 * B)(*il.tolist())
-        if regime is not None:
-            rt, ru = int(regime[0]), int(regime[1])
-            if rt <= 0 or ru <= 0:
-                raise ValueError("regime=(phonemes, utterances) must both be positive, got %r" % (regime,))
-            if compat:
-                raise ValueError("regime applies to per-utterance semantics: a padded_compat batch depends on its batch-mates anyway")
-            batch = _lib.Batch(B, Tmax, il_arr, int(compat), prec, rt, ru)
-        else:
-            batch = _lib.Batch(B, Tmax, il_arr, int(compat), prec)
-        out = {}
-        teacher = not is_inference
-        ds_dev = None
-        if teacher:
-            if ds is None or es is None or ps is None:
-                raise ValueError("teacher-forced _forward needs ds, es and ps")
-            ds_dev = ds.to(dev).long().contiguous()
-        elif d_override is not None:
-            with torch.cuda.stream(in_stream):
-                ds_dev = d_override.to(dev).long().contiguous()
-        if ds_dev is not None and tuple(ds_dev.shape) != (B, Tmax):
-            raise ValueError("ds must be [B, Tmax] = [%d, %d], got %s" % (B, Tmax, tuple(ds_dev.shape)))
+            ctl = _prosody.normalize_controls(B, Tmax, dev, **prosody) if plan.controlled else None
+            ds_dev = durations.to(dev).long().contiguous() if durations is not None else None
+        batch = _lib.Batch(B, Tmax, (C.c_int64 * B)(*il.tolist()), int(compat), _lib.PRECISIONS[self.precision], plan.regime_tokens,
+                           plan.regime_utterances)
         with torch.cuda.device(dev):
-            st = _stream(dev)
-            # Throughput mode (``overlap_encoder``, sync-free calls only): the token-level half of the forward -- encoder, duration predictor:
-            # ~30 launches that leave most of the chip idle -- runs on a side stream, so that call i + 1's encoder executes while call i's
-            # frame-level kernels still run on the caller's stream; an event hands the encoder's results to this call's fs2_decode.  The side
-            # stream does NOT wait for the caller's stream: the caller promises that xs (and d_override) are complete (see ``overlap_encoder``).
-            cur = torch.cuda.current_stream(dev)
-            side = None
-            if capacity is not None and self.overlap_encoder and not torch.cuda.is_current_stream_capturing():
-                side = self.input_stream(dev)
-                if self._enc_gen_seen.get(side.cuda_stream) != self._weights_generation:      # the weights were (re-)uploaded on some stream since this side stream last looked
-                    torch.cuda.synchronize(dev)
-                    self._enc_gen_seen[side.cuda_stream] = self._weights_generation
-            if side is not None and inputs_ready is not None:
-                side.wait_event(inputs_ready)          # the caller's marker behind whatever produces xs / d_override (otherwise: its promise that they are complete)
-            with torch.cuda.stream(side if side is not None else cur):
-                st_e = _stream(dev)
-                tok_ws = torch.empty(L.fs2_token_workspace_bytes(h, C.byref(batch)), dtype=torch.uint8, device=dev)
-                d_log = torch.empty(B, Tmax, dtype=torch.float32, device=dev) if teacher else None
-                d_int = torch.empty(B, Tmax, dtype=torch.int64, device=dev) if is_inference else None
-                olens_dev = torch.empty(B, dtype=torch.int64, device=dev)
-                enc_out = torch.empty(B, Tmax, self._cfg["adim"], device=dev) if "encoder_out" in want else None
-                eio = _lib.EncodeIO(batch, xs.data_ptr(), ds_dev.data_ptr() if ds_dev is not None else None,
-                                    d_log.data_ptr() if d_log is not None else None,
-                                    d_int.data_ptr() if d_int is not None else None, olens_dev.data_ptr(),
-                                    enc_out.data_ptr() if enc_out is not None else None, tok_ws.data_ptr(), tok_ws.numel(), float(alpha))
-                _lib.check(L.fs2_encode(h, st_e, C.byref(eio)), h)
-            if side is not None:
-                cur.wait_stream(side)                      # (this call's fs2_decode and everything behind it on the caller's stream)
-                for t_ in (tok_ws, d_log, d_int, olens_dev, enc_out):      # allocated on the side stream, used on the caller's
-                    if t_ is not None:
-                        t_.record_stream(cur)
-                xs.record_stream(side)                                      # ... and the other way round
-                if ds_dev is not None:
-                    ds_dev.record_stream(side)
-                for t_ in (ctl or {}).values():                             # made on the side stream, read by fs2_decode_ctl on the caller's
-                    if t_ is not None:
-                        t_.record_stream(cur)
+            # 3. encode; the host layout reads the frame counts back, and a decoder positional table they outgrow is reloaded and the encoder redone
+            for _ in range(2):
+                L = self._ensure_ready(dev, Tmax)
+                tok_ws, d_log, d_int, ol, enc_out = self._encode(L, plan, batch, xs, ds_dev, ctl, alpha, inputs_ready)
+                if plan.device:
+                    self.decoder.embed[-1].ensure(Lcap)      # (a grown table is picked up by the next call's fingerprint check)
+                    break
+                ol = ol.cpu()                            # the one host sync of the path (frame counts)
+                if int(ol.min()) < 0:                    # fs2_encode's marker (include/fs2.h: olens = -1)
+                    bad = [i for i, v in enumerate(ol.tolist()) if v < 0]
+                    raise Fs2IndexError("index out of range in self: utterance(s) %s hold a phoneme id outside [0, %d)" % (bad, self.idim))
+                self.last_olens = ol
+                if olens is not None:
+                    given = _host_lens(olens)
+                    if not torch.equal(given, ol):
+                        raise ValueError("olens %s do not match the sums of the durations %s" % (given.tolist(), ol.tolist()))
+                if not self.decoder.embed[-1].ensure(int(ol.max())):
+                    break
+            # 4. decode, and the result
             pro = _prosody.prosody_struct(ctl)
-            pro = C.byref(pro) if pro is not None else None
-            if capacity is not None:
-                total_cap, Lcap = int(capacity[0]), int(capacity[1])
-                self.decoder.embed[-1].ensure(Lcap)      # (a grown table is picked up by the next call's fingerprint check)
-                rows = int(L.fs2_row_capacity(C.byref(batch), total_cap))
-                frm_ws = torch.empty(L.fs2_frame_workspace_bytes_cap(h, C.byref(batch), rows, Lcap), dtype=torch.uint8, device=dev)
-                status = torch.empty(8, dtype=torch.int32, device=dev)
-                odim = self.odim
-
-                def cbuf(key, shape, dtype=torch.float32):
-                    if key in want:
-                        out[key] = torch.empty(shape, dtype=dtype, device=dev)
-                        return out[key].data_ptr()
-                    return None
-
-                if teacher:
-                    raise ValueError("the device-driven layout serves free-running synthesis")
-                dio = _lib.DecodeIO(
-                    batch, None, Lcap, 0, None, None, 0, 0,
-                    cbuf("before", (B, Lcap * self.reduction_factor, odim)), cbuf("after", (B, Lcap * self.reduction_factor, odim)),
-                    cbuf("e_outs", (B, Lcap)), cbuf("p_outs", (B, Lcap)),
-                    cbuf("qe", (B, Lcap), torch.int32), cbuf("qp", (B, Lcap), torch.int32),
-                    cbuf("lr_index", (B, Lcap), torch.int32), cbuf("decoder_out", (B, Lcap, self._cfg["ddim"])),
-                    tok_ws.data_ptr(), frm_ws.data_ptr(), frm_ws.numel(), None, rows, status.data_ptr())
-                if "after_packed" in want:
-                    prows = rows * self.reduction_factor       # mel frames: r per decoder row
-                    if packed_out is not None:
-                        if (not packed_out.is_contiguous() or packed_out.dtype != torch.float32 or packed_out.device != dev
-                                or packed_out.dim() != 2 or packed_out.shape[1] != odim or packed_out.shape[0] < prows):
-                            raise ValueError("packed_out must be a contiguous float32 [>= %d, %d] tensor on %s" % (prows, odim, dev))
-                        out["after_packed"] = packed_out[:prows]
-                    else:
-                        out["after_packed"] = torch.empty((prows, odim), dtype=torch.float32, device=dev)
-                    dio.after_packed = out["after_packed"].data_ptr()
-                if dio.after is None and dio.after_packed is None:
-                    raise ValueError("'after' or 'after_packed' must be requested")
-                _lib.check(L.fs2_decode_ctl(h, st, C.byref(dio), pro), h)
-                out["olens"], out["status"] = olens_dev, status
-                if d_int is not None:
-                    out["d_int"] = d_int if d_override is None else ds_dev
-                if enc_out is not None:
-                    out["encoder_out"] = enc_out
-                return out
-            ol = olens_dev.cpu()                     # the one host sync of the path (frame counts)
-            if int(ol.min()) < 0:                    # fs2_encode's marker (include/fs2.h: olens = -1)
-                bad = [i for i, v in enumerate(ol.tolist()) if v < 0]
-                raise Fs2IndexError("index out of range in self: utterance(s) %s hold a phoneme id outside [0, %d)" % (bad, self.idim))
-            self.last_olens = ol
-            if olens is not None:
-                given = torch.as_tensor(olens).detach().to("cpu", torch.int64)
-                if not torch.equal(given, ol):
-                    raise ValueError("olens %s do not match the sums of the durations %s" % (given.tolist(), ol.tolist()))
-            Lmax = int(ol.max())
-            if self.decoder.embed[-1].ensure(Lmax):                # pe table grew: reload and redo the encoder
-                return self._run(xs, ilens, olens, ds, es, ps, is_inference, compat, want, d_override, alpha=alpha, regime=regime, prosody=prosody)
-            ol_arr = (C.c_int64 * B)(*ol.tolist())
-            frm_ws = torch.empty(L.fs2_frame_workspace_bytes(h, C.byref(batch), ol_arr), dtype=torch.uint8, device=dev)
-            odim = self.odim
-
-            def buf(key, shape, dtype=torch.float32):
-                if key in want:
-                    out[key] = torch.empty(shape, dtype=dtype, device=dev)
-                    return out[key].data_ptr()
-                return None
-
-            es_dev = es.to(dev).float().contiguous() if teacher else None
-            ps_dev = ps.to(dev).float().contiguous() if teacher else None
-            masked = int(teacher and olens is not None) if compat else 0
-            dio = _lib.DecodeIO(
-                batch, ol_arr, Lmax, masked,
-                es_dev.data_ptr() if es_dev is not None else None, ps_dev.data_ptr() if ps_dev is not None else None,
-                es_dev.shape[1] if es_dev is not None else 0, ps_dev.shape[1] if ps_dev is not None else 0,
-                buf("before", (B, Lmax * self.reduction_factor, odim)), buf("after", (B, Lmax * self.reduction_factor, odim)),
-                buf("e_outs", (B, Lmax)), buf("p_outs", (B, Lmax)),
-                buf("qe", (B, Lmax), torch.int32), buf("qp", (B, Lmax), torch.int32),
-                buf("lr_index", (B, Lmax), torch.int32), buf("decoder_out", (B, Lmax, self._cfg["ddim"])),
-                tok_ws.data_ptr(), frm_ws.data_ptr(), frm_ws.numel(),
-                buf("after_packed", (int(ol.sum()) * self.reduction_factor, odim)))
-            if dio.after is None:
-                raise ValueError("'after' must be requested")
-            _lib.check(L.fs2_decode_ctl(h, st, C.byref(dio), pro), h)
+            out, status = self._decode(L, plan, batch, tok_ws, C.byref(pro) if pro is not None else None, es, ps, packed_out,
+                                       None if plan.device else ol, rows, Lcap)
         out["olens"] = ol
+        if plan.device:
+            out["status"] = status
         if d_log is not None:
             out["d_log"] = d_log
         if d_int is not None:
@@ -657,6 +562,80 @@ class FeedForwardTransformer(nn.Module):
         if enc_out is not None:
             out["encoder_out"] = enc_out
         return out
+
+    def _encode(self, L, plan, batch, xs, ds_dev, ctl, alpha, inputs_ready):
+        """Launches fs2_encode as ``plan`` says -> (token workspace, d_log, d_int, olens on the device, encoder_out)."""
+        dev, h = xs.device, self._handle
+        B, Tmax = xs.shape
+        # Throughput mode (``overlap_encoder``, sync-free calls only): the token-level half of the forward -- encoder, duration predictor:
+        # ~30 launches that leave most of the chip idle -- runs on a side stream, so that call i + 1's encoder executes while call i's
+        # frame-level kernels still run on the caller's stream; an event hands the encoder's results to this call's fs2_decode.  The side
+        # stream does NOT wait for the caller's stream: the caller promises that xs (and d_override) are complete (see ``overlap_encoder``).
+        cur = torch.cuda.current_stream(dev)
+        side = None
+        if plan.side_encoder:
+            side = self.input_stream(dev)
+            if self._enc_gen_seen.get(side.cuda_stream) != self._weights_generation:      # the weights were (re-)uploaded on some stream since this side stream last looked
+                torch.cuda.synchronize(dev)
+                self._enc_gen_seen[side.cuda_stream] = self._weights_generation
+            if inputs_ready is not None:
+                side.wait_event(inputs_ready)          # the caller's marker behind whatever produces xs / d_override (otherwise: its promise that they are complete)
+        with torch.cuda.stream(side if side is not None else cur):
+            tok_ws = torch.empty(L.fs2_token_workspace_bytes(h, C.byref(batch)), dtype=torch.uint8, device=dev)
+            d_log = torch.empty(B, Tmax, dtype=torch.float32, device=dev) if plan.d_log else None
+            d_int = torch.empty(B, Tmax, dtype=torch.int64, device=dev) if plan.d_int else None
+            olens_dev = torch.empty(B, dtype=torch.int64, device=dev)
+            enc_out = torch.empty(plan.encoder_out, device=dev) if plan.encoder_out is not None else None
+            eio = _lib.EncodeIO(batch, xs.data_ptr(), ds_dev.data_ptr() if ds_dev is not None else None,
+                                d_log.data_ptr() if d_log is not None else None,
+                                d_int.data_ptr() if d_int is not None else None, olens_dev.data_ptr(),
+                                enc_out.data_ptr() if enc_out is not None else None, tok_ws.data_ptr(), tok_ws.numel(), float(alpha))
+            _lib.check(L.fs2_encode(h, _stream(dev), C.byref(eio)), h)
+        if side is not None:
+            cur.wait_stream(side)                      # (this call's fs2_decode and everything behind it on the caller's stream)
+            for t_ in (tok_ws, d_log, d_int, olens_dev, enc_out):      # allocated on the side stream, used on the caller's
+                if t_ is not None:
+                    t_.record_stream(cur)
+            xs.record_stream(side)                                      # ... and the other way round
+            if ds_dev is not None:
+                ds_dev.record_stream(side)
+            for t_ in (ctl or {}).values():                             # made on the side stream, read by fs2_decode_ctl on the caller's
+                if t_ is not None:
+                    t_.record_stream(cur)
+        return tok_ws, d_log, d_int, olens_dev, enc_out
+
+    def _decode(self, L, plan, batch, tok_ws, pro, es, ps, packed_out, ol, rows, Lcap):
+        """Allocates the outputs of ``plan``'s table and launches fs2_decode_ctl on the current stream -> (dict of the outputs, status).
+        Host layout: ``ol`` holds the frame counts, the frame extent is their maximum and the workspace comes from them.  Device layout
+        (``ol`` None): the extent is ``Lcap``, the workspace comes from the ``rows`` capacity, and ``row_capacity`` / ``status`` are set."""
+        dev, h = tok_ws.device, self._handle
+        ol_arr = status = es_dev = ps_dev = None
+        if plan.device:
+            Lext, prows = Lcap, plan.packed_rows
+            frm_ws = torch.empty(L.fs2_frame_workspace_bytes_cap(h, C.byref(batch), rows, Lcap), dtype=torch.uint8, device=dev)
+            status = torch.empty(8, dtype=torch.int32, device=dev)
+        else:
+            Lext, prows, rows = int(ol.max()), int(ol.sum()) * plan.packed_per_row, 0
+            ol_arr = (C.c_int64 * batch.B)(*ol.tolist())
+            frm_ws = torch.empty(L.fs2_frame_workspace_bytes(h, C.byref(batch), ol_arr), dtype=torch.uint8, device=dev)
+            packed_out = None
+        if plan.teacher:
+            es_dev, ps_dev = es.to(dev).float().contiguous(), ps.to(dev).float().contiguous()
+        out, ptrs = {}, []
+        for o in plan.outputs:
+            if o is not None:
+                out[o.key] = torch.empty(o.shape(Lext), dtype=o.dtype, device=dev)
+            ptrs.append(out[o.key].data_ptr() if o is not None else None)
+        if plan.after_packed:      # (device layout: a packed_out the plan accepted receives the pack in place)
+            out["after_packed"] = packed_out[:prows] if packed_out is not None else torch.empty((prows, self.odim), dtype=torch.float32, device=dev)
+        dio = _lib.DecodeIO(
+            batch, ol_arr, Lext, plan.masked,
+            es_dev.data_ptr() if es_dev is not None else None, ps_dev.data_ptr() if ps_dev is not None else None,
+            es_dev.shape[1] if es_dev is not None else 0, ps_dev.shape[1] if ps_dev is not None else 0,
+            *ptrs, tok_ws.data_ptr(), frm_ws.data_ptr(), frm_ws.numel(),
+            out["after_packed"].data_ptr() if plan.after_packed else None, rows, status.data_ptr() if status is not None else None)
+        _lib.check(L.fs2_decode_ctl(h, _stream(dev), C.byref(dio), pro), h)
+        return out, status
 
     def _forward(self, xs, ilens, olens=None, ds=None, es=None, ps=None, is_inference=False):
         """reference fastspeech.py:169-243: returns (before, after, d_outs, e, p).
@@ -672,22 +651,26 @@ class FeedForwardTransformer(nn.Module):
                       want=("before", "after", "e_outs", "p_outs"))
         return r["before"], r["after"], r["d_log"], r["e_outs"], r["p_outs"]
 
+    def _recorded_batch(self, xs, ilens, olens, refusal, alpha=None):
+        """What the entry points that compare with recordings start with -> (xs cut to the longest utterance, host ilens, host olens);
+        ``refusal``: the caller's message for reduction_factor > 1."""
+        _require_device(xs)
+        if self.reduction_factor > 1:
+            raise NotImplementedError(refusal)
+        if alpha is not None:
+            _require_alpha(alpha)
+        il, ol = _host_lens(ilens), _host_lens(olens)
+        return xs[:, : int(il.max())], il, ol
+
     def forward(self, xs, ilens, ys, olens, ds, es, ps):
         """reference fastspeech.py:245-337: losses of the teacher-forced pass; returns (loss, report_keys).
 
         The forward pass runs on the device (padded_compat semantics, as the reference computes it); the
         loss algebra on its outputs is plain PyTorch, as in the reference."""
-        _require_device(xs)
+        xs, il, ol = self._recorded_batch(xs, ilens, olens, _LOSS_PATH_R)
         dev = xs.device
-        il = torch.as_tensor(ilens).to("cpu", torch.int64)
-        if self.reduction_factor > 1:
-            raise NotImplementedError("loss path with reduction_factor > 1 (the reference's own length handling for it is commented "
-                                      "out, fastspeech.py:275-276); _forward / inference are implemented")
-        ol = torch.as_tensor(olens).to("cpu", torch.int64)
-        xs = xs[:, : int(il.max())]
         ys = ys[:, : int(ol.max())].to(dev)
-        ds, es, ps = ds.to(dev), es.to(dev).float(), ps.to(dev).float()
-        ds_t = ds[:, : xs.shape[1]]
+        ds, ds_t, es, ps = _teacher_targets(xs, ds.to(dev), es, ps)
         r = self._run(xs, il, ol, ds_t, es, ps, is_inference=False, compat=True,
                       want=("before", "after", "e_outs", "p_outs"))
         before, after, d_outs, e_outs, p_outs = r["before"], r["after"], r["d_log"], r["e_outs"], r["p_outs"]
@@ -738,18 +721,11 @@ class FeedForwardTransformer(nn.Module):
         from .losses import loss_terms
         if semantics not in ("per_utterance", "padded_compat"):
             raise ValueError("semantics must be 'per_utterance' or 'padded_compat', got %r" % (semantics,))
-        _require_device(xs)
+        xs, il, ol = self._recorded_batch(xs, ilens, olens, _LOSS_PATH_R)
         dev = xs.device
-        if self.reduction_factor > 1:
-            raise NotImplementedError("loss path with reduction_factor > 1 (the reference's own length handling for it is commented "
-                                      "out, fastspeech.py:275-276); _forward / inference are implemented")
-        il = torch.as_tensor(ilens).to("cpu", torch.int64)
-        ol = torch.as_tensor(olens).to("cpu", torch.int64)
         compat = semantics == "padded_compat"
-        xs = xs[:, : int(il.max())]
         ys = ys.to(dev).float()
-        ds, es, ps = ds.to(dev).long(), es.to(dev).float(), ps.to(dev).float()
-        ds_t = ds[:, : xs.shape[1]]
+        ds, ds_t, es, ps = _teacher_targets(xs, ds.to(dev).long(), es, ps)
         r = self._run(xs, il, ol, ds_t, es, ps, is_inference=False, compat=compat, want=("before", "after", "e_outs", "p_outs"))
         return loss_terms(r["before"], r["after"], ys, r["d_log"], ds, r["e_outs"], es, r["p_outs"], ps, il, ol, pads=compat, sync=sync)
 
@@ -763,16 +739,9 @@ class FeedForwardTransformer(nn.Module):
         not depend on the batch it is in.  ``sync=False``: the records stay on the device until first read (the forward's own
         read-back of the frame counts remains)."""
         from .dtw import mel_dtw
-        _require_device(xs)
+        xs, il, ol = self._recorded_batch(xs, ilens, olens, "free-running validation with reduction_factor > 1: e_outs / p_outs are per decoder frame, "
+                                          "the mels per mel frame", alpha)
         dev = xs.device
-        if self.reduction_factor > 1:
-            raise NotImplementedError("free-running validation with reduction_factor > 1: e_outs / p_outs are per decoder frame, the mels per "
-                                      "mel frame")
-        if not float(alpha) > 0.0:
-            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
-        il = torch.as_tensor(ilens).to("cpu", torch.int64)
-        ol = torch.as_tensor(olens).to("cpu", torch.int64)
-        xs = xs[:, : int(il.max())]
         r = self._run(xs, il, is_inference=True, compat=False, want=("after", "e_outs", "p_outs"), alpha=alpha)
         ys = ys.to(dev).float()
         e = None if es is None else (r["e_outs"], es.to(dev).float())
@@ -790,17 +759,10 @@ class FeedForwardTransformer(nn.Module):
         does not depend on the batch it is in.  ``sync=False``: the records stay on the device until first read (the forward's own
         read-back of the frame counts remains)."""
         from .align import monotonic_align
-        _require_device(xs)
-        dev = xs.device
-        if self.reduction_factor > 1:
-            raise NotImplementedError("alignment with reduction_factor > 1: lr_index is per decoder frame, the mels per mel frame")
-        if not float(alpha) > 0.0:
-            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
-        il = torch.as_tensor(ilens).to("cpu", torch.int64)
-        ol = torch.as_tensor(olens).to("cpu", torch.int64)
-        xs = xs[:, : int(il.max())]
+        xs, il, ol = self._recorded_batch(xs, ilens, olens, "alignment with reduction_factor > 1: lr_index is per decoder frame, the mels per mel frame",
+                                          alpha)
         r = self._run(xs, il, is_inference=True, compat=False, want=("after", "lr_index"), alpha=alpha)
-        return monotonic_align(r["after"], r["olens"], ys.to(dev).float(), ol, labels=r["lr_index"], n_labels=il, max_step=max_step,
+        return monotonic_align(r["after"], r["olens"], ys.to(xs.device).float(), ol, labels=r["lr_index"], n_labels=il, max_step=max_step,
                                features=features, sync=sync)
 
     def _controls(self, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None):
@@ -819,9 +781,8 @@ class FeedForwardTransformer(nn.Module):
         means of its pitch and energy tracks (csrc/prosody.h: label_means; pitch over the frames with a value > 0).  ``durations``,
         edited and passed as ``d_override``, is duration control per phoneme; ``pitch_tok`` / ``energy_tok``, edited, serve as
         ``pitch_shift`` / ``energy_shift`` with a scale of 0.  The values are the controlled ones if control was given."""
-        if not float(alpha) > 0.0:
-            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
-        il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).reshape(-1)
+        _require_alpha(alpha)
+        il = _host_lens(ilens).reshape(-1)
         r = self._run(xs, il, is_inference=True, compat=False, want=("after", "e_outs", "p_outs", "lr_index"), d_override=d_override, alpha=alpha,
                       prosody=self._controls(**controls))
         Tmax = int(xs.shape[1])
@@ -837,8 +798,7 @@ class FeedForwardTransformer(nn.Module):
         predicted pitch / energy value becomes ``v * scale + shift`` before it is quantised."""
         xs, il = x.unsqueeze(0), torch.tensor([x.shape[0]])
         pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
-        if not float(alpha) > 0.0:
-            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
+        _require_alpha(alpha)
         if self._frames_per_token is not None:
             # device-driven layout inside capacities learnt from earlier utterances: the GPU runs the whole forward without
             # waiting for the host; the frame count is read once, at the end (it is needed for the shape of the result)
@@ -884,9 +844,8 @@ class FeedForwardTransformer(nn.Module):
         value per utterance, or [B, Tmax] = one per phoneme): every predicted pitch / energy value becomes ``v * scale + shift`` before it
         is quantised, in every form of the call (``ShardedSynthesizer`` slices the tensors with the batch)."""
         pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
-        il = torch.as_tensor(ilens).detach().to("cpu", torch.int64).reshape(-1)
-        if not float(alpha) > 0.0:
-            raise ValueError("alpha must be > 0 (reference length_regulator.py:57), got %r" % (alpha,))
+        il = _host_lens(ilens).reshape(-1)
+        _require_alpha(alpha)
         if il.numel() == 0:
             _require_device(xs)
             empty = torch.zeros((0, self.odim) if packed else (0, 1, self.odim), device=xs.device)
@@ -931,7 +890,7 @@ class FeedForwardTransformer(nn.Module):
         if vocoder is None and vocoder_args:
             raise TypeError("capture_graph: %s given without a vocoder" % sorted(vocoder_args))
         with torch.no_grad():
-            il = torch.as_tensor(ilens).detach().to("cpu", torch.int64)
+            il = _host_lens(ilens)
             _, ol = self.inference_batch(xs, il, d_override=d_override)            # builds the handle, learns the sizes
             total = int(float(ol.sum()) * 1.5) + 64 * int(il.numel())
             Lcap = -(-int(float(ol.max()) * 1.5 + 64) // 32) * 32
@@ -1000,7 +959,7 @@ class FeedForwardTransformer(nn.Module):
     def predict_capacity(self, ilens, alpha=1.0):
         """(total frames, frames of the longest utterance) to reserve for a batch with these phoneme counts: the
         frames-per-phoneme ratios seen so far (x the duration scale ``alpha``) plus 15 % / 25 % head-room."""
-        il = torch.as_tensor(ilens).detach().to("cpu", torch.int64)
+        il = _host_lens(ilens)
         a = float(alpha)
         mean_r, max_r = self._frames_per_token[0] * a + (0.5 if a != 1.0 else 0.0), self._frames_per_token[1] * a + (0.5 if a != 1.0 else 0.0)
         total = int(float(il.sum()) * mean_r * 1.15) + 64 * int(il.numel())

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vocoder import _i32, _lens, _require_cuda, _stream
+from ._host import _i32, _lens, _require_cuda, _stream
 
 TERMS = _lib.LOSS_TERMS
 REPORT_NAMES = ("l1_loss", "before_loss", "after_loss", "duration_loss", "energy_loss", "pitch_loss", "loss")

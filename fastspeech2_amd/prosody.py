@@ -8,25 +8,14 @@ value ``v`` of a frame becomes ``v * scale + shift`` in float32, the product and
 quantised; the units are the predictors' own, i.e. those of the training targets (with F0 in Hz, ``pitch_scale=semitones(+2)`` speaks
 two semitones higher, and ``pitch_scale=0, pitch_shift=contour`` imposes a contour).  There is no CPU fallback: CPU tensors raise.
 """
-import ctypes as C
 from typing import NamedTuple
 
 import torch
 
 from . import _lib
+from ._host import _require_cuda, _stream
 
 CONTROLS = ("pitch_scale", "pitch_shift", "energy_scale", "energy_shift")
-
-
-def _require_cuda(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not x.is_cuda:
-        raise RuntimeError("fastspeech2_amd runs on an MI355X only (no CPU fallback): %s is on %s" % (name, x.device))
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def semitones(x):

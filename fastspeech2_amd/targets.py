@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vocoder import _audio_config, _i32, _lens, _require_cuda, _stream, wav_features
+from ._host import _i32, _lens, _require_cuda, _stream
+from .vocoder import _audio_config, wav_features
 
 _INF = float("inf")
 

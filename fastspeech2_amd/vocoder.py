@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import _i32, _lens, _require_cuda, _stream
 from .fastspeech import AsyncMels, Fs2CapacityError
 
 N_FFT, HOP, WIN, N_BINS = 1024, 256, 1024, 513
@@ -275,31 +276,6 @@ class AsyncWaveforms(tuple):
         if self.padded:
             return [self[0][b, :k] for b, k in enumerate(n)]
         return list(torch.split(self[0][:sum(n)], n))
-
-
-def _require_cuda(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not x.is_cuda:
-        raise RuntimeError("fastspeech2_amd runs on an MI355X only (no CPU fallback): %s is on %s" % (name, x.device))
-
-
-def _lens(olens, B=None, name="olens"):
-    L = torch.as_tensor(olens).detach().to("cpu", torch.int64).reshape(-1)
-    if B is not None and L.numel() != B:
-        raise ValueError("%s has %d entries for %d utterances" % (name, L.numel(), B))
-    if (L < 0).any():
-        raise ValueError("%s must be >= 0" % name)
-    return L
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _i32(a):
-    a = np.ascontiguousarray(np.asarray(a, np.int32))
-    return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def _host_batch(mels, olens, name="mels", have="have"):
