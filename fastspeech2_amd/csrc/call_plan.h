@@ -34,6 +34,13 @@ inline int regime_rows_of(const fs2_batch& b, bool token_level) {
     const long utts = b.regime_utterances > 0 ? b.regime_utterances : b.B;
     return row_bound((token_level ? 1 : 8) * regime_tokens_of(b, token_level), utts);
 }
+// ... and at SHORT level (FS2_VARSHORT: the variance predictors on at most K frames per phoneme): K frames per phoneme, formed the same way
+inline int regime_short_rows_of(const fs2_batch& b, int K) {
+    const long utts = b.regime_utterances > 0 ? b.regime_utterances : b.B;
+    return row_bound((long long)K * regime_tokens_of(b, false), utts);
+}
+// K of the variance predictors: var_layers convolutions of var_kernel taps
+inline int var_window(const fs2_config& c) { return vs_window(c.var_layers, c.var_kernel); }
 
 // What fs2_encode leaves for the fs2_decode of the same batch: reset as a whole when an accepted fs2_encode starts, filled when it has launched everything.
 struct Encoded {
@@ -46,6 +53,7 @@ struct Encoded {
     const int *start = nullptr, *vlen = nullptr;      // the token layout: first row and phonemes of every utterance
     const int* cum = nullptr;               // the duration scan: running frame sums [B, Tmax] ...
     const int* o32 = nullptr;               // ... and frame counts [B] (int32; the device-driven layout is built from them)
+    const int *scum = nullptr, *so32 = nullptr;      // the same of the short durations min(d, K) (EncodePlan::short_scan; nullptr: not computed)
 };
 
 // ------------------------------------------------------------------ checks
@@ -138,9 +146,12 @@ struct EncodePlan {
     bool tok_conv = false;        // the predictors' columns too: only where fs2_decode can use them (bit 0 and the fused predictors) ...
     int tok_n0 = 0;               // ... else the launch is sliced to the input layer's columns [n0, N) (a multiple of 128 rows into the weight images: whole tiles)
     int tok_prec = kPlanFp32;     // FS2_TOKPROJ_F32: the exact fp32 GEMM instead of the precision's own arithmetic
+    // FS2_VARSHORT: the duration scan also leaves the running sums of the short durations -- wherever fs2_decode can take the short path (DecodePlan::varshort)
+    bool short_scan = false;
 };
 // tokw_N: the columns of the model's stacked tok.proj weight (0: it has none); tokp_buf: the token workspace has the buffer for its output
-inline EncodePlan plan_encode(const fs2_config& c, const Options& o, int precision, int tokw_N, bool tokp_buf) {
+// short_buf: the token workspace can hold the short scan and the batch has per-utterance semantics
+inline EncodePlan plan_encode(const fs2_config& c, const Options& o, int precision, int tokw_N, bool tokp_buf, bool short_buf = false) {
     EncodePlan p;
     p.prec = base_precision(precision); p.ffn_terms = ffn_f16_terms(precision);
     p.planes = p.prec != kPlanFp32;
@@ -149,6 +160,7 @@ inline EncodePlan plan_encode(const fs2_config& c, const Options& o, int precisi
     p.tok_conv = p.tok_proj && (o.tokproj & 1) && o.fuse_var;
     p.tok_n0 = (p.tok_proj && !p.tok_conv) ? 6 * c.var_chans : 0;
     p.tok_prec = o.tokproj_f32 ? kPlanFp32 : p.prec;
+    p.short_scan = p.tok_conv && (o.tokproj & 3) == 3 && o.varshort && short_buf;
     return p;
 }
 
@@ -161,6 +173,7 @@ struct DecodeAsk {
     bool ctl_pitch = false, ctl_energy = false;
     bool after_vec = false, before_vec = false;      // unpack_vec(odim, the rows that output is unpacked from, the output): unpack_rows4 writes it
     int compat = 0, masked = 0;
+    bool short_buf = false;                   // the frame workspace can hold the short layout (FS2_VARSHORT)
     long R = 0; long long row_capacity = 0;   // the rows of the frame layout; the capacity the caller's after_packed holds
 };
 inline DecodeAsk decode_ask(const fs2_decode_io& io, const fs2_prosody* ctl) {
@@ -187,6 +200,12 @@ struct DecodePlan {
     // layer (bit 0; where the fused predictors run) and the decoder input layer (bit 1) gather fs2_encode's token-level products; with both (3) nothing reads the
     // expanded rows, which are then not built: lr.index in place of lr.expand, no var.embed.
     int tokproj = 0;
+    // FS2_VARSHORT (layout_rule.h): the fused predictors, the control and the bucket search of the predictions run on the short rows -- at most K frames
+    // per phoneme -- which lr.index lays out beside the token index; dec.in.gather reads the bucket indices through the frame-to-short map, and e_out /
+    // p_out, where asked for, are unpacked through it.  Where nothing reads the expanded rows (tokproj == 3) and the batch has per-utterance semantics;
+    // a function of configuration and options like tokproj -- never of the batch's data.
+    bool varshort = false;
+    bool short_qe = false, short_qp = false;      // ... that index is searched per short row (else per frame: es / ps given)
     bool control = false;         // var.control: the predictions become the controlled values in place
     // Planes-only residual stream (model_launches.h: planes_only): the decoder's LayerNorm-fused launches write planes and nothing else -- the fp32 rows x0 / x1
     // are not written at all, and dec_out, where asked for, is rebuilt from the planes (dec.out.rows).
@@ -213,6 +232,8 @@ inline DecodePlan plan_decode(const fs2_config& c, const Options& o, int precisi
     p.need_e = !a.es || a.e_out; p.need_p = !a.ps || a.p_out;
     p.fused_var = p.need_e && p.need_p && p.planes && var2_ok && p.hfr_planes && o.fuse_var;
     p.tokproj = (p.planes && enc.tokP && c.decoder_input_layer) ? (o.tokproj & ((p.fused_var && enc.tokP_conv) ? 3 : 2)) : 0;
+    p.varshort = p.tokproj == 3 && o.varshort && enc.scum && a.short_buf && !a.compat;
+    p.short_qe = p.varshort && !a.es; p.short_qp = p.varshort && !a.ps;
     p.control = a.ctl_pitch || a.ctl_energy;
     p.po = p.planes && planes_only(in, dec, c.ddim, r, b, p.prec, p.ffn_terms, o);
     p.mask_q = (a.compat && a.masked) ? 1 : 0;

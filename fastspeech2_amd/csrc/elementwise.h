@@ -3,6 +3,7 @@
 // All of them move whole rows with 16-byte accesses, one wavefront per row.
 #pragma once
 #include "common.h"
+#include "layout_rule.h"
 
 namespace fs2 {
 
@@ -85,10 +86,12 @@ __device__ __forceinline__ int scaled_duration(int64_t d, float alpha) {
 // torch.nn.Embedding raises for it (fastspeech.py:65-67, core/encoder.py:196); embed_pe reads row 0 instead of indexing out of range, and
 // the marker reaches the caller with the frame counts it reads anyway (host-driven layout) or as FS2_OVF_BAD_ID in the status word of
 // fs2_decode's device-driven layout (frame_layout_dev), whose outputs are then NaN-filled.
+// scum != nullptr (FS2_VARSHORT): beside cum, the running sums of the SHORT durations min(d, K) (layout_rule.h) and, in so32[b], their total.
 __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, const int* ilen, int* cum,
-                                                int64_t* olens, int* olens32, float alpha = 1.0f, const int64_t* ids = nullptr, int idim = 0) {
-    __shared__ int wsum[4];
-    __shared__ int carry_s;
+                                                int64_t* olens, int* olens32, float alpha = 1.0f, const int64_t* ids = nullptr, int idim = 0,
+                                                int* scum = nullptr, int* so32 = nullptr, int K = 0) {
+    __shared__ int wsum[4], wsum2[4];
+    __shared__ int carry_s, carry2_s;
     __shared__ int bad_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = ilen[b];
@@ -109,29 +112,31 @@ __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, con
     const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     const bool ones = (total == 0);
     __syncthreads();
-    if (tid == 0) carry_s = 0;
+    if (tid == 0) { carry_s = 0; carry2_s = 0; }
     __syncthreads();
     for (int base = 0; base < T; base += 256) {
         const int t = base + tid;
         int v = (t < T) ? (ones ? 1 : scaled_duration(d[t], alpha)) : 0;
-        int x = v;   // inclusive scan inside the wave
+        int x = v, x2 = vs_short_dur(v, K);   // inclusive scans inside the wave
         for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane >= o) x += y;
+            const int y = __shfl_up(x, o), y2 = __shfl_up(x2, o);
+            if (lane >= o) { x += y; x2 += y2; }
         }
-        if (lane == 63) wsum[wave] = x;
+        if (lane == 63) { wsum[wave] = x; wsum2[wave] = x2; }
         __syncthreads();
-        int off = carry_s;
-        for (int w = 0; w < wave; ++w) off += wsum[w];
+        int off = carry_s, off2 = carry2_s;
+        for (int w = 0; w < wave; ++w) { off += wsum[w]; off2 += wsum2[w]; }
         if (t < T) cum[(size_t)b * Tmax + t] = off + x;
+        if (scum && t < T) scum[(size_t)b * Tmax + t] = off2 + x2;
         __syncthreads();
-        if (tid == 255) carry_s = off + x;
+        if (tid == 255) { carry_s = off + x; carry2_s = off2 + x2; }
         __syncthreads();
     }
     if (tid == 0) {
         const int tt = bad_s ? -1 : (ones ? T : total);
         if (olens) olens[b] = tt;
         if (olens32) olens32[b] = tt;
+        if (so32) so32[b] = carry2_s;
     }
 }
 
@@ -274,6 +279,9 @@ struct TokGatherArgs {
     const float *ebins, *pbins; int nb;
     const float *TE, *TP;               // [n_bins, D]: the embedding tables behind the input layer's weights (TP carries its bias)
     int *qe_rows, *qp_rows;
+    // FS2_VARSHORT: the predictions exist per SHORT row and their buckets were searched there (varshort.h): a frame reads them through f2s [R]
+    // (-1: no short row).  sqe / sqp == nullptr: that index is searched per frame, from es / ps (teacher forcing) or e_rows / p_rows
+    const int *f2s, *sqe, *sqp;
     const float *ln_g2, *ln_b2;         // LayerNorm of the input layer
     const float* pe; const float* pe_alpha; float x_scale;
     float* x0; void* x0p;               // fp32 rows (or nullptr: planes only) and split-bf16 planes of the decoder input
@@ -362,10 +370,12 @@ __global__ __launch_bounds__(256) void dec_in_gather(TokGatherArgs a) {
         return;
     }
     const int b = a.row_seq[row];
-    const float e = a.es ? (pos < a.es_stride ? a.es[(size_t)b * a.es_stride + pos] : 0.f) : a.e_rows[row];
-    const float p = a.ps ? (pos < a.ps_stride ? a.ps[(size_t)b * a.ps_stride + pos] : 0.f) : a.p_rows[row];
-    const int qe = bucket_index(e, a.ebins, a.nb);
-    const int qp = bucket_index(p, a.pbins, a.nb);
+    const int sr = a.f2s ? a.f2s[row] : -1;
+    const bool e_short = a.sqe && sr >= 0, p_short = a.sqp && sr >= 0;
+    const float e = a.es ? (pos < a.es_stride ? a.es[(size_t)b * a.es_stride + pos] : 0.f) : (a.sqe ? 0.f : a.e_rows[row]);
+    const float p = a.ps ? (pos < a.ps_stride ? a.ps[(size_t)b * a.ps_stride + pos] : 0.f) : (a.sqp ? 0.f : a.p_rows[row]);
+    const int qe = e_short ? a.sqe[sr] : bucket_index(e, a.ebins, a.nb);
+    const int qp = p_short ? a.sqp[sr] : bucket_index(p, a.pbins, a.nb);
     if (lane == 0) { if (a.qe_rows) a.qe_rows[row] = qe; if (a.qp_rows) a.qp_rows[row] = qp; }
     const int tk = a.lri[row];
     const float* ph = tk >= 0 ? a.P + (size_t)(a.tok_start[b] + tk) * a.ldp + a.col0 : nullptr;

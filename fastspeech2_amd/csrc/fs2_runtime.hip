@@ -26,6 +26,7 @@
 #include "attn_plan.h"
 #include "common.h"
 #include "elementwise.h"
+#include "varshort.h"
 #include "layout_rule.h"
 #include "layout.h"
 #include "gemm_bf16.h"
@@ -143,6 +144,7 @@ Options& opts() {
         x.nosplitk = env_int("FS2_NOSPLITK", 0) != 0; x.f32_rows = env_int("FS2_F32_ROWS", 0) != 0; x.mt8 = env_int("FS2_MT8", -1); x.qkv_split = env_int("FS2_QKV_SPLIT", -1); x.op_att_planes = env_int("FS2_OP_ATT_PLANES", 0); x.fuse_var = env_int("FS2_FUSE_VAR", 1); x.bal = env_int("FS2_BAL", 0); x.w32 = env_int("FS2_ATTN_W32", -1);
         x.row4 = env_int("FS2_ROW4", -1); x.mt4 = env_int("FS2_MT4", -1); x.ffn2_mx = env_int("FS2_FFN2_MX", 1); x.qkv4 = env_int("FS2_QKV4", -1); x.post_mx = env_int("FS2_POST_MX", 1);
         x.tokproj = env_int("FS2_TOKPROJ", 3) & 3; x.tokproj_f32 = env_int("FS2_TOKPROJ_F32", 0) != 0;
+        x.varshort = env_int("FS2_VARSHORT", 1) != 0;
         if (!audit_clean()) {
             x.w32 = 0; x.row4 = 0; x.qkv4 = 0;
             fprintf(stderr, "libfs2_hip: no clean ISA-audit record of this binary (libfs2_hip.audit.json next to it): attn_w32 and gemm_row4_bf16 are switched "
@@ -947,6 +949,9 @@ struct TokenBufs {
     int* meta; StackBufs sb; float *p0, *p1, *dlog_rows; int64_t* dint; int *cum, *o32;
     float* kp; size_t kp_cap;
     float* tokp;      // tok.proj's output rows (nullptr: this model or precision has none)
+    // the duration scan of the short durations (FS2_VARSHORT), in p0 / p1: the duration predictor's scratch is free once dur.post has run, and nothing of the
+    // workspace may grow (tests: the recorded sizes).  short_buf: they fit
+    int *scum, *so32; bool short_buf;
 };
 
 // The buffers of an FFT-block stack, x0 to xps: contiguous and in this order in both workspaces.  D: the stack's width, Dp: its attention width; hid, x0p, x1p, xps:
@@ -985,6 +990,8 @@ size_t carve_tokens(const fs2_config& c, const fs2_batch& b, const HostLayout& L
     t.kp = bp.take<float>(t.kp_cap);
     // tok.proj's output rows (taken last: every other offset is as it was; none in fp32, which never takes the path)
     t.tokp = (tok_proj_cols(c) && b.precision != FS2_PREC_FP32) ? bp.take<float>(R * (size_t)tok_proj_cols(c)) : nullptr;
+    t.scum = reinterpret_cast<int*>(t.p0); t.so32 = reinterpret_cast<int*>(t.p1);
+    t.short_buf = (size_t)b.B * b.Tmax <= R * (size_t)c.dur_chans && (size_t)b.B <= R * (size_t)c.dur_chans;
     if (tb) *tb = t;
     if (ok) *ok = bp.ok();
     return align_up(bp.off, 256);
@@ -996,6 +1003,12 @@ struct FrameBufs {
     float* kp; size_t kp_cap;
     // reduction_factor r > 1: the Postnet runs on r rows per decoder row (its own row metadata and ping-pong buffers)
     int* meta2 = nullptr; float *pa2 = nullptr, *pb2 = nullptr, *xps2 = nullptr;
+    // FS2_VARSHORT: the short layout (varshort.h: sstart | slen of B, sdims of kDimsInts; per short row position, utterance, token), the frame-to-short map
+    // and the bucket indices per short row.  The short rows are never more than the frame rows: every array holds Rpad.  They live in hfr -- the path runs where
+    // nothing reads the expanded rows (tokproj == 3), so they are not built -- because nothing of the workspace may grow (tests: the recorded sizes); the
+    // predictions per short row take e_rows / p_rows, which then hold nothing else.  short_buf: they fit
+    int *smeta = nullptr, *srow_pos = nullptr, *srow_seq = nullptr, *slri = nullptr, *f2s = nullptr, *sqe = nullptr, *sqp = nullptr;
+    bool short_buf = false;
 };
 
 size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t cap, FrameBufs* fb, bool* ok) {
@@ -1004,6 +1017,13 @@ size_t carve_frames(const fs2_config& c, const HostLayout& L, void* ws, size_t c
     FrameBufs f;
     f.meta = bp.take<int>(layout_dev_ints(L));
     f.hfr = bp.take<float>(R * c.adim);
+    {
+        Bump sh(f.hfr, R * c.adim * sizeof(float));
+        f.smeta = sh.take<int>((size_t)meta_align(2 * (long long)L.B) + kDimsInts);
+        f.srow_pos = sh.take<int>(R); f.srow_seq = sh.take<int>(R); f.slri = sh.take<int>(R); f.f2s = sh.take<int>(R);
+        f.sqe = sh.take<int>(R); f.sqp = sh.take<int>(R);
+        f.short_buf = sh.ok();
+    }
     f.t0 = bp.take<float>(R * c.var_chans);
     f.t1 = bp.take<float>(R * c.var_chans);
     f.e_rows = bp.take<float>(R);
@@ -1080,7 +1100,10 @@ TokGatherArgs tok_gather_args(const fs2_handle* h, const FrameBufs& f, const Dev
 }
 
 // dec.in.gather: bucket search + embedding add + decoder input layer as one row kernel over the token-level products
-int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, TokGatherArgs tg, const FrameBufs& f, bool po) {
+// p.varshort: the predictions are per short row; where they are the source their buckets are searched there first (var_bucket_short: two 255-bin searches per
+// short row instead of per frame), under this launch's profile name, and the row kernel reads the indices through the frame-to-short map
+int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, TokGatherArgs tg, const FrameBufs& f, const DecodePlan& p, int Rs) {
+    const bool po = p.po;
     const fs2_config& c = h->cfg;
     tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
     tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
@@ -1088,6 +1111,14 @@ int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, 
     tg.pe = h->dec.pe; tg.pe_alpha = h->dec.alpha; tg.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
     tg.x0 = po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
     Scope sc(h, s, "dec.in.gather", 0, 4.0 * tg.R * c.ddim * (po ? 2.0 : 3.0));
+    if (p.varshort) {
+        tg.f2s = f.f2s; tg.sqe = p.short_qe ? f.sqe : nullptr; tg.sqp = p.short_qp ? f.sqp : nullptr;
+        if (p.short_qe || p.short_qp) {
+            hipLaunchKernelGGL(var_bucket_short, dim3((Rs + 255) / 256), dim3(256), 0, s, p.short_qe ? f.e_rows : nullptr, p.short_qp ? f.p_rows : nullptr, f.srow_pos, Rs, h->ebins, h->pbins,
+                               c.n_bins - 1, f.sqe, f.sqp);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
     hipLaunchKernelGGL(dec_in_gather, dim3((tg.R + 3) / 4), dim3(256), 0, s, tg);
     HIP_TRY(h, hipGetLastError());
     return FS2_OK;
@@ -1138,8 +1169,17 @@ int decode_outputs(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, const 
     const int* ovf = p.devlay ? dl.dims + 2 : nullptr;
     if (io->after && (rc = unpack<float>(h, s, mel_after, c.odim, dl2.start, dl2.len, B, Lmax * rf, io->after, 0.f, ovf))) return rc;
     if (io->before && (rc = unpack<float>(h, s, f.before, c.odim, dl2.start, dl2.len, B, Lmax * rf, io->before, 0.f, ovf))) return rc;
-    if (io->e_out && (rc = unpack<float>(h, s, f.e_rows, 1, dl.start, lim_msk, B, Lmax, io->e_out, 0.f))) return rc;
-    if (io->p_out && (rc = unpack<float>(h, s, f.p_rows, 1, dl.start, lim_msk, B, Lmax, io->p_out, 0.f))) return rc;
+    if (p.varshort) {      // the predictions exist per short row: expanded through the frame-to-short map, and only here, where a caller asks for them
+        for (int k = 0; k < 2; ++k) {
+            float* dst = k ? io->p_out : io->e_out;
+            if (!dst || (int64_t)B * Lmax == 0) continue;
+            hipLaunchKernelGGL(unpack_short, dim3((unsigned)(((int64_t)B * Lmax + 255) / 256)), dim3(256), 0, s, k ? f.p_rows : f.e_rows, f.f2s, dl.start, lim_msk, B, Lmax, dst);
+            HIP_TRY(h, hipGetLastError());
+        }
+    } else {
+        if (io->e_out && (rc = unpack<float>(h, s, f.e_rows, 1, dl.start, lim_msk, B, Lmax, io->e_out, 0.f))) return rc;
+        if (io->p_out && (rc = unpack<float>(h, s, f.p_rows, 1, dl.start, lim_msk, B, Lmax, io->p_out, 0.f))) return rc;
+    }
     if (io->qe && (rc = unpack<int>(h, s, f.qe, 1, dl.start, lim_len, B, Lmax, io->qe, -1))) return rc;
     if (io->qp && (rc = unpack<int>(h, s, f.qp, 1, dl.start, lim_len, B, Lmax, io->qp, -1))) return rc;
     if (io->lr_index && (rc = unpack<int>(h, s, f.lri, 1, dl.start, dl.vlen, B, Lmax, io->lr_index, -1))) return rc;
@@ -1366,7 +1406,7 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     const StackBufs& sb = t.sb;
     const int tok_regime = regime_rows_of(b, /*token_level=*/true);
     h->cur_regime = tok_regime; h->cur_status = nullptr;
-    const EncodePlan p = plan_encode(c, opts(), b.precision, h->tokw.N, t.tokp != nullptr);
+    const EncodePlan p = plan_encode(c, opts(), b.precision, h->tokw.N, t.tokp != nullptr, t.short_buf && !b.compat_padded);
     int rc;
     DevLayout dl;
     if ((rc = upload_layout(h, s, L, t.meta, dl))) return rc;
@@ -1386,7 +1426,8 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
         hipLaunchKernelGGL(dur_finalize, dim3((n + 255) / 256), dim3(256), 0, s, t.dlog_rows, dl.start, dl.vlen, b.B, b.Tmax, io->d_log, t.dint, io->d_int);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(dur_scan, dim3(b.B), dim3(256), 0, s, io->ds ? io->ds : t.dint, b.Tmax, dl.vlen, t.cum, io->olens, t.o32,
-                           io->duration_alpha > 0.f ? io->duration_alpha : 1.f, io->xs, c.idim);
+                           io->duration_alpha > 0.f ? io->duration_alpha : 1.f, io->xs, c.idim, p.short_scan ? t.scum : nullptr, p.short_scan ? t.so32 : nullptr,
+                           var_window(c));
         HIP_TRY(h, hipGetLastError());
     }
     if (io->enc_out) {
@@ -1399,6 +1440,7 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     e.B = b.B; e.Tmax = b.Tmax; e.compat = b.compat_padded; e.ws = io->workspace;
     e.rows = sb.x0; e.tokP = p.tok_proj ? t.tokp : nullptr; e.tokP_conv = p.tok_conv;
     e.start = dl.start; e.vlen = dl.vlen; e.cum = t.cum; e.o32 = t.o32;
+    if (p.short_scan) { e.scum = t.scum; e.so32 = t.so32; }
     e.valid = true;
     return FS2_OK;
 }
@@ -1460,13 +1502,32 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
     DecIn dec_in;
     if (c.decoder_input_layer) dec_in = DecIn{&h->dec_in, h->dec_in_lng, h->dec_in_lnb, c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim)};
     const float* mel_after = c.postnet_layers > 0 ? f.after : f.before;
-    ask.R = R; ask.after_vec = unpack_vec(c.odim, mel_after, io->after); ask.before_vec = unpack_vec(c.odim, f.before, io->before);
+    ask.R = R; ask.short_buf = f.short_buf; ask.after_vec = unpack_vec(c.odim, mel_after, io->after); ask.before_vec = unpack_vec(c.odim, f.before, io->before);
     const DecodePlan p = plan_decode(c, opts(), b.precision, ask, enc, h->var2.ok, dec_in, h->dec, rows, f.sb);
     const int prec = p.prec;
 
     void* hfr_planes = p.hfr_planes ? f.sb.x1p : nullptr;
     const TokGatherArgs tg = tok_gather_args(h, f, dl, R);
-    if (p.tokproj == 3) {
+    // FS2_VARSHORT: the rows the predictors run on -- at most K frames per phoneme, laid out by lr.index; their count is the device's (sdims), the host
+    // sizes by the bound, and the kernel variants are chosen from the regime estimate at K frames per phoneme
+    const int K = var_window(c);
+    long long phonemes = 0;
+    for (int i = 0; i < b.B; ++i) phonemes += b.ilens[i];
+    const int Rs = p.varshort ? std::min(vs_row_bound(R, phonemes, b.B, K), R) : 0;
+    int* const sdims = f.smeta + meta_align(2 * (long long)b.B);
+    const Rows srows{Rs, rows_padded(Rs), f.srow_pos, sdims, regime_short_rows_of(b, K)};
+    if (p.varshort) {
+        ShortLayoutArgs sl;
+        memset(&sl, 0, sizeof sl);
+        sl.cum = enc.cum; sl.scum = enc.scum; sl.Tmax = b.Tmax; sl.ilen = enc.vlen; sl.so32 = enc.so32;
+        sl.row_pos = dl.row_pos; sl.row_seq = dl.row_seq; sl.vlen = dl.vlen; sl.R = R; sl.ovf = p.devlay ? dl.dims + 2 : nullptr;
+        sl.B = b.B; sl.gap = h->gap; sl.K = K; sl.Rs = Rs; sl.Rs_pad = srows.Rpad;
+        sl.lri = f.lri; sl.f2s = f.f2s; sl.sstart = f.smeta; sl.slen = f.smeta + b.B; sl.sdims = sdims;
+        sl.srow_pos = f.srow_pos; sl.srow_seq = f.srow_seq; sl.slri = f.slri;
+        Scope sc(h, s, "lr.index", 0, 4.0 * (2.0 * R + 3.0 * srows.Rpad));
+        hipLaunchKernelGGL(lr_index_short, dim3((std::max(R, srows.Rpad) + 255) / 256), dim3(256), 0, s, sl);
+        HIP_TRY(h, hipGetLastError());
+    } else if (p.tokproj == 3) {
         Scope sc(h, s, "lr.index", 0, 4.0 * R);
         hipLaunchKernelGGL(lr_index_only, dim3((R + 255) / 256), dim3(256), 0, s, enc.cum, b.Tmax, enc.vlen, dl.row_pos, dl.row_seq, dl.vlen, R, f.lri);
         HIP_TRY(h, hipGetLastError());
@@ -1476,7 +1537,11 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
                            dl.row_pos, dl.row_seq, 0, dl.vlen, R, f.hfr, f.lri, hfr_planes);
         HIP_TRY(h, hipGetLastError());
     }
-    if (p.fused_var) {
+    if (p.varshort) {      // the same launches on the short rows: their metadata, their device row count, their regime
+        TokGatherArgs ts = tg;
+        ts.lri = f.slri; ts.row_pos = f.srow_pos; ts.row_seq = f.srow_seq; ts.R = Rs;
+        if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, srows, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, &ts))) return rc;
+    } else if (p.fused_var) {
         if ((rc = run_predictors_fused(h, s, h->var2, f.hfr, c.adim, rows, hfr_planes, f.sb.xps, f.vp, f.vs, f.e_rows, f.p_rows, prec, (p.tokproj & 1) ? &tg : nullptr))) return rc;
     } else {
         if (p.need_e && (rc = run_predictor(h, s, "energy", h->energy, f.hfr, c.adim, rows, f.t0, f.t1, f.e_rows, prec, hfr_planes, f.sb.xps))) return rc;
@@ -1486,8 +1551,10 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         const ProsodyTrack ctl_p{ctl->pitch_scale, ctl->pitch_shift, ctl->pitch_scale_cols, ctl->pitch_shift_cols};
         const ProsodyTrack ctl_e{ctl->energy_scale, ctl->energy_shift, ctl->energy_scale_cols, ctl->energy_shift_cols};
         const int n = ask.ctl_pitch + ask.ctl_energy;
-        Scope sc(h, s, "var.control", 2.0 * R * n, 4.0 * R * (3.0 + 3.0 * n));
-        hipLaunchKernelGGL(prosody_apply, dim3((R + 255) / 256), dim3(256), 0, s, f.p_rows, f.e_rows, dl.row_pos, dl.row_seq, f.lri, R, b.B, b.Tmax, ctl_p, ctl_e);
+        const int Rc = p.varshort ? Rs : R;      // (the control is a function of utterance and phoneme alone: per short row it is what it is per frame)
+        Scope sc(h, s, "var.control", 2.0 * Rc * n, 4.0 * Rc * (3.0 + 3.0 * n));
+        if (p.varshort) hipLaunchKernelGGL(prosody_apply, dim3((Rs + 255) / 256), dim3(256), 0, s, f.p_rows, f.e_rows, f.srow_pos, f.srow_seq, f.slri, Rs, b.B, b.Tmax, ctl_p, ctl_e);
+        else hipLaunchKernelGGL(prosody_apply, dim3((R + 255) / 256), dim3(256), 0, s, f.p_rows, f.e_rows, dl.row_pos, dl.row_seq, f.lri, R, b.B, b.Tmax, ctl_p, ctl_e);
         HIP_TRY(h, hipGetLastError());
     }
     if (!(p.tokproj & 2)) {
@@ -1497,7 +1564,7 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         HIP_TRY(h, hipGetLastError());
     }
     if (p.tokproj & 2) {
-        if ((rc = dec_in_gather_launch(h, s, io, tg, f, p.po))) return rc;
+        if ((rc = dec_in_gather_launch(h, s, io, tg, f, p, Rs))) return rc;
     } else if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
         if ((rc = launch_step(h, s, nullptr, dec_in_step(dec_in, h->dec, f.hfr, c.adim, hfr_planes, rows, f.sb, prec, p.po), prec))) return rc;
     } else if ((rc = dec_in_pe_launch(h, s, f, dl, R, p.planes))) return rc;
@@ -1771,6 +1838,7 @@ int fs2_set_option(const char* name, int32_t value) {
     else if (n == "FS2_POST_MX") o.post_mx = value != 0;
     else if (n == "FS2_TOKPROJ") o.tokproj = value < 0 ? 3 : (value & 3);
     else if (n == "FS2_TOKPROJ_F32") o.tokproj_f32 = value > 0;
+    else if (n == "FS2_VARSHORT") o.varshort = value != 0;      // (-1: the default, on)
     else return fail(nullptr, FS2_ERR_ARG, "fs2_set_option: unknown option %s", name);
     return FS2_OK;
 }
@@ -1801,6 +1869,7 @@ int fs2_get_option(const char* name, int32_t* value) {
     else if (n == "FS2_POST_MX") *value = o.post_mx;
     else if (n == "FS2_TOKPROJ") *value = o.tokproj;
     else if (n == "FS2_TOKPROJ_F32") *value = o.tokproj_f32;
+    else if (n == "FS2_VARSHORT") *value = o.varshort;
     else return fail(nullptr, FS2_ERR_ARG, "fs2_get_option: unknown option %s", name);
     return FS2_OK;
 }

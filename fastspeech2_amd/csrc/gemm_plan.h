@@ -37,6 +37,8 @@ struct Options {
     int tokproj = 3;     // FS2_TOKPROJ  multiply before expanding (non-fp32 precisions): bit 0 = the predictors' first convolution (where the fused predictors run), bit 1 = the
                          //              decoder input layer from token-level products (tok.proj + var.gather0 / dec.in.gather); 0 = the frame-level launches.  Never a function of the batch.
     int tokproj_f32 = 0; // FS2_TOKPROJ_F32  tok.proj on the exact fp32 GEMM instead of the precision's own arithmetic
+    int varshort = 1;    // FS2_VARSHORT  the fused variance predictors on at most K frames per phoneme (layout_rule.h; where FS2_TOKPROJ = 3 holds and the batch
+                         //               has per-utterance semantics): 0 = on every frame.  Never a function of the batch.
 };
 
 // ------------------------------------------------------------------ the rules
@@ -57,9 +59,13 @@ inline long rows_in_use(const GemmArgs& a, long rows) { return a.regime_rows > 0
 // rounds, and a nearly empty second round costs as much as a full one (c3 at 7.87 frames per phoneme: 286 tiles of 128 rows = 256 + 30).
 // Same-box A/B: a 192-row tile costs 1.55-1.9 x a 128-row one (its epilogue spills), so it pays exactly when it turns two rounds into one
 // (c3: dec.ffn2_ln 0.174 -> 0.134 ms, step 5.68 -> 5.34 ms; c4, 15 rounds against 10: 68.0 -> 70.8 ms, so not there).  Results do not depend on MT.
-inline int row8_mt(long rows) {
+// wgs: workgroups per row tile (the grouped convolution's grid.y).  The rule above counts tiles; a grouped launch whose tiles fit one round while its workgroups do
+// not is in the same position one step earlier -- the fused predictors' second layer on the short rows of FS2_VARSHORT at c3: 175 tiles x 2 groups = 350 workgroups of 128
+// rows against 117 x 2 = 234 of 192 rows; same-box, one stream: 0.092 against 0.070 ms -- and takes the taller tile too.
+inline int row8_mt(long rows, int wgs = 1) {
     const long t128 = (rows + 127) / 128, t192 = (rows + 191) / 192;
-    return (t128 > kCus && t192 <= kCus) ? 3 : 2;
+    if (t128 > kCus && t192 <= kCus) return 3;
+    return (wgs > 1 && t128 * wgs > kCus && t192 * wgs <= kCus) ? 3 : 2;
 }
 
 // gemm_row4_bf16 (gemm_row4.h): one wave per SIMD, 128- or 160-row workgroups, one per CU.  The tile height that minimises rounds x height
@@ -259,7 +265,7 @@ inline GemmPlan plan_gemm(const GemmArgs& a, int precision, const Options& o) {
     if (a.mx == 2 && (!a.x_rowscale || !a.w_rowscale || !a.Xp || p.ksplit > 1)) return refused(kPlanErrState, "%s: the mx4 arithmetic needs mx4 planes with their row scales and the weight image's channel scales");
     p.build_planes = !a.Xp;
     p.nsplit = x3 ? 3 : 1;
-    const int mt8 = (o.mt8 > 0 ? o.mt8 : row8_mt(rows_in_use(a, a.R))) >= 3 ? 3 : 2;
+    const int mt8 = (o.mt8 > 0 ? o.mt8 : row8_mt(rows_in_use(a, a.R), a.k_groups > 1 ? a.k_groups : 1)) >= 3 ? 3 : 2;
     const bool force_mt4 = o.mt4 == 4 || o.mt4 == 5;
     if (mx_row4 || epi >= 0) {
         // The instantiations the library holds (fastspeech2_amd/_audit.py: EXPECTED_KERNELS counts them): EPI 0 x {split-bf16 arithmetic with the residual from

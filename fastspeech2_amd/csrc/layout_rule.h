@@ -133,4 +133,28 @@ struct Meta2 {          // reduction factor r > 1: the Postnet's layout, Rpad2 =
     LR_HD static constexpr long long ints(long long B, long long Rpad2) { return 4 * B + 2 * Rpad2 + kMetaSlack; }
 };
 
+// ---- the variance predictors on at most K frames per phoneme (FS2_VARSHORT; DESIGN.md: "Variance predictors on short rows"), for the host (call_plan.h,
+// fs2_runtime.hip) and the device (varshort.h; elementwise.h: dur_scan); tests/test_varshort_host.py compares it with the rule restated in Python
+// (tests/varshort_probe.cpp).  The length regulator repeats a phoneme's encoder row d times, and a predictor is a stack of convolutions whose outputs are taken
+// per frame: the output at offset o of the phoneme depends on the inputs at most h = sum of the layers' halos (kernel - 1) / 2 frames away, so every frame that
+// has h frames of its own phoneme on both sides sees the same inputs and gives the same output.  The SHORT sequence keeps min(d, K) frames of every phoneme,
+// K = 1 + 2 h: its first h, its last h and one interior frame; the predictor on the short sequence gives, row for row, the values of the full sequence at the
+// kept frames, and every other frame takes the interior one's.
+// K = 1 + sum over the layers of (kernel - 1): `layers` convolutions of `kernel` taps (odd)
+LR_HD constexpr int vs_window(int layers, int kernel) { return 1 + layers * (kernel - 1); }
+// frames a phoneme of d frames keeps
+LR_HD constexpr int vs_short_dur(int d, int K) { return d <= 0 ? 0 : (d < K ? d : K); }
+// offset inside the short phoneme of the frame at offset o (0 <= o < d) of a phoneme of d frames: the first h and the last h keep their
+// distance to their edge, everything between them is the interior frame h; d <= K: nothing is dropped
+LR_HD constexpr int vs_short_offset(int o, int d, int K) {
+    const int h = (K - 1) / 2;
+    return d <= K ? o : (o < h ? o : (o >= d - h ? K - (d - o) : h));
+}
+// rows the short layout takes at most: no phoneme keeps more than K frames and none more than it has, so the short durations sum to at most
+// min(frame bound, K x phonemes) -- the short layout cannot overflow what this sizes, and has no overflow flag
+LR_HD constexpr int vs_row_bound(long long frames_bound, long long phonemes, long long utts, int K) {
+    const long long kp = (long long)K * phonemes;
+    return row_bound(frames_bound < kp ? frames_bound : kp, utts);
+}
+
 }  // namespace fs2

@@ -256,6 +256,7 @@ inline Steps<3> fused_predictor_steps(const FusedPredictors& v, const Predictor&
     auto conv = [&](const Gemm& g, const float* in, int ld, const float* lng, const float* lnb) {
         GemmArgs a = gemm_args(g, in, ld, r.R, r.row_pos, nullptr, g.N);
         a.Rp = r.Rp; a.relu_pre = 1; a.ln_g = lng; a.ln_b = lnb; a.ln_eps = 1e-12f; a.scratch = vs;
+        a.regime_rows = r.regime_rows;      // (the rows' own: the short rows of FS2_VARSHORT are not the call's frame rows)
         return a;
     };
     if (layer0 && row_regime(r.regime_rows ? r.regime_rows : r.R, o.row8) && (chans == 256 || chans == 384)) {

@@ -688,9 +688,12 @@ int fs2_op_label_means(void *stream, const float *x, const int32_t *labels, cons
                        int32_t n_labels, int32_t positive_only, float *mean, int32_t *count);
 
 /* Kernel-choice switches for A/B measurements and tests ("FS2_BM", "FS2_ROW8", "FS2_QKV8", "FS2_NOSPLITK",
- * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX", "FS2_TOKPROJ", "FS2_TOKPROJ_F32"; -1 = automatic).
+ * "FS2_F32_ROWS", "FS2_MT8", "FS2_FUSE_VAR", "FS2_BAL", "FS2_ATTN_W32", "FS2_ROW4", "FS2_MT4", "FS2_QKV4", "FS2_FFN2_MX", "FS2_POST_MX", "FS2_TOKPROJ", "FS2_TOKPROJ_F32", "FS2_VARSHORT"; -1 = automatic).
  * "FS2_TOKPROJ": 0 = frame-level launches, 1 = the predictors' first convolution, 2 = the decoder input layer, 3 (default) = both from the token-level products of fs2_encode
- * (takes effect with the next fs2_encode; fp32 never takes it); "FS2_TOKPROJ_F32": those products on the exact fp32 GEMM.  Their initial values come from the environment variables of the same
+ * (takes effect with the next fs2_encode; fp32 never takes it); "FS2_TOKPROJ_F32": those products on the exact fp32 GEMM.
+ * "FS2_VARSHORT": 1 (default) = the fused variance predictors, the prosody control and the bucket search of the predictions run on at most K = 5 frames per phoneme (the
+ * first two, the last two and one interior frame: every other frame of a phoneme has the interior one's values) wherever FS2_TOKPROJ = 3 holds and the batch has per-utterance
+ * semantics; 0 = on every frame.  Selected by configuration and option alone, never by the batch; takes effect with the next fs2_encode.  Their initial values come from the environment variables of the same
  * names, read once when the library is first used; the launch path never reads the environment. */
 int fs2_set_option(const char *name, int32_t value);
 
