@@ -248,6 +248,9 @@ inline GemmPlan plan_gemm(const GemmArgs& a, int precision, const Options& o) {
     if ((a.residp || (need_rows && !a.Y && a.Yp && !a.dot_w && a.ktaps == 1 && !a.scratch)) && epi < 0)
         return refused(kPlanErrState, "%s: a planes-only launch (residual as planes / no fp32 rows) exists on gemm_row4_bf16 only and this one would not run there");
     if (a.yp_col_off && !(row8 && a.ktaps > 1)) return refused(kPlanErrUnsupported, "%s: a plane column offset exists in the row-complete conv kernel only");
+    // (the slice at offset 0 of such a buffer carries no offset to tell it by: every other kernel zero-pads the plane rows to yp_chunks chunks and would wipe the slices behind it)
+    if (a.Yp && a.yp_chunks * 32 >= a.N + 32 && !(row8 && a.ktaps > 1))
+        return refused(kPlanErrUnsupported, "%s: planes %d columns wide from a launch of %d: filling a slice of a plane row exists in the row-complete conv kernel only", a.yp_chunks * 32, a.N);
     const bool y_needed = (need_rows && !row8) || (!a.Yp && !a.qk_hi && !(row8 && a.dot_w));      // (row-complete + scalar head: nothing but dot_out leaves)
     p.y = a.Y ? RowsOut::Y : ((y_needed && a.scratch) ? RowsOut::Scratch : RowsOut::None);
     if (y_needed && p.y == RowsOut::None) return refused(kPlanErrArg, "%s: no output or scratch buffer");

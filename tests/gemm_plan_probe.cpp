@@ -587,6 +587,7 @@ int refusals() {
     a = conv(); a.ldy = 1022; show("row_stride", a, kBf16x3, o);
     a = big_ln(); a.residp = M; a.residp_chunks = 12; show("planes_only_off_row4", a, kBf16, o);
     a = conv(); a.yp_col_off = 256; show("col_off", a, kBf16x3, o);
+    a = conv(); a.yp_chunks = 64; show("plane_slice", a, kBf16x3, o);      // (the slice at offset 0 of a wider plane row)
     a = conv(); a.Yp = nullptr; show("no_output", a, kBf16x3, o);
     a = base(256, 1, 600, 1000, false); a.Xp = M; a.qk_hi = M; a.att_D = 200; a.Rvt = 1024; show("qkv_split", a, kBf16x3, o);
     a = base(256, 1, 1024, 1000, false); a.Xp = M; a.Yp = M; a.yp_chunks = 32; a.f16_terms = 2; show("f16_non_conv", a, kBf16x3, o);

@@ -12,7 +12,10 @@ formula on the tuples, with the mutants a broken position rule would compute.
 
 CPU-only parts (tests/test_gemm_raw_host.py): the mirror against the compiled header, the encoders, the references, the mutants, and the plan of every block of
 `all_launches()` -- built there with placeholder pointers, which plan_gemm never follows.  GPU parts: `LnCase` / `QkvCase` (tests/test_gpu_row_kernels.py),
-`ConvCase` / `Ffn2Case` / `repack_weight` (tests/test_gpu_mx_kernels.py)."""
+`ConvCase` / `Ffn2Case` / `repack_weight` (tests/test_gpu_mx_kernels.py), `PredCase` (tests/test_gpu_pred_kernels.py).
+
+The LayerNorm-terminated convolutions of the variance predictors (`PRED_CASES`) have their conv weight image (`encode_w_conv`), a row pattern in which row 0 and every
+tile edge are live, their float64 reference (`ref_pred`), the kernels' arithmetic stated in fp32 (`pred_fp32`, from which alone the bars are set) and their mutants here."""
 import collections
 import ctypes as C
 
@@ -47,6 +50,8 @@ class GemmArgs(C.Structure):
 KERNELS = ["none", "rows_f32", "tile_f32", "tile_rows_f32", "pl_bf16", "pl_f16", "pl_mx", "pl_mx4", "row8", "row8c", "row8c_grouped", "row8c_two_ln",
            "row4", "qkv8", "qkv4"]
 Plan = collections.namedtuple("Plan", "kernel nsplit nb bm mt apart epi arith res ksplit rows_pass build_planes")
+PREC_CODE = {"bf16x3": 1, "bf16": 2}      # FS2_PREC_BF16X3 / FS2_PREC_BF16 (include/fs2.h): what the plan is asked under
+PLAN_ERR_UNSUPPORTED = -6                 # FS2_ERR_UNSUPPORTED = kPlanErrUnsupported
 
 
 def rpad(R):
@@ -78,6 +83,16 @@ def encode_planes(hi, lo):
     out[:, :, _POS] = hi.reshape(rows, Cc // 32, 32)
     out[:, :, 32 + _POS] = lo.reshape(rows, Cc // 32, 32)
     return out.reshape(rows, Cc // 32 * 64)
+
+
+def encode_w_conv(hi, lo):
+    """(hi, lo) bf16 [N, C, k] -> the split-bf16 conv weight image [N, C / 32, k, 64] bf16: per (output row, 32-channel chunk, tap) [hi 32 | lo 32], the k-step
+    order chunk * k + tap of repack_weight_bf16 (csrc/gemm_bf16.h).  A grouped layer's image is its groups stacked along N, each over its own C."""
+    N, Cc, k = hi.shape
+    out = torch.empty(N, Cc // 32, k, 64, dtype=torch.bfloat16)
+    out[:, :, :, _POS] = hi.reshape(N, Cc // 32, 32, k).permute(0, 1, 3, 2)
+    out[:, :, :, 32 + _POS] = lo.reshape(N, Cc // 32, 32, k).permute(0, 1, 3, 2)
+    return out
 
 
 def decode_planes(buf, rows, Cc):
@@ -508,10 +523,142 @@ def ffn2_block(Cc, R, rm, p, ka=0, kw=0):
     return a
 
 
-def all_launches(p=None):
-    """[(id, switches, block, expected plan fields)] of every launch the GPU tests send; p: pointers (default: placeholders)."""
-    p = p if p is not None else collections.defaultdict(lambda: 0x1000)
+# ---- the LayerNorm-terminated convolutions of the variance predictors (tests/test_gpu_pred_kernels.py), formed as predictor_step / fused_predictor_steps
+# (csrc/model_launches.h) form them: relu_pre, ln_eps = 1e-12, planes in, a scratch buffer, no fp32 rows out.
+#   mid      a hidden layer: planes out                                                      gemm_row8c_bf16<.., nb, mt, 1>
+#   head     the last layer: the scalar head, nothing but dot_out leaves                      the same
+#   half0/1  energy.conv0 / pitch.conv0: N = 256 into its half of a 512-column plane row     the same, yp_col_off
+#   two_ln   var.conv0: both layers stacked, N = 512, one LayerNorm per 256 columns          gemm_row8c_bf16<.., 4, 2, 2>
+#   grouped  var.conv1: group g contracts channels [g C, (g + 1) C) of the stacked row with its own weights, LayerNorm and head; as in the model it writes
+#            no planes: its two heads are all that leaves                                    gemm_row8c_bf16<.., nb, mt, 1>, grid.y = group
+# and, where the row kernels are switched off, gemm_pl_bf16's conv form + ln_rows, with and without split-K.
+PRED_EPS = 1e-12
+PRED_TOL = MX_CEILING                  # GEMM_TOL["bf16x3"]: the pre-LayerNorm error of the split-bf16 arithmetic on these distributions
+PRED_QUIET = 2.0 ** -10                # the scale of x and bias in the `quiet` variant
+PRED_FORMS = ("mid", "head", "half0", "half1", "two_ln", "grouped")
+# (form, chans, k, R, variant).  R = 333: three 128-row tiles, two of 192 rows, each with a ragged last one; 128: exactly one 128-row tile, a partial one of 192.
+# chans 384: nb = 3.  k = 5: P = 2, the other parity of the A tile's instruction count.  The halves ride on the two_ln cases: the same stacked operands.
+PRED_CASES = ([(f, 256, 3, R, "") for R in (333, 128) for f in ("mid", "head", "two_ln", "grouped")] +
+              [(f, 384, 3, R, "") for R in (333, 128) for f in ("mid", "head", "grouped")] +
+              [(f, 256, 5, R, "") for R in (333, 128) for f in ("mid", "head")] +
+              [(f, 256, 3, 128, "quiet") for f in ("head", "grouped")] +
+              [(f, 256, 3, 128, "dead_window") for f in ("mid", "head")] +
+              [(f, 256, 3, 333, "hi_only") for f in ("mid", "two_ln", "grouped")])
+PRED_IDS = ["%s-c%d-k%d-R%d%s" % (c[:4] + ("-" + c[4] if c[4] else "",)) for c in PRED_CASES]
+# The bars: a share of the ceiling
+#     ceiling(row, col) = PRED_TOL max(1, s rstd |gamma| (2 + |yhat|)),      head: Sum_col ceiling |dot_w| + PRED_TOL
+# (a pre-LayerNorm error d moves LN(y)_i by at most rstd |gamma_i| (2 + |yhat_i|) max |d| to first order, mean |yhat| <= 1; s = 2^-10 in the quiet variant, else 1).
+# The shares come from the reference side alone: 8 x the worst error-to-ceiling ratio of the kernels' arithmetic stated in fp32 on the CPU (pred_fp32: hi.hi + hi.lo +
+# lo.hi, fp32 accumulation, fp32 ReLU / LayerNorm / head, the planes' rounding) over all PRED_CASES -- 8 x because the MFMA and wave-reduction orders differ from
+# torch's -- capped at 1.  Measured (tests/test_gemm_raw_host.py prints them per case): planes 0.01281 (grouped, chans 256, R = 128; every case lies in
+# 0.0065 .. 0.0128), heads 3.64e-4 (head, chans 256, k = 3, R = 333; 2.2e-5 .. 3.6e-4), rounded up.  The GPU's figures do not enter; for the record, its worst
+# error-to-ceiling ratios per form on the MI355X (tests/test_gpu_pred_kernels.py records them): planes mid 0.01132, two_ln 0.01124, the halves 0.01120 (share 0.1026);
+# heads head 3.55e-4, grouped 3.94e-4 (share 2.92e-3).  The planes' figure is mostly the planes' own rounding (2^-17 |v|), the same on both sides.
+PRED_FP32_RATIO = (0.01282, 3.65e-4)
+PRED_BAR_SHARE = min(1.0, 8 * PRED_FP32_RATIO[0])
+PRED_HEAD_SHARE = min(1.0, 8 * PRED_FP32_RATIO[1])
+
+
+def pred_geometry(form, chans):
+    """(C a group contracts, channels of an x row, N of the launch, columns of an output plane row, k_groups, ln_groups)."""
+    if form == "grouped":
+        return chans, 2 * chans, 2 * chans, 2 * chans, 2, 2
+    if form == "two_ln":
+        return chans, chans, 512, 512, 1, 2
+    if form in ("half0", "half1"):
+        return chans, chans, 256, 512, 1, 1
+    return chans, chans, chans, chans, 1, 1
+
+
+def pred_has_planes(form):
+    return form in ("mid", "half0", "half1", "two_ln")
+
+
+def pred_gstride(R):
+    """Floats between the two groups' head arrays: more than R, so that there is a gap between them that must stay untouched."""
+    return rpad(R) + 64
+
+
+def pred_kpart_cap(form, chans, R):
+    return 4 * rpad(R) * pred_geometry(form, chans)[2]
+
+
+def pred_ksplit(Cpad, k, N, R, allowed=3):
+    """csrc/gemm_plan.h: pick_ksplit with an ample kpart_cap (the CPU test holds it against the compiled plan of every split-K block)."""
+    nch, wgs = Cpad // 32, (N + 127) // 128 * ((R + 63) // 64)
+    for cand in (4, 3, 2):
+        if nch % cand == 0 and (nch // cand) * k >= 4 and wgs * cand <= 1024 and cand - 1 <= allowed:
+            return cand
+    return 1
+
+
+def pred_runs(form):
+    """[(run, mt)]: the row kernel at both heights (two_ln exists at 128 rows only), the sibling without and with split-K; with two_ln the two half launches, in
+    the order they are sent: half0 then half1 into one buffer at 128 rows, half1 then half0 into another at 192."""
+    runs = ([("row", 2)] if form == "two_ln" else [("row", 2), ("row", 3)]) + [("sib", 0), ("sibk", 0)]
+    return runs + ([("half0", 2), ("half1", 2), ("half1", 3), ("half0", 3)] if form == "two_ln" else [])
+
+
+def pred_options(run, mt):
+    return {"FS2_ROW8": 0} if run in ("sib", "sibk") else {"FS2_ROW8": 1, "FS2_MT8": mt}
+
+
+def pred_precision(variant):
+    return "bf16" if variant == "hi_only" else "bf16x3"
+
+
+def pred_expected(form, chans, k, R, variant, run, mt):
+    """The plan of one run: every field the GPU test asserts."""
+    f = form if run in ("row", "sib", "sibk") else run
+    Cg, _, N, _, kg, _ = pred_geometry(f, chans)
+    ns = 1 if variant == "hi_only" else 3
+    if run in ("sib", "sibk"):
+        return dict(kernel="pl_bf16", bm=64, nsplit=ns, ksplit=pred_ksplit(Cg, k, N, R) if run == "sibk" else 1, rows_pass=1, build_planes=0)
+    kernel = {"two_ln": "row8c_two_ln", "grouped": "row8c_grouped"}.get(f, "row8c")
+    return dict(kernel=kernel, nb=4 if f == "two_ln" else (3 if N // kg == 384 else 2), mt=mt, nsplit=ns, ksplit=1, rows_pass=0, build_planes=0)
+
+
+def pred_block(form, chans, k, R, p, split=False):
+    """The argument block of one predictor conv launch; p: name -> pointer (int) of the case's buffers (the halves take their slices of the stacked ones);
+    split: the call's split-K scratch named, three partial buffers allowed (call_defaults)."""
+    Cg, Cx, N, Nrow, kg, lg = pred_geometry(form, chans)
+    half = 1 if form == "half1" else 0
+    a = GemmArgs()
+    a.C = a.Cpad = Cg
+    a.ldx, a.ktaps, a.N, a.R, a.ldy = Cx, k, N, R, N
+    a.W = a.Wb = p["w"] + half * 256 * (Cg // 32) * k * 128
+    a.Xp, a.row_pos = p["x"], p["pos"]
+    a.bias, a.ln_g, a.ln_b = p["bias"] + half * 1024, p["gamma"] + half * 1024, p["beta"] + half * 1024
+    a.relu_pre, a.ln_eps, a.x_scale = 1, PRED_EPS, 1.0
+    a.scratch = p["scratch"]
+    if pred_has_planes(form):
+        a.Yp, a.yp_chunks, a.yp_col_off = p["yp"], Nrow // 32, half * 256
+    else:
+        a.dot_w, a.dot_b, a.dot_out = p["dot_w"], p["dot_b"], p["dot_out"]
+    if lg > 1:
+        a.ln_groups = lg
+    if kg > 1:
+        a.k_groups, a.xp_row_chunks, a.dot_gstride = kg, Cx // 32, pred_gstride(R)
+    if split:
+        a.kpart, a.kpart_cap, a.ksplit = p["kpart"], pred_kpart_cap(form, chans, R), 3
+    return a
+
+
+def pred_launches(p):
     out = []
+    for (form, chans, k, R, variant), cid in zip(PRED_CASES, PRED_IDS):
+        for run, mt in pred_runs(form):
+            want = pred_expected(form, chans, k, R, variant, run, mt)
+            want["precision"] = pred_precision(variant)
+            out.append(("pred-%s-%s-mt%d" % (cid, run, mt), pred_options(run, mt), pred_block(form if run in ("row", "sib", "sibk") else run, chans, k, R, p, split=run == "sibk"), want))
+    return out
+
+
+def all_launches(p=None):
+    """[(id, switches, block, expected plan fields)] of every launch the GPU tests send; p: pointers (default: placeholders).  Expected fields: those of `Plan`;
+    "precision" (default "bf16x3") is the precision the launch is sent with, not a field of the plan."""
+    p = p if p is not None else collections.defaultdict(lambda: 0x1000)
+    out = pred_launches(p)
     for arith in CONV_ARITHS:
         for k, N, R in CONV_CASES:
             for o in CONV_OUTS:
@@ -759,6 +906,188 @@ class Ffn2Operands:
         return self.formula(*mutant_mx(self.x, self.w, which), self.resid_value)
 
 
+# ---- the predictors' conv launches: operands, the float64 reference, the fp32 statement, the mutants
+def pred_positions(R):
+    """Row 0 is live, so that the tap at row -1 lies in front of the buffer: 105-row "utterances" with 4 gap rows behind each ((r + 4) % 109 < 4); rows >= R
+    are gaps.  The rows on both sides of the tile edges 127 / 128, 191 / 192, 255 / 256 and the last row (R = 333, 128) are live with live neighbours: every
+    halo tap at a tile edge and at R - 1 counts."""
+    r = torch.arange(rpad(R))
+    return torch.where(((r + 4) % 109 < 4) | (r >= R), torch.full_like(r, -1), (r + 4) % 109 - 4).int()
+
+
+PredRef = collections.namedtuple("PredRef", "v head rstd yhat")      # [R, N], [R, G] or None, [R, G], [R, N]
+
+
+def pred_conv(x, w, bias, k_groups=1, front=None):
+    """y = bias + Sum_tap Sum_c w[n, c, tap] x[r + tap - P, c] with zeros outside [0, R); group g of a grouped layer contracts channels [g C, (g + 1) C) of the
+    row.  float64 [R, N].  front: P rows that stand in front of row 0 instead of zeros (a mutant)."""
+    R, (N, Cg, k) = x.shape[0], w.shape
+    P = (k - 1) // 2
+    pad = torch.zeros(P, x.shape[1], dtype=torch.float64)
+    xx = torch.cat([pad if front is None else front, x, pad])
+    Ng = N // k_groups
+    y = bias.unsqueeze(0).expand(R, N).clone()
+    for g in range(k_groups):
+        for tap in range(k):
+            y[:, g * Ng:(g + 1) * Ng] += xx[tap:tap + R, g * Cg:(g + 1) * Cg] @ w[g * Ng:(g + 1) * Ng, :, tap].t()
+    return y
+
+
+def pred_rows(y, gamma, beta, pos, ln_groups=1, dot_w=None, dot_b=None, eps=PRED_EPS, relu=True, head_groups=None):
+    """ReLU -> LayerNorm over each group's N / G columns -> gamma, beta; gap rows zero; the head of group g = v . dot_w[g] + dot_b[g].  Also rstd and the
+    normalised rows: the bars need them."""
+    R, N = y.shape
+    G = ln_groups
+    if relu:
+        y = y.clamp(min=0.0)
+    yg = y.reshape(R, G, N // G)
+    mu = yg.mean(2, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((yg - mu) ** 2).mean(2, keepdim=True) + eps)
+    yhat = ((yg - mu) * rstd).reshape(R, N)
+    live = (pos >= 0).unsqueeze(1)
+    v = (yhat * gamma + beta) * live
+    head = None
+    if dot_w is not None:
+        H = head_groups or G
+        head = ((v * dot_w).reshape(R, H, N // H).sum(2) + dot_b[:H]) * live
+    return PredRef(v, head, rstd.reshape(R, G), yhat)
+
+
+def ref_pred(x, w, bias, gamma, beta, pos, k_groups=1, ln_groups=1, dot_w=None, dot_b=None):
+    """The predictors' conv layer in float64 on the values the kernels see."""
+    return pred_rows(pred_conv(x, w, bias, k_groups), gamma, beta, pos, ln_groups, dot_w, dot_b)
+
+
+class PredOperands:
+    """Operands of one predictor conv case on the CPU: x and w as exact bf16 pairs (the `_uni` distributions, w at 1 / sqrt(C k), dot_w at 1 / sqrt(N)), x zero in
+    gap rows (the contract of the packed layout), the float64 result, the ceilings of the bars.  The halves of a two_ln case are slices of these.
+    quiet: x and bias x 2^-10 exactly (every product and sum scales exactly in fp32, the row variance is ~5e-8: far below 1e-5, far above 1e-12).
+    dead_window: bias = -0.5 - |u| and 2 P + 3 zero x rows inside the first utterance: the rows whose whole window is zero (`dead`) have every output <= 0 in front
+    of the ReLU, variance exactly 0, rstd = 1e6, and the result exactly beta.   hi_only: every lo half zero (the one-term kernels are exact on such operands)."""
+
+    def __init__(self, form, chans, k, R, variant=""):
+        assert form in ("mid", "head", "two_ln", "grouped") and variant in ("", "quiet", "dead_window", "hi_only") and (form != "two_ln" or chans == 256)
+        self.form, self.chans, self.k, self.R, self.variant = form, chans, k, R, variant
+        self.Cg, self.Cx, self.N, self.Nrow, self.kg, self.lg = pred_geometry(form, chans)
+        self.P = P = (k - 1) // 2
+        rs = np.random.RandomState(7000 + 1000 * PRED_FORMS.index(form) + 10 * chans + 100 * k + R)      # (a variant changes the loud case's operands)
+        Rp, N = rpad(R), self.N
+        self.pos = pred_positions(R)
+        x = _uni(rs, Rp, self.Cx)
+        x = torch.where((self.pos >= 0).unsqueeze(1), x, torch.zeros_like(x))
+        w = _uni(rs, N, self.Cg, k, scale=1.0 / np.sqrt(self.Cg * k))
+        self.bias, self.gamma, self.beta = _uni(rs, N, scale=0.5), 1.0 + _uni(rs, N, scale=0.2), _uni(rs, N, scale=0.2)
+        self.dot_w, self.dot_b = _uni(rs, N, scale=1.0 / np.sqrt(N // self.lg)), _uni(rs, 2, scale=0.5)
+        self.s, self.dead = 1.0, []
+        if variant == "dead_window":
+            self.bias = -0.5 - self.bias.abs()
+            x[40:40 + 2 * P + 3] = 0.0
+            self.dead = list(range(40 + P, 40 + P + 3))
+        if variant == "quiet":
+            self.s = PRED_QUIET
+            x, self.bias = x * PRED_QUIET, self.bias * PRED_QUIET
+        self.x, self.w = split_bf16(x), split_bf16(w)
+        if variant == "hi_only":
+            self.x, self.w = (self.x[0], torch.zeros_like(self.x[1])), (self.w[0], torch.zeros_like(self.w[1]))
+        self.xv, self.wv = pair_value(*self.x)[:R], pair_value(*self.w)
+        self.has_head = not pred_has_planes(form)
+        self.ref = self.rows(self.conv())
+        # the ceilings (see PRED_BAR_SHARE)
+        rstd = self.ref.rstd.repeat_interleave(N // self.lg, dim=1)
+        self.ceiling = PRED_TOL * (self.s * rstd * self.gamma.double().abs() * (2.0 + self.ref.yhat.abs())).clamp(min=1.0)
+        self.head_ceiling = (self.ceiling * self.dot_w.double().abs()).reshape(R, self.lg, -1).sum(2) + PRED_TOL
+
+    def conv(self, x=None, w=None, bias=None, **kw):
+        return pred_conv(self.xv if x is None else x, self.wv if w is None else w, self.bias.double() if bias is None else bias, self.kg, **kw)
+
+    def rows(self, y, **kw):
+        args = dict(ln_groups=self.lg, dot_w=self.dot_w.double() if self.has_head else None, dot_b=self.dot_b.double() if self.has_head else None)
+        args.update(kw)
+        return pred_rows(y, self.gamma.double(), self.beta.double(), self.pos[:self.R], **args)
+
+    def bars(self):
+        """(the planes' bar [R, N], the heads' [R, G])."""
+        return PRED_BAR_SHARE * self.ceiling, PRED_HEAD_SHARE * self.head_ceiling
+
+    def ksplit(self):
+        return pred_ksplit(self.Cg, self.k, self.N, self.R)
+
+    # what a kernel with one broken rule would compute (tests/test_gemm_raw_host.py holds every one at >= 8 bars on the rows it concerns)
+    def mutants(self):
+        m = ["taps_reversed", "row0_front", "no_relu", "relu_per_partial"] + (["edge_plus_tap"] if self.R > 256 else []) + (["eps_1e-5"] if self.variant == "quiet" else [])
+        return m + (["one_ln"] if self.lg > 1 else []) + (["groups_crossed", "head_bias0", "head_swapped"] if self.kg > 1 else [])
+
+    def mutant(self, which):
+        """-> (PredRef of the mutant, the rows it concerns or None for all)."""
+        R, P, k = self.R, self.P, self.k
+        if which == "taps_reversed":
+            return self.rows(self.conv(w=self.wv.flip(2))), None
+        if which == "row0_front":              # the taps in front of row 0 read rows that are not zero
+            return self.rows(self.conv(front=self.xv[P + 1:2 * P + 1])), list(range(P))
+        if which == "edge_plus_tap":           # the taps behind the row just below a tile edge (128, 192, 256 rows) are missing: the halo rows of the A tile
+            edge = [e - 1 for e in (128, 192, 256) if e < R]
+            w0 = self.wv.clone()
+            w0[:, :, P + 1:] = 0.0
+            y = self.conv()
+            y[edge] = self.conv(w=w0)[edge]
+            return self.rows(y), edge
+        if which == "groups_crossed":          # the groups contract each other's channels
+            return self.rows(self.conv(x=torch.cat([self.xv[:, self.Cg:], self.xv[:, :self.Cg]], dim=1))), None
+        if which == "one_ln":                  # one LayerNorm over all the columns of a row
+            return self.rows(self.conv(), ln_groups=1, head_groups=self.lg), None
+        if which == "eps_1e-5":
+            return self.rows(self.conv(), eps=1e-5), None
+        if which == "no_relu":
+            return self.rows(self.conv(), relu=False), None
+        if which == "relu_per_partial":        # ReLU on each split-K partial sum (the chunks split as pick_ksplit splits them; bias with the first) before they are added
+            cand = self.ksplit()
+            assert cand > 1
+            per = self.Cg // cand
+            y = torch.zeros(R, self.N, dtype=torch.float64)
+            for z in range(cand):
+                keep = torch.zeros(self.Cx, dtype=torch.bool)
+                for g in range(self.kg):
+                    keep[g * self.Cg + z * per:g * self.Cg + (z + 1) * per] = True
+                y += self.conv(x=self.xv * keep, bias=self.bias.double() * (z == 0)).clamp(min=0.0)
+            return self.rows(y), None
+        if which == "head_bias0":              # dot_b[0] for dot_b[g]
+            return self.rows(self.conv(), dot_b=self.dot_b.double()[[0, 0]]), None
+        if which == "head_swapped":            # each head written to the other group's array
+            r = self.rows(self.conv())
+            return r._replace(head=r.head.flip(1)), None
+        raise KeyError(which)
+
+    def distance(self, other, rows=None):
+        """The worst |other - ref| in bars over `rows`: of the planes where the form writes planes, else of the heads."""
+        bar_v, bar_h = self.bars()
+        q = ((other.head - self.ref.head).abs() / bar_h) if self.has_head else ((other.v - self.ref.v).abs() / bar_v)
+        return float((q if rows is None else q[rows]).max())
+
+
+def pred_fp32(ops):
+    """The kernels' arithmetic stated in fp32 on the CPU: hi.hi + hi.lo + lo.hi with fp32 accumulation, fp32 ReLU / LayerNorm (two passes) / head; the values as
+    the planes hold them (hi + lo of the fp32 result).  -> (v float64 [R, N], head float64 [R, G] or None)."""
+    R, N, Cg, k, P = ops.R, ops.N, ops.Cg, ops.k, ops.P
+    pad = torch.zeros(P, ops.Cx)
+    xh, xl = (torch.cat([pad, t[:R].float(), pad]) for t in ops.x)
+    wh, wl = ops.w[0].float(), ops.w[1].float()
+    Ng = N // ops.kg
+    y = ops.bias.unsqueeze(0).expand(R, N).clone()
+    for g in range(ops.kg):
+        cs, ns = slice(g * Cg, (g + 1) * Cg), slice(g * Ng, (g + 1) * Ng)
+        for tap in range(k):
+            ah, al = xh[tap:tap + R, cs], xl[tap:tap + R, cs]
+            y[:, ns] += al @ wh[ns, :, tap].t() + ah @ wl[ns, :, tap].t() + ah @ wh[ns, :, tap].t()
+    y = y.clamp(min=0.0).reshape(R, ops.lg, N // ops.lg)
+    mu = y.mean(2, keepdim=True)
+    rstd = 1.0 / torch.sqrt(((y - mu) ** 2).mean(2, keepdim=True) + torch.tensor(PRED_EPS, dtype=torch.float32))
+    live = (ops.pos[:R] >= 0).unsqueeze(1)
+    zero = torch.zeros(1)
+    v = torch.where(live, ((y - mu) * rstd).reshape(R, N) * ops.gamma + ops.beta, zero)                   # (+0.0 in gap rows, as the kernels write it)
+    head = torch.where(live, (v * ops.dot_w).reshape(R, ops.lg, -1).sum(2) + ops.dot_b[:ops.lg], zero) if ops.has_head else None
+    return pair_value(*split_bf16(v)), (None if head is None else head.double())
+
+
 # ------------------------------------------------------------------ device side
 def _dev():
     return torch.device("cuda:0")
@@ -871,6 +1200,40 @@ class Ffn2Case:
         p.update(x=x.data_ptr(), w=w.data_ptr(), yp=yp.data_ptr())
         plan = launch(ln_block("epi0_res2", o.R, o.C, "row4", p, rm=o.rm))
         return plan, yp.cpu()
+
+
+class PredCase:
+    """One predictor conv case on the GPU: the operands uploaded once, one run per entry of pred_runs into fresh sentinel buffers (the second half launch of a pair
+    into the buffer of the first).  Behind row R the x planes hold 0xFF (NaN): the kernels have to take the rows outside [0, R) for zeros without reading them."""
+
+    def __init__(self, ops):
+        self.ops = o = ops
+        d = _dev()
+        xp = encode_planes(*o.x).contiguous()
+        xp.view(torch.uint8)[o.R:] = 0xFF
+        self.keep = dict(x=xp.to(d), w=encode_w_conv(*o.w).to(d), pos=o.pos.to(d), bias=o.bias.to(d), gamma=o.gamma.to(d), beta=o.beta.to(d),
+                         dot_w=o.dot_w.to(d), dot_b=o.dot_b.to(d))
+        Rp = rpad(o.R)
+        self.gstride = pred_gstride(o.R)
+        self.yp_bytes, self.dot_bytes, self.scratch_bytes = Rp * o.Nrow * 4, 2 * self.gstride * 4, Rp * o.N * 4
+        self.kpart_bytes = pred_kpart_cap(o.form, o.chans, o.R) * 4
+
+    def run(self, run, mt, set_option, yp=None):
+        """-> (plan, {yp, dot, scratch, kpart: bytes on the CPU, with guard}, the planes buffer on the device)."""
+        o = self.ops
+        for k, v in pred_options(run, mt).items():
+            set_option(k, v)
+        yp = sentinel(self.yp_bytes) if yp is None else yp
+        out = dict(yp=yp, dot=sentinel(self.dot_bytes), scratch=sentinel(self.scratch_bytes), kpart=sentinel(self.kpart_bytes))
+        p = {k: t.data_ptr() for k, t in self.keep.items()}
+        p.update(yp=yp.data_ptr(), dot_out=out["dot"].data_ptr(), scratch=out["scratch"].data_ptr(), kpart=out["kpart"].data_ptr())
+        form = o.form if run in ("row", "sib", "sibk") else run
+        plan = launch(pred_block(form, o.chans, o.k, o.R, p, split=run == "sibk"), pred_precision(o.variant))
+        return plan, {k: t.cpu() for k, t in out.items()}, yp
+
+    def heads(self, dot):
+        """The bytes of the dot_out buffer -> fp32 [2, gstride]: group g's array in row g."""
+        return dot[:self.dot_bytes].view(torch.float32).reshape(2, self.gstride)
 
 
 def repack_weight(w, fmt):

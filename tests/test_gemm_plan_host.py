@@ -301,6 +301,7 @@ REFUSALS = {
     "row_stride": (ERR_UNSUPPORTED, "x: bf16 path needs row strides that are multiples of 4"),
     "planes_only_off_row4": (ERR_STATE, "x: a planes-only launch (residual as planes / no fp32 rows) exists on gemm_row4_bf16 only and this one would not run there"),
     "col_off": (ERR_UNSUPPORTED, "x: a plane column offset exists in the row-complete conv kernel only"),
+    "plane_slice": (ERR_UNSUPPORTED, "x: planes 2048 columns wide from a launch of 1024: filling a slice of a plane row exists in the row-complete conv kernel only"),
     "no_output": (ERR_ARG, "x: no output or scratch buffer"),
     "qkv_split": (ERR_UNSUPPORTED, "x: fused QKV split needs D % 128 == 0"),
     "f16_non_conv": (ERR_UNSUPPORTED, "x: the fp16 arithmetic exists for plain convolutions only"),

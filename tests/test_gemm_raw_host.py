@@ -1,4 +1,4 @@
-"""CPU checks of tests/gemm_raw.py, the helper of the kernel-level GEMM tests (tests/test_gpu_row_kernels.py): all of them must pass before a block
+"""CPU checks of tests/gemm_raw.py, the helper of the kernel-level GEMM tests (tests/test_gpu_row_kernels.py, ..._mx_kernels.py, ..._pred_kernels.py): all of them must pass before a block
 is sent to a GPU.
 
 (a) the ctypes mirror of fs2::GemmArgs against csrc/gemm_args.h as the host compiler lays it out (tests/gemm_raw_probe.cpp), and the kernel names
@@ -10,7 +10,11 @@ is sent to a GPU.
     epilogue, residual form and tile height, and no refusal;
 (e) the formats of the mixed modes (tests/test_gpu_mx_kernels.py): the e2m1 codec, the scale rule against csrc/common.h compiled for the host, the byte positions
     of the mx4 planes, their scale record, both weight images and the scale image written out again element by element, the formulas near the ideal product,
-    and DISCRIMINATION: every mutant of a formula -- what a kernel with one broken position rule would compute -- at 8 bars or more from it."""
+    and DISCRIMINATION: every mutant of a formula -- what a kernel with one broken position rule would compute -- at 8 bars or more from it;
+(f) the variance predictors' conv launches (tests/test_gpu_pred_kernels.py): the conv weight image against repack_weight_bf16's index arithmetic, the row pattern,
+    ref_pred against F.conv1d + F.layer_norm utterance by utterance, the variants, the fp32 statement below an eighth of the bars, every mutant at 8 bars or more on
+    the rows it concerns, and the refusal of a half launch where the row-complete conv kernel does not run."""
+import collections
 import ctypes
 import os
 import subprocess
@@ -158,22 +162,31 @@ def test_operands_are_exact_pairs_on_the_tested_distributions():
     assert G.rpad(333) == 576 and G.rpad(128) == 384
 
 
+def _plans(probe, tmp_path, launches):
+    """The compiled plan of every (id, switches, block, expected) under its switches and its precision: {id: {field: value, "err": code}}."""
+    path = tmp_path / "blocks.txt"
+    with open(path, "w") as f:
+        for name, opts, block, want in launches:
+            f.write("%s %d %s %s\n" % (name, G.PREC_CODE[want.get("precision", "bf16x3")], ",".join("%s=%d" % kv for kv in sorted(opts.items())) or "-", bytes(block).hex()))
+    fields = ("kernel",) + G.Plan._fields[1:] + ("err",)
+    return {l[0]: dict(zip(fields, [l[1]] + [int(v) for v in l[2:]])) for l in probe("plans", path)}
+
+
 def test_every_block_the_gpu_tests_send_plans_onto_the_expected_kernel(probe, tmp_path):
     launches = G.all_launches()
     n_mixed = len(G.CONV_ARITHS) * len(G.CONV_CASES) * len(G.CONV_OUTS) + 2 * len(G.EPI4_CASES) + 3 * len(G.FFN2_CASES)
-    assert len(launches) == 4 * len(G.LN_CASES) + sum(len(r) for r in G.QKV_RUNS.values()) + n_mixed and len({l[0] for l in launches}) == len(launches)
-    path = tmp_path / "blocks.txt"
-    with open(path, "w") as f:
-        for name, opts, block, _ in launches:
-            f.write("%s 1 %s %s\n" % (name, ",".join("%s=%d" % kv for kv in sorted(opts.items())) or "-", bytes(block).hex()))
-    fields = ("kernel",) + G.Plan._fields[1:] + ("err",)
-    got = {l[0]: dict(zip(fields, [l[1]] + [int(v) for v in l[2:]])) for l in probe("plans", path)}
+    n_pred = sum(len(G.pred_runs(c[0])) for c in G.PRED_CASES)
+    assert len(launches) == 4 * len(G.LN_CASES) + sum(len(r) for r in G.QKV_RUNS.values()) + n_mixed + n_pred and len({l[0] for l in launches}) == len(launches)
+    got = _plans(probe, tmp_path, launches)
     assert sorted(got) == sorted(l[0] for l in launches)
     for name, _, _, want in launches:
+        want = {k: v for k, v in want.items() if k != "precision"}
         assert got[name]["err"] == 0, (name, got[name])
         assert {k: got[name][k] for k in want} == want, (name, got[name])
-        # (the conv in the mx arithmetics has one MFMA term per unit kind: its plan says nsplit 1, and the block's expectation names it)
-        assert got[name]["nsplit"] == want.get("nsplit", 3) and got[name]["ksplit"] == 1 and not got[name]["rows_pass"] and not got[name]["build_planes"], (name, got[name])
+        # (the conv in the mx arithmetics has one MFMA term per unit kind: its plan says nsplit 1, and the block's expectation names it; the predictors' siblings
+        #  name their split-K and their rows pass)
+        assert got[name]["nsplit"] == want.get("nsplit", 3) and got[name]["ksplit"] == want.get("ksplit", 1), (name, got[name])
+        assert got[name]["rows_pass"] == want.get("rows_pass", 0) and not got[name]["build_planes"], (name, got[name])
     # every instantiation family the issue names is reached: both heights of the four row4 forms, the QKV passes on it, gemm_qkv8_bf16 whole and apart
     reached = {(g["kernel"], g["epi"], g["res"], g["mt"], g["apart"]) for g in got.values()}
     for epi, res in ((0, 1), (0, 2), (1, 1), (2, 3), (4, 1)):
@@ -362,3 +375,180 @@ def test_e4m3_cells_contain_what_rounds_to_them():
     lo, hi = G.e4m3_cell(b)
     assert bool(((v.double() >= lo) & (v.double() <= hi)).all())
     assert bool((hi - lo <= 32.0).all()) and bool((lo <= G.e4m3_value(b)).all()) and bool((G.e4m3_value(b) <= hi).all())
+
+
+# ------------------------------------------------------------------ the variance predictors' conv launches (tests/test_gpu_pred_kernels.py)
+_pred_cache = {}
+
+
+def _pred_ops(case):
+    if case not in _pred_cache:
+        _pred_cache[case] = G.PredOperands(*case)
+    return _pred_cache[case]
+
+
+def test_conv_weight_image_round_trip_and_byte_positions():
+    """encode_w_conv against repack_weight_bf16's index arithmetic (csrc/gemm_bf16.h) written out again; at k = 1 the image is encode_planes'."""
+    rs = np.random.RandomState(6)
+    N, Cc, k = 6, 96, 3
+    hi, lo = G.split_bf16(torch.from_numpy(rs.uniform(-1, 1, size=(N, Cc, k)).astype(np.float32)))
+    img = G.encode_w_conv(hi, lo)
+    assert img.shape == (N, Cc // 32, k, 64) and img.dtype == torch.bfloat16
+    raw = img.view(torch.int16).numpy().view(np.uint16).reshape(-1)
+    hb, lb = hi.view(torch.int16).numpy().view(np.uint16), lo.view(torch.int16).numpy().view(np.uint16)
+    nchunks = Cc // 32
+    seen = set()
+    for n in range(N):
+        for chunk in range(nchunks):
+            for tap in range(k):
+                for kk in range(32):
+                    c = chunk * 32 + _kperm(kk)
+                    base = ((n * nchunks + chunk) * k + tap) * 64
+                    assert raw[base + kk] == hb[n, c, tap] and raw[base + 32 + kk] == lb[n, c, tap]
+                    seen.add((n, c, tap))
+    assert len(seen) == N * Cc * k
+    # round trip: the positions are a bijection
+    back_hi = img[:, :, :, G._POS].permute(0, 1, 3, 2).reshape(N, Cc, k)
+    back_lo = img[:, :, :, 32 + G._POS].permute(0, 1, 3, 2).reshape(N, Cc, k)
+    assert torch.equal(back_hi.view(torch.int16), hi.view(torch.int16)) and torch.equal(back_lo.view(torch.int16), lo.view(torch.int16))
+    h1, l1 = hi[:, :, :1].contiguous(), lo[:, :, :1].contiguous()
+    assert torch.equal(G.encode_w_conv(h1, l1).reshape(N, -1).view(torch.int16), G.encode_planes(h1[:, :, 0], l1[:, :, 0]).view(torch.int16))
+    # a grouped layer: the image of the stacked weights is the groups' images stacked along N
+    assert torch.equal(img[3:].view(torch.int16), G.encode_w_conv(hi[3:], lo[3:]).view(torch.int16))
+
+
+def test_pred_row_pattern_keeps_every_boundary_row_live():
+    for R in (333, 128):
+        pos = G.pred_positions(R)
+        live = pos >= 0
+        assert pos.numel() == G.rpad(R) and bool((pos[R:] == -1).all()) and int(pos[0]) == 0
+        for r in [0, R - 1] + [e + d for e in (128, 192, 256) for d in (-1, 0) if e < R]:
+            assert bool(live[r]) and (r == 0 or bool(live[r - 1])) and (r == R - 1 or bool(live[r + 1])), (R, r)
+        gaps = [r for r in range(R) if not bool(live[r])]
+        assert gaps == [r for r in range(R) if (r + 4) % 109 < 4] and len(gaps) == (12 if R == 333 else 4)
+        # positions count up inside an utterance
+        assert all(int(pos[r]) == int(pos[r - 1]) + 1 for r in range(1, R) if bool(live[r]) and bool(live[r - 1]))
+    assert sorted({c[3] for c in G.PRED_CASES}) == [128, 333] and len(G.PRED_IDS) == len(set(G.PRED_IDS)) == len(G.PRED_CASES) == 25
+
+
+@pytest.mark.parametrize("case", [("mid", 256, 3, 333, ""), ("head", 256, 5, 128, ""), ("two_ln", 256, 3, 333, ""), ("grouped", 384, 3, 333, ""), ("grouped", 256, 3, 128, "quiet"),
+                                  ("head", 256, 3, 128, "dead_window")], ids=lambda c: "-".join(str(v) for v in c if v != ""))
+def test_pred_reference_against_conv1d_and_layer_norm(case):
+    """ref_pred against F.conv1d + F.layer_norm in float64, utterance by utterance (each on its own: what the zero gap rows of the packed layout stand for)."""
+    o = _pred_ops(case)
+    R, k, P, Ng, Nl = o.R, o.k, o.P, o.N // o.kg, o.N // o.lg
+    live = (o.pos[:R] >= 0)
+    starts = [r for r in range(R) if bool(live[r]) and (r == 0 or not bool(live[r - 1]))]
+    assert len(starts) == (4 if R == 333 else 2)
+    want_v, want_h = torch.zeros(R, o.N, dtype=torch.float64), torch.zeros(R, o.lg, dtype=torch.float64)
+    for s in starts:
+        e = s
+        while e < R and bool(live[e]):
+            e += 1
+        xu = o.xv[s:e].t().unsqueeze(0)                                                    # [1, Cx, L]
+        y = torch.cat([F.conv1d(xu[:, g * o.Cg:(g + 1) * o.Cg], o.wv[g * Ng:(g + 1) * Ng], o.bias.double()[g * Ng:(g + 1) * Ng], padding=P) for g in range(o.kg)], dim=1)[0].t()
+        y = torch.relu(y)
+        for g in range(o.lg):
+            cs = slice(g * Nl, (g + 1) * Nl)
+            v = F.layer_norm(y[:, cs], (Nl,), o.gamma.double()[cs], o.beta.double()[cs], 1e-12)
+            want_v[s:e, cs] = v
+            want_h[s:e, g] = v @ o.dot_w.double()[cs] + o.dot_b.double()[g]
+    assert float((o.ref.v - want_v).abs().max()) < 1e-9 * max(1.0, float(o.ref.rstd.max()) * o.s)
+    assert float(o.ref.v[~live].abs().max()) == 0.0
+    if o.has_head:
+        assert float((o.ref.head - want_h).abs().max()) < 1e-8 * max(1.0, float(o.ref.rstd.max()) * o.s) and float(o.ref.head[~live].abs().max()) == 0.0
+    else:
+        assert o.ref.head is None
+    assert o.ref.rstd.shape == (R, o.lg) and o.ref.yhat.shape == (R, o.N)
+    assert float((o.ref.yhat.reshape(R, o.lg, -1).mean(2)).abs().max()) < 1e-9
+
+
+def test_pred_operands_are_exact_pairs_and_the_variants_what_they_claim():
+    loud, quiet = _pred_ops(("grouped", 256, 3, 128, "")), _pred_ops(("grouped", 256, 3, 128, "quiet"))
+    for o in (loud, quiet):
+        G._exact_f32(G.pair_value(*o.x))
+        G._exact_f32(o.wv)
+        assert float((o.x[1].float().abs() - 2.0 ** -8 * o.x[0].float().abs()).max()) <= 0.0
+        gap = o.pos < 0
+        assert not bool(G.encode_planes(*o.x).view(torch.int16)[gap].any())               # zero BYTES in gap rows and behind R
+    # quiet: the pairs and the bias are the loud ones x 2^-10 exactly, so every fp32 product and sum of the kernel is the loud one's x 2^-10
+    assert torch.equal(quiet.x[0].float() * 1024.0, loud.x[0].float()) and torch.equal(quiet.x[1].float() * 1024.0, loud.x[1].float())
+    assert torch.equal(quiet.bias * 1024.0, loud.bias) and torch.equal(quiet.w[0].view(torch.int16), loud.w[0].view(torch.int16))
+    assert torch.equal(quiet.conv() * 1024.0, loud.conv())
+    var = 1.0 / quiet.ref.rstd[quiet.pos[:128] >= 0] ** 2
+    assert 1e-9 < float(var.min()) and float(var.max()) < 1e-6                            # far above 1e-12, far below 1e-5
+    assert float((quiet.ceiling - loud.ceiling).abs().max()) < 1e-3 * float(loud.ceiling.max())
+    # dead_window: the rows whose whole window is zero
+    for form in ("mid", "head"):
+        o = _pred_ops((form, 256, 3, 128, "dead_window"))
+        assert o.dead == [41, 42, 43] and bool((o.pos[38:48] >= 0).all()) and float(o.xv[40:45].abs().max()) == 0.0 and float(o.xv[39].abs().min()) > 0.0
+        y = o.conv()
+        assert float(y[o.dead].max()) <= -0.5 and bool((o.ref.rstd[o.dead] == 1e6).all()) and float(o.ref.yhat[o.dead].abs().max()) == 0.0
+        assert torch.equal(o.ref.v[o.dead], o.beta.double().unsqueeze(0).expand(3, -1))
+        ordinary = (y.max(1).values > 0.0) & (o.pos[:128] >= 0)                            # (most other rows keep some outputs behind the ReLU)
+        assert int(ordinary.sum()) > 100 and not bool(ordinary[o.dead].any()) and bool(torch.isfinite(o.ref.v).all())
+    o = _pred_ops(("two_ln", 256, 3, 333, "hi_only"))
+    assert not bool(o.x[1].view(torch.int16).any()) and not bool(o.w[1].view(torch.int16).any()) and G.pred_precision("hi_only") == "bf16"
+
+
+@pytest.mark.parametrize("case", G.PRED_CASES, ids=G.PRED_IDS)
+def test_pred_fp32_statement_stays_below_an_eighth_of_the_bar(case):
+    """The kernels' arithmetic stated in fp32 on the CPU (the figure the shares are 8 x the worst of), case by case."""
+    from tests.test_gpu_ops import GEMM_TOL
+    assert G.PRED_TOL == GEMM_TOL["bf16x3"] and G.PRED_BAR_SHARE == min(1.0, 8 * G.PRED_FP32_RATIO[0]) and G.PRED_HEAD_SHARE == min(1.0, 8 * G.PRED_FP32_RATIO[1])
+    o = _pred_ops(case)
+    v, head = G.pred_fp32(o)
+    bar_v, bar_h = o.bars()
+    rv = float(((v - o.ref.v).abs() / o.ceiling).max())
+    rh = float(((head - o.ref.head).abs() / o.head_ceiling).max()) if o.has_head else 0.0
+    print("%s: fp32 statement / ceiling: planes %.4g, heads %.4g" % (case, rv, rh))
+    assert bool(torch.isfinite(v).all()) and float(o.ceiling.min()) >= G.PRED_TOL
+    assert bool(((v - o.ref.v).abs() <= bar_v / 8).all()), rv
+    if o.has_head:
+        assert bool(((head - o.ref.head).abs() <= bar_h / 8).all()), rh
+    for r in o.dead:                                                                       # exactly beta, as the planes round it
+        assert torch.equal(v[r], G.pair_value(*G.split_bf16(o.beta)))
+
+
+@pytest.mark.parametrize("case", G.PRED_CASES, ids=G.PRED_IDS)
+def test_pred_reference_tells_every_mutant_apart(case):
+    """Taps reversed, the halo tap behind a tile edge missing, the tap in front of row 0 reading a row, groups crossed, one LayerNorm over all columns, eps = 1e-5
+    (quiet variant), no ReLU, ReLU per split-K partial, dot_b[0] for dot_b[g], the heads swapped: each at 8 bars or more on some element of the rows it concerns."""
+    o = _pred_ops(case)
+    form, _, _, R, variant = case
+    want = {"taps_reversed", "row0_front", "no_relu", "relu_per_partial"} | ({"edge_plus_tap"} if R == 333 else set()) | ({"eps_1e-5"} if variant == "quiet" else set())
+    want |= ({"one_ln"} if form in ("two_ln", "grouped") else set()) | ({"groups_crossed", "head_bias0", "head_swapped"} if form == "grouped" else set())
+    assert set(o.mutants()) == want and o.ksplit() > 1
+    worst = {}
+    for m in o.mutants():
+        r, rows = o.mutant(m)
+        assert rows is None or (len(rows) > 0 and all(0 <= q < R and int(o.pos[q]) >= 0 for q in rows)), (m, rows)
+        assert {"row0_front": list(range(o.P)), "edge_plus_tap": [127, 191, 255]}.get(m) == rows
+        worst[m] = o.distance(r, rows)
+    print(case, {m: "%.3g" % d for m, d in worst.items()})
+    assert min(worst.values()) >= 8.0, worst
+    assert o.distance(o.ref) == 0.0
+
+
+def test_pred_half_blocks_are_refused_without_the_row_kernel_and_every_family_is_reached(probe, tmp_path):
+    fs2_h = open(os.path.join(ROOT, "include", "fs2.h")).read()
+    assert "#define FS2_ERR_UNSUPPORTED (-6)" in fs2_h and "#define FS2_PREC_BF16X3 1 " in fs2_h and "#define FS2_PREC_BF16 2 " in fs2_h
+    assert G.PLAN_ERR_UNSUPPORTED == -6 and G.PREC_CODE == {"bf16x3": 1, "bf16": 2}
+    p = collections.defaultdict(lambda: 0x1000)
+    refused = [("%s-R%d-split%d" % (h, R, s), {"FS2_ROW8": 0}, G.pred_block(h, 256, 3, R, p, split=bool(s)), {}) for h in ("half0", "half1") for R in (333, 128) for s in (0, 1)]
+    got = _plans(probe, tmp_path, refused)
+    assert len(got) == 8 and all(g["err"] == G.PLAN_ERR_UNSUPPORTED and g["kernel"] == "none" for g in got.values()), got
+    launches = G.pred_launches(p)
+    got = _plans(probe, tmp_path, launches)
+    assert all(g["err"] == 0 for g in got.values())
+    reached = {(g["kernel"], g["nsplit"], g["nb"], g["mt"]) for g in got.values()}
+    assert {("row8c", 3, nb, mt) for nb in (2, 3) for mt in (2, 3)} | {("row8c_grouped", 3, nb, mt) for nb in (2, 3) for mt in (2, 3)} <= reached
+    assert {("row8c_two_ln", 3, 4, 2), ("row8c_two_ln", 1, 4, 2), ("row8c", 1, 2, 2), ("row8c", 1, 2, 3), ("row8c_grouped", 1, 2, 3)} <= reached
+    sib = [g for n, g in got.items() if "-sib" in n]
+    assert all(g["kernel"] == "pl_bf16" and g["bm"] == 64 and g["rows_pass"] == 1 for g in sib)
+    assert all((g["ksplit"] > 1) == ("-sibk-" in n) for n, g in got.items()) and {g["ksplit"] for g in sib} == {1, 4}
+    # a block differs from its sibling's in nothing but the switches; from its split-K form in the three fields call_defaults sets
+    for form in ("mid", "head", "two_ln", "grouped"):
+        a, b = G.pred_block(form, 256, 3, 333, p), G.pred_block(form, 256, 3, 333, p, split=True)
+        diff = {f for f, _ in G.GemmArgs._fields_ if getattr(a, f) != getattr(b, f)}
+        assert diff == {"kpart", "kpart_cap", "ksplit"} and a.relu_pre == 1 and a.x_scale == 1.0 and abs(a.ln_eps - 1e-12) < 1e-19 and not a.Y and a.scratch and a.Xp
