@@ -117,6 +117,20 @@ class OpAlignArgs(_Sized):
 ALIGN_TERMS = 8      # FS2_ALIGN_TERMS
 
 
+class OpPitchPathArgs(_Sized):
+    """fs2_op_pitch_path_args.  ``frame_starts`` / ``frame_lens`` are HOST int32 arrays; every other pointer is a device pointer."""
+    _fields_ = ([("struct_size", C.c_uint32), ("B", C.c_int32), ("n_candidates", C.c_int32)]
+                + [(n, C.c_double) for n in ("time_step", "f0_floor", "voicing_threshold", "octave_cost", "octave_jump_cost", "voiced_unvoiced_cost")]
+                + [(n, C.c_void_p) for n in ("cand_f0", "cand_strength")]
+                + [(n, C.POINTER(C.c_int32)) for n in ("frame_starts", "frame_lens")]
+                + [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                + [(n, C.c_void_p) for n in ("f0", "state", "strength", "terms", "batch")])
+
+
+PITCH_PATH_TERMS = 8      # FS2_PITCH_PATH_TERMS
+PITCH_MAX_CANDS = 8       # FS2_PITCH_MAX_CANDS
+
+
 class Prosody(_Sized):
     """fs2_prosody: the pitch / energy control of fs2_decode_ctl.  Every pointer is a device float32 [B, cols] or None (neutral);
     ``*_cols`` is 1 (one value per utterance) or Tmax (one per phoneme)."""
@@ -132,12 +146,13 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_conv_gemm", "fs2_op_launch_gemm", "fs2_op_repack_weight", "fs2_op_attention", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
            "fs2_op_vocode_workspace_bytes", "fs2_op_griffin_lim", "fs2_op_stft_workspace_bytes", "fs2_op_stft",
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
-           "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom",
+           "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom", "fs2_op_stft_pitch_cands_workspace_bytes_geom", "fs2_op_stft_pitch_cands_geom",
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
            "fs2_op_vocode_mel_workspace_bytes_geom", "fs2_op_griffin_lim_mel_geom", "fs2_op_vocode_mel_workspace_bytes_cap", "fs2_op_griffin_lim_mel_dev",
            "fs2_op_spsi_workspace_bytes_geom", "fs2_op_spsi_workspace_bytes_cap", "fs2_op_spsi_phase_geom", "fs2_op_spsi_phase_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
            "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align",
+           "fs2_op_pitch_path_workspace_bytes", "fs2_op_pitch_path",
            "fs2_decode_ctl", "fs2_op_label_means"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
@@ -331,6 +346,10 @@ def lib():
     L.fs2_op_stft_pitch_workspace_bytes_geom.restype = C.c_size_t
     L.fs2_op_stft_pitch_geom.argtypes = L.fs2_op_stft_geom.argtypes + [i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     L.fs2_op_stft_pitch_geom.restype = C.c_int
+    L.fs2_op_stft_pitch_cands_workspace_bytes_geom.argtypes = gp + [i32, i32p]
+    L.fs2_op_stft_pitch_cands_workspace_bytes_geom.restype = C.c_size_t
+    L.fs2_op_stft_pitch_cands_geom.argtypes = L.fs2_op_stft_geom.argtypes + [i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, vp]
+    L.fs2_op_stft_pitch_cands_geom.restype = C.c_int
     L.fs2_op_vocode_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]
     L.fs2_op_vocode_workspace_bytes_cap.restype = C.c_size_t
     # stream, geometry, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, n_iter, momentum, seed, init_phase,
@@ -375,6 +394,10 @@ def lib():
     L.fs2_op_align_workspace_bytes.restype = C.c_size_t
     L.fs2_op_align.argtypes = [vp, C.POINTER(OpAlignArgs)]
     L.fs2_op_align.restype = C.c_int
+    L.fs2_op_pitch_path_workspace_bytes.argtypes = [i32, i32p]
+    L.fs2_op_pitch_path_workspace_bytes.restype = C.c_size_t
+    L.fs2_op_pitch_path.argtypes = [vp, C.POINTER(OpPitchPathArgs)]
+    L.fs2_op_pitch_path.restype = C.c_int
     L.fs2_decode_ctl.argtypes = [vp, vp, C.POINTER(DecodeIO), C.POINTER(Prosody)]
     L.fs2_decode_ctl.restype = C.c_int
     # stream, x, labels, lens_dev, B, x_stride, n_labels, positive_only, mean, count

@@ -1085,6 +1085,9 @@ int unpack(fs2_handle* h, hipStream_t s, const T* src, int W, const int* start, 
 // ---------------------------------------------------------------------------------- forced alignment: phoneme durations of a recording
 #include "align.h"
 
+// ---------------------------------------------------------------------------------- pitch path search over per-frame candidates
+#include "pitch_path.h"
+
 // ---------------------------------------------------------------------------------- pitch / energy control, per-phoneme means
 #include "prosody.h"
 
@@ -2017,6 +2020,24 @@ int fs2_op_stft_pitch_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win
     c.feat = {mag, mel_basis, logmel, energy, {sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost}, f0, strength};
     return gl_call(stream, c);
 }
+
+size_t fs2_op_stft_pitch_cands_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* wav_lens) {
+    return gl_workspace_bytes({"fs2_op_stft_pitch_cands_workspace_bytes_geom", GlKind::AnalysisPitch, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, wav_lens)});
+}
+
+int fs2_op_stft_pitch_cands_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* wav, int32_t B, const int32_t* wav_starts,
+                                 const int32_t* wav_lens, void* workspace, size_t workspace_bytes, float* mag, const float* mel_basis, float* logmel, float* energy,
+                                 int32_t sample_rate, double f0_floor, double f0_ceil, double voicing_threshold, double octave_cost, int32_t n_candidates,
+                                 float* cand_f0, float* cand_strength) {
+    if (n_candidates < 1) return fail(nullptr, FS2_ERR_ARG, "fs2_op_stft_pitch_cands_geom: n_candidates = %d outside 1 .. %d", n_candidates, FS2_PITCH_MAX_CANDS);
+    GlCall c{"fs2_op_stft_pitch_cands_geom", GlKind::AnalysisPitch, {n_fft, hop, win, n_mels}, gl_host_batch(B, wav_starts, wav_lens), {workspace, workspace_bytes}, {wav}};
+    c.feat = {mag, mel_basis, logmel, energy, {sample_rate, f0_floor, f0_ceil, voicing_threshold, octave_cost}, nullptr, nullptr, n_candidates, cand_f0, cand_strength};
+    return gl_call(stream, c);
+}
+
+size_t fs2_op_pitch_path_workspace_bytes(int32_t B, const int32_t* frame_lens) { return path_workspace_bytes(B, frame_lens); }
+
+int fs2_op_pitch_path(void* stream, const fs2_op_pitch_path_args* a) { return pp_pitch_path(stream, a); }
 
 size_t fs2_op_targets_workspace_bytes(int32_t B) { return B < 0 ? 0 : tg_layout(B).bytes; }
 

@@ -92,8 +92,12 @@ struct GlWavOut { float* wav; int32_t wav_stride; int64_t wav_capacity; int64_t*
 
 struct GlPitchOptions { int32_t sample_rate; double f0_floor, f0_ceil, voicing_threshold, octave_cost; };
 
-// Outputs of the analysis, each optional; logmel needs mel_basis; pitch, f0 and strength belong to AnalysisPitch
-struct GlFeatures { float* mag; const float* mel_basis; float *logmel, *energy; GlPitchOptions pitch; float *f0, *strength; };
+// Outputs of the analysis, each optional; logmel needs mel_basis; pitch, f0 and strength belong to AnalysisPitch, and so do the
+// candidates (n_cands = 0: the winner's f0 and strength; 1 .. FS2_PITCH_MAX_CANDS: cand_f0 and cand_strength [frames, n_cands])
+struct GlFeatures {
+    float* mag; const float* mel_basis; float *logmel, *energy; GlPitchOptions pitch; float *f0, *strength;
+    int32_t n_cands; float *cand_f0, *cand_strength;
+};
 
 struct GlPhaseOut { float *phase, *mag_out; };
 
@@ -395,8 +399,8 @@ int gl_pitch_args(const char* who, const GlGeomHost& gh, const GlPitchOptions& o
 }
 
 // Analysis and AnalysisPitch: one gl_stft launch, or with the pitch outputs the window-autocorrelation table and one gl_features
-// launch.  Order of the checks: the pitch options (AnalysisPitch; without f0 and strength it is then exactly Analysis and needs no
-// more workspace than it), null starts / lens, logmel without its basis, the plan, nothing to do (FS2_OK before any pointer is looked
+// launch (gl_candidates where the call asks for candidates).  Order of the checks: the pitch options and the candidate count
+// (AnalysisPitch; without f0 and strength, or their candidate forms, it is then exactly Analysis and needs no more workspace than it), null starts / lens, logmel without its basis, the plan, nothing to do (FS2_OK before any pointer is looked
 // at), null pointers, the workspace last.
 int gl_analyze(hipStream_t s, GlCall c) {
     const char* who = c.who;
@@ -405,7 +409,9 @@ int gl_analyze(hipStream_t s, GlCall c) {
     GlPitch pp{};
     if (c.kind == GlKind::AnalysisPitch) {
         if (int rc = gl_pitch_args(who, gh, o.pitch, pp)) return rc;
-        if (!o.f0 && !o.strength) c.kind = GlKind::Analysis;
+        if (o.n_cands < 0 || o.n_cands > FS2_PITCH_MAX_CANDS || (o.n_cands == 0 && (o.cand_f0 || o.cand_strength)))
+            return fail(nullptr, FS2_ERR_ARG, "%s: n_candidates = %d outside 1 .. %d", who, o.n_cands, FS2_PITCH_MAX_CANDS);
+        if (o.n_cands ? !o.cand_f0 && !o.cand_strength : !o.f0 && !o.strength) c.kind = GlKind::Analysis;
     }
     const bool pitch = c.kind == GlKind::AnalysisPitch;
     if (c.batch.B > 0 && (!c.batch.starts || !c.batch.lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
@@ -427,7 +433,15 @@ int gl_analyze(hipStream_t s, GlCall c) {
     const float* win = (const float*)(ws + p.at.off_win);
     gl_dispatch(gh, [&](auto n, auto h) {
         constexpr int NFFT = decltype(n)::value, HOP_C = decltype(h)::value;
-        if (pitch)
+        if (pitch && o.n_cands) {
+            // |X|, log-mel and energy beside candidates come from gl_stft itself, in a launch of its own: their bits are fs2_op_stft_geom's
+            // by construction (gl_candidates' own copy of those statements was measured to differ in the last bit at n_fft = 2048: the
+            // compiler contracts the transform differently there), and gl_candidates then skips that part of its body
+            if (o.mag || o.logmel || o.energy)
+                hipLaunchKernelGGL((gl_stft<NFFT, HOP_C>), grid, blk, 0, s, tiles, gh.g, tw, win, wav, o.mag, o.mel_basis, o.logmel, o.energy);
+            hipLaunchKernelGGL((gl_candidates<NFFT, HOP_C>), grid, blk, 0, s, tiles, gh.g, tw, win, acw, wav, (float*)nullptr, o.mel_basis, (float*)nullptr,
+                               (float*)nullptr, pp, o.n_cands, o.cand_f0, o.cand_strength);
+        } else if (pitch)
             hipLaunchKernelGGL((gl_features<NFFT, HOP_C>), grid, blk, 0, s, tiles, gh.g, tw, win, acw, wav, o.mag, o.mel_basis, o.logmel, o.energy, pp, o.f0,
                                o.strength);
         else

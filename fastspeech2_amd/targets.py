@@ -153,11 +153,12 @@ class TrainingTargets(NamedTuple):
     pitch_stats: TargetStats
 
 
-def training_targets(wav_packed, sample_lens, hp=None, **pitch_options):
-    """Waveforms to the targets the model is taught with: ``wav_features`` (log-mel, energy, F0 from one launch; the F0 is the
-    autocorrelation estimator of :func:`fastspeech2_amd.vocoder.pitch`, not the reference's DIO), then ``clean_targets`` of the energy
+def training_targets(wav_packed, sample_lens, hp=None, f0_method="frame", **pitch_options):
+    """Waveforms to the targets the model is taught with: ``wav_features`` (log-mel, energy, F0; the F0 is the autocorrelation
+    estimator of :func:`fastspeech2_amd.vocoder.pitch`, not the reference's DIO, or with ``f0_method="path"`` that of
+    :func:`fastspeech2_amd.vocoder.pitch_track`, the same candidates joined by a path search), then ``clean_targets`` of the energy
     and of the F0, in place.  ``logmel`` is ``wav_features``' bit for bit; the zeros of unvoiced frames stay zero."""
-    lm, en, f0 = wav_features(wav_packed, sample_lens, hp=hp, **pitch_options)
+    lm, en, f0 = wav_features(wav_packed, sample_lens, hp=hp, f0_method=f0_method, **pitch_options)
     frame_lens = _lens(sample_lens, name="sample_lens") // _audio_config(hp)[1].hop + 1
     _, es = clean_targets(en, frame_lens, out=en)
     _, ps = clean_targets(f0, frame_lens, out=f0)

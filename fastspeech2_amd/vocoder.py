@@ -10,7 +10,8 @@ vocoded alone or inside any batch.
 
 ``stft_magnitude`` is the analysis direction (TacotronSTFT.mel_spectrogram): waveforms -> |STFT| or log-mel on the GPU;
 ``mel_energy`` gives the log-mel and the per-frame energy (the reference preprocessing's targets) from one launch; ``wav_features``
-adds a per-frame F0 from the same launch and ``pitch`` gives it alone (an autocorrelation estimator, not the reference's DIO).  Other transform
+adds a per-frame F0 from the same launch and ``pitch`` gives it alone (an autocorrelation estimator, not the reference's DIO);
+``pitch_candidates`` / ``pitch_path`` / ``pitch_track`` add the path search across frames (``f0_method="path"``).  Other transform
 geometries (n_fft 512 / 1024 / 2048, any hop <= win_length <= n_fft with ceil(n_fft / hop) <= 8, 1 .. 128 mels) come from hp.audio.
 There is no CPU fallback: CPU tensors raise.
 
@@ -29,6 +30,7 @@ import torch
 from . import _lib
 from ._host import _i32, _lens, _require_cuda, _stream
 from .fastspeech import AsyncMels, Fs2CapacityError
+from .losses import DeviceRecords
 
 N_FFT, HOP, WIN, N_BINS = 1024, 256, 1024, 513
 _AUDIO_DEFAULTS = dict(sample_rate=22050, n_fft=1024, n_mels=80, fmin=0.0, fmax=8000.0)
@@ -611,9 +613,10 @@ def spsi_phase(src, olens=None, hp=None, magnitudes=False, return_magnitudes=Fal
     return _gl_for(hp).spsi_phase(src, olens, magnitudes=magnitudes, return_magnitudes=return_magnitudes, sync=sync)
 
 
-def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=None, pitch=None):
+def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=None, pitch=None, n_candidates=0):
     """One analysis launch.  ``pitch``: None (fs2_op_stft_geom), or (f0_floor, f0_ceil, voicing_threshold, octave_cost) as
-    ``pitch_lags`` accepted them (fs2_op_stft_pitch_geom); then f0 and strength [frames] follow (mag, mel, energy)."""
+    ``pitch_lags`` accepted them (fs2_op_stft_pitch_geom); then f0 and strength [frames] follow (mag, mel, energy).  With
+    ``n_candidates`` = K > 0 (fs2_op_stft_pitch_cands_geom) these two are cand_f0 and cand_strength [frames, K]."""
     _require_cuda(wav_packed, "wav_packed")
     if wav_packed.dim() != 1:
         raise ValueError("wav_packed must be 1-D, got %s" % (tuple(wav_packed.shape),))
@@ -627,8 +630,9 @@ def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=N
     mag = torch.empty(frames, g.n_bins, dtype=torch.float32, device=dev) if want_mag else None
     mel = torch.empty(frames, g.n_mels, dtype=torch.float32, device=dev) if want_mel else None
     en = torch.empty(frames, dtype=torch.float32, device=dev) if want_energy else None
-    f0 = torch.empty(frames, dtype=torch.float32, device=dev) if pitch is not None else None
-    st = torch.empty(frames, dtype=torch.float32, device=dev) if pitch is not None else None
+    per_frame = (frames, n_candidates) if n_candidates else (frames,)
+    f0 = torch.empty(per_frame, dtype=torch.float32, device=dev) if pitch is not None else None
+    st = torch.empty(per_frame, dtype=torch.float32, device=dev) if pitch is not None else None
     out = (mag, mel, en) if pitch is None else (mag, mel, en, f0, st)
     if frames == 0:
         return out
@@ -647,6 +651,8 @@ def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=N
                                              basis.data_ptr() if want_mel else None, ptr(mel), ptr(en))
         if pitch is None:
             _lib.check(lib.fs2_op_stft_geom(*head))
+        elif n_candidates:
+            _lib.check(lib.fs2_op_stft_pitch_cands_geom(*head, int(gl.params["sample_rate"]), *pitch, int(n_candidates), ptr(f0), ptr(st)))
         else:
             _lib.check(lib.fs2_op_stft_pitch_geom(*head, int(gl.params["sample_rate"]), *pitch, ptr(f0), ptr(st)))
     return out
@@ -713,19 +719,158 @@ def pitch(wav_packed, sample_lens, hp=None, f0_floor=71.0, f0_ceil=800.0, voicin
     return (f0, st) if return_strength else f0
 
 
-def wav_features(wav_packed, sample_lens, hp=None, **pitch_options):
-    """(log-mel [frames, n_mels], energy [frames], f0 [frames]) of packed waveforms from one launch: the three arrays the reference's
-    preprocessing saves per utterance (nvidia_preprocessing.py), with the F0 of :func:`pitch` (an autocorrelation estimator, not the
-    reference's DIO) and its options (f0_floor, f0_ceil, voicing_threshold, octave_cost).  The log-mel and the energy are
-    ``mel_energy``'s bit for bit."""
+MAX_CANDIDATES = _lib.PITCH_MAX_CANDS
+# index of a record of the path search (include/fs2.h)
+PATH_FRAMES, PATH_FLAGS, PATH_SCORE, PATH_VOICED, PATH_SWITCHES, PATH_MAX_STEP, PATH_CHANGED = range(7)
+
+
+def _check_n_candidates(n_candidates):
+    if not (isinstance(n_candidates, (int, np.integer)) and 1 <= n_candidates <= MAX_CANDIDATES):
+        raise ValueError("n_candidates must be an integer in 1 .. %d, got %r" % (MAX_CANDIDATES, n_candidates))
+    return int(n_candidates)
+
+
+def _check_path_options(time_step, f0_floor, voicing_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost):
+    """The six numbers of the path search as floats, checked before anything touches the GPU (csrc/pitch_path.h: pp_pitch_path
+    checks the same)."""
+    ts, lo = float(time_step), float(f0_floor)
+    if not (ts > 0 and math.isfinite(ts) and lo > 0 and math.isfinite(lo)):
+        raise ValueError("need time_step > 0 and f0_floor > 0, both finite, got %r, %r" % (time_step, f0_floor))
+    vt, oc = float(voicing_threshold), float(octave_cost)
+    if not (math.isfinite(vt) and math.isfinite(oc)):
+        raise ValueError("voicing_threshold and octave_cost must be finite, got %r, %r" % (voicing_threshold, octave_cost))
+    oj, vu = float(octave_jump_cost), float(voiced_unvoiced_cost)
+    if not (oj >= 0 and math.isfinite(oj) and vu >= 0 and math.isfinite(vu)):
+        raise ValueError("octave_jump_cost and voiced_unvoiced_cost must be finite and not negative, got %r, %r"
+                         % (octave_jump_cost, voiced_unvoiced_cost))
+    return ts, lo, vt, oc, oj, vu
+
+
+def pitch_candidates(wav_packed, sample_lens, hp=None, n_candidates=8, f0_floor=71.0, f0_ceil=800.0, octave_cost=0.02):
+    """(cand_f0 [frames, n_candidates], cand_strength [frames, n_candidates]) of packed waveforms: per frame of ``pitch`` the first
+    ``n_candidates`` (1 .. 8) candidates of its definition in the order "larger S, then smaller lag", as f0 = sr / t* and strength = p;
+    empty slots are 0 / 0.  Slot 0 is ``pitch``'s winner bit for bit: its strength everywhere and its f0 wherever ``pitch`` calls
+    the frame voiced (csrc/gl_pitch.h: gl_candidates).  What ``pitch_path`` takes.  CPU tensors raise."""
+    K = _check_n_candidates(n_candidates)
+    gl, opt = _pitch_setup(hp, f0_floor, f0_ceil, 0.45, octave_cost)
+    _, _, _, cf, cs = _analysis(wav_packed, sample_lens, hp, False, False, False, gl, opt, K)
+    return cf, cs
+
+
+class PitchTrack(DeviceRecords):
+    """The result of the path search.  ``f0`` [frames] float32: the chosen candidate's f0, 0 = unvoiced; ``state`` [frames] int32:
+    its slot, -1 = unvoiced; ``strength`` [frames] float32: its strength, 0 = unvoiced (device tensors).  ``terms`` [B, 8] /
+    ``batch`` [8]: the records (float64 numpy; include/fs2.h lists the indices)."""
+    TERMS = _lib.PITCH_PATH_TERMS
+
+    def __init__(self, f0, state, strength, terms, batch, _device=None):
+        super().__init__(terms, batch, _device)
+        self.f0, self.state, self.strength = f0, state, strength
+
+    def per_utterance(self):
+        """Per utterance, as a dict of arrays [B]: ``voiced_share`` = voiced frames / frames (NaN without frames), ``vuv_switches``
+        = changes between voiced and unvoiced, ``max_octave_step`` = the largest |log2| step between consecutive voiced frames,
+        ``changed_frames`` = the frames whose choice differs from the frame's own best candidate, ``flags`` (0 fine, 2 a candidate
+        value was not finite or was negative: the utterance is all unvoiced)."""
+        t = self.terms
+        i64 = lambda x: x.astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return dict(voiced_share=t[:, PATH_VOICED] / t[:, PATH_FRAMES], vuv_switches=i64(t[:, PATH_SWITCHES]),
+                        max_octave_step=t[:, PATH_MAX_STEP].copy(), changed_frames=i64(t[:, PATH_CHANGED]), flags=i64(t[:, PATH_FLAGS]))
+
+
+def pitch_path(cand_f0, cand_strength, frame_lens, time_step, f0_floor=71.0, voicing_threshold=0.45, octave_cost=0.02,
+               octave_jump_cost=0.35, voiced_unvoiced_cost=0.14):
+    """The path search over per-frame candidates (Boersma 1993, the step ``pitch`` leaves out) -> :class:`PitchTrack`
+    (csrc/pitch_path.h, include/fs2.h: fs2_op_pitch_path).
+
+    ``cand_f0`` / ``cand_strength``: float32 device tensors [frames, K], K = 1 .. 8, the utterances packed back to back
+    (``pitch_candidates``' output, or candidates from any other source; a slot with f0 = 0 is empty); ``frame_lens``: host lengths;
+    ``time_step``: seconds per frame (hop / sample_rate).  Per utterance the sequence of states (unvoiced, or one of the frame's
+    candidates) with the largest sum of local scores -- ``voicing_threshold`` for unvoiced, p - octave_cost log2(f0_floor / f)
+    for a candidate -- minus transition costs: ``voiced_unvoiced_cost`` s for a change of voicing and ``octave_jump_cost`` s
+    |log2 (f_a / f_b)| between voiced frames, s = 0.01 / time_step.  Everything is formed in double in a fixed order, so an utterance's
+    track does not depend on its batch.  With both costs 0 it is the per-frame best.  CPU tensors raise."""
+    opt = _check_path_options(time_step, f0_floor, voicing_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost)
+    _require_cuda(cand_f0, "cand_f0")
+    _require_cuda(cand_strength, "cand_strength")
+    if cand_f0.dim() != 2 or cand_f0.shape != cand_strength.shape or cand_f0.device != cand_strength.device:
+        raise ValueError("cand_f0 and cand_strength must be [frames, K] tensors of one shape on one device, got %s and %s"
+                         % (tuple(cand_f0.shape), tuple(cand_strength.shape)))
+    K = cand_f0.shape[1]
+    if not 1 <= K <= MAX_CANDIDATES:
+        raise ValueError("the candidates per frame must be 1 .. %d, got %d" % (MAX_CANDIDATES, K))
+    L = _lens(frame_lens, name="frame_lens")
+    rows = int(cand_f0.shape[0])
+    if int(L.sum()) != rows:
+        raise ValueError("frame_lens sum to %d, the candidates have %d frames" % (int(L.sum()), rows))
+    dev = cand_f0.device
+    B = int(L.numel())
+    cf, cs = cand_f0.contiguous().float(), cand_strength.contiguous().float()
+    lib = _lib.lib()
+    st_keep, st_p = _i32(np.concatenate([[0], np.cumsum(L.numpy())[:-1]]) if B else np.zeros(0))
+    ln_keep, ln_p = _i32(L.numpy())
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    with torch.cuda.device(dev):
+        f0 = torch.empty(rows, dtype=torch.float32, device=dev)
+        state = torch.empty(rows, dtype=torch.int32, device=dev)
+        strength = torch.empty(rows, dtype=torch.float32, device=dev)
+        rec, terms_p, batch_p = PitchTrack._on_device(B, dev)
+        ws_bytes = int(lib.fs2_op_pitch_path_workspace_bytes(B, ln_p if B else None))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        args = _lib.OpPitchPathArgs(B, K, *opt, ptr(cf), ptr(cs), st_p if B else None, ln_p if B else None, ws.data_ptr(), ws_bytes,
+                                    ptr(f0), ptr(state), ptr(strength), terms_p, batch_p)
+        _lib.check(lib.fs2_op_pitch_path(_stream(dev), C.byref(args)))
+    return PitchTrack(f0, state, strength, None, None, _device=rec)
+
+
+def pitch_track(wav_packed, sample_lens, hp=None, n_candidates=8, f0_floor=71.0, f0_ceil=800.0, voicing_threshold=0.45, octave_cost=0.02,
+                octave_jump_cost=0.35, voiced_unvoiced_cost=0.14):
+    """``pitch_candidates`` then ``pitch_path`` -> :class:`PitchTrack`: the F0 of packed waveforms with the path search, one value
+    per frame of ``stft_magnitude``, 0 where unvoiced.  ``time_step`` is hop / sample_rate of ``hp.audio``."""
+    K = _check_n_candidates(n_candidates)
+    gl, opt = _pitch_setup(hp, f0_floor, f0_ceil, voicing_threshold, octave_cost)
+    time_step = gl.geometry.hop / float(gl.params["sample_rate"])
+    _check_path_options(time_step, f0_floor, voicing_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost)
+    return _track(wav_packed, sample_lens, hp, gl, opt, K, octave_jump_cost, voiced_unvoiced_cost, False)[1]
+
+
+def _track(wav_packed, sample_lens, hp, gl, opt, K, octave_jump_cost, voiced_unvoiced_cost, features):
+    """((log-mel, energy) or (None, None), PitchTrack): one candidates call, with the log-mel and the energy when ``features``
+    (gl_stft's launch beside gl_candidates'), and the path over it."""
+    _, lm, en, cf, cs = _analysis(wav_packed, sample_lens, hp, False, features, features, gl, opt, K)
+    frame_lens = _lens(sample_lens, name="sample_lens") // gl.geometry.hop + 1
+    time_step = gl.geometry.hop / float(gl.params["sample_rate"])
+    return (lm, en), pitch_path(cf, cs, frame_lens, time_step, opt[0], opt[2], opt[3], octave_jump_cost, voiced_unvoiced_cost)
+
+
+F0_METHODS = ("frame", "path")
+
+
+def wav_features(wav_packed, sample_lens, hp=None, f0_method="frame", **pitch_options):
+    """(log-mel [frames, n_mels], energy [frames], f0 [frames]) of packed waveforms: the three arrays the reference's preprocessing
+    saves per utterance (nvidia_preprocessing.py).  ``f0_method="frame"``: the F0 of :func:`pitch` (an autocorrelation estimator,
+    not the reference's DIO) with its options (f0_floor, f0_ceil, voicing_threshold, octave_cost), all from one launch.
+    ``f0_method="path"``: the F0 of :func:`pitch_track` -- the same candidates joined by a path search across frames -- which also
+    takes octave_jump_cost, voiced_unvoiced_cost and n_candidates; ``mel_energy``'s launch, one for the candidates and one for the
+    path.  The log-mel and the energy are ``mel_energy``'s bit for bit in both."""
     if "return_strength" in pitch_options:
         raise TypeError("wav_features returns (logmel, energy, f0); use pitch(..., return_strength=True) for the strength")
+    if f0_method not in F0_METHODS:
+        raise ValueError("f0_method must be one of %s, got %r" % (F0_METHODS, f0_method))
     o = dict(f0_floor=71.0, f0_ceil=800.0, voicing_threshold=0.45, octave_cost=0.02)
+    if f0_method == "path":
+        o.update(octave_jump_cost=0.35, voiced_unvoiced_cost=0.14, n_candidates=8)
     unknown = sorted(set(pitch_options) - set(o))
     if unknown:
         raise TypeError("unknown pitch option(s) %s" % ", ".join(unknown))
     o.update(pitch_options)
     gl, opt = _pitch_setup(hp, o["f0_floor"], o["f0_ceil"], o["voicing_threshold"], o["octave_cost"])
+    if f0_method == "path":
+        K = _check_n_candidates(o["n_candidates"])
+        _check_path_options(gl.geometry.hop / float(gl.params["sample_rate"]), *opt[:1], *opt[2:], o["octave_jump_cost"], o["voiced_unvoiced_cost"])
+        (lm, en), track = _track(wav_packed, sample_lens, hp, gl, opt, K, o["octave_jump_cost"], o["voiced_unvoiced_cost"], True)
+        return lm, en, track.f0
     _, lm, en, f0, _ = _analysis(wav_packed, sample_lens, hp, False, True, True, gl, opt)
     return lm, en, f0
 

@@ -383,6 +383,23 @@ int fs2_op_stft_pitch_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win
                            const float *mel_basis, float *logmel, float *energy, int32_t sample_rate, double f0_floor, double f0_ceil,
                            double voicing_threshold, double octave_cost, float *f0, float *strength);
 
+/* ---- The first n_candidates candidates per frame instead of the winner alone (gl_pitch.h: gl_candidates):
+ * the arguments of fs2_op_stft_pitch_geom with n_candidates, cand_f0 and cand_strength in place of f0 and strength.  The frames, rho,
+ * the candidate rule, t*, p and S are those above; the candidates of a frame are put in the order "larger S, then smaller t" and the
+ * first n_candidates are written: cand_f0 [frames, n_candidates] = sample_rate / t*, cand_strength [frames, n_candidates] = p, both
+ * float32, empty slots 0 / 0, each optional (NULL).  Slot 0 is the winner of fs2_op_stft_pitch_geom bit for bit (its f0 whatever the
+ * voicing threshold, which this entry point checks and does not use); mag, logmel and energy are those of fs2_op_stft_geom bit for
+ * bit.  FS2_ERR_ARG: n_candidates outside [1, FS2_PITCH_MAX_CANDS]; otherwise as fs2_op_stft_pitch_geom, whose workspace it
+ * uses. ---- */
+#define FS2_PITCH_MAX_CANDS 8
+
+size_t fs2_op_stft_pitch_cands_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *wav_lens);
+
+int fs2_op_stft_pitch_cands_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *wav, int32_t B,
+                                 const int32_t *wav_starts, const int32_t *wav_lens, void *workspace, size_t workspace_bytes, float *mag,
+                                 const float *mel_basis, float *logmel, float *energy, int32_t sample_rate, double f0_floor, double f0_ceil,
+                                 double voicing_threshold, double octave_cost, int32_t n_candidates, float *cand_f0, float *cand_strength);
+
 /* ---- Device-driven Griffin-Lim: the frame counts stay on the device (what fs2_decode's device-driven layout leaves there), so mel
  * frames become waveforms without a host read-back in between.  The tiles are planned by kernels inside capacities the host knows;
  * grids are sized for the capacities and surplus workgroups exit at once.  Results equal those of fs2_op_griffin_lim_geom for the same
@@ -650,6 +667,56 @@ size_t fs2_op_align_workspace_bytes(int32_t B, const int32_t *a_lens, const int3
  * without n_labels (or the reverse), a null workspace with B > 0; FS2_ERR_WORKSPACE: workspace_bytes below
  * fs2_op_align_workspace_bytes(B, a_lens, b_lens, 0). */
 int fs2_op_align(void *stream, const fs2_op_align_args *a);
+
+/* ---- Pitch path search over B utterances (fastspeech2_amd/csrc/pitch_path.h): per utterance of T frames
+ * with n_candidates = K candidates each (fs2_op_stft_pitch_cands_geom's, or any other source's), the best sequence of states.  State
+ * 0 is "unvoiced", state c = 1 .. K is candidate c - 1, which exists iff cand_f0 > 0.  All in double, from the float32 inputs:
+ *   u(t, 0) = voicing_threshold;  u(t, c) = p - octave_cost log2(f0_floor / f)
+ *   trans(j -> c) = 0 (both unvoiced), voiced_unvoiced_cost s (exactly one unvoiced), octave_jump_cost s |log2 f_j - log2 f_c| (both
+ *   voiced), s = 0.01 / time_step (time_step: seconds per frame)
+ *   D(0, c) = u(0, c);  D(t, c) = u(t, c) + max over the existing j, ascending, of [D(t-1, j) - trans(j -> c)] with a strict ">" (a
+ *   tie keeps the smaller j); the end state is the largest D(T-1, c), a tie to the smaller c; then the walk back.
+ * Results per frame: f0 (the chosen candidate's, 0 = unvoiced), state (c - 1, -1 = unvoiced), strength (the chosen p, 0 = unvoiced);
+ * per utterance a record of FS2_PITCH_PATH_TERMS doubles:
+ *   [0] T   [1] flags: 0 fine, 2 a candidate value (f0 or strength) is not finite or is negative   [2] D of the path
+ *   [3] voiced frames   [4] voiced / unvoiced switches   [5] the largest |log2 f(t-1) - log2 f(t)| over consecutive voiced frames
+ *   [6] frames whose state differs from the frame's own argmax of u (ties to the smaller state)   [7] 0
+ * With flags 2 the utterance's frames are 0 / -1 / 0 and [2] .. [6] are 0.  T = 0 writes no frame (its record is zeros).  An
+ * utterance's results depend on its own values only: not on B, on its place in the batch or on the workspace.  The batch record:
+ * [1] = the utterances with flags != 0, [5] the maximum and every other entry the sum over the utterances with flags 0, in index
+ * order. ---- */
+#define FS2_PITCH_PATH_TERMS 8
+
+/* cand_f0, cand_strength: device float32 [rows, n_candidates]; frame_starts / frame_lens: HOST int32 [B], the first row and the
+ * frames of every utterance; f0 / strength: device float32 [rows], state: device int32 [rows], terms: device double
+ * [B, FS2_PITCH_PATH_TERMS], batch: device double [FS2_PITCH_PATH_TERMS], each of the five optional.  B = 0 writes a zero batch
+ * record.  (Declared in two statements for the reason given at fs2_op_loss_args; _lib.py: OpPitchPathArgs.) */
+struct fs2_op_pitch_path_args {
+    uint32_t struct_size;     /* = sizeof(fs2_op_pitch_path_args) */
+    int32_t B, n_candidates;
+    double time_step, f0_floor, voicing_threshold, octave_cost, octave_jump_cost, voiced_unvoiced_cost;
+    const float *cand_f0, *cand_strength;
+    const int32_t *frame_starts, *frame_lens;
+    void *workspace;
+    size_t workspace_bytes;
+    float *f0;
+    int32_t *state;
+    float *strength;
+    double *terms, *batch;
+};
+typedef struct fs2_op_pitch_path_args fs2_op_pitch_path_args;
+
+/* workspace bytes of fs2_op_pitch_path: 8 bytes per frame (a frame's back pointers) plus the records; host only; 0 on a bad
+ * argument (negative B or length, null frame_lens with B > 0). */
+size_t fs2_op_pitch_path_workspace_bytes(int32_t B, const int32_t *frame_lens);
+
+/* Asynchronous on `stream`: no allocation, no host read of device memory, no synchronisation; legal during stream capture.  One
+ * launch per 128 utterances (one wave per utterance; their rows travel as kernel arguments) and one combining launch.  FS2_ERR_ARG:
+ * wrong struct_size, n_candidates outside [1, FS2_PITCH_MAX_CANDS], time_step or f0_floor not positive and finite, a non-finite
+ * voicing_threshold or octave_cost, an octave_jump_cost or voiced_unvoiced_cost that is negative or not finite, a negative B, start
+ * or length, null starts / lens / candidates / workspace with B > 0; FS2_ERR_UNSUPPORTED: more than INT32_MAX candidate slots;
+ * FS2_ERR_WORKSPACE: workspace_bytes below fs2_op_pitch_path_workspace_bytes(B, frame_lens). */
+int fs2_op_pitch_path(void *stream, const fs2_op_pitch_path_args *a);
 
 /* ---- Pitch and energy control of the free-running synthesis (fastspeech2_amd/csrc/prosody.h).  Between the
  * variance predictors and the quantisation of their outputs, every predicted value v of a frame of utterance b that was expanded from
