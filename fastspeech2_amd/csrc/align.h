@@ -20,7 +20,8 @@
 // are non-decreasing, so a label's frames are one run and its count is written once, when the run ends -- no atomics.  Every loop
 // is bounded by N, M or dur_stride; nothing waits on another workgroup.
 //
-// align_combine (one workgroup): copies the records out and forms the batch record over the pairs in index order.
+// records_combine<8, 2, -1> (record_op.h; one workgroup): copies the records out and forms the batch record over the pairs in index
+// order -- column 2 counts the pairs without an alignment, the other columns are sums over the aligned ones.
 
 constexpr int kAlignThreads = 256;          // threads of align_sweep
 constexpr int kAlignUnroll = 4;             // states a thread has in flight per pass over a row
@@ -125,21 +126,6 @@ __global__ __launch_bounds__(kAlignThreads) void align_sweep(const DtwPair* recs
     out[4] = (double)used; out[5] = (double)longest; out[6] = (double)(nl - seen); out[7] = 0.0;
 }
 
-__global__ __launch_bounds__(256) void align_combine(const double* recs, int B, double* terms, double* batch) {
-    const int tid = threadIdx.x;
-    if (terms)
-        for (int64_t i = tid; i < (int64_t)B * kAlignTerms; i += 256) terms[i] = recs[i];
-    if (batch && tid < kAlignTerms) {
-        double s = 0.0;
-        for (int b = 0; b < B; ++b) {
-            const bool fine = recs[(size_t)b * kAlignTerms + 2] == 0.0;
-            if (tid == 2) s += fine ? 0.0 : 1.0;
-            else if (fine) s += recs[(size_t)b * kAlignTerms + tid];
-        }
-        batch[tid] = s;
-    }
-}
-
 // ---- host side: pair_plan.h's plan, then per group dtw_dist (on the swapped sides) and align_sweep ----
 size_t align_workspace_bytes(int32_t B, const int32_t* a_lens, const int32_t* b_lens, size_t cap) { return pair_workspace_bytes(kAlignOp, B, a_lens, b_lens, cap); }
 
@@ -160,9 +146,9 @@ int al_align(void* stream, const fs2_op_align_args* a) {
     if (const int rc = pair_plan(kAlignOp, a, a->labels ? a->n_labels : nullptr, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
-    DtwPair* recs = p.recs(ws);
-    double* recs_out = p.terms(ws);
-    dtw_upload(p, recs, s);
+    DtwPair* recs = p.at.recs;
+    double* recs_out = p.at.terms;
+    dtw_upload(p, s);
     // one dtw_dist and one align_sweep per group, in stream order: a group's matrices are dead when the next group's are written
     pair_groups(p, [&](const PairGroup& g) {
         dtw_launch_dist(p, g, recs, ws, s);
@@ -170,7 +156,6 @@ int al_align(void* stream, const fs2_op_align_args* a) {
                            a->durations ? a->durations + (int64_t)g.first * a->dur_stride : nullptr, a->dur_stride, a->state,
                            recs_out + (size_t)g.first * kAlignTerms);
     });
-    hipLaunchKernelGGL(align_combine, dim3(1), dim3(256), 0, s, recs_out, B, a->terms, a->batch);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FS2_OK : fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL((records_combine<kAlignTerms, 2, -1>), dim3(1), dim3(256), 0, s, recs_out, B, a->terms, a->batch);
+    return rec_finish(who);
 }

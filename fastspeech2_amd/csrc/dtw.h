@@ -24,7 +24,8 @@
 // chunk behind); the two edge buffers of a pair alternate between column blocks.  The d values and the a-side tracks of the next
 // chunk are loaded while the current one is computed.  No floating-point atomics, nothing waits on another workgroup.
 //
-// dtw_combine (one workgroup): copies the records out and adds the batch record, term by term, over the pairs in index order.
+// records_combine<12, -1, -1> (record_op.h; one workgroup): copies the records out and adds the batch record, term by term, over the
+// pairs in index order.
 
 #include "pair_plan.h"
 constexpr int kDtwCols = 256;             // threads of dtw_sweep = columns of a column block
@@ -41,11 +42,6 @@ struct DtwCell {
     int steps, nv, mis, pad;
 };
 static_assert(sizeof(DtwCell) == kDtwCellBytes && kDtwCols == kPairCols && kDtwTile == kPairTile, "pair_plan.h sizes the matrices and edge buffers");
-
-__global__ void dtw_upload_pairs(DtwPairChunk c, DtwPair* dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c.n) dst[c.base + i] = c.r[i];
-}
 
 __global__ __launch_bounds__(256) void dtw_dist(const DtwPair* recs, int npairs, const float* a, const float* b, int64_t a_stride,
                                                 int64_t b_stride, int D, char* ws) {
@@ -217,22 +213,9 @@ __global__ __launch_bounds__(kDtwCols) void dtw_sweep(const DtwPair* recs, const
     }
 }
 
-__global__ __launch_bounds__(256) void dtw_combine(const double* recs, int B, double* terms, double* batch) {
-    const int tid = threadIdx.x;
-    if (terms)
-        for (int64_t i = tid; i < (int64_t)B * kDtwTerms; i += 256) terms[i] = recs[i];
-    if (batch && tid < kDtwTerms) {
-        double s = 0.0;
-        for (int b = 0; b < B; ++b) s += recs[(size_t)b * kDtwTerms + tid];
-        batch[tid] = s;
-    }
-}
-
 // ---- host side: pair_plan.h's plan, then per group dtw_dist and dtw_sweep ----
 // the pair records travel as kernel arguments: no host copy, no synchronisation
-inline void dtw_upload(const PairPlan& p, DtwPair* recs, hipStream_t s) {
-    pair_chunks(p, [&](const DtwPairChunk& c) { hipLaunchKernelGGL(dtw_upload_pairs, dim3((kDtwRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs); });
-}
+inline void dtw_upload(const PairPlan& p, hipStream_t s) { pair_chunks(p, upload_launch<DtwPair, kDtwRecsPerChunk>(p.at.recs, s)); }
 inline void dtw_launch_dist(const PairPlan& p, const PairGroup& g, const DtwPair* recs, char* ws, hipStream_t s) {
     if (g.tiles > 0)
         hipLaunchKernelGGL(dtw_dist, dim3((unsigned)g.tiles), dim3(256), 0, s, recs + g.first, g.count, p.a, p.b, p.a_stride, p.b_stride, p.D, ws);
@@ -250,16 +233,15 @@ int dt_dtw(void* stream, const fs2_op_dtw_args* a) {
     if (const int rc = pair_plan(kDtwOp, a, nullptr, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
-    DtwPair* recs = p.recs(ws);
-    double* recs_out = p.terms(ws);
-    dtw_upload(p, recs, s);
+    DtwPair* recs = p.at.recs;
+    double* recs_out = p.at.terms;
+    dtw_upload(p, s);
     // one dtw_dist and one dtw_sweep per group, in stream order: a group's matrices are dead when the next group's are written
     pair_groups(p, [&](const PairGroup& g) {
         dtw_launch_dist(p, g, recs, ws, s);
         hipLaunchKernelGGL(dtw_sweep, dim3((unsigned)g.count), dim3(kDtwCols), 0, s, recs + g.first, a->e_a, a->e_b, a->p_a, a->p_b, ws,
                            recs_out + (size_t)g.first * kDtwTerms);
     });
-    hipLaunchKernelGGL(dtw_combine, dim3(1), dim3(256), 0, s, recs_out, a->B, a->terms, a->batch);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FS2_OK : fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL((records_combine<kDtwTerms, -1, -1>), dim3(1), dim3(256), 0, s, recs_out, a->B, a->terms, a->batch);
+    return rec_finish(who);
 }

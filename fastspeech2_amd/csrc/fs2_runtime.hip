@@ -1228,8 +1228,8 @@ int32_t fs2_abi_version(void) { return FS2_ABI_VERSION; }
 #define ABI_CHECK(h, what, ptr, type)                                                                                         \
     do {                                                                                                                      \
         if ((ptr)->struct_size != (uint32_t)sizeof(type))                                                                     \
-            return fail(h, FS2_ERR_ARG, "%s: " #type ".struct_size is %u but this library (ABI %d) expects %zu: the binding " \
-                        "does not match include/fs2.h", what, (unsigned)(ptr)->struct_size, FS2_ABI_VERSION, sizeof(type));     \
+            return fail(h, FS2_ERR_ARG, FS2_STRUCT_SIZE_FMT, what, #type, (unsigned)(ptr)->struct_size, FS2_ABI_VERSION,         \
+                        sizeof(type)); /* (the wording of record_op.h's rec_check_struct) */                                  \
     } while (0)
 
 int fs2_create(const fs2_config* cfg, fs2_handle** out) {
@@ -2039,7 +2039,7 @@ size_t fs2_op_pitch_path_workspace_bytes(int32_t B, const int32_t* frame_lens) {
 
 int fs2_op_pitch_path(void* stream, const fs2_op_pitch_path_args* a) { return pp_pitch_path(stream, a); }
 
-size_t fs2_op_targets_workspace_bytes(int32_t B) { return B < 0 ? 0 : tg_layout(B).bytes; }
+size_t fs2_op_targets_workspace_bytes(int32_t B) { return tg_workspace_bytes(B); }
 
 int fs2_op_clean_targets(void* stream, const float* x, int32_t B, const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes,
                          float* y, float* quartiles, int32_t* n_outliers, double* stats) {

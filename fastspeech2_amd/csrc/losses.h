@@ -8,7 +8,7 @@
 // reduced in a fixed order -- no floating-point atomics.  Per utterance a record of FS2_LOSS_TERMS doubles (include/fs2.h lists it).
 //
 // lt_terms: one workgroup of 256 threads per TILE of kLtFrames frames of one utterance; an utterance of olen frames has
-// max(1, ceil(olen / kLtFrames)) tiles (uploaded with its record, as tg_upload_recs ships its records: kernel arguments, no copy).  The
+// max(1, ceil(olen / kLtFrames)) tiles (uploaded with its record by record_op.h's upload_recs: kernel arguments, no copy).  The
 // rows of an utterance lie back to back, so a tile's part of before / after / ys is one run of floats each, read once:
 //   thread t takes the quads t, t + 256, ... of the run (a quad's four values in order; 16-byte loads where the run starts on a 16-byte
 //   boundary, four 4-byte loads otherwise -- the same values in the same order, so the path changes no bit), then thread t < n % 4 takes
@@ -20,6 +20,7 @@
 // read.  lt_combine (one workgroup) folds the tiles of each utterance in index order into its record and the B records into the batch
 // record: thread t takes utterances t, t + 256, ... in order, then lane l takes lane l + o for o = 32 .. 1, then the four waves in order.
 
+#include "record_op.h"
 constexpr int kLtThreads = 256;
 constexpr int kLtFrames = 32;             // frames of a tile (odim = 80: 10 KB of each of before / after / ys)
 constexpr int kLtRecsPerChunk = 250;      // records per upload launch (kernel-argument bytes: 250 * 16 + 8 < 4 KB)
@@ -34,15 +35,6 @@ enum { kLtBefore = 0, kLtAfter, kLtDurSq, kLtEnergySq, kLtPitchSq, kLtDurAbs, kL
        kLtPadBefore, kLtPadAfter, kLtPadDurSq, kLtPadEnergySq, kLtPadPitchSq };
 
 struct LtRec { int ilen, olen, tile0, ntiles; };
-struct LtRecChunk {
-    int n, base;
-    LtRec r[kLtRecsPerChunk];
-};
-
-__global__ void lt_upload_recs(LtRecChunk c, LtRec* dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c.n) dst[c.base + i] = c.r[i];
-}
 
 struct LtArgs {
     const float *before, *after, *ys, *d_outs;
@@ -206,37 +198,34 @@ __global__ __launch_bounds__(kLtThreads) void lt_combine(const LtRec* recs, cons
     if (tid < kLtTerms) batch[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// ---- host side: workspace = the records, then one partial per tile, each 256-byte aligned ----
-struct LtLayout { size_t off_recs = 0, off_partials = 0, bytes = 0; int64_t tiles = 0; };
+// ---- host side: workspace = the records, then one partial per tile ----
+struct LtRegions { LtRec* recs; double* partials; size_t bytes; int64_t tiles; };
 
 inline int64_t lt_tiles(int32_t olen) { return std::max<int64_t>(1, ((int64_t)olen + kLtFrames - 1) / kLtFrames); }
 
 // false: a negative length, or more tiles than a grid holds
-bool lt_layout(int32_t B, const int32_t* olens, LtLayout& l) {
-    l = LtLayout{};
+bool lt_regions(int32_t B, const int32_t* olens, void* ws, LtRegions& r) {
+    int64_t tiles = 0;
     for (int b = 0; b < B; ++b) {
         if (olens[b] < 0) return false;
-        l.tiles += lt_tiles(olens[b]);
+        tiles += lt_tiles(olens[b]);
     }
-    if (l.tiles > INT32_MAX) return false;
-    const size_t nb = (size_t)std::max(B, 1);
-    l.off_partials = align_up(nb * sizeof(LtRec), 256);
-    l.bytes = align_up(l.off_partials + (size_t)std::max<int64_t>(l.tiles, 1) * kLtPartial * sizeof(double), 256);
+    if (tiles > INT32_MAX) return false;
+    Carve c{(char*)ws};
+    r = LtRegions{c.take<LtRec>(B), c.take<double>(tiles, kLtPartial), 0, tiles};
+    r.bytes = c.off;
     return true;
 }
 
 size_t lt_workspace_bytes(int32_t B, const int32_t* olens) {
-    LtLayout l;
-    if (B < 0 || (B > 0 && !olens) || !lt_layout(B, olens, l)) return 0;
-    return l.bytes;
+    LtRegions r;
+    if (B < 0 || (B > 0 && !olens) || !lt_regions(B, olens, nullptr, r)) return 0;
+    return r.bytes;
 }
 
 int lt_loss_terms(void* stream, const fs2_op_loss_args* a) {
     const char* who = "fs2_op_loss_terms";
-    if (!a) return fail(nullptr, FS2_ERR_ARG, "%s: null argument", who);
-    if (a->struct_size != (uint32_t)sizeof(fs2_op_loss_args))
-        return fail(nullptr, FS2_ERR_ARG, "%s: fs2_op_loss_args.struct_size is %u but this library (ABI %d) expects %zu: the binding does not match include/fs2.h",
-                    who, (unsigned)a->struct_size, FS2_ABI_VERSION, sizeof(fs2_op_loss_args));
+    if (const int rc = rec_check_struct(who, "fs2_op_loss_args", a)) return rc;
     const int32_t B = a->B;
     if (B < 0 || (B > 0 && (!a->ilens || !a->olens))) return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d) or null ilens / olens", who, B);
     if (a->Tmax < 0 || a->Lmax < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative Tmax %d / Lmax %d", who, a->Tmax, a->Lmax);
@@ -258,33 +247,22 @@ int lt_loss_terms(void* stream, const fs2_op_loss_args* a) {
     if (a->d_outs && a->Tmax > a->pred_stride_t) return fail(nullptr, FS2_ERR_ARG, "%s: Tmax %d > pred_stride_t %d", who, a->Tmax, a->pred_stride_t);
     if (a->d_outs && a->Tmax > a->ds_stride_t) return fail(nullptr, FS2_ERR_ARG, "%s: Tmax %d > ds_stride_t %d", who, a->Tmax, a->ds_stride_t);
     if (!a->terms && !a->batch) return FS2_OK;
-    LtLayout at;
-    if (!lt_layout(B, a->olens, at)) return fail(nullptr, FS2_ERR_ARG, "%s: more tiles than one launch holds", who);
-    if (B > 0 && !a->workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null workspace", who);
-    if (B > 0 && a->workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, a->workspace_bytes, at.bytes);
+    LtRegions at;                                       // (B = 0: no workspace, and lt_combine reads neither region)
+    if (!lt_regions(B, a->olens, a->workspace, at)) return fail(nullptr, FS2_ERR_ARG, "%s: more tiles than one launch holds", who);
+    if (const int rc = rec_check_workspace(who, B, a->workspace, a->workspace_bytes, at.bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)a->workspace;
-    LtRec* recs = ws ? (LtRec*)(ws + at.off_recs) : nullptr;                // (B = 0: lt_combine reads neither)
-    double* partials = ws ? (double*)(ws + at.off_partials) : nullptr;
+    auto up = rec_uploader<LtRec, kLtRecsPerChunk>(B, at.recs, s);
     int64_t tile0 = 0;
-    for (int i = 0; i < B; i += kLtRecsPerChunk) {      // records travel as kernel arguments: no host copy, no synchronisation
-        LtRecChunk c{};
-        c.n = std::min(kLtRecsPerChunk, B - i);
-        c.base = i;
-        for (int k = 0; k < c.n; ++k) {
-            const int nt = (int)lt_tiles(a->olens[i + k]);
-            c.r[k] = LtRec{a->ilens[i + k], a->olens[i + k], (int)tile0, nt};
-            tile0 += nt;
-        }
-        hipLaunchKernelGGL(lt_upload_recs, dim3((kLtRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs);
+    for (int b = 0; b < B; ++b) {
+        const int nt = (int)lt_tiles(a->olens[b]);
+        up.put(b, LtRec{a->ilens[b], a->olens[b], (int)tile0, nt});
+        tile0 += nt;
     }
     if (B > 0) {
         LtArgs k{a->before, a->after, a->ys, a->d_outs, a->ds, a->e_outs, a->es, a->p_outs, a->ps,
                  a->pred_stride_f, a->y_stride_f, a->pred_stride_t, a->ds_stride_t, a->tgt_stride_f, a->odim, B, a->Tmax, a->Lmax, a->pads != 0};
-        hipLaunchKernelGGL(lt_terms, dim3((unsigned)at.tiles), dim3(kLtThreads), 0, s, recs, k, partials);
+        hipLaunchKernelGGL(lt_terms, dim3((unsigned)at.tiles), dim3(kLtThreads), 0, s, at.recs, k, at.partials);
     }
-    hipLaunchKernelGGL(lt_combine, dim3(1), dim3(kLtThreads), 0, s, recs, partials, B, a->Tmax, a->Lmax, a->terms, a->batch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FS2_OK;
+    hipLaunchKernelGGL(lt_combine, dim3(1), dim3(kLtThreads), 0, s, at.recs, at.partials, B, a->Tmax, a->Lmax, a->terms, a->batch);
+    return rec_finish(who);
 }

@@ -25,8 +25,10 @@
 // No atomics, nothing waits on another workgroup, every loop is bounded by T, K or the chunk.  A back pointer is at most K by
 // construction and is clamped to K where it is read, so whatever the inputs hold every access stays in the utterance's own rows.
 //
-// pitch_path_combine (one workgroup): copies the records out and forms the batch record over the utterances in index order.
+// records_combine<8, 1, 5> (record_op.h; one workgroup): copies the records out and forms the batch record over the utterances in index
+// order -- column 1 counts the refused utterances, column 5 is the maximum and the others are sums over the rest.
 
+#include "record_op.h"
 constexpr int kPathChunk = 64;                          // frames staged in LDS at a time (= the lanes of the wave)
 constexpr int kPathStates = FS2_PITCH_MAX_CANDS + 1;
 constexpr int kPathTerms = FS2_PITCH_PATH_TERMS;
@@ -185,49 +187,31 @@ __global__ __launch_bounds__(kPathChunk) void pitch_path(PathBatch pb, int K, Pa
     }
 }
 
-__global__ __launch_bounds__(256) void pitch_path_combine(const double* recs, int B, double* terms, double* batch) {
-    const int tid = threadIdx.x;
-    if (terms)
-        for (int64_t i = tid; i < (int64_t)B * kPathTerms; i += 256) terms[i] = recs[i];
-    if (batch && tid < kPathTerms) {
-        double s = 0.0;
-        for (int b = 0; b < B; ++b) {
-            const bool fine = recs[(size_t)b * kPathTerms + 1] == 0.0;
-            const double v = recs[(size_t)b * kPathTerms + tid];
-            if (tid == 1) s += fine ? 0.0 : 1.0;
-            else if (fine && tid == 5) s = v > s ? v : s;
-            else if (fine) s += v;
-        }
-        batch[tid] = s;
-    }
-}
-
-// ---- host side ----
-struct PathLayout { size_t off_recs = 0, off_words = 0, bytes = 0; int64_t frames = 0; };
+// ---- host side: workspace = one record per utterance, then one word per frame ----
+struct PathRegions { double* recs; uint64_t* words; size_t bytes; int64_t frames; };
 
 // false: a negative B or length, or null lens with B > 0
-inline bool path_layout(int32_t B, const int32_t* lens, PathLayout& l) {
+inline bool path_regions(int32_t B, const int32_t* lens, void* ws, PathRegions& r) {
     if (B < 0 || (B > 0 && !lens)) return false;
     int64_t frames = 0;
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 0) return false;
         frames += lens[b];
     }
-    l.frames = frames;
-    l.off_recs = 0;
-    l.off_words = align_up((size_t)std::max(B, 1) * kPathTerms * sizeof(double), 256);
-    l.bytes = l.off_words + align_up((size_t)std::max<int64_t>(frames, 1) * sizeof(uint64_t), 256);
+    Carve c{(char*)ws};
+    r = PathRegions{c.take<double>(B, kPathTerms), c.take<uint64_t>(frames), 0, frames};
+    r.bytes = c.off;
     return true;
 }
 
 size_t path_workspace_bytes(int32_t B, const int32_t* frame_lens) {
-    PathLayout l;
-    return path_layout(B, frame_lens, l) ? l.bytes : 0;
+    PathRegions r;
+    return path_regions(B, frame_lens, nullptr, r) ? r.bytes : 0;
 }
 
 int pp_pitch_path(void* stream, const fs2_op_pitch_path_args* a) {
     const char* who = "fs2_op_pitch_path";
-    if (!a || a->struct_size != sizeof(fs2_op_pitch_path_args)) return fail(nullptr, FS2_ERR_ARG, "%s: struct_size mismatch", who);
+    if (const int rc = rec_check_struct(who, "fs2_op_pitch_path_args", a)) return rc;
     const int32_t B = a->B, K = a->n_candidates;
     if (K < 1 || K > FS2_PITCH_MAX_CANDS) return fail(nullptr, FS2_ERR_ARG, "%s: n_candidates = %d outside 1 .. %d", who, K, FS2_PITCH_MAX_CANDS);
     if (!(a->time_step > 0.0) || !std::isfinite(a->time_step) || !(a->f0_floor > 0.0) || !std::isfinite(a->f0_floor))
@@ -237,18 +221,15 @@ int pp_pitch_path(void* stream, const fs2_op_pitch_path_args* a) {
     if (!(a->octave_jump_cost >= 0.0) || !std::isfinite(a->octave_jump_cost) || !(a->voiced_unvoiced_cost >= 0.0) || !std::isfinite(a->voiced_unvoiced_cost))
         return fail(nullptr, FS2_ERR_ARG, "%s: octave_jump_cost %g and voiced_unvoiced_cost %g must be finite and not negative", who, a->octave_jump_cost,
                     a->voiced_unvoiced_cost);
-    PathLayout l;
-    if (!path_layout(B, a->frame_lens, l) || (B > 0 && !a->frame_starts)) return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d, a negative or missing length or start)", who, B);
+    PathRegions l;                                      // (B = 0: no workspace, and nothing is launched that reads a region)
+    if (!path_regions(B, a->frame_lens, a->workspace, l) || (B > 0 && !a->frame_starts))
+        return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d, a negative or missing length or start)", who, B);
     for (int b = 0; b < B; ++b)
         if (a->frame_starts[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative start of utterance %d", who, b);
     if (l.frames * K > INT32_MAX) return fail(nullptr, FS2_ERR_UNSUPPORTED, "%s: %lld frames of %d candidates", who, (long long)l.frames, K);
     hipStream_t s = (hipStream_t)stream;
-    if (B > 0) {
-        if (!a->workspace || (l.frames > 0 && (!a->cand_f0 || !a->cand_strength))) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
-        if (a->workspace_bytes < l.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, a->workspace_bytes, l.bytes);
-    }
-    char* ws = (char*)a->workspace;
-    double* recs = (double*)(ws + l.off_recs);
+    if (l.frames > 0 && (!a->cand_f0 || !a->cand_strength)) return fail(nullptr, FS2_ERR_ARG, "%s: null candidates", who);
+    if (const int rc = rec_check_workspace(who, B, a->workspace, a->workspace_bytes, l.bytes)) return rc;
     const double scale = 0.01 / a->time_step;
     const PathCosts pc{a->f0_floor, a->voicing_threshold, a->octave_cost, a->octave_jump_cost * scale, a->voiced_unvoiced_cost * scale};
     int64_t word0 = 0;
@@ -260,10 +241,9 @@ int pp_pitch_path(void* stream, const fs2_op_pitch_path_args* a) {
             pb.u[i] = PathUtt{a->frame_starts[base + i], a->frame_lens[base + i], word0};
             word0 += a->frame_lens[base + i];
         }
-        hipLaunchKernelGGL(pitch_path, dim3((unsigned)pb.n), dim3(kPathChunk), 0, s, pb, K, pc, a->cand_f0, a->cand_strength, (uint64_t*)(ws + l.off_words),
-                           a->f0, a->state, a->strength, recs);
+        hipLaunchKernelGGL(pitch_path, dim3((unsigned)pb.n), dim3(kPathChunk), 0, s, pb, K, pc, a->cand_f0, a->cand_strength, l.words, a->f0, a->state,
+                           a->strength, l.recs);
     }
-    if (a->terms || a->batch) hipLaunchKernelGGL(pitch_path_combine, dim3(1), dim3(256), 0, s, recs, B, a->terms, a->batch);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FS2_OK : fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (a->terms || a->batch) hipLaunchKernelGGL((records_combine<kPathTerms, 1, 5>), dim3(1), dim3(256), 0, s, l.recs, B, a->terms, a->batch);
+    return rec_finish(who);
 }

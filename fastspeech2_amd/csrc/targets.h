@@ -1,7 +1,8 @@
 // Training targets from the per-frame energy and F0 arrays: the reference's remove_outlier (utils/util.py:26-49, applied to every
 // energy and pitch array the data loader returns) and the corpus statistics of compute_statistics.py, behind
 // fs2_op_clean_targets (include/fs2.h; tests/targets_oracle.py states the same in numpy).
-// Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up().  Plain HIP C++.
+// Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up(); the checks, the
+// workspace carve and the record upload are record_op.h's.  Plain HIP C++.
 //
 // Per utterance x (float32, n >= 1 values), every operation rounded to float32 on its own (nothing here may be contracted into a
 // fused multiply-add: a fused p25 - 1.5 iqr decides a value that ties with the threshold the other way):
@@ -20,6 +21,7 @@
 // in double and reduced in a fixed tree (xor butterfly in the wave, then the four waves in order): no floating-point atomics, and an
 // utterance's numbers depend on its own values only.  tg_combine folds the per-utterance records in a fixed order with Chan's update.
 
+#include "record_op.h"
 constexpr int kTgThreads = 256;
 constexpr int kTgStage = 4096;            // keys of an utterance kept in LDS (16 KB); a longer one is re-read from global memory
 constexpr int kTgRecsPerChunk = 500;      // (start, length) records per upload launch (kernel-argument bytes: 500 * 8 + 8 < 4 KB)
@@ -29,15 +31,6 @@ constexpr int kTgStats = 12;              // doubles of a statistics record
 enum { kTgNTotal = 0, kTgNOutliers, kTgNNonfinite, kTgNNoPositive, kTgN, kTgMin, kTgNonzeroMin, kTgMax, kTgMean, kTgStd, kTgM2, kTgReserved };
 
 struct TgRec { int start, len; };
-struct TgRecChunk {
-    int n, base;
-    TgRec r[kTgRecsPerChunk];
-};
-
-__global__ void tg_upload_recs(TgRecChunk c, TgRec* dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c.n) dst[c.base + i] = c.r[i];
-}
 
 __device__ inline uint32_t tg_key(float v) {
     const uint32_t u = __float_as_uint(v);
@@ -322,47 +315,29 @@ __global__ __launch_bounds__(kTgThreads) void tg_combine(const double* partials,
     }
 }
 
-// ---- host side: workspace = the (start, length) records, then one statistics record per utterance, each 256-byte aligned ----
-struct TgLayout { size_t off_recs = 0, off_partials = 0, bytes = 0; };
-
-TgLayout tg_layout(int32_t B) {
-    TgLayout l;
-    const size_t nb = (size_t)std::max(B, 1);
-    l.off_recs = 0;
-    l.off_partials = align_up(nb * sizeof(TgRec), 256);
-    l.bytes = align_up(l.off_partials + nb * kTgStats * sizeof(double), 256);
-    return l;
+// ---- host side: workspace = the (start, length) records, then one statistics record per utterance ----
+struct TgLayout { TgRec* recs; double* partials; size_t bytes; };
+inline TgLayout tg_layout(int32_t B, void* ws = nullptr) {
+    Carve c{(char*)ws};
+    TgLayout r{c.take<TgRec>(B), c.take<double>(B, kTgStats), 0};
+    r.bytes = c.off;
+    return r;
 }
+size_t tg_workspace_bytes(int32_t B) { return B < 0 ? 0 : tg_layout(B).bytes; }
 
 int tg_clean_targets(void* stream, const float* x, int32_t B, const int32_t* starts, const int32_t* lens, void* workspace, size_t workspace_bytes,
                      float* y, float* quartiles, int32_t* n_outliers, double* stats) {
     const char* who = "fs2_op_clean_targets";
     if (B < 0 || (B > 0 && (!starts || !lens))) return fail(nullptr, FS2_ERR_ARG, "%s: bad batch (B = %d) or null starts / lens", who, B);
-    int64_t total = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 0 || starts[b] < 0) return fail(nullptr, FS2_ERR_ARG, "%s: negative length / start of utterance %d", who, b);
-        if ((int64_t)starts[b] + lens[b] > INT32_MAX) return fail(nullptr, FS2_ERR_ARG, "%s: utterance %d ends beyond 2^31 - 1 values", who, b);
-        total += lens[b];
-    }
+    if (const int rc = rec_check_rows(who, "utterance", B, starts, lens)) return rc;
     if (B == 0 && !stats) return FS2_OK;
-    if (total > 0 && (!x || !y)) return fail(nullptr, FS2_ERR_ARG, "%s: null x / y", who);
-    const TgLayout at = tg_layout(B);
-    if (B > 0 && !workspace) return fail(nullptr, FS2_ERR_ARG, "%s: null workspace", who);
-    if (B > 0 && workspace_bytes < at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, at.bytes);
+    if (std::any_of(lens, lens + B, [](int32_t n) { return n > 0; }) && (!x || !y)) return fail(nullptr, FS2_ERR_ARG, "%s: null x / y", who);
+    const TgLayout at = tg_layout(B, workspace);      // (B = 0: no workspace, and tg_combine reads none)
+    if (const int rc = rec_check_workspace(who, B, workspace, workspace_bytes, at.bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    TgRec* recs = (TgRec*)(ws + at.off_recs);
-    double* partials = ws ? (double*)(ws + at.off_partials) : nullptr;      // (B = 0: tg_combine reads none)
-    for (int i = 0; i < B; i += kTgRecsPerChunk) {      // records travel as kernel arguments: no host copy, no synchronisation
-        TgRecChunk c{};
-        c.n = std::min(kTgRecsPerChunk, B - i);
-        c.base = i;
-        for (int k = 0; k < c.n; ++k) c.r[k] = TgRec{starts[i + k], lens[i + k]};
-        hipLaunchKernelGGL(tg_upload_recs, dim3((kTgRecsPerChunk + 255) / 256), dim3(256), 0, s, c, recs);
-    }
-    if (B > 0) hipLaunchKernelGGL(tg_clean, dim3((unsigned)B), dim3(kTgThreads), 0, s, recs, x, y, quartiles, n_outliers, partials);
-    if (stats) hipLaunchKernelGGL(tg_combine, dim3(1), dim3(kTgThreads), 0, s, partials, B, stats);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return FS2_OK;
+    auto up = rec_uploader<TgRec, kTgRecsPerChunk>(B, at.recs, s);
+    for (int b = 0; b < B; ++b) up.put(b, TgRec{starts[b], lens[b]});
+    if (B > 0) hipLaunchKernelGGL(tg_clean, dim3((unsigned)B), dim3(kTgThreads), 0, s, at.recs, x, y, quartiles, n_outliers, at.partials);
+    if (stats) hipLaunchKernelGGL(tg_combine, dim3(1), dim3(kTgThreads), 0, s, at.partials, B, stats);
+    return rec_finish(who);
 }

@@ -5,12 +5,9 @@
 //   OUT: float64 terms[B][8], float64 batch[8], int64 durations[B][dur_stride], int32 state[b_rows]
 // The workspace is what fs2_op_align_workspace_bytes answers for cap_bytes.  --checks: one line "name code" per refused (or accepted)
 // argument set.  Every buffer is a heap block of exactly its size, so that a sanitizer build sees an access beyond it.
-#include "hip_standin.h"
+#include "standin_host.h"
 #include "hip_standin_record.h"      // (for dtw_sweep, which is compiled with dtw.h; only dtw_dist runs here)
-#include "fs2.h"
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 #include "dtw.h"
 #include "align.h"
 

@@ -4,12 +4,9 @@
 //   OUT: float64 terms[B][12], float64 batch[12]
 // The workspace is what fs2_op_dtw_workspace_bytes answers for cap_bytes.  --checks: one line "name code" per refused (or accepted)
 // argument set.  Every buffer is a heap block of exactly its size, so that a sanitizer build sees a read beyond it.
-#include "hip_standin.h"
+#include "standin_host.h"
 #include "hip_standin_record.h"
-#include "fs2.h"
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 #include "dtw.h"
 
 template <typename T> bool read_into(FILE* f, std::vector<T>& v, size_t n) {

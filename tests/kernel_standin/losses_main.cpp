@@ -5,11 +5,8 @@
 //   OUT: float64 terms[B][20], float64 batch[20]
 // misalign: before / after / ys start 4 bytes off a 16-byte boundary (the 4-byte load path).  --checks: one line "name code" per
 // refused (or accepted) argument set.  Every buffer is a heap block of exactly its size, so that a sanitizer build sees a read beyond it.
-#include "hip_standin.h"
-#include "fs2.h"
+#include "standin_host.h"
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 #include "targets.h"
 #include "losses.h"
 

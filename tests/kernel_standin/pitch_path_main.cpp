@@ -4,13 +4,10 @@
 //   OUT: float64 terms[B][8], float64 batch[8], float32 f0[rows], int32 state[rows], float32 strength[rows]
 // Rows no utterance covers keep -777.  --checks: one line "name code" per refused (or accepted) argument set.  Every buffer is a
 // heap block of exactly its size, so that a sanitizer build sees an access beyond it.
-#include "hip_standin.h"
-#include "fs2.h"
+#include "standin_host.h"
 // the indexed shuffle, which the stand-in does not have: the value of lane `src` of the caller's wave
 template <typename T> T __shfl(T v, int src) { return shfl_from(v, src); }
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 #include "pitch_path.h"
 
 template <typename T> bool read_into(FILE* f, std::vector<T>& v, size_t n) {

@@ -7,10 +7,8 @@
 //         OUT: float32 p_rows[R], e_rows[R]
 // --checks: one line "name code" per refused (or accepted) argument set.  Every buffer is a heap block of exactly its size, so that a
 // sanitizer build sees an access beyond it.
-#include "hip_standin.h"
-#include "fs2.h"
+#include "standin_host.h"
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
 #include "prosody.h"
 
 template <typename T> bool read_into(FILE* f, std::vector<T>& v, size_t n) {

@@ -1,11 +1,8 @@
 // tg_clean_targets of csrc/targets.h on the host stand-in.  Usage: targets_main IN OUT [inplace]
 //   IN:  int32 B, int32 lens[B], float32 x[sum lens]
 //   OUT: float32 y[sum lens], float32 quartiles[B][2], int32 n_outliers[B], float64 stats[12]
-#include "hip_standin.h"
-#include "fs2.h"
+#include "standin_host.h"
 namespace {
-int fail(void*, int code, const char* fmt, ...) { fprintf(stderr, "fail: %s\n", fmt); return code; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 #include "targets.h"
 }  // namespace
 
@@ -23,7 +20,7 @@ int main(int argc, char** argv) {
     double stats[12];
     if (total && fread(x.data(), 4, total, f) != (size_t)total) return 2;
     fclose(f);
-    std::vector<char> ws(tg_layout(B).bytes);
+    std::vector<char> ws(tg_workspace_bytes(B));
     float* yp = argc > 3 ? x.data() : y.data();
     if (int rc = tg_clean_targets(nullptr, x.data(), B, starts.data(), lens.data(), ws.data(), ws.size(), yp, q.data(), n_out.data(), stats)) return rc;
     FILE* o = fopen(argv[2], "wb");

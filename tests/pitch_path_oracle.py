@@ -1,5 +1,5 @@
 """Float64 numpy statement of the pitch path search of fastspeech2_amd.vocoder.pitch_candidates / pitch_path / pitch_track
-(csrc/gl_pitch.h: gl_candidates; csrc/pitch_path.h: pitch_path, pitch_path_combine), on top of
+(csrc/gl_pitch.h: gl_candidates; csrc/pitch_path.h: pitch_path, records_combine<8, 1, 5>), on top of
 tests/pitch_oracle.py, whose frames, rho and candidate rule are used as they are.
 
 Candidates.  Per frame the candidates of tests/pitch_oracle.py (integer lags t with rho[t] > rho[t-1], rho[t] >= rho[t+1], rho[t] > 0,
@@ -362,4 +362,20 @@ def synthetic_batch(C, K, seed=0):
     f, p = one(C + 1, 0.3)
     f[C // 2, K - 1] = np.nan
     out.append((f, p))
+    return out
+
+
+def boundary_batch(C, per_launch, K=2, seed=0):
+    """per_launch + 1 utterances of 0 .. 3 frames, the last one of the first launch with C + 1 frames (one more than a chunk): the
+    second launch's only utterance follows it in the workspace's words and in the records.  Same slots as synthetic_batch."""
+    rs = np.random.RandomState(77 + seed)
+    out = []
+    for i in range(per_launch + 1):
+        T = C + 1 if i == per_launch - 1 else (i + 1) % 4
+        f = rs.uniform(60.0, 700.0, (T, K)).astype(np.float32)
+        p = rs.uniform(0.0, 1.0, (T, K)).astype(np.float32)
+        gone = rs.uniform(size=(T, K)) < 0.3
+        f[gone] = 0
+        p[gone] = 0
+        out.append((f, p))
     return out

@@ -1,4 +1,4 @@
-"""CPU: the code of the alignment kernels (csrc/align.h: align_sweep, align_combine and their host side, with dtw_dist of csrc/dtw.h
+"""CPU: the code of the alignment kernels (csrc/align.h: align_sweep, records_combine<8, 2, -1> and their host side, with dtw_dist of csrc/dtw.h
 on the swapped sides) compiled for the host against the stand-in of the HIP constructs it uses (tests/kernel_standin: one thread per
 lane, one workgroup at a time) and run on the edge batch of tests/test_gpu_align.py.  This checks the kernels' logic -- the swapped
 matrix, what is read after which barrier, the walk back and its counts, the grouping -- and every index they form without a GPU;
@@ -11,13 +11,12 @@ chosen predecessor), so nothing is left to differ.
 Built with -fsanitize=address,undefined when FS2_STANDIN_ASAN=1 (a stand-alone host program: the sanitizer never sees the GPU)."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import align_oracle as A
+from tests import align_oracle as A, standin_build
 from tests.test_gpu_align import T, W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,15 +35,7 @@ def test_W_and_T_are_the_kernels():
 
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    cxx = os.environ.get("CXX", "g++")
-    if shutil.which(cxx) is None:
-        pytest.fail("no C++ compiler (%s) to build the kernel stand-in" % cxx)
-    exe = str(tmp_path_factory.mktemp("standin") / "align_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-    subprocess.run([cxx, "-std=c++20", "-O1", "-pthread"] + san + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "fastspeech2_amd", "csrc"),
-                    "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "align_main.cpp"), "-o", exe],
-                   check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/align_main.cpp")
 
 
 _edges = {}

@@ -18,7 +18,7 @@ import torch
 
 from tests import pitch_oracle as P
 from tests import pitch_path_oracle as Q
-from tests.test_pitch_path_kernel_host import COSTS, assert_records, chunk
+from tests.test_pitch_path_kernel_host import COSTS, assert_records, chunk, utts_per_launch
 
 pytestmark = pytest.mark.gpu
 
@@ -219,6 +219,19 @@ def test_path_kernel_on_the_edge_lengths(k):
         want = _assert_track_equals_oracle(track, cf_np, cs_np, lens, ts, costs, k)
         assert [int(w.record[Q.FLAGS]) for w in want] == [0] * 9 + [2] and track.per_utterance()["flags"].tolist() == [0] * 9 + [2]
         assert track.batch[Q.FLAGS] == 1 and track.batch[Q.N_FRAMES] == lens[:-1].sum()
+
+
+def test_more_utterances_than_one_launch_holds():
+    """129 utterances at K = 2: the last one travels with a second launch, behind an utterance one frame longer than a chunk."""
+    from fastspeech2_amd.vocoder import pitch_path
+    utts = Q.boundary_batch(chunk(), utts_per_launch())
+    lens = np.asarray([len(f) for f, _ in utts])
+    assert len(utts) == 129 and lens[127] == 65 and lens[128] > 0 and np.delete(lens, 127).max() == 3
+    cf_np, cs_np = np.concatenate([f for f, _ in utts]), np.concatenate([p for _, p in utts])
+    ts = 256 / 22050
+    track = pitch_path(torch.from_numpy(cf_np).cuda(), torch.from_numpy(cs_np).cuda(), lens, ts, **COSTS["default"])
+    _assert_track_equals_oracle(track, cf_np, cs_np, lens, ts, COSTS["default"], "boundary")
+    assert track.batch[Q.FLAGS] == 0 and track.batch[Q.N_FRAMES] == lens.sum()
 
 
 # ---- 4. end to end against the pure oracle ----

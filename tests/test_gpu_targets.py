@@ -76,9 +76,16 @@ def _edge_utterances():
     return u
 
 
+def _many_utterances():
+    """501 utterances of 0 .. 3 values: one more than an upload launch of records holds (csrc/targets.h: kTgRecsPerChunk = 500).  Most
+    are empty (the host stand-in runs a workgroup's 256 threads as threads); the ends of the batch and every 50th utterance are not."""
+    rng = np.random.default_rng(501)
+    return [("u%d" % i, rng.normal(1.0, 2.0, (i + 3) % 4 if i < 4 or i > 495 or i % 50 == 0 else 0).astype(F)) for i in range(501)]
+
+
 class Edge:
-    def __init__(self):
-        self.named = _edge_utterances()
+    def __init__(self, named=None):
+        self.named = _edge_utterances() if named is None else named
         self.names = [n for n, _ in self.named]
         self.utts = [x for _, x in self.named]
         self.lens = [x.size for x in self.utts]
@@ -127,6 +134,22 @@ def test_edge_batch_equals_the_oracle(edge):
     assert no[edge.names.index("long")] > 100 and no[edge.names.index("on_upper")] >= 1 and no[edge.names.index("on_lower")] >= 1
     assert st.n_nonfinite == 2 and st.n_total == sum(edge.lens) - 80
     assert _same(remove_outlier(edge.x, edge.lens).cpu().numpy(), y)
+
+
+def test_more_utterances_than_an_upload_chunk():
+    """Record 500 travels alone in a second upload launch: every utterance still finds its own (start, length)."""
+    from fastspeech2_amd.targets import clean_targets
+    many = Edge(_many_utterances())
+    assert len(many.utts) == 501 and sorted(set(many.lens)) == [0, 1, 2, 3] and many.lens[500] == 3
+    assert many.stats.mean <= 10 * many.stats.std
+    y, st, q, no = clean_targets(many.x, many.lens, return_quartiles=True)
+    y, q, no = y.cpu().numpy(), q.cpu().numpy(), no.cpu().numpy()
+    off = np.concatenate([[0], np.cumsum(many.lens)])
+    for i, (name, c) in enumerate(zip(many.names, many.cleaned)):
+        assert _same(y[off[i]:off[i + 1]], c.y), name
+        assert _same(q[i], [c.p25, c.p75]), (name, q[i], c.p25, c.p75)
+        assert no[i] == c.n_outliers, (name, no[i], c.n_outliers)
+    _stats_close(st, many.stats)
 
 
 def test_batch_invariance(edge):

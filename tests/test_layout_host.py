@@ -20,6 +20,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import standin_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fastspeech2_amd", "csrc")
 INT32_MAX = 2 ** 31 - 1
@@ -75,10 +77,6 @@ def batches():
 BATCHES = batches()
 
 
-def _san():
-    return ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-
-
 def _checked(r):
     assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     return r.stdout.splitlines()
@@ -86,8 +84,7 @@ def _checked(r):
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("layout") / "probe")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + _san() + ["-I", CSRC, os.path.join(ROOT, "tests", "layout_probe.cpp"), "-o", exe], check=True)
+    exe = standin_build.build(tmp_path_factory, "tests/layout_probe.cpp", flags=("-std=c++17", "-Wall", "-Werror"))
 
     def run(*args):
         out = {}
@@ -198,10 +195,7 @@ def test_overflow_flags(probe):
 # ---- the kernels' code on the host stand-in
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("standin") / "layout_main")
-    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++20", "-O1", "-pthread"] + _san() + ["-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "layout_main.cpp"), "-o", exe], check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/layout_main.cpp")
 
 
 def _launch(standin, tmp_path, counts, gap=4, compat=0, masked=0, row_cap=0, work_cap=0, lmax_cap=0, pe_rows=1 << 20, refused=False):

@@ -14,13 +14,12 @@ a term, far below the bar.)
 Built with -fsanitize=address,undefined when FS2_STANDIN_ASAN=1 (a stand-alone host program: the sanitizer never sees the GPU)."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import losses_oracle as O
+from tests import losses_oracle as O, standin_build
 from tests.test_gpu_losses import K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,15 +32,7 @@ def test_K_is_the_kernels_tile():
 
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    cxx = os.environ.get("CXX", "g++")
-    if shutil.which(cxx) is None:
-        pytest.fail("no C++ compiler (%s) to build the kernel stand-in" % cxx)
-    exe = str(tmp_path_factory.mktemp("standin") / "losses_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-    subprocess.run([cxx, "-std=c++20", "-O1", "-pthread"] + san + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "fastspeech2_amd", "csrc"),
-                    "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "losses_main.cpp"), "-o", exe],
-                   check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/losses_main.cpp")
 
 
 @pytest.fixture(scope="module")

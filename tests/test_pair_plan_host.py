@@ -13,11 +13,12 @@ without looking at the header:
 
 Built with -fsanitize=address,undefined when FS2_STANDIN_ASAN=1 (a stand-alone host program)."""
 import os
+import re
 import subprocess
 
 import pytest
 
-from tests import align_oracle, dtw_oracle
+from tests import align_oracle, dtw_oracle, standin_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fastspeech2_amd", "csrc")
@@ -72,10 +73,7 @@ def want_groups(op, shapes, ws_bytes):
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("pair_plan") / "probe")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + san + ["-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "pair_plan_probe.cpp"), "-o", exe], check=True)
+    exe = standin_build.build(tmp_path_factory, "tests/pair_plan_probe.cpp", flags=("-std=c++17", "-Wall", "-Werror"))
 
     def run(op, mode, ws, shapes, *flags):
         r = subprocess.run([exe, op, mode, str(ws)] + list(flags) + ["%d:%d" % s for s in shapes], capture_output=True, text=True, timeout=120)
@@ -158,9 +156,15 @@ def check_plan(op, shapes, ws_bytes, got, labels=False):
 
 
 def test_pair_plan_header_is_plain_cpp():
+    """No HIP construct in pair_plan.h, whose one include is record_op.h; none either, and no include, in the half of record_op.h that a
+    plain host compiler sees (what stands ahead of its device half)."""
+    hip = ("__global__", "__device__", "__shared__", "hipLaunch", "hipStream", "hipError", "threadIdx", "blockIdx")
     src = open(os.path.join(CSRC, "pair_plan.h")).read()
-    for word in ("#include", "__global__", "__device__", "__shared__", "hipLaunch", "hipStream", "hipError", "threadIdx", "blockIdx"):
-        assert word not in src, word
+    assert re.findall(r"#\s*(?:include|import)\s*(\S+)", src) == ['"record_op.h"']
+    plain, guard, device = open(os.path.join(CSRC, "record_op.h")).read().partition("#ifdef __global__")
+    assert guard and device.rstrip().endswith("#endif") and device.count("#if") == 0 and not re.search(r"#\s*(?:include|import)", plain)
+    for word in hip:
+        assert word not in src and word not in plain, word
 
 
 @pytest.mark.parametrize("op", OPS)

@@ -8,29 +8,17 @@ divides once; prosody_apply rounds a float32 product and then a float32 sum: num
 order, so nothing is left to differ.
 
 Built with -fsanitize=address,undefined when FS2_STANDIN_ASAN=1 (a stand-alone host program: the sanitizer never sees the GPU)."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import prosody_oracle as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import prosody_oracle as P, standin_build
 
 
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    cxx = os.environ.get("CXX", "g++")
-    if shutil.which(cxx) is None:
-        pytest.fail("no C++ compiler (%s) to build the kernel stand-in" % cxx)
-    exe = str(tmp_path_factory.mktemp("standin") / "prosody_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-    subprocess.run([cxx, "-std=c++20", "-O1", "-pthread"] + san + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "fastspeech2_amd", "csrc"),
-                    "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "prosody_main.cpp"), "-o", exe],
-                   check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/prosody_main.cpp")
 
 
 def _exec(standin, args):

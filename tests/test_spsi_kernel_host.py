@@ -6,30 +6,17 @@ index they form without a GPU; what hipcc makes of the arithmetic only tests/tes
 The bar: EQUALITY of bits of the phase with the numpy statement (each float32 operation rounded on its own in both).
 
 Built with -fsanitize=address,undefined when FS2_STANDIN_ASAN=1 (a stand-alone host program: the sanitizer never sees the GPU)."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import spsi_oracle as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import spsi_oracle as S, standin_build
 
 
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    cxx = os.environ.get("CXX", "g++")
-    if shutil.which(cxx) is None:
-        pytest.fail("no C++ compiler (%s) to build the kernel stand-in" % cxx)
-    exe = str(tmp_path_factory.mktemp("standin") / "spsi_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("FS2_STANDIN_ASAN") == "1" else []
-    subprocess.run([cxx, "-std=c++20", "-O1", "-pthread", "-ffp-contract=off"] + san
-                   + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "fastspeech2_amd", "csrc"),
-                      "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "spsi_main.cpp"), "-o", exe],
-                   check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/spsi_main.cpp", extra=("-ffp-contract=off",))
 
 
 def run(standin, tmp_path, n_fft, hop, src, starts, lens, pinv=None, dev=False, stride=0, cap=0, expect=0):

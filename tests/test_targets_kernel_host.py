@@ -3,8 +3,6 @@ against a stand-in of the HIP constructs it uses (tests/kernel_standin: one thre
 whole edge batch of tests/test_gpu_targets.py: every cleaned value, quartile and outlier count equals the oracle, out of place and in
 place.  This checks the kernels' logic without a GPU; what hipcc makes of the arithmetic (contraction) only tests/test_gpu_targets.py
 can see.  Built with -fsanitize=thread when FS2_STANDIN_TSAN=1 (slower; finds an LDS word reused without a barrier)."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -12,22 +10,13 @@ import numpy as np
 import pytest
 
 from fastspeech2_amd.targets import TargetStats
-from tests.test_gpu_targets import Edge, _same, _stats_close
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import standin_build
+from tests.test_gpu_targets import Edge, _many_utterances, _same, _stats_close
 
 
 @pytest.fixture(scope="module")
 def standin(tmp_path_factory):
-    cxx = os.environ.get("CXX", "g++")
-    if shutil.which(cxx) is None:
-        pytest.fail("no C++ compiler (%s) to build the kernel stand-in" % cxx)
-    exe = str(tmp_path_factory.mktemp("standin") / "targets_main")
-    tsan = ["-fsanitize=thread", "-g"] if os.environ.get("FS2_STANDIN_TSAN") == "1" else []
-    subprocess.run([cxx, "-std=c++20", "-O1", "-pthread"] + tsan + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "fastspeech2_amd", "csrc"),
-                    "-I", os.path.join(ROOT, "tests", "kernel_standin"), os.path.join(ROOT, "tests", "kernel_standin", "targets_main.cpp"), "-o", exe],
-                   check=True)
-    return exe
+    return standin_build.build(tmp_path_factory, "tests/kernel_standin/targets_main.cpp", tsan=True)
 
 
 @pytest.fixture(scope="module")
@@ -35,8 +24,19 @@ def edge():
     return Edge()
 
 
+def test_more_utterances_than_an_upload_chunk(standin, tmp_path):
+    """501 utterances of 0 .. 3 values: record 500 travels alone in a second upload launch."""
+    many = Edge(_many_utterances())
+    assert len(many.utts) == 501 and many.lens[500] == 3 and max(many.lens) == 3
+    _run_and_compare(standin, many, tmp_path, False)
+
+
 @pytest.mark.parametrize("inplace", [False, True], ids=["out_of_place", "in_place"])
 def test_kernel_code_on_the_host_equals_the_oracle(standin, edge, tmp_path, inplace):
+    _run_and_compare(standin, edge, tmp_path, inplace)
+
+
+def _run_and_compare(standin, edge, tmp_path, inplace):
     B, total = len(edge.utts), sum(edge.lens)
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     with open(src, "wb") as f:

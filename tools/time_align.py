@@ -1,5 +1,5 @@
 """The forced alignment on one MI355X: fs2_op_align (csrc/align.h: dtw_dist on the swapped sides + align_sweep with its walk back +
-align_combine) beside fs2_op_dtw on the SAME 64 pairs.  Prints one JSON line.
+records_combine<8, 2, -1>) beside fs2_op_dtw on the SAME 64 pairs.  Prints one JSON line.
 
 Workload: 64 pairs of 80-dimensional frames; M = the c3 batch's recorded lengths, N = M scaled by a factor in [0.85, 1.15] (what a
 free-running synthesis of the same text gives); b is a time-warped noisy copy of a, so every pair has an alignment.  Both ops are

@@ -1,4 +1,4 @@
-"""The DTW of the free-running validation on one MI355X: fs2_op_dtw (csrc/dtw.h: dtw_dist + dtw_sweep + dtw_combine) on the c3-shaped
+"""The DTW of the free-running validation on one MI355X: fs2_op_dtw (csrc/dtw.h: dtw_dist + dtw_sweep + records_combine<12, -1, -1>) on the c3-shaped
 validation batch, beside (a) the free-running forward that produces its input and (b) what a user would write today -- torch.cdist
 plus one torch step per anti-diagonal -- for ONE pair of median length.  Prints one JSON line.
 

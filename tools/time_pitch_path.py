@@ -1,5 +1,5 @@
 """wav -> (log-mel, energy, f0) at c3 on one MI355X with and without the pitch path search: wav_features(f0_method="frame") (one
-gl_features launch) against wav_features(f0_method="path") (one gl_candidates launch, then pitch_path and pitch_path_combine;
+gl_features launch) against wav_features(f0_method="path") (one gl_candidates launch, then pitch_path and records_combine<8, 1, 5>;
 csrc/gl_pitch.h, csrc/pitch_path.h), and the pitch_path call alone on the candidates of the same batch.
 Prints one JSON line.
 
