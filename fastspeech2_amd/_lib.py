@@ -150,6 +150,8 @@ EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs
            "fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev",
            "fs2_op_vocode_mel_workspace_bytes_geom", "fs2_op_griffin_lim_mel_geom", "fs2_op_vocode_mel_workspace_bytes_cap", "fs2_op_griffin_lim_mel_dev",
            "fs2_op_spsi_workspace_bytes_geom", "fs2_op_spsi_workspace_bytes_cap", "fs2_op_spsi_phase_geom", "fs2_op_spsi_phase_dev",
+           "fs2_op_f0_phase_workspace_bytes_geom", "fs2_op_f0_phase_workspace_bytes_cap", "fs2_op_f0_phase_geom", "fs2_op_f0_phase_dev",
+           "fs2_op_excitation_geom", "fs2_op_excitation_dev",
            "fs2_op_targets_workspace_bytes", "fs2_op_clean_targets", "fs2_op_loss_workspace_bytes", "fs2_op_loss_terms",
            "fs2_op_dtw_workspace_bytes", "fs2_op_dtw", "fs2_op_align_workspace_bytes", "fs2_op_align",
            "fs2_op_pitch_path_workspace_bytes", "fs2_op_pitch_path",
@@ -377,6 +379,21 @@ def lib():
     # stream, geometry, src, src_width, mel_pinv, B, lens_dev, src_stride, frame_capacity, upstream_status, workspace, workspace_bytes, phase, mag_out
     L.fs2_op_spsi_phase_dev.argtypes = [vp] + gp + [vp, i32, vp, i32, vp, i32, C.c_int64, vp, vp, C.c_size_t, vp, vp]
     L.fs2_op_spsi_phase_dev.restype = C.c_int
+    L.fs2_op_f0_phase_workspace_bytes_geom.argtypes = gp + [i32, i32p]
+    L.fs2_op_f0_phase_workspace_bytes_geom.restype = C.c_size_t
+    L.fs2_op_f0_phase_workspace_bytes_cap.argtypes = gp + [i32, C.c_int64]
+    L.fs2_op_f0_phase_workspace_bytes_cap.restype = C.c_size_t
+    # stream, geometry, f0, B, starts, lens, f0_floor, f0_ceil, sample_rate, seed, workspace, workspace_bytes, phase (excitation: wav)
+    for f in (L.fs2_op_f0_phase_geom, L.fs2_op_excitation_geom):
+        f.argtypes = [vp] + gp + [vp, i32, i32p, i32p, C.c_double, C.c_double, i32, C.c_uint32, vp, C.c_size_t, vp]
+        f.restype = C.c_int
+    # stream, geometry, f0, B, lens_dev, src_stride, frame_capacity, upstream_status, f0_floor, f0_ceil, sample_rate, seed, workspace,
+    # workspace_bytes, phase (excitation: wav, wav_stride, wav_capacity)
+    dev = [vp] + gp + [vp, i32, vp, i32, C.c_int64, vp, C.c_double, C.c_double, i32, C.c_uint32, vp, C.c_size_t, vp]
+    L.fs2_op_f0_phase_dev.argtypes = dev
+    L.fs2_op_f0_phase_dev.restype = C.c_int
+    L.fs2_op_excitation_dev.argtypes = dev + [i32, C.c_int64]
+    L.fs2_op_excitation_dev.restype = C.c_int
     L.fs2_op_targets_workspace_bytes.argtypes = [i32]
     L.fs2_op_targets_workspace_bytes.restype = C.c_size_t
     # stream, x, B, starts, lens, workspace, workspace_bytes, y, quartiles, n_outliers, stats

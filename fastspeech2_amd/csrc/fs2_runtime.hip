@@ -41,6 +41,7 @@
 #include "griffin_lim.h"
 #include "gl_pitch.h"
 #include "gl_spsi.h"
+#include "gl_excite.h"
 
 using namespace fs2;
 
@@ -1986,6 +1987,53 @@ int fs2_op_spsi_phase_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win,
     GlCall c{"fs2_op_spsi_phase_dev", GlKind::SpsiPhase, {n_fft, hop, win, n_mels}, gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status),
              {workspace, workspace_bytes}, {src, src_width, mel_pinv, nullptr}};
     c.spsi = {phase, mag_out};
+    return gl_call(stream, c);
+}
+
+size_t fs2_op_f0_phase_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t* lens) {
+    return gl_workspace_bytes({"fs2_op_f0_phase_workspace_bytes_geom", GlKind::F0Phase, {n_fft, hop, win, n_mels}, gl_host_batch(B, nullptr, lens)});
+}
+
+size_t fs2_op_f0_phase_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity) {
+    return gl_workspace_bytes({"fs2_op_f0_phase_workspace_bytes_cap", GlKind::F0Phase, {n_fft, hop, win, n_mels},
+                               gl_device_batch(B, nullptr, 0, frame_capacity, nullptr)});
+}
+
+int fs2_op_f0_phase_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* f0, int32_t B, const int32_t* starts,
+                         const int32_t* lens, double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed, void* workspace, size_t workspace_bytes,
+                         float* phase) {
+    GlCall c{"fs2_op_f0_phase_geom", GlKind::F0Phase, {n_fft, hop, win, n_mels}, gl_host_batch(B, starts, lens), {workspace, workspace_bytes}, {},
+             {0, 0.f, seed, nullptr}};
+    c.spsi = {phase, nullptr};
+    c.exc = {f0, f0_floor, f0_ceil, sample_rate};
+    return gl_call(stream, c);
+}
+
+int fs2_op_f0_phase_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* f0, int32_t B, const int64_t* lens_dev,
+                        int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, double f0_floor, double f0_ceil, int32_t sample_rate,
+                        uint32_t seed, void* workspace, size_t workspace_bytes, float* phase) {
+    GlCall c{"fs2_op_f0_phase_dev", GlKind::F0Phase, {n_fft, hop, win, n_mels}, gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status),
+             {workspace, workspace_bytes}, {}, {0, 0.f, seed, nullptr}};
+    c.spsi = {phase, nullptr};
+    c.exc = {f0, f0_floor, f0_ceil, sample_rate};
+    return gl_call(stream, c);
+}
+
+int fs2_op_excitation_geom(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* f0, int32_t B, const int32_t* starts,
+                           const int32_t* lens, double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed, void* workspace,
+                           size_t workspace_bytes, float* wav) {
+    GlCall c{"fs2_op_excitation_geom", GlKind::F0Phase, {n_fft, hop, win, n_mels}, gl_host_batch(B, starts, lens), {workspace, workspace_bytes}, {},
+             {0, 0.f, seed, nullptr}, {wav, 0, 0, nullptr, nullptr}};
+    c.exc = {f0, f0_floor, f0_ceil, sample_rate};
+    return gl_call(stream, c);
+}
+
+int fs2_op_excitation_dev(void* stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float* f0, int32_t B, const int64_t* lens_dev,
+                          int32_t src_stride, int64_t frame_capacity, const int32_t* upstream_status, double f0_floor, double f0_ceil, int32_t sample_rate,
+                          uint32_t seed, void* workspace, size_t workspace_bytes, float* wav, int32_t wav_stride, int64_t wav_capacity) {
+    GlCall c{"fs2_op_excitation_dev", GlKind::F0Phase, {n_fft, hop, win, n_mels}, gl_device_batch(B, lens_dev, src_stride, frame_capacity, upstream_status),
+             {workspace, workspace_bytes}, {}, {0, 0.f, seed, nullptr}, {wav, wav_stride, wav_capacity, nullptr, nullptr}};
+    c.exc = {f0, f0_floor, f0_ceil, sample_rate};
     return gl_call(stream, c);
 }
 

@@ -1,4 +1,4 @@
-// Host side of the vocoder (kernels: griffin_lim.h, gl_spsi.h, gl_pitch.h): one description of a call, GlCall, and one path over it
+// Host side of the vocoder (kernels: griffin_lim.h, gl_spsi.h, gl_pitch.h, gl_excite.h): one description of a call, GlCall, and one path over it
 // (include/fs2.h).
 // A GlCall says what the call computes (GlKind), on which transform (GlGeomArgs), for which batch (GlBatch: host-planned or
 // device-driven), where it may work (GlWork), from what (GlSource), how it iterates (GlIter) and what it writes (GlWavOut, GlFeatures,
@@ -6,10 +6,11 @@
 // gl_workspace_bytes (the queries), which make the geometry first.  The kind alone decides which workspace regions exist and which
 // argument checks apply: the mel-constrained call is the plain call with another kind, pitch an optional part of the one analysis.
 // A query and the call it sizes go through the same sizing function with the same description -- gl_size (synthesis and analysis:
-// gl_plan and gl_layout), spsi_size (SPSI: spsi_layout) -- so they agree by construction.  Only the domain differs: a query answers a
+// gl_plan and gl_layout), spsi_size (SPSI: spsi_layout), exc_size (excitation: exc_layout) -- so they agree by construction.  Only
+// the domain differs: a query answers a
 // size (or 0) where the call refuses in its own words, so the sizing of a device-driven batch fails without a text and the call gives it.
-// The order of the checks is part of the interface (the message names the check that fired): gl_synthesize, gl_analyze and
-// spsi_phase each state theirs.
+// The order of the checks is part of the interface (the message names the check that fired): gl_synthesize, gl_analyze,
+// spsi_phase and f0_phase each state theirs.
 // Not a header of its own: fs2_runtime.hip includes it inside its unnamed namespace, after fail() and align_up(), so the library
 // stays one translation unit.
 
@@ -57,8 +58,9 @@ auto gl_dispatch(const GlGeomHost& gh, Fn&& f) {
 
 // What a call computes.  Synthesis projects every iteration onto the fixed M, MelSynthesis onto the magnitudes whose mel is the
 // source's (gl_iterate's PROJ = 1; it reads GlSource::mel_basis); Analysis is the STFT with its features, AnalysisPitch adds f0 and
-// strength; SpsiPhase is the initial phase of gl_spsi.h (a workspace of its own: spsi_layout).
-enum class GlKind { Synthesis, MelSynthesis, Analysis, AnalysisPitch, SpsiPhase };
+// strength; SpsiPhase is the initial phase of gl_spsi.h (a workspace of its own: spsi_layout); F0Phase the excitation from F0 of
+// gl_excite.h with its STFT phase (GlExcite; a workspace of its own: exc_layout; it writes the phase, the waveform, or both).
+enum class GlKind { Synthesis, MelSynthesis, Analysis, AnalysisPitch, SpsiPhase, F0Phase };
 
 constexpr bool gl_is_analysis(GlKind k) { return k == GlKind::Analysis || k == GlKind::AnalysisPitch; }
 
@@ -101,10 +103,13 @@ struct GlFeatures {
 
 struct GlPhaseOut { float *phase, *mag_out; };
 
+// F0Phase: one f0 per source row (Hz), which frames count as voiced, the rate the samples are spaced at
+struct GlExcite { const float* f0; double f0_floor, f0_ceil; int32_t sample_rate; };
+
 // who: the entry point, for the messages.  gh: made from geom by gl_call / gl_workspace_bytes before anything else is looked at.
 struct GlCall {
     const char* who; GlKind kind; GlGeomArgs geom; GlBatch batch; GlWork work; GlSource source; GlIter iter; GlWavOut out;
-    GlFeatures feat; GlPhaseOut spsi; GlGeomHost gh;
+    GlFeatures feat; GlPhaseOut spsi; GlGeomHost gh; GlExcite exc;
 };
 
 // ---- sizing of the synthesis and the analysis ----
@@ -521,12 +526,67 @@ int spsi_phase(hipStream_t s, const GlCall& c) {
     return FS2_OK;
 }
 
+// ---- excitation from F0 and its phase (kernels and launch sequences: gl_excite.h) ----
+
+struct ExcSize {
+    int64_t frames = 0;
+    ExcLayout at;
+};
+
+// The one sizing of F0Phase, for the queries and the calls alike, by the rules of spsi_size; on top of them the samples, hop per
+// frame, must index with an int.
+int exc_size(const GlCall& c, ExcSize& z) {
+    const GlBatch& b = c.batch;
+    if (b.on_device && !spsi_caps_ok(c.gh, b.B, b.src_stride, b.frame_capacity)) return FS2_ERR_ARG;
+    z.frames = b.on_device ? b.frame_capacity : spsi_host_frames(c);
+    if (z.frames < 0) return (int)z.frames;
+    if (z.frames * c.gh.hop > INT32_MAX) return b.on_device ? FS2_ERR_ARG : fail(nullptr, FS2_ERR_ARG, "%s: batch too large (%lld frames)", c.who, (long long)z.frames);
+    z.at = exc_layout(c.gh.n_fft, c.gh.hop, b.B, z.frames);
+    return FS2_OK;
+}
+
+// Order of the checks: the options; then host-planned: null starts / lens, the frames, no frames (FS2_OK before any pointer is
+// looked at), null pointers; device-driven: the capacities, null pointers; for both the workspace last.
+int f0_phase(hipStream_t s, const GlCall& c) {
+    const char* who = c.who;
+    const GlGeomHost& gh = c.gh;
+    const GlBatch& b = c.batch;
+    const GlExcite& x = c.exc;
+    const GlWavOut& w = c.out;
+    if (x.sample_rate < 1 || !(x.f0_floor > 0.0) || !(x.f0_ceil >= x.f0_floor) || !std::isfinite(x.f0_ceil))
+        return fail(nullptr, FS2_ERR_ARG, "%s: sample_rate %d, f0_floor %g, f0_ceil %g (sample_rate >= 1, 0 < f0_floor <= f0_ceil, finite)", who, x.sample_rate,
+                    x.f0_floor, x.f0_ceil);
+    ExcSize z;
+    if (b.on_device) {
+        if (exc_size(c, z) || w.wav_stride < 0 || w.wav_capacity < 0 || w.wav_capacity > INT32_MAX || (int64_t)b.B * w.wav_stride > w.wav_capacity)
+            return fail(nullptr, FS2_ERR_ARG,
+                        "%s: B %d, frame_capacity %lld, src_stride %d, wav_stride %d, wav_capacity %lld (B >= 1, 1 <= frame_capacity, rows * bins < 2^31, "
+                        "hop * frame_capacity < 2^31, B * wav_stride <= wav_capacity < 2^31)", who, b.B, (long long)b.frame_capacity, b.src_stride, w.wav_stride,
+                        (long long)w.wav_capacity);
+        if (!x.f0 || !b.lens_dev || !c.work.ptr || (!c.spsi.phase && !w.wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    } else {
+        if (b.B > 0 && (!b.starts || !b.lens)) return fail(nullptr, FS2_ERR_ARG, "%s: null starts / lens", who);
+        if (int rc = exc_size(c, z)) return rc;
+        if (z.frames == 0) return FS2_OK;
+        if (!x.f0 || !c.work.ptr || (!c.spsi.phase && !w.wav)) return fail(nullptr, FS2_ERR_ARG, "%s: null pointer", who);
+    }
+    if (c.work.bytes < z.at.bytes) return fail(nullptr, FS2_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, c.work.bytes, z.at.bytes);
+    char* ws = (char*)c.work.ptr;
+    const ExcOptions o{x.f0_floor, x.f0_ceil, (double)x.sample_rate, c.iter.seed, gh.hop};
+    const hipError_t e = b.on_device ? exc_run_dev(s, gh.n_fft, gh.win, o, x.f0, b.B, b.lens_dev, b.src_stride, b.frame_capacity, b.upstream_status, ws, z.at,
+                                                   w.wav, w.wav_stride, w.wav_capacity, c.spsi.phase)
+                                     : exc_run_host(s, gh.n_fft, gh.win, o, x.f0, b.B, b.starts, b.lens, z.frames, ws, z.at, w.wav, c.spsi.phase);
+    if (e != hipSuccess) return fail(nullptr, FS2_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return FS2_OK;
+}
+
 // ---- the one path ----
 
 int gl_call(void* stream, GlCall c) {
     if (int rc = gl_geom(c.geom.n_fft, c.geom.hop, c.geom.win, c.geom.n_mels, c.who, c.gh)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (c.kind == GlKind::SpsiPhase) return spsi_phase(s, c);
+    if (c.kind == GlKind::F0Phase) return f0_phase(s, c);
     return gl_is_analysis(c.kind) ? gl_analyze(s, c) : gl_synthesize(s, c);
 }
 
@@ -534,7 +594,9 @@ int gl_call(void* stream, GlCall c) {
 size_t gl_workspace_bytes(GlCall c) {
     GlPlan p;
     SpsiSize z;
+    ExcSize x;
     if (gl_geom(c.geom.n_fft, c.geom.hop, c.geom.win, c.geom.n_mels, c.who, c.gh)) return 0;
     if (c.kind == GlKind::SpsiPhase) return spsi_size(c, z) == FS2_OK ? z.at.bytes : 0;
+    if (c.kind == GlKind::F0Phase) return exc_size(c, x) == FS2_OK ? x.at.bytes : 0;
     return gl_size(c, p) == FS2_OK ? p.at.bytes : 0;
 }

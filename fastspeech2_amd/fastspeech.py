@@ -45,11 +45,12 @@ class AsyncMels(tuple):
     record.  ``status`` is the device int32[8] of fs2_decode ({rows, work items, overflow flags, longest utterance, valid frames,
     ...}); ``ok()`` waits for THIS call (its own event and pinned copy of the flags) and tells whether its capacities
     sufficed; ``check()`` raises ``Fs2CapacityError`` instead.  On overflow the mels are NaN-filled on the device, so a caller
-    that never looks still cannot mistake them for audio."""
+    that never looks still cannot mistake them for audio.  ``pitch``: the predicted F0 in Hz per frame in the layout of the mels
+    (``inference_batch_pitch``), else None; ``GriffinLim(...)(mels, init="f0", sync=False)`` takes it."""
 
-    def __new__(cls, mels, olens, status, record):
+    def __new__(cls, mels, olens, status, record, pitch=None):
         self = super().__new__(cls, (mels, olens))
-        self.status, self._record = status, record
+        self.status, self._record, self.pitch = status, record, pitch
         return self
 
     def ok(self):
@@ -63,6 +64,16 @@ class AsyncMels(tuple):
             raise Fs2CapacityError("device-driven layout overflow (flags %d): rerun this batch with sync=True or a larger "
                                    "capacity" % fl)
         return self
+
+
+def _pack_frames_dev(x, lens_dev, rows):
+    """[B, Lcap] per-frame values -> [rows] with the first sum(lens) entries the valid frames back to back and the rest 0, the frame
+    counts staying on the device (no host read: frames beyond an utterance's count, and beyond ``rows``, land in a spare slot)."""
+    t = torch.arange(x.shape[1], device=x.device)[None, :]
+    L = lens_dev.reshape(-1, 1).to(torch.int64)
+    at = torch.cumsum(L, 0) - L + t
+    at = torch.where((t < L) & (at < rows), at, torch.full_like(at, rows))
+    return torch.zeros(rows + 1, dtype=x.dtype, device=x.device).scatter_(0, at.reshape(-1), x.reshape(-1))[:rows]
 
 
 class _AsyncRecord:
@@ -842,31 +853,65 @@ class FeedForwardTransformer(nn.Module):
 
         ``pitch_scale`` / ``pitch_shift`` / ``energy_scale`` / ``energy_shift`` (prosody.py; each None, a number, a float32 [B, 1] tensor = one
         value per utterance, or [B, Tmax] = one per phoneme): every predicted pitch / energy value becomes ``v * scale + shift`` before it
-        is quantised, in every form of the call (``ShardedSynthesizer`` slices the tensors with the batch)."""
-        pro = self._controls(pitch_scale, pitch_shift, energy_scale, energy_shift)
+        is quantised, in every form of the call (``ShardedSynthesizer`` slices the tensors with the batch).
+
+        :meth:`inference_batch_pitch` is the same call that also returns the per-frame pitch."""
+        return self._inference_batch(xs, ilens, d_override, packed, sync, capacity, alpha, packed_out, regime, inputs_ready,
+                                     dict(pitch_scale=pitch_scale, pitch_shift=pitch_shift, energy_scale=energy_scale, energy_shift=energy_shift), False)
+
+    def inference_batch_pitch(self, xs, ilens, **options):
+        """``inference_batch`` (every keyword of it) that also returns the predicted (and controlled) F0 in Hz per frame, float32 in
+        the layout of the mels without the last axis ([B, Lmax], or with ``packed=True`` [rows]): ``(mels, olens, pitch)`` with
+        ``sync=True``, the attribute ``pitch`` of the ``AsyncMels`` with ``sync=False``.  What
+        ``GriffinLim(...)(mels, olens, init="f0", f0=pitch)`` takes; an ``AsyncMels`` brings it along.  Refused with
+        reduction_factor > 1 (p_outs is per decoder frame, the mels per mel frame)."""
+        names = ("d_override", "packed", "sync", "capacity", "alpha", "packed_out", "regime", "inputs_ready")
+        defaults = dict(d_override=None, packed=False, sync=True, capacity=None, alpha=1.0, packed_out=None, regime=None, inputs_ready=None)
+        unknown = sorted(set(options) - set(names) - set(_prosody.CONTROLS))
+        if unknown:
+            raise TypeError("inference_batch_pitch() got an unexpected keyword argument %r" % unknown[0])
+        defaults.update({k: v for k, v in options.items() if k in names})
+        return self._inference_batch(xs, ilens, *[defaults[k] for k in names], {k: options.get(k) for k in _prosody.CONTROLS}, True)
+
+    def _inference_batch(self, xs, ilens, d_override, packed, sync, capacity, alpha, packed_out, regime, inputs_ready, controls, want_pitch):
+        """What ``inference_batch`` and ``inference_batch_pitch`` run."""
+        pro = self._controls(**controls)
         il = _host_lens(ilens).reshape(-1)
         _require_alpha(alpha)
+        if want_pitch and self.reduction_factor > 1:
+            raise ValueError("inference_batch_pitch with reduction_factor > 1: p_outs is per decoder frame, the mels per mel frame")
+        more = ("p_outs",) if want_pitch else ()
         if il.numel() == 0:
             _require_device(xs)
             empty = torch.zeros((0, self.odim) if packed else (0, 1, self.odim), device=xs.device)
-            return empty, (torch.zeros(0, dtype=torch.int64) if sync else torch.zeros(0, dtype=torch.int64, device=xs.device))
+            olens0 = torch.zeros(0, dtype=torch.int64) if sync else torch.zeros(0, dtype=torch.int64, device=xs.device)
+            return (empty, olens0, empty[..., 0]) if want_pitch and sync else (empty, olens0)
         if not sync and (self._frames_per_token is not None or capacity is not None):
             self._harvest_async(block=False)
             total, Lcap = capacity if capacity is not None else self.predict_capacity(il, alpha)
             key = "after_packed" if packed else "after"         # (packed: the padded mels are neither built nor written)
-            r = self._run(xs, il, is_inference=True, compat=False, want=(key,), d_override=d_override, capacity=(total, Lcap), alpha=alpha,
+            r = self._run(xs, il, is_inference=True, compat=False, want=(key,) + more, d_override=d_override, capacity=(total, Lcap), alpha=alpha,
                           packed_out=packed_out if packed else None, regime=regime, inputs_ready=inputs_ready, prosody=pro)
             mel_lens = r["olens"] if self.reduction_factor == 1 else r["olens"] * self.reduction_factor     # mel frames per utterance
+            f0 = None
+            if want_pitch:
+                f0 = _pack_frames_dev(r["p_outs"], r["olens"], r[key].shape[0]) if packed else r["p_outs"]
             if torch.cuda.is_current_stream_capturing():     # graph capture: no host-side bookkeeping inside the graph
-                return AsyncMels(r[key], mel_lens, r["status"], None)
-            return AsyncMels(r[key], mel_lens, r["status"], self._record_async(il, r, xs.device, alpha))
+                return AsyncMels(r[key], mel_lens, r["status"], None, f0)
+            return AsyncMels(r[key], mel_lens, r["status"], self._record_async(il, r, xs.device, alpha), f0)
         want = ("after", "after_packed") if packed else ("after",)
-        r = self._run(xs, il, is_inference=True, compat=False, want=want, d_override=d_override, alpha=alpha, regime=regime, prosody=pro)
+        r = self._run(xs, il, is_inference=True, compat=False, want=want + more, d_override=d_override, alpha=alpha, regime=regime, prosody=pro)
         if d_override is None:
             self._learn_ratio(il, r["olens"], alpha)
         else:
             self._learn_ratio(il, r["olens"], 1.0)
-        return (r["after_packed"] if packed else r["after"]), r["olens"] * self.reduction_factor
+        out = (r["after_packed"] if packed else r["after"]), r["olens"] * self.reduction_factor
+        if want_pitch:
+            f0 = r["p_outs"]
+            if packed:
+                f0 = f0[(torch.arange(f0.shape[1])[None, :] < r["olens"].reshape(-1, 1)).to(f0.device)]
+            out += (f0,)
+        return out
 
     def capture_graph(self, xs, ilens, d_override=None, vocoder=None, pitch_scale=None, pitch_shift=None, energy_scale=None, energy_shift=None,
                       **vocoder_args):
@@ -886,9 +931,13 @@ class FeedForwardTransformer(nn.Module):
         vocoder on the mels (``vocoder(AsyncMels, sync=False, padded_out=True)``: the frame counts never leave the device), and
         ``run(new_xs)`` returns ``(wav [B, hop (Lcap - 1)] zero-padded, sample_lens_dev, status_dev)`` instead -- text to waveform
         in one graph launch.  ``status_dev`` is the vocoder's, with the mel status folded in: a mel overflow shows as
-        FS2_OVF_UPSTREAM plus the mel call's own flags, and the waveforms are then NaN."""
+        FS2_OVF_UPSTREAM plus the mel call's own flags, and the waveforms are then NaN.  With ``init="f0"`` the model's own
+        pitch prediction (``p_outs``) is wired to the vocoder inside the graph; reduction_factor > 1 is refused for it."""
         if vocoder is None and vocoder_args:
             raise TypeError("capture_graph: %s given without a vocoder" % sorted(vocoder_args))
+        f0_init = vocoder is not None and vocoder_args.get("init") == "f0"
+        if f0_init and self.reduction_factor > 1:
+            raise ValueError("capture_graph(init='f0') with reduction_factor > 1: p_outs is per decoder frame, the mels per mel frame")
         with torch.no_grad():
             il = _host_lens(ilens)
             _, ol = self.inference_batch(xs, il, d_override=d_override)            # builds the handle, learns the sizes
@@ -903,7 +952,7 @@ class FeedForwardTransformer(nn.Module):
             if pro is not None:
                 static_pro = {k: (None if v is None else v.clone())
                               for k, v in _prosody.normalize_controls(xs.shape[0], xs.shape[1], xs.device, **pro).items()}
-            run_mel = lambda: self._run(static_xs, il, is_inference=True, compat=False, want=("after",), d_override=static_ds,
+            run_mel = lambda: self._run(static_xs, il, is_inference=True, compat=False, want=("after", "p_outs") if f0_init else ("after",), d_override=static_ds,
                                         capacity=(total, Lcap), prosody=static_pro)
 
             def run_once():
@@ -911,7 +960,8 @@ class FeedForwardTransformer(nn.Module):
                 if vocoder is None:
                     return r["after"], r["olens"], r["status"]
                 mel_lens = r["olens"] if self.reduction_factor == 1 else r["olens"] * self.reduction_factor
-                w = vocoder(AsyncMels(r["after"], mel_lens, r["status"], None), sync=False, padded_out=True, **vocoder_args)
+                w = vocoder(AsyncMels(r["after"], mel_lens, r["status"], None, r["p_outs"] if f0_init else None), sync=False, padded_out=True,
+                            **vocoder_args)
                 return w[0], w[1], w.status
             side = torch.cuda.Stream(device=xs.device)
             side.wait_stream(torch.cuda.current_stream(xs.device))

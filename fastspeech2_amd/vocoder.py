@@ -308,7 +308,7 @@ def _device_batch(mels, olens):
     return olens, B, B * mels.shape[1], mels.shape[1], mels.shape[1]
 
 
-INITS = ("seeded", "spsi")
+INITS = ("seeded", "spsi", "f0")
 CONSTRAINTS = ("magnitude", "mel")
 # (workspace query, call) of include/fs2.h by (device-driven, mel-constrained): the one place a synthesis picks its entry points
 _SYNTHESIS = {(False, False): ("fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom"),
@@ -325,11 +325,48 @@ def _check_constraint(constraint, magnitudes):
     return constraint == "mel"
 
 
-def _check_init(init, init_phase):
+def _check_init(init, init_phase, f0=None, f0_floor=71.0, f0_ceil=800.0):
     if init not in INITS:
         raise ValueError("init must be one of %s, got %r" % (INITS, init))
     if init == "spsi" and init_phase is not None:
         raise ValueError("init='spsi' computes the initial phase itself: pass init_phase or init='spsi', not both")
+    if f0 is not None and init_phase is not None:
+        raise ValueError("f0 gives the initial phase (init='f0'): pass init_phase or f0, not both")
+    if init == "f0":
+        if init_phase is not None:
+            raise ValueError("init='f0' computes the initial phase itself: pass init_phase or init='f0', not both")
+        if f0 is None:
+            raise ValueError("init='f0' needs f0: one value in Hz per row of mels (or an AsyncMels of inference_batch_pitch)")
+        _check_f0_limits(f0_floor, f0_ceil)
+    elif f0 is not None:
+        raise ValueError("f0 belongs to init='f0', got init=%r" % (init,))
+
+
+def _check_f0_limits(f0_floor, f0_ceil):
+    """(f0_floor, f0_ceil) as floats: positive, finite and ordered (csrc/griffin_lim_host.h: f0_phase checks the same)."""
+    lo, hi = float(f0_floor), float(f0_ceil)
+    if not (lo > 0 and math.isfinite(lo) and math.isfinite(hi) and hi >= lo):
+        raise ValueError("need 0 < f0_floor <= f0_ceil, both finite, got %r, %r" % (f0_floor, f0_ceil))
+    return lo, hi
+
+
+def _checked_f0(f0, like, name="mels"):
+    """f0 as a contiguous float32 [rows] tensor: one value per row of ``like`` ([N, W] or [B, Lmax, W]; None: f0 itself is [N] or
+    [B, Lmax]), on its device.  There is no CPU fallback."""
+    if not isinstance(f0, torch.Tensor):
+        raise TypeError("f0 must be a float32 CUDA tensor, got %s" % type(f0).__name__)
+    _require_cuda(f0, "f0")
+    if f0.dtype != torch.float32:
+        raise TypeError("f0 must be float32 (Hz), got %s" % f0.dtype)
+    if like is None:
+        if f0.dim() not in (1, 2):
+            raise ValueError("f0 must be [N] (packed) or [B, Lmax] (padded), got %s" % (tuple(f0.shape),))
+    else:
+        if tuple(f0.shape) != tuple(like.shape[:-1]):
+            raise ValueError("f0 must have one value per row of %s, %s, got %s" % (name, tuple(like.shape[:-1]), tuple(f0.shape)))
+        if f0.device != like.device:
+            raise ValueError("f0 on %s, %s on %s" % (f0.device, name, like.device))
+    return f0.reshape(-1).contiguous()
 
 
 class GriffinLim:
@@ -385,7 +422,7 @@ class GriffinLim:
         return mels.reshape(-1, W).contiguous().float(), init_phase, W, n_iter, momentum
 
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
-                 padded_out=False, init="seeded", constraint="magnitude"):
+                 padded_out=False, init="seeded", constraint="magnitude", f0=None, f0_floor=71.0, f0_ceil=800.0):
         """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
         with ``olens`` [B] <= Lmax (None: every utterance Lmax frames; packed: one utterance).  ``magnitudes=True``: linear magnitudes
         [.., n_fft / 2 + 1] instead (the reference's ``griffin_lim(magnitudes, ...)`` contract).  ``init_phase``: angles in the layout
@@ -393,6 +430,13 @@ class GriffinLim:
         :func:`spsi_phase` instead of the seeded random one (``seed`` is ignored; together with ``init_phase`` it raises): on
         harmonic signals 10 iterations from it beat 20 from the seeded start.  ``momentum`` > 0: fast
         Griffin-Lim (0 = the reference).  Runs on the current stream of the input's device without synchronising.
+
+        ``init="f0"``: start from the phase of an excitation built from ``f0`` (:func:`f0_phase`; float32 Hz, one value per row of
+        ``mels``, packed or padded like them; a frame is voiced where ``f0_floor <= f0 <= f0_ceil``; ``seed`` seeds the noise of the
+        unvoiced stretches).  With ``n_iter=0`` this is a one-pass source-filter vocoder: the magnitudes filter the excitation and
+        the pitch of the waveform is ``f0``.  It is for few iterations and an ``f0`` that matches the
+        mel, which the model's own prediction does: an ``AsyncMels`` of ``inference_batch_pitch(sync=False)`` brings
+        its pitch along.  Without ``f0``, together with ``init_phase``, or with ``f0`` of another shape, dtype or device it raises.
 
         ``constraint="magnitude"`` (default) projects every iteration onto the fixed ``M = max(pinv . exp(mel), 0)``.
         ``constraint="mel"`` keeps the magnitudes of the current STFT and rescales them per mel band so that their mel is the
@@ -404,13 +448,18 @@ class GriffinLim:
         from it.  ``sync=False``: the frame counts stay on the device -- ``olens`` must be a CUDA int64 tensor, or ``mels`` an
         :class:`AsyncMels` (``inference_batch(sync=False)``), whose mels, ``olens`` and status are taken -- and nothing waits for
         the GPU; see :meth:`_call_dev`.  Returns an :class:`AsyncWaveforms`."""
-        _check_init(init, init_phase)
+        if f0 is None and init == "f0" and isinstance(mels, AsyncMels):
+            f0 = getattr(mels, "pitch", None)
+        _check_init(init, init_phase, f0, f0_floor, f0_ceil)
         mel_proj = _check_constraint(constraint, magnitudes)
         if not sync:
-            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init, constraint)
+            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init, constraint, f0, f0_floor,
+                                  f0_ceil)
         if capacity is not None or padded_out:
             raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
+        if init == "f0":
+            f0 = _checked_f0(f0, mels)
         g = self.geometry
         L, starts = _host_batch(mels, olens)
         sample_lens = g.hop * torch.clamp(L - 1, min=0)
@@ -424,6 +473,8 @@ class GriffinLim:
         B = len(l_np)
         if init == "spsi":
             init_phase = self._spsi_host(src, W, s_np, l_np, magnitudes, False)[0]
+        elif init == "f0":
+            init_phase = self._f0_host(f0, s_np, l_np, f0_floor, f0_ceil, seed, True)
         self._synthesize((False, mel_proj), src, W, magnitudes, (B, l_p), (B, s_p, l_p), (n_iter, momentum, seed, init_phase), (wav.data_ptr(),))
         return Waveforms(wav, sample_lens)
 
@@ -474,6 +525,84 @@ class GriffinLim:
                                                  olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
                                                  ws.data_ptr(), ws_bytes, phase.data_ptr(), mag.data_ptr() if want_mag else None))
         return phase, mag
+
+    def _f0_host(self, f0, starts_np, lens_np, f0_floor, f0_ceil, seed, phase):
+        """fs2_op_f0_phase_geom (``phase``: [rows, bins], zeros where no utterance is) or fs2_op_excitation_geom (the packed waveforms)
+        on a checked flat ``f0``."""
+        g, dev = self.geometry, f0.device
+        s_np, s_p = _i32(starts_np)
+        l_np, l_p = _i32(lens_np)
+        if phase:
+            out = torch.zeros(f0.numel(), g.n_bins, dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty(int(g.hop * np.clip(l_np.astype(np.int64) - 1, 0, None).sum()), dtype=torch.float32, device=dev)
+        if int(l_np.sum()) == 0 or out.numel() == 0:
+            return out
+        lib = _lib.lib()
+        ws_bytes = int(lib.fs2_op_f0_phase_workspace_bytes_geom(*g, len(l_np), l_p))
+        call = lib.fs2_op_f0_phase_geom if phase else lib.fs2_op_excitation_geom
+        with torch.cuda.device(dev):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(call(_stream(dev), *g, f0.data_ptr(), len(l_np), s_p, l_p, float(f0_floor), float(f0_ceil), int(self.params["sample_rate"]),
+                            int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, out.data_ptr()))
+        return out
+
+    def _f0_dev(self, f0, olens, stride, cap, upstream, f0_floor, f0_ceil, seed):
+        """fs2_op_f0_phase_dev on a checked flat ``f0`` (``olens`` a contiguous CUDA int64 [B], B >= 1, cap >= 1)."""
+        g, dev = self.geometry, f0.device
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            phase = torch.zeros(f0.numel(), g.n_bins, dtype=torch.float32, device=dev)
+            ws_bytes = int(lib.fs2_op_f0_phase_workspace_bytes_cap(*g, olens.numel(), cap))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.fs2_op_f0_phase_dev(_stream(dev), *g, f0.data_ptr(), olens.numel(), olens.data_ptr(), stride, cap,
+                                               upstream.data_ptr() if upstream is not None else None, float(f0_floor), float(f0_ceil),
+                                               int(self.params["sample_rate"]), int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, phase.data_ptr()))
+        return phase
+
+    def _f0_batch_limits(self, rows):
+        g = self.geometry
+        if rows * g.n_bins >= 2 ** 31 or rows * g.hop >= 2 ** 31:
+            raise ValueError("batch too large for one call (%d rows)" % rows)
+
+    def f0_phase(self, f0, olens=None, f0_floor=71.0, f0_ceil=800.0, seed=0, sync=True):
+        """The phase of the excitation from F0 (:func:`f0_phase`) in this GriffinLim's geometry and sample rate."""
+        lo, hi = _check_f0_limits(f0_floor, f0_ceil)
+        upstream = None
+        if isinstance(f0, AsyncMels):
+            if sync:
+                raise ValueError("an AsyncMels belongs to sync=False (its frame counts are on the device)")
+            if olens is not None:
+                raise ValueError("olens is taken from the AsyncMels given as f0; pass one or the other")
+            if getattr(f0, "pitch", None) is None:
+                raise ValueError("this AsyncMels carries no pitch: call inference_batch_pitch(sync=False)")
+            upstream, olens, f0 = f0.status, f0[1], f0.pitch
+        if not sync and (not isinstance(olens, torch.Tensor) or not olens.is_cuda or olens.dtype != torch.int64):
+            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device)")
+        flat = _checked_f0(f0, None)
+        if not sync and olens.device != f0.device:
+            raise ValueError("olens on %s, f0 on %s" % (olens.device, f0.device))
+        NB = self.geometry.n_bins
+        rows_like = f0.unsqueeze(-1)                    # the row layout of f0, as _host_batch / _device_batch read it from mels
+        self._f0_batch_limits(flat.numel())
+        if sync:
+            L, starts = _host_batch(rows_like, olens, "f0", "has")
+            phase = self._f0_host(flat, starts, L.numpy(), lo, hi, seed, True)
+        else:
+            olens, B, rows, stride, _ = _device_batch(rows_like, olens)
+            if B == 0 or rows == 0:
+                phase = torch.zeros(rows, NB, dtype=torch.float32, device=f0.device)
+            else:
+                phase = self._f0_dev(flat, olens, stride, rows, upstream, lo, hi, seed)
+        return phase.reshape(tuple(f0.shape) + (NB,))
+
+    def excitation(self, f0, olens=None, seed=0, f0_floor=71.0, f0_ceil=800.0):
+        """The excitation from F0 itself (:func:`excitation`) at this GriffinLim's hop and sample rate -> ``Waveforms``."""
+        lo, hi = _check_f0_limits(f0_floor, f0_ceil)
+        flat = _checked_f0(f0, None)
+        self._f0_batch_limits(flat.numel())
+        L, starts = _host_batch(f0.unsqueeze(-1), olens, "f0", "has")
+        return Waveforms(self._f0_host(flat, starts, L.numpy(), lo, hi, seed, False), self.geometry.hop * torch.clamp(L - 1, min=0))
 
     def spsi_phase(self, src, olens=None, magnitudes=False, return_magnitudes=False, sync=True):
         """The phase-continuity initial phase (:func:`spsi_phase`) in this GriffinLim's geometry."""
@@ -527,17 +656,20 @@ class GriffinLim:
         return slot[1]
 
     def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init="seeded",
-                  constraint="magnitude"):
+                  constraint="magnitude", f0=None, f0_floor=71.0, f0_ceil=800.0):
         """The device-driven call (include/fs2.h: fs2_op_griffin_lim_dev).  ``capacity``: bound on the batch's total frames (default:
         the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the waveform is
         sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only) [B, hop (Lcap - 1)].
         Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own call overflowed, give
         a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``.  ``init="spsi"``: the initial phase is computed on the device
         from the same frame counts first (fs2_op_spsi_phase_dev), equally without a host read.  ``constraint="mel"``: the
-        mel-constrained projection (fs2_op_griffin_lim_mel_dev), as in :meth:`__call__`."""
-        _check_init(init, init_phase)
-        mel_proj = _check_constraint(constraint, magnitudes)
+        mel-constrained projection (fs2_op_griffin_lim_mel_dev), as in :meth:`__call__`.  ``init="f0"``: the phase of the excitation
+        from ``f0`` (fs2_op_f0_phase_dev), likewise; an ``AsyncMels`` with a ``pitch`` brings its own."""
         upstream = None
+        if f0 is None and init == "f0" and isinstance(mels, AsyncMels):
+            f0 = getattr(mels, "pitch", None)
+        _check_init(init, init_phase, f0, f0_floor, f0_ceil)
+        mel_proj = _check_constraint(constraint, magnitudes)
         if isinstance(mels, AsyncMels):
             if olens is not None:
                 raise ValueError("olens is taken from the AsyncMels given as mels; pass one or the other")
@@ -554,6 +686,8 @@ class GriffinLim:
             raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), it is on %s; "
                             "use sync=True for host lengths" % olens.device)
         src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes, olens)
+        if init == "f0":
+            f0 = _checked_f0(f0, mels)
         g = self.geometry
         NB = g.n_bins
         olens, B, rows, stride, Lcap = _device_batch(mels, olens)
@@ -578,6 +712,8 @@ class GriffinLim:
             status = torch.empty(8, dtype=torch.int32, device=dev)
             if init == "spsi":
                 init_phase = self._spsi_dev(src, W, olens, stride, cap, upstream, magnitudes, False)[0]
+            elif init == "f0":
+                init_phase = self._f0_dev(f0, olens, stride, cap, upstream, f0_floor, f0_ceil, seed)
             self._synthesize((True, mel_proj), src, W, magnitudes, (B, cap),
                              (B, olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None),
                              (n_iter, momentum, seed, init_phase),
@@ -611,6 +747,28 @@ def spsi_phase(src, olens=None, hp=None, magnitudes=False, return_magnitudes=Fal
     the GPU; invalid frame counts leave the phase zero (the vocoder call that follows reports them).  Every utterance with at least
     one frame is computed; an utterance's phase is bit-identical alone or in any batch.  CPU tensors raise."""
     return _gl_for(hp).spsi_phase(src, olens, magnitudes=magnitudes, return_magnitudes=return_magnitudes, sync=sync)
+
+
+def f0_phase(f0, olens=None, hp=None, f0_floor=71.0, f0_ceil=800.0, seed=0, sync=True):
+    """Initial phase for Griffin-Lim from an F0 contour (csrc/gl_excite.h, include/fs2.h: fs2_op_f0_phase_geom, DESIGN.md section
+    14.12): the STFT phase of an excitation -- a band-limited pulse train of the frequency ``f0`` where voiced, hashed noise where not.
+    ``f0``: float32 Hz on the GPU, one value per frame, packed [N] with ``olens`` [B] summing to N or padded [B, Lmax] with ``olens``
+    <= Lmax, in the geometry and at the sample rate of ``hp.audio``; a frame is voiced where ``f0_floor <= f0 <= f0_ceil`` (NaN,
+    infinities, 0 and negative values are unvoiced), a stretch between two frames where both are.  Returns the angles (float32 radians)
+    in the layout of ``f0`` with n_fft / 2 + 1 columns, zeros in the rows no utterance covers and in utterances too short for the
+    reflect padding: what ``init_phase=`` takes (``GriffinLim()(mels, olens, init="f0", f0=f0)`` does both).  ``seed`` changes the
+    unvoiced stretches only.  ``sync=False``: ``olens`` is a CUDA int64 tensor and nothing waits for the GPU; invalid frame counts
+    leave the phase zero (the vocoder call that follows reports them).  An utterance's phase is bit-identical alone or in any batch.
+    The F0 must match the magnitudes it is used with: with a 3 % error per frame the advantage over ``init="spsi"`` is lost after a
+    few iterations.  CPU tensors raise."""
+    return _gl_for(hp).f0_phase(f0, olens, f0_floor=f0_floor, f0_ceil=f0_ceil, seed=seed, sync=sync)
+
+
+def excitation(f0, olens=None, hp=None, seed=0, f0_floor=71.0, f0_ceil=800.0):
+    """The excitation :func:`f0_phase` transforms -> ``Waveforms``: hop (L - 1) samples of unit power per utterance of L frames (host
+    ``olens``), sum_{h = 1..Hn} cos(h phase) sqrt(2 / Hn) with every harmonic below half the sample rate where voiced, uniform noise
+    from a counter hash of (seed, sample) where not (include/fs2.h: fs2_op_excitation_geom).  CPU tensors raise."""
+    return _gl_for(hp).excitation(f0, olens, seed=seed, f0_floor=f0_floor, f0_ceil=f0_ceil)
 
 
 def _analysis(wav_packed, sample_lens, hp, want_mag, want_mel, want_energy, gl=None, pitch=None, n_candidates=0):

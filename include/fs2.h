@@ -493,6 +493,60 @@ int fs2_op_spsi_phase_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win,
                           const float *mel_pinv, int32_t B, const int64_t *lens_dev, int32_t src_stride, int64_t frame_capacity,
                           const int32_t *upstream_status, void *workspace, size_t workspace_bytes, float *phase, float *mag_out);
 
+/* ---- Excitation from F0 and its STFT phase as the initial phase of Griffin-Lim (fastspeech2_amd/csrc/gl_excite.h; DESIGN.md section
+ * 14.12).  f0 holds one float32 value in Hz per source row (the rows that starts / lens, or lens_dev / src_stride, name exactly as for
+ * fs2_op_spsi_phase_*).  Per utterance of L frames at hop H: N = H (L - 1) samples, frame t centred on sample t H.  Frame t is voiced
+ * iff f0[t] is finite and f0_floor <= f0[t] <= f0_ceil; segment t (samples t H .. t H + H - 1, t <= L - 2) is voiced iff frames t and
+ * t + 1 are: a = f0[t], d = f0[t+1] - f0[t], else a = d = 0.  In double, every operation rounded on its own, sr = sample_rate:
+ *   S_t = (H a + d (H - 1) 0.5) / sr;  Theta_0 = 0, Theta_{t+1} = frac(Theta_t + S_t) in frame order (turns; frac(x) = x - floor(x))
+ *   sample n = t H + i: theta = frac(Theta_t + ((i + 1) a + (d (i (i + 1))) / (2 H)) / sr), f = a + (d i) / H,
+ *   Hn = the largest integer with Hn f < sr / 2 (at least 1)
+ *   voiced:   e[n] = sqrt(2 / Hn) sum_{h = 1..Hn} cos(2 pi h theta): a band-limited pulse train of unit power (the kernel evaluates
+ *             the sum's closed form in float32; tests/excitation_oracle.py states the sum and the tolerance)
+ *   unvoiced: e[n] = (u - 0.5) sqrt(12), u = (mix32(n ^ mix32(seed + 0x9E3779B9)) >> 8) / 2^24 with the hash of the seeded initial
+ *             phase and n the utterance-local sample: uniform noise of unit power.  The seed changes unvoiced samples only.
+ * fs2_op_excitation_* write e; fs2_op_f0_phase_* write phase[row][k] = atan2f(Im, Re) of the STFT of e as fs2_op_stft_geom transforms
+ * a waveform (reflect padding, periodic Hann of win in n_fft), 0 where both parts are 0, every row of an utterance 0 where
+ * N <= n_fft / 2: float32 radians [rows, bins] in the row layout of f0, what `init_phase` of the synthesis takes.  Rows no utterance
+ * covers are not written.  With n_iter = 0 the synthesis from this phase is a one-pass source-filter vocoder whose pitch is the f0
+ * given.  An utterance's samples and phase are bit-identical alone or inside any batch, packed or padded, host-planned or
+ * device-driven.  No atomics.  FS2_ERR_ARG: sample_rate < 1, f0_floor <= 0, f0_ceil < f0_floor or not finite. ---- */
+
+/* workspace bytes of all four calls below for B utterances of lens[b] frames (HOST array; 0 on a bad argument) */
+size_t fs2_op_f0_phase_workspace_bytes_geom(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, const int32_t *lens);
+
+/* workspace bytes of the device-driven forms for B utterances whose frame counts sum to at most frame_capacity (0 on a bad argument) */
+size_t fs2_op_f0_phase_workspace_bytes_cap(int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, int32_t B, int64_t frame_capacity);
+
+/* starts / lens: HOST int32 arrays as in fs2_op_griffin_lim_geom.  Every launch goes to `stream`; nothing synchronises. */
+int fs2_op_f0_phase_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *f0, int32_t B,
+                         const int32_t *starts, const int32_t *lens, double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed,
+                         void *workspace, size_t workspace_bytes, float *phase);
+
+/* wav: the waveforms packed back to back, sum_b hop max(lens[b] - 1, 0) samples */
+int fs2_op_excitation_geom(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *f0, int32_t B,
+                           const int32_t *starts, const int32_t *lens, double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed,
+                           void *workspace, size_t workspace_bytes, float *wav);
+
+/* lens_dev (DEVICE int64 [B]), src_stride, frame_capacity and upstream_status as in fs2_op_spsi_phase_dev; f0 and phase hold
+ * frame_capacity rows (packed) or B * src_stride rows (padded).  The lengths are validated on the device before anything is indexed
+ * with them: on a negative length, a sum beyond frame_capacity, a length above src_stride or upstream flags the call writes nothing
+ * outside the workspace, whose first four ints are then {0, flags (FS2_OVF_*), 0, 0} (without a flag: {frames, 0, samples, 0}).  No
+ * allocation, no host read of device memory, no synchronisation; may be captured into a graph.  Host-checked limits: B >= 1,
+ * 1 <= frame_capacity, rows * bins < 2^31, hop * frame_capacity < 2^31. */
+int fs2_op_f0_phase_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *f0, int32_t B,
+                        const int64_t *lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t *upstream_status,
+                        double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed, void *workspace, size_t workspace_bytes,
+                        float *phase);
+
+/* wav [wav_capacity]: wav_stride 0: the waveforms packed back to back; else utterance b at b * wav_stride (B * wav_stride <=
+ * wav_capacity < 2^31).  Samples that do not fit (their sum beyond wav_capacity, hop (L - 1) > wav_stride) are FS2_OVF_WAV: nothing
+ * is written.  Samples no utterance owns are not written. */
+int fs2_op_excitation_dev(void *stream, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mels, const float *f0, int32_t B,
+                          const int64_t *lens_dev, int32_t src_stride, int64_t frame_capacity, const int32_t *upstream_status,
+                          double f0_floor, double f0_ceil, int32_t sample_rate, uint32_t seed, void *workspace, size_t workspace_bytes,
+                          float *wav, int32_t wav_stride, int64_t wav_capacity);
+
 /* ---- Training targets from the per-frame energy and F0 arrays (fastspeech2_amd/csrc/targets.h): the
  * reference's remove_outlier (utils/util.py:26-49, applied to every energy and pitch array its data loader returns) and the corpus
  * statistics of its compute_statistics.py, for B utterances packed in x: utterance b = x[starts[b] .. + lens[b]).  Per utterance
