@@ -29,6 +29,7 @@ import torch
 
 from . import _lib
 from ._host import _i32, _lens, _require_cuda, _stream
+from ._vocode_plan import CONSTRAINTS, EXCITATION, F0, INITS, SPSI, SYNTHESIS, Arg, plan_vocode       # noqa: F401  (INITS, CONSTRAINTS: public here)
 from .fastspeech import AsyncMels, Fs2CapacityError
 from .losses import DeviceRecords
 
@@ -280,93 +281,26 @@ class AsyncWaveforms(tuple):
         return list(torch.split(self[0][:sum(n)], n))
 
 
-def _host_batch(mels, olens, name="mels", have="have"):
-    """(L int64 [B] on the host, starts [B]) of a packed [N, W] or padded [B, Lmax, W] ``mels`` with host ``olens`` (None: one
-    utterance of N rows / every utterance Lmax frames).  ``name``, ``have``: how the messages call the argument."""
-    if mels.dim() == 2:
-        N = mels.shape[0]
-        L = _lens([N] if olens is None else olens)
-        if int(L.sum()) != N:
-            raise ValueError("packed %s: olens sum to %d, %s %s %d rows" % (name, int(L.sum()), name, have, N))
-        return L, np.concatenate([[0], np.cumsum(L.numpy())[:-1]]).astype(np.int64)
-    Bp, Lmax = mels.shape[0], mels.shape[1]
-    L = _lens([Lmax] * Bp if olens is None else olens, Bp)
-    if Bp and int(L.max()) > Lmax:
-        raise ValueError("padded %s: an olens entry exceeds Lmax = %d" % (name, Lmax))
-    return L, np.arange(Bp, dtype=np.int64) * Lmax
+# ---- what plan_vocode (_vocode_plan.py) is told about a call's arguments: plain values, read here ----
+def _describe(x):
+    if x is None:
+        return None
+    if not isinstance(x, torch.Tensor):
+        return Arg(type(x).__name__, False, False, None, None, None)
+    return Arg(type(x).__name__, True, x.is_cuda, x.dtype, tuple(x.shape), x.device)
 
 
-def _device_batch(mels, olens):
-    """(olens contiguous [B], B, rows, stride, Lcap) of a packed (stride 0, Lcap None) or padded [B, Lcap, W] ``mels`` whose frame
-    counts ``olens`` stay on the device."""
-    olens = olens.reshape(-1).contiguous()
-    B = olens.numel()
-    if mels.dim() == 2:
-        return olens, B, mels.shape[0], 0, None
-    if mels.shape[0] != B:
-        raise ValueError("olens has %d entries for %d utterances" % (B, mels.shape[0]))
-    return olens, B, B * mels.shape[1], mels.shape[1], mels.shape[1]
+def _host_lens(olens):
+    """Host frame counts as a tuple of ints (a CUDA ``olens`` is copied back, which waits for the GPU); None stays None."""
+    return None if olens is None else tuple(torch.as_tensor(olens).detach().to("cpu", torch.int64).reshape(-1).tolist())
 
 
-INITS = ("seeded", "spsi", "f0")
-CONSTRAINTS = ("magnitude", "mel")
-# (workspace query, call) of include/fs2.h by (device-driven, mel-constrained): the one place a synthesis picks its entry points
-_SYNTHESIS = {(False, False): ("fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom"),
-              (False, True): ("fs2_op_vocode_mel_workspace_bytes_geom", "fs2_op_griffin_lim_mel_geom"),
-              (True, False): ("fs2_op_vocode_workspace_bytes_cap", "fs2_op_griffin_lim_dev"),
-              (True, True): ("fs2_op_vocode_mel_workspace_bytes_cap", "fs2_op_griffin_lim_mel_dev")}
-
-
-def _check_constraint(constraint, magnitudes):
-    if constraint not in CONSTRAINTS:
-        raise ValueError("constraint must be one of %s, got %r" % (CONSTRAINTS, constraint))
-    if constraint == "mel" and magnitudes:
-        raise ValueError("constraint='mel' needs log-mel frames: with magnitudes=True there is no mel to constrain to")
-    return constraint == "mel"
-
-
-def _check_init(init, init_phase, f0=None, f0_floor=71.0, f0_ceil=800.0):
-    if init not in INITS:
-        raise ValueError("init must be one of %s, got %r" % (INITS, init))
-    if init == "spsi" and init_phase is not None:
-        raise ValueError("init='spsi' computes the initial phase itself: pass init_phase or init='spsi', not both")
-    if f0 is not None and init_phase is not None:
-        raise ValueError("f0 gives the initial phase (init='f0'): pass init_phase or f0, not both")
-    if init == "f0":
-        if init_phase is not None:
-            raise ValueError("init='f0' computes the initial phase itself: pass init_phase or init='f0', not both")
-        if f0 is None:
-            raise ValueError("init='f0' needs f0: one value in Hz per row of mels (or an AsyncMels of inference_batch_pitch)")
-        _check_f0_limits(f0_floor, f0_ceil)
-    elif f0 is not None:
-        raise ValueError("f0 belongs to init='f0', got init=%r" % (init,))
-
-
-def _check_f0_limits(f0_floor, f0_ceil):
-    """(f0_floor, f0_ceil) as floats: positive, finite and ordered (csrc/griffin_lim_host.h: f0_phase checks the same)."""
-    lo, hi = float(f0_floor), float(f0_ceil)
-    if not (lo > 0 and math.isfinite(lo) and math.isfinite(hi) and hi >= lo):
-        raise ValueError("need 0 < f0_floor <= f0_ceil, both finite, got %r, %r" % (f0_floor, f0_ceil))
-    return lo, hi
-
-
-def _checked_f0(f0, like, name="mels"):
-    """f0 as a contiguous float32 [rows] tensor: one value per row of ``like`` ([N, W] or [B, Lmax, W]; None: f0 itself is [N] or
-    [B, Lmax]), on its device.  There is no CPU fallback."""
-    if not isinstance(f0, torch.Tensor):
-        raise TypeError("f0 must be a float32 CUDA tensor, got %s" % type(f0).__name__)
-    _require_cuda(f0, "f0")
-    if f0.dtype != torch.float32:
-        raise TypeError("f0 must be float32 (Hz), got %s" % f0.dtype)
-    if like is None:
-        if f0.dim() not in (1, 2):
-            raise ValueError("f0 must be [N] (packed) or [B, Lmax] (padded), got %s" % (tuple(f0.shape),))
-    else:
-        if tuple(f0.shape) != tuple(like.shape[:-1]):
-            raise ValueError("f0 must have one value per row of %s, %s, got %s" % (name, tuple(like.shape[:-1]), tuple(f0.shape)))
-        if f0.device != like.device:
-            raise ValueError("f0 on %s, %s on %s" % (f0.device, name, like.device))
-    return f0.reshape(-1).contiguous()
+def _async_parts(x, olens):
+    """(rows, olens, status, pitch, whether ``x`` is an AsyncMels, whether ``olens`` was given beside one) of a source argument: an
+    AsyncMels is taken apart, its own frame counts standing in where none were given; anything else passes through."""
+    if not isinstance(x, AsyncMels):
+        return x, olens, None, None, False, False
+    return x[0], x[1] if olens is None else olens, x.status, getattr(x, "pitch", None), True, olens is not None
 
 
 class GriffinLim:
@@ -396,31 +330,6 @@ class GriffinLim:
                                  torch.tensor(self._basis_np, dtype=torch.float32, device=device).contiguous())
         return self._dev[device]
 
-    def _checked(self, mels, n_iter, momentum, init_phase, magnitudes, olens=None):
-        """What both forms of the call check of ``mels``, ``n_iter``, ``momentum`` and ``init_phase`` (and of a device ``olens``: that
-        it lives where ``mels`` does).  Returns (source rows [rows, W] and initial phase [rows, bins] or None, both contiguous fp32,
-        W, n_iter, momentum)."""
-        _require_cuda(mels, "mels")
-        NB = self.geometry.n_bins
-        W = NB if magnitudes else self.geometry.n_mels
-        if mels.dim() not in (2, 3) or mels.shape[-1] != W:
-            raise ValueError("mels must be [N, %d] (packed) or [B, Lmax, %d] (padded), got %s" % (W, W, tuple(mels.shape)))
-        if self.device is not None and mels.device != self.device:
-            raise ValueError("mels on %s, this GriffinLim on %s" % (mels.device, self.device))
-        if olens is not None and olens.device != mels.device:
-            raise ValueError("olens on %s, mels on %s" % (olens.device, mels.device))
-        n_iter, momentum = int(n_iter), float(momentum)
-        if n_iter < 0:
-            raise ValueError("n_iter must be >= 0")
-        if not (momentum >= 0.0 and math.isfinite(momentum)):
-            raise ValueError("momentum must be finite and >= 0")
-        if init_phase is not None:
-            _require_cuda(init_phase, "init_phase")
-            if tuple(init_phase.shape[:-1]) != tuple(mels.shape[:-1]) or init_phase.shape[-1] != NB:
-                raise ValueError("init_phase must have the layout of mels with %d bins, got %s" % (NB, tuple(init_phase.shape)))
-            init_phase = init_phase.reshape(-1, NB).contiguous().float()
-        return mels.reshape(-1, W).contiguous().float(), init_phase, W, n_iter, momentum
-
     def __call__(self, mels, olens=None, n_iter=30, momentum=0.0, seed=0, init_phase=None, magnitudes=False, sync=True, capacity=None,
                  padded_out=False, init="seeded", constraint="magnitude", f0=None, f0_floor=71.0, f0_ceil=800.0):
         """mels: packed [N, n_mels] (``inference_batch(packed=True)``) with ``olens`` [B] summing to N, or padded [B, Lmax, n_mels]
@@ -447,195 +356,114 @@ class GriffinLim:
         ``sync=True`` reads ``olens`` on the host (a CUDA ``olens`` is copied back, which waits for the GPU) and sizes the result
         from it.  ``sync=False``: the frame counts stay on the device -- ``olens`` must be a CUDA int64 tensor, or ``mels`` an
         :class:`AsyncMels` (``inference_batch(sync=False)``), whose mels, ``olens`` and status are taken -- and nothing waits for
-        the GPU; see :meth:`_call_dev`.  Returns an :class:`AsyncWaveforms`."""
-        if f0 is None and init == "f0" and isinstance(mels, AsyncMels):
-            f0 = getattr(mels, "pitch", None)
-        _check_init(init, init_phase, f0, f0_floor, f0_ceil)
-        mel_proj = _check_constraint(constraint, magnitudes)
-        if not sync:
-            return self._call_dev(mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init, constraint, f0, f0_floor,
-                                  f0_ceil)
-        if capacity is not None or padded_out:
-            raise ValueError("capacity / padded_out belong to sync=False (sync=True sizes the waveform from olens)")
-        src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes)
-        if init == "f0":
-            f0 = _checked_f0(f0, mels)
-        g = self.geometry
-        L, starts = _host_batch(mels, olens)
-        sample_lens = g.hop * torch.clamp(L - 1, min=0)
-        wav = torch.empty(int(sample_lens.sum()), dtype=torch.float32, device=mels.device)
-        if wav.numel() == 0:
-            return Waveforms(wav, sample_lens)
-        if int(L.sum()) * g.n_bins >= 2 ** 31 or wav.numel() >= 2 ** 31:
-            raise ValueError("batch too large for one call (%d frames)" % int(L.sum()))
-        s_np, s_p = _i32(starts)
-        l_np, l_p = _i32(L.numpy())
-        B = len(l_np)
-        if init == "spsi":
-            init_phase = self._spsi_host(src, W, s_np, l_np, magnitudes, False)[0]
-        elif init == "f0":
-            init_phase = self._f0_host(f0, s_np, l_np, f0_floor, f0_ceil, seed, True)
-        self._synthesize((False, mel_proj), src, W, magnitudes, (B, l_p), (B, s_p, l_p), (n_iter, momentum, seed, init_phase), (wav.data_ptr(),))
-        return Waveforms(wav, sample_lens)
-
-    def _synthesize(self, which, src, W, magnitudes, size, batch, iteration, out):
-        """Size and make the synthesis call ``which`` (a key of _SYNTHESIS) on checked arguments.  ``size``: what the query takes after
-        the geometry; ``batch``, ``out``: what the call takes before the iteration arguments and after the workspace."""
-        lib, g, dev = _lib.lib(), self.geometry, src.device
-        query, call = (getattr(lib, name) for name in _SYNTHESIS[which])
-        n_iter, momentum, seed, init_phase = iteration
-        ws_bytes = int(query(*g, *size))
-        with torch.cuda.device(dev):
-            source = (src.data_ptr(), W, None if magnitudes else self.constants(dev)[0].data_ptr())
-            if which[1]:
-                source += (self.constants(dev)[1].data_ptr(),)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(call(_stream(dev), *g, *source, *batch, n_iter, momentum, int(seed) & 0xFFFFFFFF,
-                            init_phase.data_ptr() if init_phase is not None else None, ws.data_ptr(), ws_bytes, *out))
-
-    def _spsi_host(self, src, W, starts_np, lens_np, magnitudes, want_mag):
-        """fs2_op_spsi_phase_geom on checked arguments: (phase [rows, bins], M [rows, bins] or None), zeros where no utterance is."""
-        g, dev = self.geometry, src.device
-        phase = torch.zeros(src.shape[0], g.n_bins, dtype=torch.float32, device=dev)
-        mag = torch.zeros_like(phase) if want_mag else None
-        if int(lens_np.sum()) == 0:
-            return phase, mag
-        lib = _lib.lib()
-        s_np, s_p = _i32(starts_np)
-        l_np, l_p = _i32(lens_np)
-        ws_bytes = int(lib.fs2_op_spsi_workspace_bytes_geom(*g, len(l_np), l_p))
-        with torch.cuda.device(dev):
-            pinv = self.constants(dev)[0] if not magnitudes else None
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_spsi_phase_geom(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, len(l_np),
-                                                  s_p, l_p, ws.data_ptr(), ws_bytes, phase.data_ptr(), mag.data_ptr() if want_mag else None))
-        return phase, mag
-
-    def _spsi_dev(self, src, W, olens, stride, cap, upstream, magnitudes, want_mag):
-        """fs2_op_spsi_phase_dev on checked arguments (``olens`` a contiguous CUDA int64 [B], B >= 1, cap >= 1)."""
-        g, dev = self.geometry, src.device
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            phase = torch.zeros(src.shape[0], g.n_bins, dtype=torch.float32, device=dev)
-            mag = torch.zeros_like(phase) if want_mag else None
-            pinv = self.constants(dev)[0] if not magnitudes else None
-            ws_bytes = int(lib.fs2_op_spsi_workspace_bytes_cap(*g, olens.numel(), cap))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_spsi_phase_dev(_stream(dev), *g, src.data_ptr(), W, pinv.data_ptr() if pinv is not None else None, olens.numel(),
-                                                 olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None,
-                                                 ws.data_ptr(), ws_bytes, phase.data_ptr(), mag.data_ptr() if want_mag else None))
-        return phase, mag
-
-    def _f0_host(self, f0, starts_np, lens_np, f0_floor, f0_ceil, seed, phase):
-        """fs2_op_f0_phase_geom (``phase``: [rows, bins], zeros where no utterance is) or fs2_op_excitation_geom (the packed waveforms)
-        on a checked flat ``f0``."""
-        g, dev = self.geometry, f0.device
-        s_np, s_p = _i32(starts_np)
-        l_np, l_p = _i32(lens_np)
-        if phase:
-            out = torch.zeros(f0.numel(), g.n_bins, dtype=torch.float32, device=dev)
-        else:
-            out = torch.empty(int(g.hop * np.clip(l_np.astype(np.int64) - 1, 0, None).sum()), dtype=torch.float32, device=dev)
-        if int(l_np.sum()) == 0 or out.numel() == 0:
-            return out
-        lib = _lib.lib()
-        ws_bytes = int(lib.fs2_op_f0_phase_workspace_bytes_geom(*g, len(l_np), l_p))
-        call = lib.fs2_op_f0_phase_geom if phase else lib.fs2_op_excitation_geom
-        with torch.cuda.device(dev):
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(call(_stream(dev), *g, f0.data_ptr(), len(l_np), s_p, l_p, float(f0_floor), float(f0_ceil), int(self.params["sample_rate"]),
-                            int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, out.data_ptr()))
-        return out
-
-    def _f0_dev(self, f0, olens, stride, cap, upstream, f0_floor, f0_ceil, seed):
-        """fs2_op_f0_phase_dev on a checked flat ``f0`` (``olens`` a contiguous CUDA int64 [B], B >= 1, cap >= 1)."""
-        g, dev = self.geometry, f0.device
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            phase = torch.zeros(f0.numel(), g.n_bins, dtype=torch.float32, device=dev)
-            ws_bytes = int(lib.fs2_op_f0_phase_workspace_bytes_cap(*g, olens.numel(), cap))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.fs2_op_f0_phase_dev(_stream(dev), *g, f0.data_ptr(), olens.numel(), olens.data_ptr(), stride, cap,
-                                               upstream.data_ptr() if upstream is not None else None, float(f0_floor), float(f0_ceil),
-                                               int(self.params["sample_rate"]), int(seed) & 0xFFFFFFFF, ws.data_ptr(), ws_bytes, phase.data_ptr()))
-        return phase
-
-    def _f0_batch_limits(self, rows):
-        g = self.geometry
-        if rows * g.n_bins >= 2 ** 31 or rows * g.hop >= 2 ** 31:
-            raise ValueError("batch too large for one call (%d rows)" % rows)
-
-    def f0_phase(self, f0, olens=None, f0_floor=71.0, f0_ceil=800.0, seed=0, sync=True):
-        """The phase of the excitation from F0 (:func:`f0_phase`) in this GriffinLim's geometry and sample rate."""
-        lo, hi = _check_f0_limits(f0_floor, f0_ceil)
-        upstream = None
-        if isinstance(f0, AsyncMels):
-            if sync:
-                raise ValueError("an AsyncMels belongs to sync=False (its frame counts are on the device)")
-            if olens is not None:
-                raise ValueError("olens is taken from the AsyncMels given as f0; pass one or the other")
-            if getattr(f0, "pitch", None) is None:
-                raise ValueError("this AsyncMels carries no pitch: call inference_batch_pitch(sync=False)")
-            upstream, olens, f0 = f0.status, f0[1], f0.pitch
-        if not sync and (not isinstance(olens, torch.Tensor) or not olens.is_cuda or olens.dtype != torch.int64):
-            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device)")
-        flat = _checked_f0(f0, None)
-        if not sync and olens.device != f0.device:
-            raise ValueError("olens on %s, f0 on %s" % (olens.device, f0.device))
-        NB = self.geometry.n_bins
-        rows_like = f0.unsqueeze(-1)                    # the row layout of f0, as _host_batch / _device_batch read it from mels
-        self._f0_batch_limits(flat.numel())
+        the GPU (include/fs2.h: fs2_op_griffin_lim_dev).  Returns an :class:`AsyncWaveforms`.  ``capacity``: bound on the batch's total
+        frames (default: the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the
+        waveform is sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only)
+        [B, hop (Lcap - 1)].  Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own
+        call overflowed, give a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``.  ``init="spsi"`` / ``init="f0"``
+        compute the initial phase on the device from the same frame counts first (fs2_op_spsi_phase_dev, fs2_op_f0_phase_dev),
+        equally without a host read; an ``AsyncMels`` with a ``pitch`` brings its own ``f0``."""
+        lens = _host_lens(olens) if sync else None
+        mels, olens, status, pitch, was_async, clash = _async_parts(mels, olens)
+        if f0 is None and init == "f0":
+            f0 = pitch
+        p = plan_vocode(SYNTHESIS, sync, self.geometry, self.params["sample_rate"], _describe(mels), None if sync else _describe(olens), lens, clash,
+                        was_async, pitch is not None, status is not None, _describe(init_phase), _describe(f0), self.device, magnitudes, init,
+                        constraint, n_iter, momentum, seed, capacity, padded_out, f0_floor, f0_ceil)
+        dev = mels.device
+        src = mels.reshape(-1, p.W).contiguous().float()
+        if init_phase is not None:
+            init_phase = init_phase.reshape(-1, self.geometry.n_bins).contiguous().float()
+        if p.f0_options is not None:
+            f0 = f0.reshape(-1).contiguous()
         if sync:
-            L, starts = _host_batch(rows_like, olens, "f0", "has")
-            phase = self._f0_host(flat, starts, L.numpy(), lo, hi, seed, True)
-        else:
-            olens, B, rows, stride, _ = _device_batch(rows_like, olens)
-            if B == 0 or rows == 0:
-                phase = torch.zeros(rows, NB, dtype=torch.float32, device=f0.device)
-            else:
-                phase = self._f0_dev(flat, olens, stride, rows, upstream, lo, hi, seed)
-        return phase.reshape(tuple(f0.shape) + (NB,))
-
-    def excitation(self, f0, olens=None, seed=0, f0_floor=71.0, f0_ceil=800.0):
-        """The excitation from F0 itself (:func:`excitation`) at this GriffinLim's hop and sample rate -> ``Waveforms``."""
-        lo, hi = _check_f0_limits(f0_floor, f0_ceil)
-        flat = _checked_f0(f0, None)
-        self._f0_batch_limits(flat.numel())
-        L, starts = _host_batch(f0.unsqueeze(-1), olens, "f0", "has")
-        return Waveforms(self._f0_host(flat, starts, L.numpy(), lo, hi, seed, False), self.geometry.hop * torch.clamp(L - 1, min=0))
+            wav = torch.empty(p.out_shapes[0], dtype=torch.float32, device=dev)
+            if not p.empty:
+                self._run(p, dev, src, f0, None, None, init_phase, (wav.data_ptr(),))
+            return Waveforms(wav, torch.tensor(p.sample_lens, dtype=torch.int64))
+        olens = olens.reshape(-1).contiguous()
+        with torch.cuda.device(dev):
+            wav = torch.empty(p.wav_cap, dtype=torch.float32, device=dev)
+            shaped = wav.reshape(p.result_shape[0])
+            if p.empty:
+                return AsyncWaveforms(shaped, torch.zeros(p.B, dtype=torch.int64, device=dev), torch.zeros(8, dtype=torch.int32, device=dev),
+                                      None, p.padded)
+            sample_lens = torch.empty(p.B, dtype=torch.int64, device=dev)        # both written in full by the planner
+            done = torch.empty(8, dtype=torch.int32, device=dev)
+            self._run(p, dev, src, f0, olens, status, init_phase,
+                      (wav.data_ptr() if p.wav_cap else None, p.wav_stride, p.wav_cap, sample_lens.data_ptr(), done.data_ptr()))
+            rec = None if torch.cuda.is_current_stream_capturing() else self._record(done, dev)
+        return AsyncWaveforms(shaped, sample_lens, done, rec, p.padded)
 
     def spsi_phase(self, src, olens=None, magnitudes=False, return_magnitudes=False, sync=True):
         """The phase-continuity initial phase (:func:`spsi_phase`) in this GriffinLim's geometry."""
-        upstream = None
-        if isinstance(src, AsyncMels):
-            if sync:
-                raise ValueError("an AsyncMels belongs to sync=False (its frame counts are on the device)")
-            if olens is not None:
-                raise ValueError("olens is taken from the AsyncMels given as src; pass one or the other")
-            upstream = src.status
-            src, olens = src
-        if not sync:
-            if not isinstance(olens, torch.Tensor) or not olens.is_cuda or olens.dtype != torch.int64:
-                raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device)")
-        mels = src
-        src, _, W, _, _ = self._checked(mels, 0, 0.0, None, magnitudes, olens if not sync else None)
-        NB = self.geometry.n_bins
-        shape = tuple(mels.shape[:-1]) + (NB,)
-        if sync:
-            L, starts = _host_batch(mels, olens, "src", "has")
-            if src.shape[0] * NB >= 2 ** 31:
-                raise ValueError("batch too large for one call (%d rows)" % src.shape[0])
-            phase, mag = self._spsi_host(src, W, starts, L.numpy(), magnitudes, return_magnitudes)
+        lens = _host_lens(olens) if sync else None
+        src, olens, status, _, was_async, clash = _async_parts(src, olens)
+        p = plan_vocode(SPSI, sync, self.geometry, self.params["sample_rate"], _describe(src), None if sync else _describe(olens), lens, clash,
+                        was_async, upstream=status is not None, own_device=self.device, magnitudes=magnitudes, return_magnitudes=return_magnitudes)
+        dev = src.device
+        outs = [torch.zeros(s, dtype=torch.float32, device=dev) for s in p.out_shapes]
+        if not p.empty:
+            self._run(p, dev, src.reshape(-1, p.W).contiguous().float(), None, None if sync else olens.reshape(-1).contiguous(), status, None,
+                      (outs[0].data_ptr(), outs[1].data_ptr() if return_magnitudes else None))
+        outs = [o.reshape(s) for o, s in zip(outs, p.result_shape)]
+        return tuple(outs) if return_magnitudes else outs[0]
+
+    def f0_phase(self, f0, olens=None, f0_floor=71.0, f0_ceil=800.0, seed=0, sync=True):
+        """The phase of the excitation from F0 (:func:`f0_phase`) in this GriffinLim's geometry and sample rate."""
+        lens = _host_lens(olens) if sync else None
+        rows, olens, status, pitch, was_async, clash = _async_parts(f0, olens)
+        f0 = pitch if was_async else rows
+        p = plan_vocode(F0, sync, self.geometry, self.params["sample_rate"], _describe(f0), None if sync else _describe(olens), lens, clash,
+                        was_async, pitch is not None, status is not None, seed=seed, f0_floor=f0_floor, f0_ceil=f0_ceil)
+        dev = f0.device
+        phase = torch.zeros(p.out_shapes[0], dtype=torch.float32, device=dev)
+        if not p.empty:
+            self._run(p, dev, None, f0.reshape(-1).contiguous(), None if sync else olens.reshape(-1).contiguous(), status, None, (phase.data_ptr(),))
+        return phase.reshape(p.result_shape[0])
+
+    def excitation(self, f0, olens=None, seed=0, f0_floor=71.0, f0_ceil=800.0):
+        """The excitation from F0 itself (:func:`excitation`) at this GriffinLim's hop and sample rate -> ``Waveforms``."""
+        p = plan_vocode(EXCITATION, True, self.geometry, self.params["sample_rate"], _describe(f0), None, _host_lens(olens), seed=seed,
+                        f0_floor=f0_floor, f0_ceil=f0_ceil)
+        wav = torch.empty(p.out_shapes[0], dtype=torch.float32, device=f0.device)
+        if not p.empty:
+            self._run(p, f0.device, None, f0.reshape(-1).contiguous(), None, None, None, (wav.data_ptr(),))
+        return Waveforms(wav, torch.tensor(p.sample_lens, dtype=torch.int64))
+
+    def _run(self, p, dev, src, f0, olens, status, init_phase, output):
+        """Follow the stages of plan ``p`` on converted inputs: the one that computes the initial phase, if it names one, then its
+        main one, which writes ``output`` (its output group).  The groups are those of csrc/griffin_lim_host.h's GlCall."""
+        if p.sync:
+            s_np, s_p = _i32(p.starts)
+            l_np, l_p = _i32(p.lens)
+            size, groups = (p.B, l_p), dict(batch=(p.B, s_p, l_p))
         else:
-            olens, B, rows, stride, _ = _device_batch(mels, olens)
-            if rows * NB >= 2 ** 31:
-                raise ValueError("batch too large for one call (%d rows)" % rows)
-            if B == 0 or rows == 0:
-                phase = torch.zeros(rows, NB, dtype=torch.float32, device=mels.device)
-                mag = torch.zeros_like(phase) if return_magnitudes else None
-            else:
-                phase, mag = self._spsi_dev(src, W, olens, stride, rows, upstream, magnitudes, return_magnitudes)
-        return (phase.reshape(shape), mag.reshape(shape)) if return_magnitudes else phase.reshape(shape)
+            size = (p.B, p.cap)
+            groups = dict(batch=(p.B, olens.data_ptr(), p.stride, p.cap, status.data_ptr() if p.upstream else None))
+        if p.W is not None:
+            pinv, basis = self.constants(dev)
+            groups["source"] = (src.data_ptr(), p.W, pinv.data_ptr() if p.pinv else None)
+            if p.basis:
+                groups["mel_source"] = groups["source"] + (basis.data_ptr(),)
+        if p.f0_options is not None:
+            groups.update(f0_source=(f0.data_ptr(),), f0_options=p.f0_options + (p.seed,))
+        if p.init_entry is not None:
+            init_phase = torch.zeros(p.rows, self.geometry.n_bins, dtype=torch.float32, device=dev)      # zeros where no utterance is
+            self._launch(p.init_entry, dev, size, groups, (init_phase.data_ptr(),) + (None,) * (p.init_entry.n_out - 1))
+        if p.kind == SYNTHESIS:
+            groups["iteration"] = (p.n_iter, p.momentum, p.seed, init_phase.data_ptr() if init_phase is not None else None)
+        self._launch(p.entry, dev, size, groups, output)
+
+    def _launch(self, entry, dev, size, groups, output):
+        """The one launch site.  ``entry``: a row of _vocode_plan._ENTRIES.  Query its workspace (``size``: what the query takes after
+        the geometry), allocate it, and make the call with the argument groups in the order the row names."""
+        lib, g = _lib.lib(), self.geometry
+        ws_bytes = int(getattr(lib, entry.query)(*g, *size))
+        with torch.cuda.device(dev):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            groups = dict(groups, stream=(_stream(dev),), geometry=g, workspace=(ws.data_ptr(), ws_bytes), output=output)
+            _lib.check(getattr(lib, entry.call)(*[a for name in entry.order for a in groups[name]]))
 
     _PIN_SLOTS = 16
 
@@ -654,72 +482,6 @@ class GriffinLim:
         ev.record(torch.cuda.current_stream(dev))
         slot[1] = _WavRecord(ev, slot[0])
         return slot[1]
-
-    def _call_dev(self, mels, olens, n_iter, momentum, seed, init_phase, magnitudes, capacity, padded_out, init="seeded",
-                  constraint="magnitude", f0=None, f0_floor=71.0, f0_ceil=800.0):
-        """The device-driven call (include/fs2.h: fs2_op_griffin_lim_dev).  ``capacity``: bound on the batch's total frames (default:
-        the rows of a packed ``mels``, B * Lcap of a padded one); the tiles are planned on the GPU inside it and the waveform is
-        sized from it: packed float32 [hop * (capacity - 1)], or with ``padded_out=True`` (padded ``mels`` only) [B, hop (Lcap - 1)].
-        Frame counts that are negative, sum beyond ``capacity`` or exceed Lcap, and an ``AsyncMels`` whose own call overflowed, give
-        a NaN-filled ``wav``, zero ``sample_lens`` and ``ok() == False``.  ``init="spsi"``: the initial phase is computed on the device
-        from the same frame counts first (fs2_op_spsi_phase_dev), equally without a host read.  ``constraint="mel"``: the
-        mel-constrained projection (fs2_op_griffin_lim_mel_dev), as in :meth:`__call__`.  ``init="f0"``: the phase of the excitation
-        from ``f0`` (fs2_op_f0_phase_dev), likewise; an ``AsyncMels`` with a ``pitch`` brings its own."""
-        upstream = None
-        if f0 is None and init == "f0" and isinstance(mels, AsyncMels):
-            f0 = getattr(mels, "pitch", None)
-        _check_init(init, init_phase, f0, f0_floor, f0_ceil)
-        mel_proj = _check_constraint(constraint, magnitudes)
-        if isinstance(mels, AsyncMels):
-            if olens is not None:
-                raise ValueError("olens is taken from the AsyncMels given as mels; pass one or the other")
-            upstream = mels.status
-            mels, olens = mels
-        if not isinstance(olens, torch.Tensor):
-            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), got %s"
-                            % type(olens).__name__)
-        if olens.dtype != torch.int64:
-            raise TypeError("olens must be int64 with sync=False, got %s" % olens.dtype)
-        if capacity is not None and int(capacity) < 1:
-            raise ValueError("capacity must be >= 1, got %r" % (capacity,))
-        if not olens.is_cuda:
-            raise TypeError("olens must be a CUDA int64 tensor with sync=False (the frame counts stay on the device), it is on %s; "
-                            "use sync=True for host lengths" % olens.device)
-        src, init_phase, W, n_iter, momentum = self._checked(mels, n_iter, momentum, init_phase, magnitudes, olens)
-        if init == "f0":
-            f0 = _checked_f0(f0, mels)
-        g = self.geometry
-        NB = g.n_bins
-        olens, B, rows, stride, Lcap = _device_batch(mels, olens)
-        if Lcap is None and padded_out:
-            raise ValueError("padded_out needs padded mels [B, Lcap, %d] (the waveform's row length is hop * (Lcap - 1))" % W)
-        if Lcap is None and capacity is not None and int(capacity) > rows:
-            raise ValueError("capacity %d exceeds the %d rows of the packed mels" % (int(capacity), rows))
-        cap = rows if capacity is None else min(int(capacity), rows)
-        dev = mels.device
-        padded = bool(padded_out) and Lcap >= 2
-        wav_stride = g.hop * (Lcap - 1) if padded else 0
-        wav_cap = B * wav_stride if padded_out else g.hop * max(cap - 1, 0)        # (padded_out at Lcap < 2: no utterance owns a sample)
-        if cap * NB >= 2 ** 31 or wav_cap >= 2 ** 31:
-            raise ValueError("capacity too large for one call (%d frames)" % cap)
-        with torch.cuda.device(dev):
-            wav = torch.empty(wav_cap, dtype=torch.float32, device=dev)
-            shaped = wav.reshape(B, wav_stride) if padded_out else wav
-            if B == 0 or cap == 0:
-                return AsyncWaveforms(shaped, torch.zeros(B, dtype=torch.int64, device=dev), torch.zeros(8, dtype=torch.int32, device=dev),
-                                      None, bool(padded_out))
-            sample_lens = torch.empty(B, dtype=torch.int64, device=dev)        # both written in full by the planner
-            status = torch.empty(8, dtype=torch.int32, device=dev)
-            if init == "spsi":
-                init_phase = self._spsi_dev(src, W, olens, stride, cap, upstream, magnitudes, False)[0]
-            elif init == "f0":
-                init_phase = self._f0_dev(f0, olens, stride, cap, upstream, f0_floor, f0_ceil, seed)
-            self._synthesize((True, mel_proj), src, W, magnitudes, (B, cap),
-                             (B, olens.data_ptr(), stride, cap, upstream.data_ptr() if upstream is not None else None),
-                             (n_iter, momentum, seed, init_phase),
-                             (wav.data_ptr() if wav_cap else None, wav_stride, wav_cap, sample_lens.data_ptr(), status.data_ptr()))
-            rec = None if torch.cuda.is_current_stream_capturing() else self._record(status, dev)
-        return AsyncWaveforms(shaped, sample_lens, status, rec, bool(padded_out))
 
 
 _DEFAULT_GL = None

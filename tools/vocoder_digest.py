@@ -10,8 +10,8 @@ parent (profiles/vocoder_call_digest.txt).
 Cases, at the four geometries that take the four branches of gl_dispatch: a batch of (0, 1, L_min - 1, L_min, F, F + 1, 2 F + 5) frames
 (nobody owns a sample / too short / the first real one / the tile edge / three tiles) through every form of the synthesis -- n_iter 0
 and 3 against momentum 0 and 0.99, constraint magnitude and mel, init seeded / init_phase / spsi, a magnitude source, host-planned
-packed and padded, device-driven packed, padded and padded_out -- spsi_phase with its magnitudes in both forms, the analysis with and
-without pitch, 125 utterances of L_min frames (more tile records than one upload chunk) and 245 of one frame (more than one SPSI
+packed and padded, device-driven packed, padded and padded_out -- spsi_phase with its magnitudes in both forms, init="f0" in the same
+forms (padded_out also at n_iter 0), f0_phase host and device, packed and padded, the excitation, the analysis with and without pitch, 125 utterances of L_min frames (more tile records than one upload chunk) and 245 of one frame (more than one SPSI
 chunk), and the two fixed-geometry entry points called directly.  The largest case has under 600 frames."""
 import argparse
 import ctypes as C
@@ -91,6 +91,32 @@ def synthesis_cases(gl, name, lens, iters=((0, 0.0), (0, 0.99), (3, 0.0), (3, 0.
     yield name + "/spsi_phase/mel/host/padded", gl.spsi_phase(pm, olens, return_magnitudes=True)
     yield name + "/spsi_phase/mel/dev/padded", gl.spsi_phase(pm, olens.cuda(), return_magnitudes=True, sync=False)
     yield name + "/spsi_phase/mel/host/phase only", (gl.spsi_phase(mels, olens),)
+    yield from f0_cases(gl, name, lens, mels, pm, olens, gen)
+
+
+def f0_cases(gl, name, lens, mels, pm, olens, gen):
+    """init="f0" in every form of the synthesis, f0_phase host and device, packed and padded, and the excitation"""
+    import torch
+    f0 = 120.0 + 100.0 * torch.rand(sum(lens), generator=gen)
+    f0[::5] = 0.0
+    f0 = f0.cuda()
+    pf = pad(f0[:, None], lens, 1)[:, :, 0].contiguous()
+    dev = lambda w: (w.wav, w.sample_lens, w.status)
+    for con in ("magnitude", "mel"):
+        kw = dict(n_iter=3, momentum=0.99, seed=9, init="f0", constraint=con)
+        tag = "%s/%s/f0" % (name, con)
+        yield tag + "/host/packed", gl(mels, olens, f0=f0, **kw)
+        yield tag + "/host/padded", gl(pm, olens, f0=pf, **kw)
+        yield tag + "/dev/packed", dev(gl(mels, olens.cuda(), f0=f0, sync=False, **kw))
+        yield tag + "/dev/padded", dev(gl(pm, olens.cuda(), f0=pf, sync=False, **kw))
+        yield tag + "/dev/padded_out", dev(gl(pm, olens.cuda(), f0=pf, sync=False, padded_out=True, **kw))
+        yield tag + "/dev/padded_out/it0", dev(gl(pm, olens.cuda(), f0=pf, sync=False, padded_out=True, **dict(kw, n_iter=0)))
+    yield name + "/f0_phase/host/packed", (gl.f0_phase(f0, olens, seed=9),)
+    yield name + "/f0_phase/host/padded", (gl.f0_phase(pf, olens, seed=9),)
+    yield name + "/f0_phase/dev/packed", (gl.f0_phase(f0, olens.cuda(), seed=9, sync=False),)
+    yield name + "/f0_phase/dev/padded", (gl.f0_phase(pf, olens.cuda(), seed=9, sync=False),)
+    yield name + "/excitation", gl.excitation(f0, olens, seed=9)
+    yield name + "/excitation/padded", gl.excitation(pf, olens, seed=9)
 
 
 def analysis_cases(fs, hp, name, g, F):
@@ -155,8 +181,8 @@ def all_cases():
 
 
 def trace_cases():
-    """The few cases whose kernel trace is compared (--trace-subset): a host-planned, a device-driven, a mel-constrained, an SPSI and
-    a pitch call at the default geometry and at one other."""
+    """The few cases whose kernel trace is compared (--trace-subset): a host-planned, a device-driven, a mel-constrained, an SPSI, a
+    device-driven init="f0" and a pitch call at the default geometry and at one other."""
     import torch
     import fastspeech2_amd as fs
     from fastspeech2_amd import vocoder as V
@@ -171,7 +197,10 @@ def trace_cases():
         yield name + "/dev", (w.wav, w.sample_lens, w.status)
         yield name + "/mel", gl(mels, olens, n_iter=3, momentum=0.99, constraint="mel")
         yield name + "/spsi", gl(mels, olens, n_iter=3, init="spsi")
-        x = gl(mels, olens, n_iter=0).wav
+        f0 = torch.full((sum(lens),), 150.0).cuda()
+        w = gl(mels, olens.cuda(), n_iter=3, init="f0", f0=f0, sync=False)
+        yield name + "/f0", (w.wav, w.sample_lens, w.status)
+        x =gl(mels, olens, n_iter=0).wav
         yield name + "/pitch", fs.wav_features(x, [x.numel()], hp=hp)
 
 
