@@ -86,6 +86,13 @@ class OpLossArgs(_Sized):
            ("terms", C.c_void_p), ("batch", C.c_void_p)])
 
 
+class OpAttnArgs(_Sized):
+    """fs2_op_attn_args (test hook fs2_op_launch_attention).  Every pointer is a device pointer; ``qkv``, ``dims`` and ``slow_count`` may be None."""
+    _fields_ = ([("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("nitems", "D", "heads", "dk_true", "R", "Rvt", "regime_rows", "mask_q", "precision")]
+                + [(n, C.c_void_p) for n in ("qkv", "qk_hi", "qk_lo", "vt_hi", "vt_lo", "ctx", "ctxp", "start", "len", "klen", "work", "dims", "slow_count")])
+
+
+ATTN_PLAN_FIELDS = 7       # FS2_ATTN_PLAN_FIELDS
 GEMM_PLAN_FIELDS = 12      # FS2_GEMM_PLAN_FIELDS
 REPACK_MX, REPACK_MX4 = 1, 2      # FS2_REPACK_MX / FS2_REPACK_MX4 (fs2_op_repack_weight)
 
@@ -143,7 +150,7 @@ ABI_VERSION = 4      # FS2_ABI_VERSION of the include/fs2.h these mirrors were w
 
 EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs2_load_weights", "fs2_token_workspace_bytes",
            "fs2_encode", "fs2_frame_workspace_bytes", "fs2_row_capacity", "fs2_frame_workspace_bytes_cap", "fs2_decode", "fs2_set_profiling", "fs2_set_profile_filter", "fs2_get_profile",
-           "fs2_op_conv_gemm", "fs2_op_launch_gemm", "fs2_op_repack_weight", "fs2_op_attention", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
+           "fs2_op_conv_gemm", "fs2_op_launch_gemm", "fs2_op_repack_weight", "fs2_op_attention", "fs2_op_launch_attention", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
            "fs2_op_vocode_workspace_bytes", "fs2_op_griffin_lim", "fs2_op_stft_workspace_bytes", "fs2_op_stft",
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom", "fs2_op_stft_pitch_cands_workspace_bytes_geom", "fs2_op_stft_pitch_cands_geom",
@@ -308,6 +315,8 @@ def lib():
     L.fs2_op_repack_weight.restype = C.c_int
     L.fs2_op_attention.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32]
     L.fs2_op_attention.restype = C.c_int
+    L.fs2_op_launch_attention.argtypes = [vp, C.POINTER(OpAttnArgs), C.POINTER(i32), i32]      # test hook: tests/attn_raw.py
+    L.fs2_op_launch_attention.restype = C.c_int
     L.fs2_op_length_regulate.argtypes = [vp, vp, vp, i64p, i32, i32, i32, i32, C.c_float, vp, vp, vp]
     L.fs2_op_length_regulate.restype = C.c_int
     L.fs2_op_unpack_rows.argtypes = [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, vp]

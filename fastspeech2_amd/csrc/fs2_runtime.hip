@@ -474,7 +474,7 @@ struct AttnIo {
     const DevLayout* dl = nullptr;
     int mask_q = 0; double flops = 0.0;
     AttnCall c;
-    int *slow_count = nullptr, *slow_count2 = nullptr;      // attn_w32's counters of the handle and of the call in progress (launch_attention sets them)
+    int *slow_count = nullptr, *slow_count2 = nullptr;      // attn_w32's counters of the handle (without one: the caller's, if any) and of the call in progress (launch_attention sets them)
 };
 
 // the layout fields AttnArgs and AttnB16Args share
@@ -511,13 +511,19 @@ hipError_t run_attn_plan(hipStream_t s, const AttnPlan& p, const AttnIo& io) {
 }
 #undef CV
 
+// what the plan reads of the pointers
+void attn_call_pointers(AttnIo& io) {
+    io.c.qkv_rows = io.qkv != nullptr;
+    io.c.qk_lo_dist = reinterpret_cast<const char*>(io.qkl) - reinterpret_cast<const char*>(io.qkh);
+    io.c.vt_lo_dist = reinterpret_cast<const char*>(io.vtl) - reinterpret_cast<const char*>(io.vth);
+}
+
 // Plan (attn_plan.h), then execute: qkv_split under "<name>.split" where the operands arrive as fp32 rows, the kernel under `name`.
 int launch_attention(fs2_handle* h, hipStream_t s, const char* name, AttnIo io) {
+    attn_call_pointers(io);
     AttnCall& c = io.c;
-    c.qkv_rows = io.qkv != nullptr;
-    c.qk_lo_dist = reinterpret_cast<const char*>(io.qkl) - reinterpret_cast<const char*>(io.qkh);
-    c.vt_lo_dist = reinterpret_cast<const char*>(io.vtl) - reinterpret_cast<const char*>(io.vth);
-    io.slow_count = h ? h->counters : nullptr; io.slow_count2 = (h && h->cur_status) ? h->cur_status + 5 : nullptr;
+    if (h) io.slow_count = h->counters;      // (without a handle the caller's counter stays: fs2_op_launch_attention)
+    io.slow_count2 = (h && h->cur_status) ? h->cur_status + 5 : nullptr;
     const AttnPlan p = plan_attention(c, opts());
     if (p.err) return fail(h, p.err, p.msg, p.m0);
     if (p.kernel == AttnKernel::None) return FS2_OK;
@@ -1742,6 +1748,32 @@ int fs2_op_attention(void* stream, const float* qkv, float* ctx, int32_t D, int3
         OP_TRY(hipGetLastError());
     }
     return rc;      // (tmp drains the stream and frees)
+}
+
+// Test hook (include/fs2.h): the launch path of the model -- plan_attention, then launch_attention -- on the caller's device buffers; the plan goes back to the
+// caller first, so that a test knows which kernel its numbers came from.
+int fs2_op_launch_attention(void* stream, const fs2_op_attn_args* o, int32_t* plan_out, int32_t plan_cap) {
+    if (!o || !plan_out) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_attention: null argument");
+    if (o->struct_size != sizeof(fs2_op_attn_args)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_attn_args.struct_size %u != %zu", o->struct_size, sizeof(fs2_op_attn_args));
+    if (plan_cap < FS2_ATTN_PLAN_FIELDS) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_attention: plan_out holds %d fields, %d are written", plan_cap, FS2_ATTN_PLAN_FIELDS);
+    if (o->precision != FS2_PREC_FP32 && o->precision != FS2_PREC_BF16X3 && o->precision != FS2_PREC_BF16) return fail(nullptr, FS2_ERR_ARG, "unknown precision %d", o->precision);
+    const bool f32 = o->precision == FS2_PREC_FP32;
+    if (!o->start || !o->len || !o->klen || !o->work || (f32 ? !o->qkv || !o->ctx : !o->qk_hi || !o->qk_lo || !o->vt_hi || !o->vt_lo || (!o->ctx && !o->ctxp)))
+        return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_attention: null buffer (precision %d)", o->precision);
+    if (o->nitems < 0 || o->D <= 0 || o->heads <= 0 || o->R < 0 || o->Rvt < 0 || (!f32 && o->Rvt % 32)) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_attention: bad sizes");
+    DevLayout dl;
+    dl.start = const_cast<int*>(o->start); dl.len = const_cast<int*>(o->len); dl.klen = const_cast<int*>(o->klen);
+    dl.work = reinterpret_cast<int2*>(const_cast<int*>(o->work)); dl.dims = const_cast<int*>(o->dims);
+    AttnIo io{o->qkv, o->ctx, f32 ? nullptr : o->ctxp, (__bf16*)o->qk_hi, (__bf16*)o->qk_lo, (__bf16*)o->vt_hi, (__bf16*)o->vt_lo, &dl, o->mask_q, 0.0,
+              AttnCall{o->D, o->heads, o->dk_true, o->precision, o->R, o->Rvt, o->regime_rows, o->nitems}};
+    io.slow_count = o->slow_count;
+    attn_call_pointers(io);
+    const AttnPlan p = plan_attention(io.c, opts());
+    int32_t scale_bits;
+    memcpy(&scale_bits, &p.softmax_scale, sizeof scale_bits);
+    const int32_t fields[FS2_ATTN_PLAN_FIELDS] = {(int32_t)p.kernel, p.dk, p.nsplit, (int32_t)p.grid_x, (int32_t)p.grid_y, (int32_t)p.split_pass, scale_bits};
+    memcpy(plan_out, fields, sizeof fields);
+    return launch_attention(nullptr, (hipStream_t)stream, "op.launch_attention", io);
 }
 
 int fs2_op_length_regulate(void* stream, const float* hs, const int64_t* ds, const int64_t* ilens_host, int32_t B, int32_t Tmax,

@@ -281,6 +281,38 @@ int fs2_op_attention(void *stream, const float *qkv, float *ctx, int32_t D, int3
                      const int32_t *seq_start, const int32_t *seq_len, const int32_t *seq_klen,
                      int32_t mask_q, int32_t precision);
 
+/* TEST HOOK: plan and run ONE self-attention launch exactly as the model's are planned and run (csrc/attn_plan.h:
+ * plan_attention, then the split pass where fp32 QKV rows are given, then the kernel), the sibling of fs2_op_launch_gemm and
+ * the way the kernel-level tests (tests/test_gpu_attn_kernels.py) reach what the operator above cannot express: operand planes
+ * of known values (or the planes a QKV projection left), the model's dealt, padded and counted work lists, the context as
+ * planes, attn_w32's slow-path counter.  Nothing is allocated or converted: every pointer is a DEVICE buffer the caller owns and
+ * sizes as the kernels read and write it.
+ *   qkv                fp32 rows [R][3 D], or NULL (FS2_PREC_FP32 needs them; the bf16 modes run qkv_split on them first)
+ *   qk_hi/lo, vt_hi/lo the bf16 operand planes [Rvt][2 D] and [D][Rvt] (the bf16 modes; Rvt % 32 == 0)
+ *   ctx, ctxp          the context as fp32 rows [R][D] and / or (bf16 modes) as split-bf16 planes; at least one
+ *   start, len, klen   per utterance; work: (utterance, 128-query block) items, (-1, 0) = padding
+ *   dims               NULL: `nitems` items are valid; else the kernels read the valid count from dims[1] and `nitems` is the
+ *                      capacity the grid is sized for (the device-driven layout)
+ *   slow_count         NULL, or the counter attn_w32 adds one to per wave that leaves its fast path
+ * plan_out[0 .. FS2_ATTN_PLAN_FIELDS) receives the decision before anything is launched: kernel (the AttnKernel enumerator),
+ * dk, nsplit, grid_x, grid_y, split_pass, the bits of softmax_scale.  A launch the plan refuses returns the plan's error code
+ * and message and launches nothing.  FS2_ERR_ARG: a struct_size other than sizeof(fs2_op_attn_args), a NULL argument or a NULL
+ * buffer the precision needs, a precision other than FS2_PREC_FP32 / _BF16X3 / _BF16, a `plan_cap` below FS2_ATTN_PLAN_FIELDS. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(fs2_op_attn_args) */
+    int32_t nitems, D, heads, dk_true, R, Rvt, regime_rows, mask_q, precision;
+    const float *qkv;
+    void *qk_hi, *qk_lo, *vt_hi, *vt_lo;
+    float *ctx;
+    void *ctxp;
+    const int32_t *start, *len, *klen;
+    const int32_t *work;
+    const int32_t *dims;
+    int32_t *slow_count;
+} fs2_op_attn_args;
+#define FS2_ATTN_PLAN_FIELDS 7
+int fs2_op_launch_attention(void *stream, const fs2_op_attn_args *a, int32_t *plan_out, int32_t plan_cap);
+
 /* length regulator on a padded batch: hs [B,Tmax,D], ds [B,Tmax] (i64), ilens HOST [B] ->
  * out [B,Lmax,D] (pads 0), index [B,Lmax] (-1 pads), olens device [B].  Lmax must be >= max olens.
  * alpha > 0: speed control, durations become round(d * alpha) (1 = unchanged).

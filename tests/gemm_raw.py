@@ -1263,11 +1263,13 @@ class QkvCase:
         self.Rvt = rpad(ops.R)
         self.qk_bytes, self.vt_bytes = self.Rvt * 2 * ops.D * 2, ops.D * self.Rvt * 2
 
-    def run(self, kind, mt, split, set_option):
-        """-> (plan, {qk_hi, qk_lo, vt_hi, vt_lo: bytes on the CPU, with guard})."""
+    def run(self, kind, mt, split, set_option, out=None):
+        """-> (plan, {qk_hi, qk_lo, vt_hi, vt_lo: bytes on the CPU, with guard}).  out: the caller's device buffers of the four planes (a consumer then reads what the
+        launch left: tests/test_gpu_attn_kernels.py)."""
         for k, v in qkv_options(kind, mt, split).items():
             set_option(k, v)
-        out = dict(qk_hi=sentinel(self.qk_bytes), qk_lo=sentinel(self.qk_bytes), vt_hi=sentinel(self.vt_bytes), vt_lo=sentinel(self.vt_bytes))
+        if out is None:
+            out = dict(qk_hi=sentinel(self.qk_bytes), qk_lo=sentinel(self.qk_bytes), vt_hi=sentinel(self.vt_bytes), vt_lo=sentinel(self.vt_bytes))
         p = {k: t.data_ptr() for k, t in self.keep.items()}
         p.update({k: t.data_ptr() for k, t in out.items()})
         plan = launch(qkv_block(self.ops.D, self.ops.R, p))

@@ -138,6 +138,31 @@ def test_struct_size_mismatch_is_rejected(libpath):
     assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, 1, plan, len(plan) - 1) == -1 and b"plan_out" in L.fs2_last_error(None)
     for precision in (-1, 3, 6):
         assert L.fs2_op_launch_gemm(None, ctypes.byref(blk), n, precision, plan, len(plan)) == -1 and b"precision" in L.fs2_last_error(None)
+    # the attention launch hook: a wrong struct_size, a null argument, a null buffer the precision needs, an unknown precision or a short plan buffer is refused
+    # before anything is planned or launched (the pointers are placeholders that nothing follows)
+    aplan, p = (ctypes.c_int32 * _lib.ATTN_PLAN_FIELDS)(), 0x1000
+
+    def attn(**kw):
+        f = dict(nitems=1, D=256, heads=2, dk_true=0, R=64, Rvt=128, regime_rows=0, mask_q=0, precision=1, qkv=None, qk_hi=p, qk_lo=p, vt_hi=p, vt_lo=p, ctx=p, ctxp=None,
+                 start=p, len=p, klen=p, work=p, dims=None, slow_count=None)
+        f.update(kw)
+        return _lib.OpAttnArgs(**f)
+
+    la = L.fs2_op_launch_attention
+    a = attn()
+    a.struct_size -= 8
+    assert la(None, ctypes.byref(a), aplan, len(aplan)) == -1 and b"struct_size" in L.fs2_last_error(None)
+    assert la(None, None, aplan, len(aplan)) == -1 and b"null" in L.fs2_last_error(None)
+    assert la(None, ctypes.byref(attn()), None, len(aplan)) == -1 and b"null" in L.fs2_last_error(None)
+    assert la(None, ctypes.byref(attn()), aplan, len(aplan) - 1) == -1 and b"plan_out" in L.fs2_last_error(None)
+    for precision in (-1, 3, 6):
+        assert la(None, ctypes.byref(attn(precision=precision)), aplan, len(aplan)) == -1 and b"precision" in L.fs2_last_error(None)
+    for missing in (dict(start=None), dict(len=None), dict(klen=None), dict(work=None), dict(qk_lo=None), dict(vt_hi=None), dict(ctx=None),
+                    dict(precision=0), dict(precision=0, qkv=p, ctx=None), dict(precision=2, qk_hi=None)):      # (fp32 needs qkv rows and fp32 ctx rows)
+        assert la(None, ctypes.byref(attn(**missing)), aplan, len(aplan)) == -1 and b"null buffer" in L.fs2_last_error(None), missing
+    # a launch the plan refuses returns the plan's code and message, with the plan reported, and launches nothing; an empty work list is no launch at all
+    assert la(None, ctypes.byref(attn(D=200, heads=2)), aplan, len(aplan)) == -6 and b"head dim 100" in L.fs2_last_error(None) and aplan[0] == 0
+    assert la(None, ctypes.byref(attn(nitems=0)), aplan, len(aplan)) == 0 and list(aplan) == [0] * _lib.ATTN_PLAN_FIELDS
     # the repack hook: a null argument, an unknown format, a shape the formats do not exist for, or an image of another size is refused before anything is
     # launched (the pointers are placeholders that nothing follows)
     kw, p = ctypes.c_int32(7), ctypes.c_void_p(0x1000)
