@@ -93,6 +93,8 @@ class OpAttnArgs(_Sized):
 
 
 ATTN_PLAN_FIELDS = 7       # FS2_ATTN_PLAN_FIELDS
+# FS2_ROW_STEP_* (test hook fs2_op_launch_row_step), in enumerator order
+ROW_STEPS = ("embed", "dur_post", "lr_index", "lr_index_short", "lr_expand", "var_gather0", "var_embed", "dec_in_gather", "to_planes", "planes_to_rows")
 GEMM_PLAN_FIELDS = 12      # FS2_GEMM_PLAN_FIELDS
 REPACK_MX, REPACK_MX4 = 1, 2      # FS2_REPACK_MX / FS2_REPACK_MX4 (fs2_op_repack_weight)
 
@@ -150,7 +152,7 @@ ABI_VERSION = 4      # FS2_ABI_VERSION of the include/fs2.h these mirrors were w
 
 EXPORTS = ["fs2_abi_version", "fs2_create", "fs2_destroy", "fs2_last_error", "fs2_load_weights", "fs2_token_workspace_bytes",
            "fs2_encode", "fs2_frame_workspace_bytes", "fs2_row_capacity", "fs2_frame_workspace_bytes_cap", "fs2_decode", "fs2_set_profiling", "fs2_set_profile_filter", "fs2_get_profile",
-           "fs2_op_conv_gemm", "fs2_op_launch_gemm", "fs2_op_repack_weight", "fs2_op_attention", "fs2_op_launch_attention", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
+           "fs2_op_conv_gemm", "fs2_op_launch_gemm", "fs2_op_repack_weight", "fs2_op_attention", "fs2_op_launch_attention", "fs2_op_launch_row_step", "fs2_op_length_regulate", "fs2_op_unpack_rows", "fs2_op_unpack_rows_dev", "fs2_op_transpose", "fs2_op_bucketize", "fs2_op_duration", "fs2_set_option", "fs2_get_option", "fs2_get_counter",
            "fs2_op_vocode_workspace_bytes", "fs2_op_griffin_lim", "fs2_op_stft_workspace_bytes", "fs2_op_stft",
            "fs2_op_vocode_workspace_bytes_geom", "fs2_op_griffin_lim_geom", "fs2_op_stft_workspace_bytes_geom", "fs2_op_stft_geom",
            "fs2_op_stft_pitch_workspace_bytes_geom", "fs2_op_stft_pitch_geom", "fs2_op_stft_pitch_cands_workspace_bytes_geom", "fs2_op_stft_pitch_cands_geom",
@@ -317,6 +319,8 @@ def lib():
     L.fs2_op_attention.restype = C.c_int
     L.fs2_op_launch_attention.argtypes = [vp, C.POINTER(OpAttnArgs), C.POINTER(i32), i32]      # test hook: tests/attn_raw.py
     L.fs2_op_launch_attention.restype = C.c_int
+    L.fs2_op_launch_row_step.argtypes = [vp, i32, vp, C.c_uint32]      # test hook: the blocks are tests/rowstep_raw.py's mirrors of csrc/row_step_args.h
+    L.fs2_op_launch_row_step.restype = C.c_int
     L.fs2_op_length_regulate.argtypes = [vp, vp, vp, i64p, i32, i32, i32, i32, C.c_float, vp, vp, vp]
     L.fs2_op_length_regulate.restype = C.c_int
     L.fs2_op_unpack_rows.argtypes = [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, vp]

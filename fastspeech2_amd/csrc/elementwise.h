@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "layout_rule.h"
+#include "row_step_args.h"
 
 namespace fs2 {
 
@@ -75,22 +76,29 @@ __global__ void dur_finalize(const float* dlog_rows, const int* start, const int
 // Per-utterance inclusive prefix sum of the durations actually used (reference length_regulator.py:60,
 // 85-88: slice to ilen, an all-zero row becomes all ones).  One workgroup per utterance.
 // alpha: the length regulator's speed control (length_regulator.py:57-59): d <- round_half_even(float(d) * alpha) when alpha != 1.
+// A duration beyond the int range saturates at kDurMax (duration_from_log saturates at INT64_MAX for +inf; a caller's ds may hold anything): narrowed blindly, 2^32 + 5
+// frames became 5 and INT64_MAX became -1, and the utterance came back with a small positive frame count.
+constexpr int kDurMax = 0x7fffffff;
 __device__ __forceinline__ int scaled_duration(int64_t d, float alpha) {
     if (d <= 0) return 0;
-    if (alpha == 1.0f) return (int)d;
+    if (alpha == 1.0f) return d > kDurMax ? kDurMax : (int)d;
     const float f = rintf((float)d * alpha);
-    return f > 0.f ? (int)f : 0;
+    return f > 0.f ? (f >= 2147483648.f ? kDurMax : (int)f) : 0;
 }
 
 // ids != nullptr (fs2_encode): an utterance whose row of xs (all Tmax positions, pads included) holds a phoneme id outside [0, idim) gets the frame count -1 -- the reference's
 // torch.nn.Embedding raises for it (fastspeech.py:65-67, core/encoder.py:196); embed_pe reads row 0 instead of indexing out of range, and
 // the marker reaches the caller with the frame counts it reads anyway (host-driven layout) or as FS2_OVF_BAD_ID in the status word of
 // fs2_decode's device-driven layout (frame_layout_dev), whose outputs are then NaN-filled.
+// An utterance whose durations sum beyond the int range gets the frame count kDurMax (the total is formed in 64 bits and saturates; its cum entries are then
+// meaningless): no positional table and no row capacity holds it, so fs2_decode refuses it (host-driven layout) or flags it (FS2_OVF_LMAX / _PE) instead of
+// running on a wrapped count.
 // scum != nullptr (FS2_VARSHORT): beside cum, the running sums of the SHORT durations min(d, K) (layout_rule.h) and, in so32[b], their total.
 __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, const int* ilen, int* cum,
                                                 int64_t* olens, int* olens32, float alpha = 1.0f, const int64_t* ids = nullptr, int idim = 0,
                                                 int* scum = nullptr, int* so32 = nullptr, int K = 0) {
     __shared__ int wsum[4], wsum2[4];
+    __shared__ long long wtot[4];
     __shared__ int carry_s, carry2_s;
     __shared__ int bad_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -99,7 +107,8 @@ __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, con
     if (tid == 0) bad_s = 0;
     __syncthreads();
     // pass 1: total
-    int tot = 0, bad = 0;
+    long long tot = 0;
+    int bad = 0;
     for (int t = tid; t < T; t += 256) tot += scaled_duration(d[t], alpha);
     // (ALL Tmax positions of the row, pads included: the reference's nn.Embedding indexes the whole padded xs, so an id outside [0, idim) in the pad
     //  region -- a -1 padding convention, say -- raises there too; round-5 advisor finding)
@@ -107,9 +116,10 @@ __global__ __launch_bounds__(256) void dur_scan(const int64_t* ds, int Tmax, con
         for (int t = tid; t < Tmax; t += 256) { const int64_t id = ids[(size_t)b * Tmax + t]; bad |= (id < 0 || id >= idim) ? 1 : 0; }
     if (bad) bad_s = 1;
     for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-    if (lane == 0) wsum[wave] = tot;
+    if (lane == 0) wtot[wave] = tot;
     __syncthreads();
-    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const long long total64 = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    const int total = total64 > kDurMax ? kDurMax : (int)total64;
     const bool ones = (total == 0);
     __syncthreads();
     if (tid == 0) { carry_s = 0; carry2_s = 0; }
@@ -258,34 +268,7 @@ __global__ __launch_bounds__(256) void bucket_embed(float* h, int D, const int* 
     }
 }
 
-// ---- multiply before expanding (fs2_runtime.hip: tok.proj) ----
-// The length regulator repeats every encoder row once per frame, and the first layer behind it is linear: the products of the encoder rows with the
-// weights of the predictors' first convolution (one k = 1 product per tap) and of the decoder input layer are computed once per TOKEN, as the rows
-// P [token rows, ldp] = [tap0: energy | pitch][tap1: energy | pitch][tap2: energy | pitch][dec.in], and the two kernels below gather them per frame.
-struct TokGatherArgs {
-    const float* P; int ldp;            // token-level products (fs2_encode), fp32 rows
-    const int* tok_start;               // [B] first token row of every utterance
-    const int* lri;                     // [R] token of every frame row (lr_index_only), -1: none
-    const int *row_pos, *row_seq;       // frame-row metadata
-    int R;
-    // var_gather0
-    int chans;                          // channels of one predictor's first layer
-    const float *bias, *ln_g, *ln_b;    // stacked energy | pitch: [2 chans]
-    void* vp;                           // planes of the stacked hidden layer [R][2 chans]
-    // dec_in_gather
-    int col0, D;                        // first dec.in column of P; decoder width
-    const float *es, *ps; int es_stride, ps_stride;      // teacher forcing ([B, stride]) or nullptr
-    const float *e_rows, *p_rows;       // the predictions per packed row
-    const float *ebins, *pbins; int nb;
-    const float *TE, *TP;               // [n_bins, D]: the embedding tables behind the input layer's weights (TP carries its bias)
-    int *qe_rows, *qp_rows;
-    // FS2_VARSHORT: the predictions exist per SHORT row and their buckets were searched there (varshort.h): a frame reads them through f2s [R]
-    // (-1: no short row).  sqe / sqp == nullptr: that index is searched per frame, from es / ps (teacher forcing) or e_rows / p_rows
-    const int *f2s, *sqe, *sqp;
-    const float *ln_g2, *ln_b2;         // LayerNorm of the input layer
-    const float* pe; const float* pe_alpha; float x_scale;
-    float* x0; void* x0p;               // fp32 rows (or nullptr: planes only) and split-bf16 planes of the decoder input
-};
+// ---- multiply before expanding (fs2_runtime.hip: tok.proj): the two kernels below gather the token-level products per frame (row_step_args.h: TokGatherArgs) ----
 
 // First layer of both variance predictors from the token-level products: y[f] = P0[tok(f-1)] + P1[tok(f)] + P2[tok(f+1)] + b -> ReLU -> LayerNorm(1e-12),
 // written as split-bf16 planes at the column offset of the group.  A neighbour that is a gap row or lies beyond the utterance contributes zero, as the

@@ -613,6 +613,105 @@ int launch_step(fs2_handle* h, hipStream_t s, const char* tag, const Step& st, i
     return st.kind == StepKind::LayerNorm ? launch_ln(h, s, nm, st.a) : launch_gemm(h, s, nm, st.a, prec);
 }
 
+// ------------------------------------------------------------------ the row steps between the GEMMs
+// One function per step: it owns the profile name and the grid and block arithmetic.  fs2_encode / fs2_decode_ctl call it with their handle, the test hook
+// fs2_op_launch_row_step with h == nullptr (no profile record, errors to the process-wide message), as launch_gemm and launch_attention allow.
+#define ROW_STEP_TRY(h, name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(h, FS2_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e_)); } while (0)
+
+// enc.embed: rows = E[xs] x_scale + alpha pe[pos], optionally also as planes
+int embed_launch(fs2_handle* h, hipStream_t s, const RowStepArgs& a) {
+    Scope sc(h, s, "enc.embed", 0, 4.0 * a.R * a.D * 2);
+    hipLaunchKernelGGL(embed_pe, dim3((a.R + 3) / 4), dim3(256), 0, s, a.xs, a.Tmax, a.E, a.idim, a.D, a.pe, a.pe_alpha, a.x_scale, a.row_pos, a.row_seq, a.R, a.rows, a.planes);
+    ROW_STEP_TRY(h, "enc.embed");
+    return FS2_OK;
+}
+
+// dur.post: the padded duration outputs, then the scan of the durations actually used (a.ds, or the ones just written)
+int dur_post_launch(fs2_handle* h, hipStream_t s, const RowStepArgs& a) {
+    Scope sc(h, s, "dur.post", 0, 0);
+    const int n = a.B * a.Tmax;
+    hipLaunchKernelGGL(dur_finalize, dim3((n + 255) / 256), dim3(256), 0, s, a.dlog_rows, a.start, a.vlen, a.B, a.Tmax, a.d_log, a.d_int, a.d_int2);
+    ROW_STEP_TRY(h, "dur.post");
+    hipLaunchKernelGGL(dur_scan, dim3(a.B), dim3(256), 0, s, a.ds ? a.ds : a.d_int, a.Tmax, a.vlen, a.cum, a.olens, a.olens32, a.alpha, a.xs, a.idim, a.scum, a.so32, a.K);
+    ROW_STEP_TRY(h, "dur.post");
+    return FS2_OK;
+}
+
+// lr.index under FS2_VARSHORT: the frames' tokens and the short layout in one launch
+int lr_index_short_launch(fs2_handle* h, hipStream_t s, const ShortLayoutArgs& sl) {
+    Scope sc(h, s, "lr.index", 0, 4.0 * (2.0 * sl.R + 3.0 * sl.Rs_pad));
+    hipLaunchKernelGGL(lr_index_short, dim3((std::max(sl.R, sl.Rs_pad) + 255) / 256), dim3(256), 0, s, sl);
+    ROW_STEP_TRY(h, "lr.index");
+    return FS2_OK;
+}
+
+// lr.index: the length regulator's index alone
+int lr_index_launch(fs2_handle* h, hipStream_t s, const RowStepArgs& a) {
+    Scope sc(h, s, "lr.index", 0, 4.0 * a.R);
+    hipLaunchKernelGGL(lr_index_only, dim3((a.R + 255) / 256), dim3(256), 0, s, a.cum_in, a.Tmax, a.ilen, a.row_pos, a.row_seq, a.vlen, a.R, a.index_rows);
+    ROW_STEP_TRY(h, "lr.index");
+    return FS2_OK;
+}
+
+// lr.expand: the length regulator, rows (and planes) with the index
+int lr_expand_launch(fs2_handle* h, hipStream_t s, const RowStepArgs& a) {
+    Scope sc(h, s, "lr.expand", 0, 4.0 * a.R * a.D * 2);
+    hipLaunchKernelGGL(lr_expand, dim3((a.R + 3) / 4), dim3(256), 0, s, a.src_rows, a.D, a.tok_start, a.ilen, a.cum_in, a.Tmax, a.row_pos, a.row_seq, 0, a.vlen, a.R, a.rows, a.index_rows,
+                       a.planes);
+    ROW_STEP_TRY(h, "lr.expand");
+    return FS2_OK;
+}
+
+// var.gather0: layer 0 of both predictors from the token-level products (one wavefront per (row, predictor))
+int var_gather0_launch(fs2_handle* h, hipStream_t s, const TokGatherArgs& tg) {
+    Scope sc(h, s, "var.gather0", 0.0, 4.0 * tg.R * tg.chans * (6.0 + 2.0));
+    hipLaunchKernelGGL(var_gather0, dim3((2 * (size_t)tg.R + 3) / 4), dim3(256), 0, s, tg);
+    ROW_STEP_TRY(h, "var.gather0");
+    return FS2_OK;
+}
+
+// var.embed: bucket search and embedding add in place
+int var_embed_launch(fs2_handle* h, hipStream_t s, const RowStepArgs& a) {
+    Scope sc(h, s, "var.embed", 0, 4.0 * a.R * a.D * 4);
+    hipLaunchKernelGGL(bucket_embed, dim3((a.R + 3) / 4), dim3(256), 0, s, a.rows, a.D, a.row_pos, a.row_seq, a.R, a.es, a.es_stride, a.ps, a.ps_stride, a.e_rows, a.p_rows, a.ebins, a.pbins,
+                       a.nb, a.Te, a.Tp, a.qe_rows, a.qp_rows, a.planes);
+    ROW_STEP_TRY(h, "var.embed");
+    return FS2_OK;
+}
+
+// dec.in.gather: bucket search + embedding add + decoder input layer as one row kernel over the token-level products.  FS2_VARSHORT (tg.f2s): the predictions
+// are per short row; where they are the source (tg.sqe / tg.sqp) their buckets are searched there first (var_bucket_short: two 255-bin searches per short row
+// instead of per frame), under this launch's profile name, and the row kernel reads the indices through the frame-to-short map
+int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const TokGatherArgs& tg) {
+    Scope sc(h, s, "dec.in.gather", 0, 4.0 * tg.R * tg.D * (tg.x0 ? 3.0 : 2.0));
+    if (tg.f2s && (tg.sqe || tg.sqp)) {
+        hipLaunchKernelGGL(var_bucket_short, dim3((tg.Rs + 255) / 256), dim3(256), 0, s, tg.sqe ? tg.e_rows : nullptr, tg.sqp ? tg.p_rows : nullptr, tg.srow_pos, tg.Rs, tg.ebins, tg.pbins,
+                           tg.nb, const_cast<int*>(tg.sqe), const_cast<int*>(tg.sqp));
+        ROW_STEP_TRY(h, "dec.in.gather");
+    }
+    hipLaunchKernelGGL(dec_in_gather, dim3((tg.R + 3) / 4), dim3(256), 0, s, tg);
+    ROW_STEP_TRY(h, "dec.in.gather");
+    return FS2_OK;
+}
+
+// <tag>.in.planes: fp32 rows -> split-bf16 planes, for a stack whose producer wrote none
+int to_planes_launch(fs2_handle* h, hipStream_t s, const char* name, const float* rows, int R, int D, void* planes) {
+    Scope sc(h, s, name, 0.0, 8.0 * R * D);
+    const int64_t n = (int64_t)R * (D / 4);
+    hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rows, D, D, R, D / 32, planes);
+    ROW_STEP_TRY(h, name);
+    return FS2_OK;
+}
+
+// dec.out.rows: fp32 rows rebuilt from the planes (hi + lo)
+int planes_to_rows_launch(fs2_handle* h, hipStream_t s, const char* name, const void* planes, int R, int D, float* rows) {
+    Scope sc(h, s, name, 0.0, 8.0 * R * D);
+    const int64_t n = (int64_t)R * (D / 4);
+    hipLaunchKernelGGL(planes_to_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, D / 32, R, D, rows, D);
+    ROW_STEP_TRY(h, name);
+    return FS2_OK;
+}
+
 // FFT-block stack, every block variant (block_steps).  b.x0 holds the input and then the output; po: the planes b.x0p alone do.
 int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, int D, int heads, const Rows& r, const HostLayout& L, const DevLayout& dl,
               int mask_q, const StackBufs& b, int prec, bool x0p_ready, int ffn_terms, bool po = false) {
@@ -623,9 +722,7 @@ int run_stack(fs2_handle* h, hipStream_t s, const char* tag, const Stack& st, in
     int rc;
     if (pl && !st.pre_ln && !x0p_ready) {
         snprintf(nm, sizeof nm, "%s.in.planes", tag);
-        Scope sc(h, s, nm, 0.0, 8.0 * r.R * D);
-        const int64_t n = (int64_t)r.R * (D / 4);
-        hipLaunchKernelGGL(to_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.x0, D, D, r.R, D / 32, b.x0p);
+        if ((rc = to_planes_launch(h, s, nm, b.x0, r.R, D, b.x0p))) return rc;
     }
     for (const Layer& ly : st.layers)
         for (const Step& step : block_steps(st, ly, D, r, b, prec, ffn_terms, po, opts())) {
@@ -654,12 +751,8 @@ int run_predictor(fs2_handle* h, hipStream_t s, const char* tag, const Predictor
 // tg: layer 0 from the token-level products (tok.proj): a row kernel in place of the convolution(s)
 int run_predictors_fused(fs2_handle* h, hipStream_t s, const FusedPredictors& v, const float* X, int ldx, const Rows& r, const void* Xp, void* xps, float* vp, float* vs,
                          float* e_rows, float* p_rows, int prec, const TokGatherArgs* tg = nullptr) {
-    if (tg) {
-        Scope sc(h, s, "var.gather0", 0.0, 4.0 * r.R * (v.c0.N / 2) * (6.0 + 2.0));
-        hipLaunchKernelGGL(var_gather0, dim3((2 * (size_t)r.R + 3) / 4), dim3(256), 0, s, *tg);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(h, FS2_ERR_HIP, "var.gather0 launch: %s", hipGetErrorString(e));
-    }
+    if (tg)
+        if (int rc = var_gather0_launch(h, s, *tg)) return rc;
     for (const Step& st : fused_predictor_steps(v, h->energy, h->pitch, !tg, X, ldx, r, Xp, xps, vp, vs, e_rows, p_rows, opts()))
         if (int rc = launch_step(h, s, nullptr, st, prec)) return rc;
     return FS2_OK;
@@ -1109,29 +1202,20 @@ TokGatherArgs tok_gather_args(const fs2_handle* h, const FrameBufs& f, const Dev
     return tg;
 }
 
-// dec.in.gather: bucket search + embedding add + decoder input layer as one row kernel over the token-level products
-// p.varshort: the predictions are per short row; where they are the source their buckets are searched there first (var_bucket_short: two 255-bin searches per
-// short row instead of per frame), under this launch's profile name, and the row kernel reads the indices through the frame-to-short map
-int dec_in_gather_launch(fs2_handle* h, hipStream_t s, const fs2_decode_io* io, TokGatherArgs tg, const FrameBufs& f, const DecodePlan& p, int Rs) {
-    const bool po = p.po;
+// dec.in.gather's block: the frame rows of tok_gather_args plus the tables of the variance adaptor's tail and of the decoder input layer; p.varshort: the frame-to-short
+// map and, where the predictions are the source, the short rows whose buckets var_bucket_short searches first (dec_in_gather_launch)
+TokGatherArgs dec_in_gather_args(const fs2_handle* h, const fs2_decode_io* io, TokGatherArgs tg, const FrameBufs& f, const DecodePlan& p, int Rs) {
     const fs2_config& c = h->cfg;
     tg.col0 = 6 * c.var_chans; tg.D = c.ddim; tg.es = io->es; tg.ps = io->ps; tg.es_stride = io->es_stride; tg.ps_stride = io->ps_stride;
     tg.e_rows = f.e_rows; tg.p_rows = f.p_rows; tg.ebins = h->ebins; tg.pbins = h->pbins; tg.nb = c.n_bins - 1; tg.TE = h->TEd; tg.TP = h->TPd;
     tg.qe_rows = f.qe; tg.qp_rows = f.qp; tg.ln_g2 = h->dec_in_lng; tg.ln_b2 = h->dec_in_lnb;
     tg.pe = h->dec.pe; tg.pe_alpha = h->dec.alpha; tg.x_scale = c.use_scaled_pos_enc ? 1.f : sqrtf((float)c.ddim);
-    tg.x0 = po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
-    Scope sc(h, s, "dec.in.gather", 0, 4.0 * tg.R * c.ddim * (po ? 2.0 : 3.0));
+    tg.x0 = p.po ? nullptr : f.sb.x0; tg.x0p = f.sb.x0p;
     if (p.varshort) {
         tg.f2s = f.f2s; tg.sqe = p.short_qe ? f.sqe : nullptr; tg.sqp = p.short_qp ? f.sqp : nullptr;
-        if (p.short_qe || p.short_qp) {
-            hipLaunchKernelGGL(var_bucket_short, dim3((Rs + 255) / 256), dim3(256), 0, s, p.short_qe ? f.e_rows : nullptr, p.short_qp ? f.p_rows : nullptr, f.srow_pos, Rs, h->ebins, h->pbins,
-                               c.n_bins - 1, f.sqe, f.sqp);
-            HIP_TRY(h, hipGetLastError());
-        }
+        tg.srow_pos = f.srow_pos; tg.Rs = Rs;
     }
-    hipLaunchKernelGGL(dec_in_gather, dim3((tg.R + 3) / 4), dim3(256), 0, s, tg);
-    HIP_TRY(h, hipGetLastError());
-    return FS2_OK;
+    return tg;
 }
 
 // dec.in.pe, the TorchScript twin: the decoder input is just x (* sqrt(d)) + alpha * pe   (encoder.py:138-141)
@@ -1420,26 +1504,18 @@ int fs2_encode(fs2_handle* h, void* stream, const fs2_encode_io* io) {
     int rc;
     DevLayout dl;
     if ((rc = upload_layout(h, s, L, t.meta, dl))) return rc;
-    {
-        Scope sc(h, s, "enc.embed", 0, 4.0 * L.R * c.adim * 2);
-        hipLaunchKernelGGL(embed_pe, dim3((L.R + 3) / 4), dim3(256), 0, s, io->xs, b.Tmax, h->enc_embed, c.idim, c.adim, h->enc.pe,
-                           h->enc.alpha, c.use_scaled_pos_enc ? 1.0f : sqrtf((float)c.adim), dl.row_pos, dl.row_seq, L.R, sb.x0,
-                           p.embed_planes ? sb.x0p : nullptr);
-        HIP_TRY(h, hipGetLastError());
-    }
+    RowStepArgs ra;      // enc.embed and dur.post on the token rows
+    memset(&ra, 0, sizeof ra);
+    ra.row_pos = dl.row_pos; ra.row_seq = dl.row_seq; ra.R = L.R; ra.start = dl.start; ra.vlen = dl.vlen; ra.B = b.B; ra.Tmax = b.Tmax; ra.D = c.adim;
+    ra.rows = sb.x0; ra.planes = p.embed_planes ? sb.x0p : nullptr;
+    ra.xs = io->xs; ra.E = h->enc_embed; ra.idim = c.idim; ra.pe = h->enc.pe; ra.pe_alpha = h->enc.alpha; ra.x_scale = c.use_scaled_pos_enc ? 1.0f : sqrtf((float)c.adim);
+    ra.dlog_rows = t.dlog_rows; ra.d_log = io->d_log; ra.d_int = t.dint; ra.d_int2 = io->d_int; ra.ds = io->ds; ra.cum = t.cum; ra.olens = io->olens; ra.olens32 = t.o32;
+    ra.alpha = io->duration_alpha > 0.f ? io->duration_alpha : 1.f; ra.scum = p.short_scan ? t.scum : nullptr; ra.so32 = p.short_scan ? t.so32 : nullptr; ra.K = var_window(c);
+    if ((rc = embed_launch(h, s, ra))) return rc;
     const Rows rows{L.R, L.Rpad, dl.row_pos, dl.dims, tok_regime};
     if ((rc = run_stack(h, s, "enc", h->enc, c.adim, c.aheads, rows, L, dl, /*mask_q=*/1, sb, p.prec, /*x0p_ready=*/p.embed_planes, p.ffn_terms))) return rc;
     if ((rc = run_predictor(h, s, "dur", h->dur, sb.x0, c.adim, rows, t.p0, t.p1, t.dlog_rows, p.prec, p.planes ? sb.x0p : nullptr, sb.xps))) return rc;
-    {
-        Scope sc(h, s, "dur.post", 0, 0);
-        const int n = b.B * b.Tmax;
-        hipLaunchKernelGGL(dur_finalize, dim3((n + 255) / 256), dim3(256), 0, s, t.dlog_rows, dl.start, dl.vlen, b.B, b.Tmax, io->d_log, t.dint, io->d_int);
-        HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(dur_scan, dim3(b.B), dim3(256), 0, s, io->ds ? io->ds : t.dint, b.Tmax, dl.vlen, t.cum, io->olens, t.o32,
-                           io->duration_alpha > 0.f ? io->duration_alpha : 1.f, io->xs, c.idim, p.short_scan ? t.scum : nullptr, p.short_scan ? t.so32 : nullptr,
-                           var_window(c));
-        HIP_TRY(h, hipGetLastError());
-    }
+    if ((rc = dur_post_launch(h, s, ra))) return rc;
     if (io->enc_out) {
         if ((rc = unpack<float>(h, s, sb.x0, c.adim, dl.start, dl.vlen, b.B, b.Tmax, io->enc_out, 0.f))) return rc;
     }
@@ -1534,18 +1610,13 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         sl.B = b.B; sl.gap = h->gap; sl.K = K; sl.Rs = Rs; sl.Rs_pad = srows.Rpad;
         sl.lri = f.lri; sl.f2s = f.f2s; sl.sstart = f.smeta; sl.slen = f.smeta + b.B; sl.sdims = sdims;
         sl.srow_pos = f.srow_pos; sl.srow_seq = f.srow_seq; sl.slri = f.slri;
-        Scope sc(h, s, "lr.index", 0, 4.0 * (2.0 * R + 3.0 * srows.Rpad));
-        hipLaunchKernelGGL(lr_index_short, dim3((std::max(R, srows.Rpad) + 255) / 256), dim3(256), 0, s, sl);
-        HIP_TRY(h, hipGetLastError());
-    } else if (p.tokproj == 3) {
-        Scope sc(h, s, "lr.index", 0, 4.0 * R);
-        hipLaunchKernelGGL(lr_index_only, dim3((R + 255) / 256), dim3(256), 0, s, enc.cum, b.Tmax, enc.vlen, dl.row_pos, dl.row_seq, dl.vlen, R, f.lri);
-        HIP_TRY(h, hipGetLastError());
-    } else {   // length regulator
-        Scope sc(h, s, "lr.expand", 0, 4.0 * R * c.adim * 2);
-        hipLaunchKernelGGL(lr_expand, dim3((R + 3) / 4), dim3(256), 0, s, enc.rows, c.adim, enc.start, enc.vlen, enc.cum, b.Tmax,
-                           dl.row_pos, dl.row_seq, 0, dl.vlen, R, f.hfr, f.lri, hfr_planes);
-        HIP_TRY(h, hipGetLastError());
+        if ((rc = lr_index_short_launch(h, s, sl))) return rc;
+    } else {      // the length regulator: its index alone where every consumer gathers from the token-level products, else rows (and planes) with it
+        RowStepArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.row_pos = dl.row_pos; ra.row_seq = dl.row_seq; ra.R = R; ra.vlen = dl.vlen; ra.B = b.B; ra.Tmax = b.Tmax; ra.D = c.adim;
+        ra.cum_in = enc.cum; ra.ilen = enc.vlen; ra.tok_start = enc.start; ra.src_rows = enc.rows; ra.index_rows = f.lri; ra.rows = f.hfr; ra.planes = hfr_planes;
+        if ((rc = p.tokproj == 3 ? lr_index_launch(h, s, ra) : lr_expand_launch(h, s, ra))) return rc;
     }
     if (p.varshort) {      // the same launches on the short rows: their metadata, their device row count, their regime
         TokGatherArgs ts = tg;
@@ -1568,22 +1639,21 @@ int fs2_decode_ctl(fs2_handle* h, void* stream, const fs2_decode_io* io, const f
         HIP_TRY(h, hipGetLastError());
     }
     if (!(p.tokproj & 2)) {
-        Scope sc(h, s, "var.embed", 0, 4.0 * R * c.adim * 4);
-        hipLaunchKernelGGL(bucket_embed, dim3((R + 3) / 4), dim3(256), 0, s, f.hfr, c.adim, dl.row_pos, dl.row_seq, R, io->es, io->es_stride,
-                           io->ps, io->ps_stride, f.e_rows, f.p_rows, h->ebins, h->pbins, c.n_bins - 1, h->Te, h->Tp, f.qe, f.qp, hfr_planes);
-        HIP_TRY(h, hipGetLastError());
+        RowStepArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.row_pos = dl.row_pos; ra.row_seq = dl.row_seq; ra.R = R; ra.D = c.adim; ra.rows = f.hfr; ra.planes = hfr_planes;
+        ra.es = io->es; ra.es_stride = io->es_stride; ra.ps = io->ps; ra.ps_stride = io->ps_stride; ra.e_rows = f.e_rows; ra.p_rows = f.p_rows;
+        ra.ebins = h->ebins; ra.pbins = h->pbins; ra.nb = c.n_bins - 1; ra.Te = h->Te; ra.Tp = h->Tp; ra.qe_rows = f.qe; ra.qp_rows = f.qp;
+        if ((rc = var_embed_launch(h, s, ra))) return rc;
     }
     if (p.tokproj & 2) {
-        if ((rc = dec_in_gather_launch(h, s, io, tg, f, p, Rs))) return rc;
+        if ((rc = dec_in_gather_launch(h, s, dec_in_gather_args(h, io, tg, f, p, Rs)))) return rc;
     } else if (c.decoder_input_layer) {   // decoder input layer: Linear -> LN -> ReLU -> + alpha * pe   (reference encoder.py:118-125)
         if ((rc = launch_step(h, s, nullptr, dec_in_step(dec_in, h->dec, f.hfr, c.adim, hfr_planes, rows, f.sb, prec, p.po), prec))) return rc;
     } else if ((rc = dec_in_pe_launch(h, s, f, dl, R, p.planes))) return rc;
     if ((rc = run_stack(h, s, "dec", h->dec, c.ddim, c.aheads, rows, L, dl, p.mask_q, f.sb, prec, /*x0p_ready=*/p.planes, p.ffn_terms, p.po))) return rc;
     if (p.po && io->dec_out) {      // the API hands the decoder output out as fp32 rows: rebuilt from the planes (hi + lo) only when asked for
-        Scope sc(h, s, "dec.out.rows", 0.0, 8.0 * R * c.ddim);
-        const int64_t n = (int64_t)R * (c.ddim / 4);
-        hipLaunchKernelGGL(planes_to_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f.sb.x0p, c.ddim / 32, R, c.ddim, f.sb.x0, c.ddim);
-        HIP_TRY(h, hipGetLastError());
+        if ((rc = planes_to_rows_launch(h, s, "dec.out.rows", f.sb.x0p, R, c.ddim, f.sb.x0))) return rc;
     }
     const int rf = p.rf;
     DevLayout dl2;      // the Postnet's and the mel outputs' layout: rf rows per decoder row
@@ -1774,6 +1844,39 @@ int fs2_op_launch_attention(void* stream, const fs2_op_attn_args* o, int32_t* pl
     const int32_t fields[FS2_ATTN_PLAN_FIELDS] = {(int32_t)p.kernel, p.dk, p.nsplit, (int32_t)p.grid_x, (int32_t)p.grid_y, (int32_t)p.split_pass, scale_bits};
     memcpy(plan_out, fields, sizeof fields);
     return launch_attention(nullptr, (hipStream_t)stream, "op.launch_attention", io);
+}
+
+// Test hook (include/fs2.h): ONE row step between the GEMMs through the function fs2_encode / fs2_decode_ctl launch it with, on the library's own argument block.
+int fs2_op_launch_row_step(void* stream, int32_t step, const void* args, uint32_t args_size) {
+    if (!args) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_row_step: null argument block");
+    hipStream_t s = (hipStream_t)stream;
+    const bool gather = step == FS2_ROW_STEP_VAR_GATHER0 || step == FS2_ROW_STEP_DEC_IN_GATHER, shortl = step == FS2_ROW_STEP_LR_INDEX_SHORT;
+    if (step < 0 || step >= FS2_ROW_STEP_COUNT) return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_row_step: unknown step %d", step);
+    const size_t want = gather ? sizeof(TokGatherArgs) : (shortl ? sizeof(ShortLayoutArgs) : sizeof(RowStepArgs));
+    if (args_size != want)
+        return fail(nullptr, FS2_ERR_ARG, "fs2_op_launch_row_step: argument block of %u bytes, this library's %s has %zu", args_size,
+                    gather ? "TokGatherArgs" : (shortl ? "ShortLayoutArgs" : "RowStepArgs"), want);
+    if (gather) {
+        TokGatherArgs tg;
+        memcpy(&tg, args, sizeof tg);
+        return step == FS2_ROW_STEP_VAR_GATHER0 ? var_gather0_launch(nullptr, s, tg) : dec_in_gather_launch(nullptr, s, tg);
+    }
+    if (shortl) {
+        ShortLayoutArgs sl;
+        memcpy(&sl, args, sizeof sl);
+        return lr_index_short_launch(nullptr, s, sl);
+    }
+    RowStepArgs a;
+    memcpy(&a, args, sizeof a);
+    switch (step) {
+        case FS2_ROW_STEP_EMBED: return embed_launch(nullptr, s, a);
+        case FS2_ROW_STEP_DUR_POST: return dur_post_launch(nullptr, s, a);
+        case FS2_ROW_STEP_LR_INDEX: return lr_index_launch(nullptr, s, a);
+        case FS2_ROW_STEP_LR_EXPAND: return lr_expand_launch(nullptr, s, a);
+        case FS2_ROW_STEP_VAR_EMBED: return var_embed_launch(nullptr, s, a);
+        case FS2_ROW_STEP_TO_PLANES: return to_planes_launch(nullptr, s, "op.in.planes", a.rows, a.R, a.D, a.planes);
+        default: return planes_to_rows_launch(nullptr, s, "op.out.rows", a.planes, a.R, a.D, a.rows);
+    }
 }
 
 int fs2_op_length_regulate(void* stream, const float* hs, const int64_t* ds, const int64_t* ilens_host, int32_t B, int32_t Tmax,

@@ -7,24 +7,7 @@
 
 namespace fs2 {
 
-struct ShortLayoutArgs {
-    // in: the duration scan (dur_scan) and the token layout
-    const int *cum, *scum; int Tmax;      // running sums of the durations and of the short durations [B, Tmax]
-    const int* ilen;                      // [B] phonemes
-    const int* so32;                      // [B] short frames
-    // in: the frame rows
-    const int *row_pos, *row_seq, *vlen; int R;
-    const int* ovf;                       // device-driven layout: its overflow flags (set: the frame layout is empty, and so is the short one); nullptr: host-driven
-    int B, gap, K;
-    int Rs, Rs_pad;                       // rows the short arrays hold (vs_row_bound, never more than the frame rows); srow_* are written up to Rs_pad
-    // out: per frame row
-    int* lri;                             // [R] token of the frame (lr_index_only's output)
-    int* f2s;                             // [R] short row of the frame, -1: none
-    // out: the short layout
-    int *sstart, *slen;                   // [B]
-    int* sdims;                           // [0] = short rows in use (the launches on short rows take it as Rp)
-    int *srow_pos, *srow_seq, *slri;      // [Rs_pad] position, utterance and token of a short row (-1: gap row)
-};
+// (the argument block: row_step_args.h: ShortLayoutArgs)
 
 // One thread per row of the longer of the two row ranges.  Every workgroup walks the utterances itself (row_start / row_after / rows_used over the
 // short lengths: B steps on one thread, operands staged in LDS), which is cheaper than a launch of its own in front of this one.

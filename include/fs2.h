@@ -313,6 +313,30 @@ typedef struct {
 #define FS2_ATTN_PLAN_FIELDS 7
 int fs2_op_launch_attention(void *stream, const fs2_op_attn_args *a, int32_t *plan_out, int32_t plan_cap);
 
+/* TEST HOOK: run ONE of the row steps that stand between the dense launches of fs2_encode / fs2_decode -- the sibling of
+ * fs2_op_launch_gemm and fs2_op_launch_attention, and the way the kernel-level tests (tests/test_gpu_rowstep_kernels.py) reach
+ * them.  The step is launched by the very function the model launches it with (fs2_runtime.hip: *_launch, which owns the grid
+ * and block arithmetic), from the library's own internal argument block of that step (csrc/row_step_args.h), copied from `args`:
+ *   FS2_ROW_STEP_VAR_GATHER0, _DEC_IN_GATHER   fs2::TokGatherArgs (dec.in.gather runs var_bucket_short first where sqe / sqp are given)
+ *   FS2_ROW_STEP_LR_INDEX_SHORT               fs2::ShortLayoutArgs
+ *   every other step                          fs2::RowStepArgs
+ * The blocks are NOT a stable ABI -- they change with the kernels -- which is why `args_size` must equal this library's sizeof of
+ * the step's block.  Nothing is allocated, converted or checked on the caller's behalf: every pointer is a DEVICE buffer the
+ * caller owns and sizes as the kernels read and write it.  FS2_ERR_ARG, before anything is launched: a NULL `args`, an unknown
+ * `step`, an `args_size` other than the block's. */
+#define FS2_ROW_STEP_EMBED 0          /* enc.embed: embed_pe                                        */
+#define FS2_ROW_STEP_DUR_POST 1       /* dur.post: dur_finalize, dur_scan                           */
+#define FS2_ROW_STEP_LR_INDEX 2       /* lr.index: lr_index_only                                    */
+#define FS2_ROW_STEP_LR_INDEX_SHORT 3 /* lr.index under FS2_VARSHORT: lr_index_short                */
+#define FS2_ROW_STEP_LR_EXPAND 4      /* lr.expand: lr_expand                                       */
+#define FS2_ROW_STEP_VAR_GATHER0 5    /* var.gather0: var_gather0                                   */
+#define FS2_ROW_STEP_VAR_EMBED 6      /* var.embed: bucket_embed                                    */
+#define FS2_ROW_STEP_DEC_IN_GATHER 7  /* dec.in.gather: var_bucket_short, dec_in_gather             */
+#define FS2_ROW_STEP_TO_PLANES 8      /* <tag>.in.planes: to_planes (rows -> planes)                */
+#define FS2_ROW_STEP_PLANES_TO_ROWS 9 /* dec.out.rows: planes_to_rows (planes -> rows)              */
+#define FS2_ROW_STEP_COUNT 10
+int fs2_op_launch_row_step(void *stream, int32_t step, const void *args, uint32_t args_size);
+
 /* length regulator on a padded batch: hs [B,Tmax,D], ds [B,Tmax] (i64), ilens HOST [B] ->
  * out [B,Lmax,D] (pads 0), index [B,Lmax] (-1 pads), olens device [B].  Lmax must be >= max olens.
  * alpha > 0: speed control, durations become round(d * alpha) (1 = unchanged).
